@@ -7,7 +7,9 @@ SparseArray (Elias-Fano + DenseSelect) images of the KmerSet, all on the device.
 every rank counts its own 100 M reads (weak scaling), the sorted key space is range-partitioned
 with one RCCL all-to-all(v), and rank 0 assembles and emits the object.
 
-Prints ONE JSON line on rank 0 (contract in the task description).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the steps
+and prints that line; the side records (packed input form, CPU baseline, end-to-end CLI, C4, multi-GPU probe) run
+only with --full.  --dump-outputs DIR writes what the last timed step emitted as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -351,6 +353,45 @@ def c4_record(g, torch, device, local_rank):
         return {"failed": repr(e)[:300]}
 
 
+DUMP_BYTES = 60_000_000          # --dump-outputs: what all .npy files of one run hold at most (float32 = 4 bytes per file byte)
+
+
+def dump_outputs(ctx, out_dir, counts, prefix="", budget=DUMP_BYTES):
+    """What the last timed step left for a caller: its counts ([windows, keys, distinct] as float64 in counts.npy) and
+    the bytes of every file it emitted (file_<suffix>.npy, one float32 per byte).  When the files hold more bytes than
+    the budget allows, small files are written whole and every larger one gets an equal share of what is left: one
+    byte from each of that many equal stretches of the file, at an offset drawn from a generator seeded by the file's
+    suffix and size -- the same sample in every run."""
+    import re
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "counts.npy"), np.asarray(counts, dtype=np.float64))
+    files = [(name, size) for name, size, _ in ctx.file_list() if not name.startswith(".part.")]
+    room = max(0, budget // 4 - len(counts) * 2)          # float32 elements
+    share = {}
+    left = sorted(files, key=lambda f: f[1])
+    while left:
+        each = room // len(left)
+        name, size = left.pop(0)
+        share[name] = min(size, each)
+        room -= share[name]
+    used = set()
+    for name, size in files:
+        key = prefix + "file_" + (re.sub(r"[^A-Za-z0-9]+", "_", name).strip("_") or "x")
+        while key in used:
+            key += "_"
+        used.add(key)
+        data = np.frombuffer(ctx.read_file(name), dtype=np.uint8)
+        n = share[name]
+        if n == 0:
+            data = data[:0]
+        elif n < size:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), size])
+            data = data[np.minimum(((np.arange(n) + rng.random(n)) * (size / n)).astype(np.int64), size - 1)]
+        np.save(os.path.join(out_dir, key + ".npy"), data.astype(np.float32))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -442,7 +483,15 @@ def main():
                     "this many ranks would (the rank then receives all its own parts: one rank's load of an N-rank build)")
     ap.add_argument("--graph", action="store_true", help="build-graph instead of build-kmer-set (windows are (k+1)-mers, "
                     "two keys per window); not the headline metric")
+    ap.add_argument("--full", action="store_true", help="after the headline, the side records as well: packed input form, "
+                    "CPU baseline, end-to-end CLI, C4 and the multi-GPU probe (each can still be left out with its --no-* / "
+                    "--e2e-reads 0 option); off by default: a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "computed (its counts and the bytes of the emitted files, a fixed sample of the larger ones) to "
+                    "DIR/<name>.npy as float32 / float64, %d MB at most" % (DUMP_BYTES // 1_000_000))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.k, args.read_len, args.genome, args.seed, args.cpu_sample_reads)), flush=True)
@@ -520,14 +569,20 @@ def main():
     ctx.synth_reads(bases.data_ptr(), nreads, L, genome_len, seed=args.seed, first_read=rank * nreads)
     torch.cuda.synchronize(device)
 
+    # what the last step counted (--dump-outputs): [windows, keys, distinct]; on the multi-GPU path [this rank's windows,
+    # the distinct keys of its range, the distinct keys of the whole build]
+    last = []
+
     def step():
         if not use_dist:
             ctx.reset()
             ctx.push_device(bases.data_ptr(), nbytes)
             c = ctx.finish()
             ctx.emit_device()
+            last[:] = [c.windows, c.keys, c.distinct]
             return c.windows, c.distinct
         r = gdist.count_distributed(ctx, bases.data_ptr(), nbytes, 2 * (k + 1 if args.graph else k), device, exchange=args.exchange)
+        last[:] = [r["windows"], r["m_range"], r["M"]]
         return r["windows"], r["M"]
 
     def barrier():
@@ -552,6 +607,8 @@ def main():
     fused = ctx.stat("fused_chunks") > 0
     narrow = ctx.stat("narrow_chunks") > 0        # ... and reads remainder + digit (5.33 bytes a key) from the first level
     rem32 = ctx.stat("rem32_chunks") > 0          # second level writes / counting reads 4-byte remainders
+    if args.dump_outputs:          # (every rank its own files: the slices of its range on the multi-GPU path)
+        dump_outputs(ctx, args.dump_outputs, last, prefix="rank%d_" % rank if world > 1 else "", budget=DUMP_BYTES // world)
 
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=xdev)
@@ -656,7 +713,7 @@ def main():
         # base: what the `goss` parser's threads hand over and SURVEY.md section 8(d)'s read term counts) -- packed on the
         # device by goss_gpu_pack_bases_device outside the timed region, counted by goss_gpu_push_packed_device: the same
         # kernels fetching 0.45 instead of 1.2 bytes per window and encoding nothing.
-        if world == 1 and not use_dist and not args.graph and not args.no_packed:
+        if args.full and world == 1 and not use_dist and not args.graph and not args.no_packed:
             try:
                 groups = (nbytes + 15) // 16
                 dcodes = torch.empty(groups, dtype=torch.int32, device=device)
@@ -696,7 +753,7 @@ def main():
                 del dcodes, dflags
             except Exception as e:          # the headline line must not be lost to the side record
                 out["packed_input"] = {"failed": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("headline done: %.1f ms per step; CPU baseline (child process, <= 420 s)" % (dt / args.steps * 1e3))
             out["cpu_baseline"] = cpu_baseline_child(k, L, genome_len, args.seed, args.cpu_sample_reads)
             # BASELINE.md holds no published figure for this metric: the ratio is against the CPU port timed on
@@ -706,7 +763,7 @@ def main():
                 out["vs_baseline_of"] = "cpu_baseline.value (oracle port, %d threads, this box)" % out["cpu_baseline"]["cores"]
         # beside the headline, never part of `value`: the end-to-end CLI on a bounded FASTQ sample, and
         # BASELINE config C4 (build-graph k = 55, 200 M x 150 bp reads) through the same library
-        if world == 1 and not use_dist and not args.graph:
+        if args.full and world == 1 and not use_dist and not args.graph:
             ctx.close()
             if args.e2e_reads > 0:
                 n_e2e = min(args.e2e_reads, nreads)

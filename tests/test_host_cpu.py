@@ -359,6 +359,45 @@ def test_bench_children_have_time_limits():
     assert err is None and p.returncode == 0
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: the counts and every emitted file's bytes as float32 .npy, the transport files left out;
+    files larger than their share of the budget sampled at the same offsets in every run, all files within the budget."""
+    import importlib
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(5)
+    files = {".header": rng.integers(0, 256, 64, dtype=np.uint8).tobytes(),
+             ".low-bits.lwr": rng.integers(0, 256, 3_000_000, dtype=np.uint8).tobytes(),
+             "-d1": rng.integers(0, 256, 900_000, dtype=np.uint8).tobytes(), ".part.span": b"\1" * 99}
+
+    class Emitted:
+        def file_list(self):
+            return [(n, len(b), None) for n, b in files.items()]
+
+        def read_file(self, name):
+            return files[name]
+
+    budget = 4_000_000
+    for d in ("a", "b"):
+        bench.dump_outputs(Emitted(), str(tmp_path / d), [12578353894, 12578353894, 99999960], budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["counts.npy", "file_d1.npy", "file_header.npy", "file_low_bits_lwr.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= budget + 128 * len(names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "counts.npy").tolist() == [12578353894, 12578353894, 99999960]
+    # the small file whole; the two large ones share what is left equally, each a sample of its own bytes
+    assert np.array_equal(np.load(tmp_path / "a" / "file_header.npy"), np.frombuffer(files[".header"], dtype=np.uint8))
+    d1, lwr = np.load(tmp_path / "a" / "file_d1.npy"), np.load(tmp_path / "a" / "file_low_bits_lwr.npy")
+    assert d1.size == lwr.size == (budget // 4 - 6 - 64) // 2
+    for sample, name in ((d1, "-d1"), (lwr, ".low-bits.lwr")):
+        counts = np.bincount(np.frombuffer(files[name], dtype=np.uint8), minlength=256)
+        assert (np.bincount(sample.astype(np.int64), minlength=256) <= counts).all()
+
+
 def test_tmp_dir_must_be_a_directory(tmp_path):
     """--tmp-dir (App.cc:233-240): checked before anything else is done -- a name that does not exist or is not a
     directory ends the command with the name in the message (no GPU is touched before that: runs here)."""

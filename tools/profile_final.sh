@@ -8,4 +8,4 @@ bash tools/profile_round.sh $R
 OUT=gpurun_out/profile_$R
 python3 tools/traffic_from_pmc.py $OUT/pmc_summary.txt 12578353894 > profiles/traffic.json 2> $OUT/traffic.err
 cp profiles/traffic.json $OUT/traffic.json
-python3 bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err
+python3 bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err

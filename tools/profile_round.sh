@@ -6,7 +6,8 @@
 R=${1:-r03}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$R
 mkdir -p $OUT/pmc $OUT/pmc_rec
-python3 $GRAFT_REPO_ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
+# the round's record: the headline with every side record (--full)
+python3 "$(dirname "$(readlink -f "$0")")/../bench.py" --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --e2e-reads 0 --no-extra --no-packed > $OUT/bench_profiled.json 2> $OUT/trace.err
 cp "$(ls -S $OUT/trace/*/*kernel_stats.csv | head -1)" $OUT/kernel_stats.csv

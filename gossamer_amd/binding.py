@@ -29,6 +29,9 @@ SYMBOLS = [
     "goss_gpu_push_keys_host", "goss_gpu_push_keys_device", "goss_gpu_push_packed_device", "goss_gpu_pack_bases_device", "goss_gpu_expect_bases",
     "goss_gpu_route_records_device", "goss_gpu_push_records_device",
     "goss_gpu_push_bases_host_async", "goss_gpu_push_packed_host", "goss_gpu_push_packed_host_async", "goss_gpu_flush",
+    "goss_gpu_object_open", "goss_gpu_object_open_emitted", "goss_gpu_object_close", "goss_gpu_object_last_error",
+    "goss_gpu_object_info", "goss_gpu_object_rank", "goss_gpu_object_select", "goss_gpu_object_multiplicity",
+    "goss_gpu_object_lookup", "goss_gpu_object_node_ranks",
 ]
 
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
@@ -210,6 +213,7 @@ class Context:
             raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode())
         self.k = k
         self.mode = mode
+        self.device = device
         self.key_words = 1 if 2 * (k + (1 if mode == MODE_GRAPH else 0)) <= 62 else 2
 
     def close(self):
@@ -635,3 +639,211 @@ class Context:
 
     def synth_reads(self, dev_ptr, nreads, read_len, genome_len, seed=1, first_read=0):
         self._check(self._L.goss_gpu_synth_reads(self._h, C.c_void_p(dev_ptr), nreads, read_len, genome_len, seed, first_read))
+
+
+# ---- objects opened for queries (goss_gpu_object_*) ------------------------------------------
+
+OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY = 0, 1, 2
+QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
+
+
+def encode_kmers(strings, k):
+    """2-bit codes of k-mer strings (A=0 C=1 G=2 T=3, first base most significant; either case): a numpy uint64
+    array of n values when 2k <= 62, else of n {lo, hi} rows -- the key layout of the C ABI."""
+    import numpy as np
+    strings = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+    if any(len(s) != k for s in strings):
+        raise ValueError("every k-mer must have %d bases" % k)
+    lut = np.full(256, 255, dtype=np.uint8)
+    for ch, v in zip(b"ACGTacgt", (0, 1, 2, 3, 0, 1, 2, 3)):
+        lut[ch] = v
+    codes = lut[np.frombuffer(b"".join(strings), dtype=np.uint8)].reshape(len(strings), k).astype(np.uint64)
+    if (codes == 255).any():
+        raise ValueError("a k-mer holds a character other than ACGT")
+    shift = 2 * (k - 1 - np.arange(k, dtype=np.uint64))            # bit position of each base
+
+    def word(sel, sub):
+        if not sel.any():
+            return np.zeros(len(strings), dtype=np.uint64)
+        return np.bitwise_or.reduce(codes[:, sel] << (shift[sel] - np.uint64(sub)), axis=1).astype(np.uint64)
+    if 2 * k <= 62:
+        return word(np.ones(k, dtype=bool), 0)
+    lo, hi = word(shift < 64, 0), word(shift >= 64, 64)
+    return np.ascontiguousarray(np.stack([lo, hi], axis=1))
+
+
+class ObjectDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("K", C.c_uint32), ("count", C.c_uint64), ("key_words", C.c_uint32),
+                ("asymmetric", C.c_uint32), ("N_lo", C.c_uint64), ("N_hi", C.c_uint64), ("D", C.c_uint64),
+                ("resident_bytes", C.c_uint64)]
+
+
+class NamedFile(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("bytes", C.c_uint64)]
+
+
+def _declare_object(L):
+    if getattr(L, "_object_declared", False):
+        return
+    P, U64 = C.c_void_p, C.c_uint64
+    L.goss_gpu_object_open.argtypes = [C.POINTER(P), C.c_int, P, C.c_int, C.c_char_p, C.POINTER(NamedFile), C.c_uint32]
+    L.goss_gpu_object_open_emitted.argtypes = [C.POINTER(P), P]
+    L.goss_gpu_object_close.argtypes = [P]
+    L.goss_gpu_object_close.restype = None
+    L.goss_gpu_object_last_error.argtypes = [P]
+    L.goss_gpu_object_last_error.restype = C.c_char_p
+    L.goss_gpu_object_info.argtypes = [P, C.POINTER(ObjectDesc)]
+    L.goss_gpu_object_rank.argtypes = [P, P, U64, C.c_uint32, P, P]
+    L.goss_gpu_object_select.argtypes = [P, P, U64, P]
+    L.goss_gpu_object_multiplicity.argtypes = [P, P, U64, P]
+    L.goss_gpu_object_lookup.argtypes = [P, P, U64, C.c_uint32, P]
+    L.goss_gpu_object_node_ranks.argtypes = [P, P, U64, C.c_uint32, P, P]
+    L._object_declared = True
+
+
+class Object:
+    """One KmerSet, Graph or bare SparseArray resident in HBM, with batched queries (goss_gpu_object_*).
+
+    Every query takes device torch tensors (used in place; results come back as torch tensors on the same device)
+    or numpy arrays (staged through the device; results come back as numpy).  Keys: uint64 values when
+    key_words == 1, else rows of {lo, hi} (torch: int64 with the same bits)."""
+
+    def __init__(self, handle, L, device):
+        self._L = L
+        self._h = handle
+        self.device = device
+        d = ObjectDesc()
+        self._check(L.goss_gpu_object_info(self._h, C.byref(d)))
+        self.kind, self.K, self.count, self.key_words = d.kind, d.K, d.count, d.key_words
+        self.asymmetric = bool(d.asymmetric)
+        self.N = d.N_lo | (d.N_hi << 64)
+        self.D, self.resident_bytes = d.D, d.resident_bytes
+        self.node_words = 1 if 2 * self.K <= 62 else 2
+
+    @classmethod
+    def open(cls, files, base, kind, device=0, stream=None):
+        """files: {name as on disk: bytes} (e.g. "gr.header", "gr-edges.low-bits.lwr", ...); kind OBJECT_*"""
+        L = load()
+        _declare_object(L)
+        names = sorted(files)
+        arr = (NamedFile * max(1, len(names)))()
+        keep = []
+        for i, n in enumerate(names):
+            data = bytes(files[n])
+            buf = C.create_string_buffer(data, max(1, len(data)))
+            keep.append(buf)
+            arr[i] = NamedFile(n.encode(), C.cast(buf, C.c_void_p), len(data))
+        h = C.c_void_p()
+        rc = L.goss_gpu_object_open(C.byref(h), device, stream, kind, base.encode(), arr, len(names))
+        if rc:
+            raise GossGpuError(rc, L.goss_gpu_strerror(rc).decode(), L.goss_gpu_object_last_error(None).decode())
+        return cls(h, L, device)
+
+    @classmethod
+    def from_context(cls, ctx):
+        """What the context has just emitted, device to device (goss_gpu_object_open_emitted)."""
+        L = load()
+        _declare_object(L)
+        h = C.c_void_p()
+        rc = L.goss_gpu_object_open_emitted(C.byref(h), ctx._h)
+        if rc:
+            raise GossGpuError(rc, L.goss_gpu_strerror(rc).decode(), L.goss_gpu_object_last_error(None).decode())
+        return cls(h, L, ctx.device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.goss_gpu_object_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc):
+        if rc:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), self._L.goss_gpu_object_last_error(self._h).decode())
+
+    def info(self):
+        return {"kind": self.kind, "K": self.K, "count": self.count, "key_words": self.key_words,
+                "asymmetric": self.asymmetric, "N": self.N, "D": self.D, "resident_bytes": self.resident_bytes}
+
+    # -- staging: (device pointer, n, torch tensor kept alive, numpy?) --
+    def _input(self, a, words):
+        import numpy as np
+        import torch
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise ValueError("torch inputs must be device tensors")
+            t = a.contiguous()
+            if t.element_size() != 8:
+                raise ValueError("keys and ranks are 64-bit")
+            _torch_ready()
+            return t, t.numel() // words, False
+        arr = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        t = torch.from_numpy(arr.view(np.int64)).to("cuda:%d" % self.device)
+        return t, arr.size // words, True
+
+    def _out(self, like, n, dtype, cols=1):
+        import torch
+        shape = (n,) if cols == 1 else (n, cols)
+        return torch.empty(shape, dtype=dtype, device=like.device)
+
+    @staticmethod
+    def _back(t, staged, np_dtype):
+        if not staged:
+            return t
+        return t.cpu().numpy().view(np_dtype)
+
+    def rank(self, keys, normalize=False):
+        """(rank, present) of every key: SparseArray::accessAndRank"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(keys, self.key_words)
+        r = self._out(t, n, torch.int64)
+        p = self._out(t, n, torch.bool)
+        self._check(self._L.goss_gpu_object_rank(self._h, t.data_ptr(), n, QUERY_NORMALIZE if normalize else 0, r.data_ptr(), p.data_ptr()))
+        return self._back(r, staged, np.uint64), self._back(p, staged, np.bool_)
+
+    def select(self, ranks):
+        """the key of every rank: SparseArray::select"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(ranks, 1)
+        k = self._out(t, n, torch.int64, self.key_words)
+        self._check(self._L.goss_gpu_object_select(self._h, t.data_ptr(), n, k.data_ptr()))
+        return self._back(k, staged, np.uint64)
+
+    def multiplicity(self, ranks):
+        """Graph::multiplicity of every edge rank (u32; torch: int32 with the same bits)"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(ranks, 1)
+        c = self._out(t, n, torch.int32)
+        self._check(self._L.goss_gpu_object_multiplicity(self._h, t.data_ptr(), n, c.data_ptr()))
+        return self._back(c, staged, np.uint32)
+
+    def lookup(self, keys, normalize=False):
+        """the count of every key, 0 when absent (1 / 0 in a KmerSet): rank + multiplicity in one kernel"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(keys, self.key_words)
+        c = self._out(t, n, torch.int32)
+        self._check(self._L.goss_gpu_object_lookup(self._h, t.data_ptr(), n, QUERY_NORMALIZE if normalize else 0, c.data_ptr()))
+        return self._back(c, staged, np.uint32)
+
+    def node_ranks(self, nodes, incoming=False, normalize=False):
+        """(begin, end) edge ranks of every node (K-mers): GraphEssentials::beginEndRank; out-degree = end - begin,
+        incoming=True: of the node's reverse complement (the in-degree)"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(nodes, self.node_words)
+        b = self._out(t, n, torch.int64)
+        e = self._out(t, n, torch.int64)
+        flags = (QUERY_INCOMING if incoming else 0) | (QUERY_NORMALIZE if normalize else 0)
+        self._check(self._L.goss_gpu_object_node_ranks(self._h, t.data_ptr(), n, flags, b.data_ptr(), e.data_ptr()))
+        return self._back(b, staged, np.uint64), self._back(e, staged, np.uint64)

@@ -5434,25 +5434,35 @@ int goss_gpu_select_normal(goss_gpu_ctx* c)
     });
 }
 
-// DenseSelect::DenseSelect (DenseArray.cc:36-91): header checks, then the device view of the file
-static RdDenseSelect open_dense_select(goss_gpu_ctx* c, const void* host, uint64_t size, int invert)
+// DenseSelect::DenseSelect (DenseArray.cc:36-91): the header's checks against the size of its file (`head`: at
+// least the header's bytes of it on the host); the device view without its data pointer
+static RdDenseSelect parse_dense_select(const void* head, uint64_t size, int invert, const std::string& name = "DenseSelect file")
 {
-    if (!host || size < sizeof(DsHeader)) throw StatusError{GOSS_ERR_INVALID_ARG, "DenseSelect file too short"};
+    if (!head || size < sizeof(DsHeader)) throw StatusError{GOSS_ERR_INVALID_ARG, name + " too short"};
     DsHeader h;
-    std::memcpy(&h, host, sizeof h);
-    if (h.version != 2012092701ULL) throw StatusError{GOSS_ERR_INVALID_ARG, "DenseSelect version mismatch"};
+    std::memcpy(&h, head, sizeof h);
+    if (h.version != 2012092701ULL) throw StatusError{GOSS_ERR_INVALID_ARG, name + ": DenseSelect version mismatch"};
     if (h.logBlockSize > 40 || h.logSampleRate > h.logBlockSize || (1ULL << h.logBlockSize) != h.blockSize ||
         (1ULL << h.logSampleRate) != h.sampleRate || h.smallBlocks + h.intermediateBlocks + h.largeBlocks != h.numBlocks)
-        throw StatusError{GOSS_ERR_INVALID_ARG, "Corrupt DenseSelect index header"};
-    if ((int)(h.flags & 1) != invert) throw StatusError{GOSS_ERR_INVALID_ARG, "DenseSelect index does not have the expected sense"};
-    if (h.indexArrayOffset + h.numBlocks * 8 > size || h.rankArrayOffset + h.numBlocks * 8 > size)
-        throw StatusError{GOSS_ERR_INVALID_ARG, "DenseSelect arrays lie outside the file"};
-    uint8_t* d = (uint8_t*)c->arena.temp(size + 16);
-    HIP_TRY(hipMemcpyAsync(d, host, size, hipMemcpyHostToDevice, c->stream));
+        throw StatusError{GOSS_ERR_INVALID_ARG, name + ": Corrupt DenseSelect index header"};
+    if ((int)(h.flags & 1) != invert) throw StatusError{GOSS_ERR_INVALID_ARG, name + ": DenseSelect index does not have the expected sense"};
+    if (h.indexArrayOffset > size || h.numBlocks > (size - h.indexArrayOffset) / 8 ||
+        h.rankArrayOffset > size || h.numBlocks > (size - h.rankArrayOffset) / 8)
+        throw StatusError{GOSS_ERR_INVALID_ARG, name + ": DenseSelect arrays lie outside the file"};
     RdDenseSelect r{};
-    r.data = d; r.size = size; r.flags = h.flags; r.indexArrayOffset = h.indexArrayOffset; r.rankArrayOffset = h.rankArrayOffset;
+    r.size = size; r.flags = h.flags; r.indexArrayOffset = h.indexArrayOffset; r.rankArrayOffset = h.rankArrayOffset;
     r.logBlockSize = h.logBlockSize; r.blockSize = h.blockSize; r.logSampleRate = h.logSampleRate; r.sampleRate = h.sampleRate;
     r.numBlocks = h.numBlocks;
+    return r;
+}
+
+// ... then the device view of the file, copied into the context's arena
+static RdDenseSelect open_dense_select(goss_gpu_ctx* c, const void* host, uint64_t size, int invert)
+{
+    RdDenseSelect r = parse_dense_select(host, size, invert);
+    uint8_t* d = (uint8_t*)c->arena.temp(size + 16);
+    HIP_TRY(hipMemcpyAsync(d, host, size, hipMemcpyHostToDevice, c->stream));
+    r.data = d;
     return r;
 }
 
@@ -5692,6 +5702,366 @@ int goss_synth_reads_host(char* out, uint64_t nreads, uint32_t read_len, uint64_
         for (uint32_t j = 0; j <= read_len; ++j)
             out[r * stride + j] = synth_read_byte(seed, genome_len, read_len, first_read + r, j);
     return GOSS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================================
+// Objects opened for queries (goss_gpu_object_*): one KmerSet, Graph or SparseArray in one
+// allocation of its own, outside every context's arena
+// ============================================================================================
+
+struct goss_gpu_object {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int kind = 0;
+    uint32_t K = 0, key_words = 1, node_words = 1;
+    bool asymmetric = false;
+    uint8_t* mem = nullptr;                 // every image, then the query's failure word
+    uint64_t bytes = 0;
+    unsigned long long* d_bad = nullptr;
+    unsigned long long* h_bad = nullptr;    // (page-locked)
+    QueryObj q{};
+    std::string last_error;
+};
+
+namespace {
+
+thread_local std::string t_open_error;      // why the calling thread's last open failed (goss_gpu_object_last_error(NULL))
+
+struct ObjSrc { const uint8_t* p = nullptr; uint64_t n = 0; bool dev = false; };
+typedef std::map<std::string, ObjSrc> ObjFiles;
+
+// The images an object needs, laid out in its one allocation: what is read from where, and which device
+// pointer of the object's view points at it.
+struct ObjPlan {
+    const ObjFiles& files;
+    struct Piece { ObjSrc src; uint64_t bytes, off; const void** dst; };
+    std::vector<Piece> pieces;
+    uint64_t total = 0;
+
+    const ObjSrc& need(const std::string& name) const
+    {
+        auto it = files.find(name);
+        if (it == files.end()) throw StatusError{GOSS_ERR_INVALID_ARG, "missing file " + name};
+        if (!it->second.p && it->second.n) throw StatusError{GOSS_ERR_INVALID_ARG, "no data for file " + name};
+        return it->second;
+    }
+    // the first n bytes of a file on the host
+    std::vector<uint8_t> head(const ObjSrc& s, uint64_t n) const
+    {
+        std::vector<uint8_t> v(n);
+        if (!n) return v;
+        if (s.dev) HIP_TRY(hipMemcpy(v.data(), s.p, n, hipMemcpyDeviceToHost));
+        else std::memcpy(v.data(), s.p, n);
+        return v;
+    }
+    void place(const ObjSrc& s, uint64_t bytes, const void** dst)
+    {
+        pieces.push_back(Piece{s, bytes, total, dst});
+        total = (total + bytes + 16 + 255) & ~255ULL;            // (16: the walkers never read past an image; slack only)
+    }
+};
+
+uint64_t pow4(uint32_t n, uint64_t* hi) { *hi = 2 * n >= 64 ? 1ULL << (2 * n - 64) : 0; return 2 * n < 64 ? 1ULL << (2 * n) : 0; }
+
+// SparseArray(base, fac) (SparseArray.hh:60-72, SparseArray.cc:133-170): header, high-bits, -d0, -d1 and the low-bits
+// columns of quantizedD bits (IntegerArray.cc:259-357), every size checked against the header
+void plan_sparse(ObjPlan& pl, const std::string& sa, RdSparse& s)
+{
+    const ObjSrc& hs = pl.need(sa + ".header");
+    if (hs.n < sizeof(SaHeader)) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header is too short"};
+    SaHeader h;
+    std::memcpy(&h, pl.head(hs, sizeof h).data(), sizeof h);
+    if (h.version != 2012030501ULL) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: SparseArray version mismatch"};
+    std::vector<IaCol> cols;
+    if (h.D == 0 || h.D > 128 || h.quantizedD != 8 * ((h.D + 7) / 8) || !ia_layout((uint32_t)h.quantizedD, "", 0, cols) || cols.size() > 4)
+        throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: corrupt SparseArray header"};
+    s = RdSparse{};
+    s.D = h.D; s.count = h.count; s.size_lo = h.size_lo; s.size_hi = h.size_hi;
+    // N >> D bits of zeros and count ones (SparseArray.cc:79-86)
+    uint64_t nd = 0;
+    if (h.D < 64)
+    {
+        if (h.size_hi >> h.D) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: N >> D does not fit 64 bits"};
+        nd = (h.size_lo >> h.D) | (h.size_hi << (64 - h.D));
+    }
+    else if (h.D < 128) nd = h.size_hi >> (h.D - 64);
+    const ObjSrc& hb = pl.need(sa + ".high-bits");
+    const uint64_t words = hb.n / 8;
+    if (nd > (~0ULL >> 2) || h.count > (~0ULL >> 2) || words < (nd + h.count + 63) / 64)
+        throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".high-bits is shorter than its header says"};
+    s.hi.nwords = words;
+    pl.place(hb, words * 8, (const void**)&s.hi.w);
+    const ObjSrc& d0 = pl.need(sa + "-d0");
+    const ObjSrc& d1 = pl.need(sa + "-d1");
+    s.d0 = parse_dense_select(pl.head(d0, std::min<uint64_t>(d0.n, sizeof(DsHeader))).data(), d0.n, 1, sa + "-d0");
+    s.d1 = parse_dense_select(pl.head(d1, std::min<uint64_t>(d1.n, sizeof(DsHeader))).data(), d1.n, 0, sa + "-d1");
+    pl.place(d0, d0.n, (const void**)&s.d0.data);
+    pl.place(d1, d1.n, (const void**)&s.d1.data);
+    s.ncols = (uint32_t)cols.size();
+    for (size_t i = 0; i < cols.size(); ++i)
+    {
+        const std::string name = sa + ".low-bits" + cols[i].suffix;
+        const ObjSrc& c = pl.need(name);
+        if (h.count > c.n / cols[i].bytes) throw StatusError{GOSS_ERR_INVALID_ARG, name + " is shorter than its header's count"};
+        s.col_bytes[i] = cols[i].bytes; s.col_shift[i] = cols[i].shift;
+        pl.place(c, h.count * cols[i].bytes, (const void**)&s.col[i]);
+    }
+}
+
+// Graph::open / Graph::Graph (Graph.cc:366-410), KmerSet's constructor (KmerSet.hh:170-190), SparseArray(base, fac)
+void open_object(goss_gpu_object* o, int kind, const std::string& base, const ObjFiles& files)
+{
+    ObjPlan pl{files};
+    QueryObj& q = o->q;
+    o->kind = kind;
+    if (kind == GOSS_OBJECT_SPARSE_ARRAY)
+    {
+        plan_sparse(pl, base, q.s);
+        o->key_words = q.s.size_hi ? 2 : 1;
+    }
+    else
+    {
+        const ObjSrc& hs = pl.need(base + ".header");
+        if (hs.n < 24) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header is too short"};
+        uint64_t h[3];
+        std::memcpy(h, pl.head(hs, 24).data(), 24);
+        const bool graph = kind == GOSS_OBJECT_GRAPH;
+        if (h[0] != (graph ? 2011101014ULL : 2011101701ULL))
+            throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: " + (graph ? "Graph" : "KmerSet") + " version mismatch"};
+        if (h[1] == 0 || h[1] > (graph ? 62u : 63u)) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: K out of range"};
+        o->K = (uint32_t)h[1];
+        q.len = graph ? o->K + 1 : o->K;
+        q.graph = graph;
+        o->key_words = 2 * q.len <= 62 ? 1 : 2;
+        o->node_words = 2 * o->K <= 62 ? 1 : 2;
+        o->asymmetric = graph && (h[2] & 1);
+        const std::string sa = base + (graph ? "-edges" : ".kmers");
+        plan_sparse(pl, sa, q.s);
+        uint64_t nhi, nlo = pow4(q.len, &nhi);
+        if (q.s.size_lo != nlo || q.s.size_hi != nhi) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: the universe is not 4^len"};
+        if (!graph && h[2] != q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: count differs from " + sa};
+        if (graph)
+        {
+            // VariableByteArray(base, fac) (VariableByteArray.hh:120-160)
+            const std::string vb = base + "-counts";
+            const ObjSrc& o0 = pl.need(vb + ".ord0");
+            if (o0.n < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord0 is shorter than the edge count"};
+            pl.place(o0, q.s.count, (const void**)&q.v.ord0);
+            plan_sparse(pl, vb + ".ord1p", q.v.p1);
+            plan_sparse(pl, vb + ".ord2p", q.v.p2);
+            if (q.v.p1.size_hi || q.v.p2.size_hi) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ": presence arrays wider than 64 bits"};
+            const ObjSrc& o1 = pl.need(vb + ".ord1");
+            const ObjSrc& o2 = pl.need(vb + ".ord2");
+            if (o1.n < q.v.p1.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord1 is shorter than the ord1p count"};
+            if (o2.n / 2 < q.v.p2.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord2 is shorter than the ord2p count"};
+            pl.place(o1, q.v.p1.count, (const void**)&q.v.ord1);
+            pl.place(o2, q.v.p2.count * 2, (const void**)&q.v.ord2);
+        }
+    }
+    // one allocation: the images, then the failure word
+    const uint64_t bad_off = pl.total;
+    o->bytes = pl.total + 256;
+    HIP_TRY(hipMalloc((void**)&o->mem, o->bytes));
+    o->d_bad = (unsigned long long*)(o->mem + bad_off);
+    for (auto& pc : pl.pieces)
+    {
+        *pc.dst = o->mem + pc.off;
+        if (pc.bytes)
+            HIP_TRY(hipMemcpyAsync(o->mem + pc.off, pc.src.p, pc.bytes, pc.src.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(o->stream));
+}
+
+int usable_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return GOSS_ERR_NO_DEVICE;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return GOSS_ERR_NO_DEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GOSS_ERR_NO_DEVICE;
+    return GOSS_OK;
+}
+
+// guarded() for objects: no exception crosses the ABI; the message goes to `err`
+template <class F>
+int obj_guarded(int device, std::string& err, F&& f)
+{
+    try
+    {
+        HIP_TRY(hipSetDevice(device));
+        (void)hipGetLastError();
+        f();
+        check_launch("a kernel launch was refused");
+        return GOSS_OK;
+    }
+    catch (const HipError& e) { err = std::string(e.what) + ": " + hipGetErrorString(e.e); return GOSS_ERR_HIP; }
+    catch (const StatusError& e) { err = e.msg; return e.status; }
+    catch (const std::bad_alloc&) { err = "host allocation failed"; return GOSS_ERR_OOM; }
+    catch (const std::exception& e) { err = std::string("unexpected failure: ") + e.what(); return GOSS_ERR_STATE; }
+}
+
+void object_free(goss_gpu_object* o)
+{
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    if (o->stream) (void)hipStreamSynchronize(o->stream);
+    if (o->mem) (void)hipFree(o->mem);
+    if (o->h_bad) (void)hipHostFree(o->h_bad);
+    if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
+    delete o;
+}
+
+int object_open(goss_gpu_object** out, int device, void* stream, int kind, const std::string& base, const ObjFiles& files)
+{
+    goss_gpu_object* o = new (std::nothrow) goss_gpu_object();
+    if (!o) return GOSS_ERR_OOM;
+    o->device = device;
+    int rc = obj_guarded(device, t_open_error, [&]() {
+        if (stream) o->stream = (hipStream_t)stream;
+        else { HIP_TRY(hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking)); o->own_stream = true; }
+        HIP_TRY(hipHostMalloc((void**)&o->h_bad, 8, hipHostMallocDefault));
+        open_object(o, kind, base, files);
+    });
+    if (rc != GOSS_OK) { object_free(o); return rc; }
+    *out = o;
+    return GOSS_OK;
+}
+
+inline dim3 query_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)); }
+
+// one batched query: launch, then the lowest failing query index, if any, becomes the call's error
+template <class L>
+int object_query(goss_gpu_object* o, uint64_t n, L&& launch)
+{
+    if (n == 0) return GOSS_OK;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
+        launch(query_grid(n));
+        HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        const unsigned long long bad = *o->h_bad;
+        if (bad != ~0ULL)
+        {
+            static const char* const why[4] = {"", "a key has bits at or above 2*len (or lies at or past N)",
+                                               "a rank is not below the count", "the index walk cannot answer (damaged object)"};
+            throw StatusError{GOSS_ERR_INVALID_ARG, "query " + std::to_string(bad >> 2) + ": " + why[bad & 3]};
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int goss_gpu_object_open(goss_gpu_object** out, int device, void* stream, int kind, const char* base,
+                         const goss_gpu_named_file* files, uint32_t nfiles)
+{
+    if (!out) return GOSS_ERR_INVALID_ARG;
+    *out = nullptr;
+    t_open_error.clear();
+    if (kind != GOSS_OBJECT_KMER_SET && kind != GOSS_OBJECT_GRAPH && kind != GOSS_OBJECT_SPARSE_ARRAY) return GOSS_ERR_INVALID_ARG;
+    if (!base || (!files && nfiles)) return GOSS_ERR_INVALID_ARG;
+    if (int rc = usable_device(device)) return rc;
+    ObjFiles fs;
+    for (uint32_t i = 0; i < nfiles; ++i)
+    {
+        if (!files[i].name) return GOSS_ERR_INVALID_ARG;
+        fs[files[i].name] = ObjSrc{(const uint8_t*)files[i].data, files[i].bytes, false};
+    }
+    return object_open(out, device, stream, kind, base, fs);
+}
+
+int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* c)
+{
+    if (!out || !c) return GOSS_ERR_INVALID_ARG;
+    *out = nullptr;
+    t_open_error.clear();
+    ObjFiles fs;
+    for (auto& f : c->files) fs[f.suffix] = ObjSrc{f.dev ? f.dev : f.host.data(), f.size, f.dev != nullptr};
+    int kind = -1;
+    if (fs.count(".kmers.header")) kind = GOSS_OBJECT_KMER_SET;
+    else if (fs.count("-edges.header")) kind = GOSS_OBJECT_GRAPH;
+    else if (fs.count(".high-bits")) kind = GOSS_OBJECT_SPARSE_ARRAY;
+    if (kind < 0) { t_open_error = "the context holds no emitted KmerSet, Graph or SparseArray"; return GOSS_ERR_STATE; }
+    // what the context's stream still writes into its files
+    int rc = guarded(c, [&]() { HIP_TRY(hipStreamSynchronize(c->stream)); });
+    if (rc != GOSS_OK) { t_open_error = c->last_error; return rc; }
+    return object_open(out, c->device, nullptr, kind, "", fs);
+}
+
+void goss_gpu_object_close(goss_gpu_object* o) { object_free(o); }
+
+const char* goss_gpu_object_last_error(const goss_gpu_object* o) { return o ? o->last_error.c_str() : t_open_error.c_str(); }
+
+int goss_gpu_object_info(const goss_gpu_object* o, goss_gpu_object_desc* out)
+{
+    if (!o || !out) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    out->kind = o->kind; out->K = o->K; out->count = o->q.s.count; out->key_words = o->key_words;
+    out->asymmetric = o->asymmetric ? 1 : 0; out->N_lo = o->q.s.size_lo; out->N_hi = o->q.s.size_hi; out->D = o->q.s.D;
+    out->resident_bytes = o->bytes;
+    return GOSS_OK;
+}
+
+int goss_gpu_object_rank(goss_gpu_object* o, const void* d_keys, uint64_t n, uint32_t flags, uint64_t* d_rank, uint8_t* d_present)
+{
+    if (!o || (!d_keys && n) || (flags & ~(uint32_t)GOSS_QUERY_NORMALIZE)) return GOSS_ERR_INVALID_ARG;
+    if ((flags & GOSS_QUERY_NORMALIZE) && o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "a bare SparseArray has no strands"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        if (o->key_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_rank_kernel<Key1>), grid, dim3(256), 0, o->stream, o->q, (const Key1*)d_keys, n, flags, d_rank, d_present, o->d_bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_rank_kernel<Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key2*)d_keys, n, flags, d_rank, d_present, o->d_bad);
+    });
+}
+
+int goss_gpu_object_select(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t n, void* d_keys)
+{
+    if (!o || ((!d_ranks || !d_keys) && n)) return GOSS_ERR_INVALID_ARG;
+    return object_query(o, n, [&](dim3 grid) {
+        if (o->key_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_select_kernel<Key1>), grid, dim3(256), 0, o->stream, o->q, d_ranks, n, (Key1*)d_keys, o->d_bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_select_kernel<Key2>), grid, dim3(256), 0, o->stream, o->q, d_ranks, n, (Key2*)d_keys, o->d_bad);
+    });
+}
+
+int goss_gpu_object_multiplicity(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t n, uint32_t* d_counts)
+{
+    if (!o || ((!d_ranks || !d_counts) && n)) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_GRAPH) { o->last_error = "multiplicity needs a Graph"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        hipLaunchKernelGGL(query_multiplicity_kernel, grid, dim3(256), 0, o->stream, o->q, d_ranks, n, d_counts, o->d_bad);
+    });
+}
+
+int goss_gpu_object_lookup(goss_gpu_object* o, const void* d_keys, uint64_t n, uint32_t flags, uint32_t* d_counts)
+{
+    if (!o || ((!d_keys || !d_counts) && n) || (flags & ~(uint32_t)GOSS_QUERY_NORMALIZE)) return GOSS_ERR_INVALID_ARG;
+    if ((flags & GOSS_QUERY_NORMALIZE) && o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "a bare SparseArray has no strands"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        if (o->key_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_lookup_kernel<Key1>), grid, dim3(256), 0, o->stream, o->q, (const Key1*)d_keys, n, flags, d_counts, o->d_bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_lookup_kernel<Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key2*)d_keys, n, flags, d_counts, o->d_bad);
+    });
+}
+
+int goss_gpu_object_node_ranks(goss_gpu_object* o, const void* d_nodes, uint64_t n, uint32_t flags, uint64_t* d_begin, uint64_t* d_end)
+{
+    if (!o || (!d_nodes && n) || (flags & ~(uint32_t)(GOSS_QUERY_NORMALIZE | GOSS_QUERY_INCOMING))) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_GRAPH) { o->last_error = "node ranks need a Graph"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        if (o->key_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_node_ranks_kernel<Key1, Key1>), grid, dim3(256), 0, o->stream, o->q, (const Key1*)d_nodes, n, flags, d_begin, d_end, o->d_bad);
+        else if (o->node_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_node_ranks_kernel<Key1, Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key1*)d_nodes, n, flags, d_begin, d_end, o->d_bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(query_node_ranks_kernel<Key2, Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key2*)d_nodes, n, flags, d_begin, d_end, o->d_bad);
+    });
 }
 
 }  // extern "C"

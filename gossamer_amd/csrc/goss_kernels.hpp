@@ -19,3 +19,4 @@
 #include "kernels_count.hpp"
 #include "kernels_merge.hpp"
 #include "kernels_emit.hpp"
+#include "kernels_query.hpp"

@@ -82,59 +82,77 @@ __device__ inline uint64_t rd_u(const uint8_t* p, uint32_t bytes, uint64_t i)
 //   * "two-level" -- per sample a 32-bit offset and a 16-bit reference to a scan or explicit table of
 //                    its own.
 // The reference walks this in DenseSelect::select + lookupSubBlock (DenseArray.cc:134-258).
-struct RdRef { const uint8_t* at; uint32_t kind; };
-__device__ inline RdRef rd_ref(const uint8_t* origin, uint64_t word)
+// A reference is followed only when what it points at lies inside the image (`off` = byte offset from the image's
+// start): a damaged file gives "cannot answer", never a read outside the image's allocation.
+struct RdRef { const uint8_t* at; uint64_t off; uint32_t kind; };
+__device__ inline RdRef rd_ref(const uint8_t* origin, uint64_t origin_off, uint64_t word)
 {
-    return RdRef{origin + (word & ~(uint64_t)kRdTypeMask), (uint32_t)(word & kRdTypeMask)};
+    const uint64_t rel = word & ~(uint64_t)kRdTypeMask;
+    return RdRef{origin + rel, origin_off + rel, (uint32_t)(word & kRdTypeMask)};
+}
+// true when bytes [off, off + n) lie inside an image of `size` bytes
+__device__ inline bool rd_inside(uint64_t size, uint64_t off, uint64_t n) { return off <= size && n <= size - off; }
+__device__ inline uint32_t rd_entry_bytes(uint32_t kind)
+{
+    return kind == kRdFull64 ? 8u : kind == kRdFull32 ? 4u : kind == kRdFull16 ? 2u : kind == kRdFull8 ? 1u : 0u;
 }
 // entry j of an explicit table, relative to `base` (absolute for 64-bit entries)
-__device__ inline bool rd_explicit(const RdRef& t, uint64_t base, uint64_t j, uint64_t* out)
+__device__ inline bool rd_explicit(const RdRef& t, uint64_t size, uint64_t base, uint64_t j, uint64_t* out)
 {
+    const uint32_t eb = rd_entry_bytes(t.kind);
+    if (!eb || !rd_inside(size, t.off, (j + 1) * eb)) return false;            // (j < 8192: no overflow)
     switch (t.kind)
     {
         case kRdFull64: *out = reinterpret_cast<const uint64_t*>(t.at)[j]; return true;
         case kRdFull32: *out = base + reinterpret_cast<const uint32_t*>(t.at)[j]; return true;
         case kRdFull16: *out = base + reinterpret_cast<const uint16_t*>(t.at)[j]; return true;
-        case kRdFull8:  *out = base + t.at[j]; return true;
-        default: return false;
+        default:        *out = base + t.at[j]; return true;
     }
 }
 __device__ inline bool rd_dense_select(const RdDenseSelect& d, const RdBits& bits, uint64_t i, uint64_t* out)
 {
     const uint64_t blk = i >> d.logBlockSize;
-    if (blk >= d.numBlocks) return false;
+    if (blk >= d.numBlocks) return false;                          // (index / rank arrays: checked against the size at open)
     const uint64_t in_blk = i & (d.blockSize - 1);                 // which of the block's positions
     const uint64_t sample = in_blk >> d.logSampleRate;             // which sample interval
     const uint64_t behind = in_blk & (d.sampleRate - 1);           // how far behind the sample
     const bool zeros = d.flags & 1;                                // the index is over the zero bits
     const uint64_t base = reinterpret_cast<const uint64_t*>(d.data + d.rankArrayOffset)[blk];
-    const RdRef top = rd_ref(d.data, reinterpret_cast<const uint64_t*>(d.data + d.indexArrayOffset)[blk]);
+    const RdRef top = rd_ref(d.data, 0, reinterpret_cast<const uint64_t*>(d.data + d.indexArrayOffset)[blk]);
     if (top.kind == kRdSmall)                                      // scan from a 16-bit sample offset
+    {
+        if (!rd_inside(d.size, top.off, 2 * (sample + 1))) return false;
         return rd_bits_select(bits, zeros, base + reinterpret_cast<const uint16_t*>(top.at)[sample], behind, out);
-    if (top.kind != kRdIntermediate) return rd_explicit(top, base, in_blk, out);
+    }
+    if (top.kind != kRdIntermediate) return rd_explicit(top, d.size, base, in_blk, out);
     // two-level: 32-bit sample offsets, then 16-bit references relative to the block
     const uint64_t nsamples = 1ULL << (d.logBlockSize - d.logSampleRate);
+    if (!rd_inside(d.size, top.off, 6 * nsamples)) return false;
     const uint64_t from = base + reinterpret_cast<const uint32_t*>(top.at)[sample];
     const uint16_t word = reinterpret_cast<const uint16_t*>(top.at + 4 * nsamples)[sample];
     if (word == 0) return rd_bits_select(bits, zeros, from, behind, out);
-    const RdRef sub = rd_ref(top.at, word);
-    return sub.kind == kRdFull64 ? false : rd_explicit(sub, from, behind, out);
+    const RdRef sub = rd_ref(top.at, top.off, word);
+    return sub.kind == kRdFull64 ? false : rd_explicit(sub, d.size, from, behind, out);
 }
 
 // low D bits of element i, from the IntegerArray column files (IntegerArray.cc:259-357)
 template <class K> __device__ inline K rd_low(const RdSparse& s, uint64_t i);
 template <> __device__ inline Key1 rd_low<Key1>(const RdSparse& s, uint64_t i)
 {
+    // (unrolled over the four possible columns: constant indices keep the array's fields out of scratch memory)
     uint64_t v = 0;
-    for (uint32_t c = 0; c < s.ncols; ++c)
-        if (s.col_shift[c] < 64) v |= rd_u(s.col[c], s.col_bytes[c], i) << s.col_shift[c];
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c)
+        if (c < s.ncols && s.col_shift[c] < 64) v |= rd_u(s.col[c], s.col_bytes[c], i) << s.col_shift[c];
     return Key1{v};
 }
 template <> __device__ inline Key2 rd_low<Key2>(const RdSparse& s, uint64_t i)
 {
     Key2 v{0, 0};
-    for (uint32_t c = 0; c < s.ncols; ++c)
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c)
     {
+        if (c >= s.ncols) break;
         const uint64_t x = rd_u(s.col[c], s.col_bytes[c], i);
         const uint32_t sh = s.col_shift[c];
         if (sh < 64) { v.lo |= x << sh; if (sh) v.hi |= x >> (64 - sh); }
@@ -208,6 +226,32 @@ __device__ inline bool rd_sparse_rank(const RdSparse& s, const K& pos, uint64_t*
     uint64_t b, e;
     if (!rd_group<K>(s, rd_high(pos, (uint32_t)s.D), &b, &e)) return false;
     if (e > s.count) e = s.count;
+    const K want = rd_mask(pos, (uint32_t)s.D);
+    const uint64_t end = e;
+    while (b < e)
+    {
+        const uint64_t m = b + ((e - b) >> 1);
+        if (rd_low<K>(s, m) < want) b = m + 1; else e = m;
+    }
+    *rank = b;
+    *present = b < end && rd_low<K>(s, b) == want;
+    return true;
+}
+
+// pos < N (the header's size, {lo, hi})
+__device__ inline bool rd_below(const Key1& k, uint64_t n_lo, uint64_t n_hi) { return n_hi != 0 || k.lo < n_lo; }
+__device__ inline bool rd_below(const Key2& k, uint64_t n_lo, uint64_t n_hi) { return k.hi < n_hi || (k.hi == n_hi && k.lo < n_lo); }
+
+// SparseArray::accessAndRank (SparseArray.hh:262-276) with rank's answer for a position at or past the
+// universe (SparseArray.hh:296-301: the count, absent).  Stricter than rd_sparse_rank: a group that does not
+// lie inside [0, count] is a damaged index and gives "cannot answer" instead of a clamped rank.
+template <class K>
+__device__ inline bool rd_sparse_access_rank(const RdSparse& s, const K& pos, uint64_t* rank, bool* present)
+{
+    *present = false;
+    if (!s.count || !rd_below(pos, s.size_lo, s.size_hi)) { *rank = s.count; return true; }
+    uint64_t b, e;
+    if (!rd_group<K>(s, rd_high(pos, (uint32_t)s.D), &b, &e) || b > e || e > s.count) return false;
     const K want = rd_mask(pos, (uint32_t)s.D);
     const uint64_t end = e;
     while (b < e)

@@ -628,6 +628,79 @@ int goss_gpu_synth_reads(goss_gpu_ctx* ctx, void* d_out, uint64_t nreads, uint32
 int goss_synth_reads_host(char* out, uint64_t nreads, uint32_t read_len,
                           uint64_t genome_len, uint64_t seed, uint64_t first_read);
 
+/*
+ * Objects opened for queries: one KmerSet, Graph or bare SparseArray resident in HBM, independent of every
+ * context, with batched read-side queries against it -- what Graph / KmerSet / SparseArray answer once opened
+ * (Graph::open, Graph.cc:366-410; KmerSet's constructor; SparseArray(base, fac), SparseArray.hh:60-72).
+ *
+ * goss_gpu_object_open: the object's files in host memory, named as on disk:
+ *   kmer set      <base>.header, <base>.kmers.header / .high-bits / -d0 / -d1 / .low-bits*
+ *   graph         <base>.header, <base>-edges.*, <base>-counts.ord0 / .ord1 / .ord2, <base>-counts.ord1p.*,
+ *                 <base>-counts.ord2p.* (the -counts-hist.txt is not needed)
+ *   sparse array  <base>.header, <base>.high-bits, <base>-d0, <base>-d1, <base>.low-bits*
+ * The library parses every header itself (KmerSet / Graph: K, count, the asymmetric flag; SparseArray: D, qD,
+ * N, count; DenseSelect: offsets and block counts), derives the low-bits columns from qD (IntegerArray.cc:259-357)
+ * and checks every file's size against its header before anything runs: a missing or short file is
+ * GOSS_ERR_INVALID_ARG naming the file.  Every image is copied into ONE device allocation of the object's own.
+ * stream: the stream every call of the object runs on (NULL: a stream of its own).
+ * goss_gpu_object_open_emitted: the same, device to device, from what a context has just emitted
+ * (goss_gpu_emit, goss_gpu_emit_sparse_array, goss_gpu_group_emit's contexts[0]); the object stays valid when
+ * the context is reset or destroyed.  GOSS_ERR_STATE when the context holds no emitted object.
+ * goss_gpu_object_last_error(NULL): why the calling thread's last open failed.
+ *
+ * Queries.  Keys are 1 u64 when 2 * len <= 62, else {lo, hi} pairs, as goss_gpu_result lays them out; len = K
+ * for k-mers and nodes, K + 1 for graph edges; a bare array's keys are 2 words when N >= 2^64.  Every buffer is a
+ * device pointer on the object's device; every call is synchronous on the object's stream; n = 0 does nothing.
+ * An empty object answers rank 0, absent.  A key with a bit at or above 2 * len (at or past N for a bare array),
+ * a rank at or past the count, or an index walk that cannot answer (a damaged image: the walkers check every
+ * reference they follow against the image's size) fails the call with GOSS_ERR_INVALID_ARG, and
+ * goss_gpu_object_last_error names the lowest such query index; no call returns a silent wrong answer.
+ * GOSS_QUERY_NORMALIZE maps each key to its canonical form first (position_type::normalize, RankSelect.hh:126-140),
+ * so either strand can be looked up in a KmerSet, which stores canonical k-mers only; refused for a bare array.
+ *
+ *   rank          SparseArray::accessAndRank (SparseArray.hh:262-276) / rank (:296-309): u64 rank and u8 presence
+ *                 per key; either output may be NULL.
+ *   select        SparseArray::select (SparseArray.hh:311-325): the key of each rank (< count).
+ *   multiplicity  Graph only: Graph::multiplicity(rank) (Graph.hh:425-428), VariableByteArray::operator[]
+ *                 (VariableByteArray.hh:227-247); an opened graph has no removed edges, originalRank is the identity.
+ *   lookup        rank, then multiplicity, in one kernel: the count of each key, 0 when absent (1 / 0 in a KmerSet
+ *                 or a bare array).
+ *   node_ranks    Graph only: GraphEssentials::beginEndRank (GraphEssentials.hh:88-96) of each node (K bases):
+ *                 out-degree = end - begin; GOSS_QUERY_INCOMING: of the node's reverse complement, i.e. inDegree
+ *                 (GraphEssentials.hh:74-77).  Either output may be NULL.
+ */
+typedef struct goss_gpu_object goss_gpu_object;
+enum { GOSS_OBJECT_KMER_SET = 0, GOSS_OBJECT_GRAPH = 1, GOSS_OBJECT_SPARSE_ARRAY = 2 };
+enum { GOSS_QUERY_NORMALIZE = 1, GOSS_QUERY_INCOMING = 2 };
+typedef struct {
+    const char* name;           /* e.g. "gr.header", "gr-edges.low-bits.lwr" */
+    const void* data;           /* host memory */
+    uint64_t bytes;
+} goss_gpu_named_file;
+typedef struct {
+    int32_t kind;               /* GOSS_OBJECT_* */
+    uint32_t K;                 /* 0 for a bare array */
+    uint64_t count;             /* elements: k-mers, edges */
+    uint32_t key_words;         /* u64 per key (edges for a graph) */
+    uint32_t asymmetric;        /* Graph::Header flag fAsymmetric */
+    uint64_t N_lo, N_hi;        /* the SparseArray's universe */
+    uint64_t D;
+    uint64_t resident_bytes;    /* the object's device allocation */
+} goss_gpu_object_desc;
+int goss_gpu_object_open(goss_gpu_object** out, int device, void* stream, int kind, const char* base,
+                         const goss_gpu_named_file* files, uint32_t nfiles);
+int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* ctx);
+void goss_gpu_object_close(goss_gpu_object* obj);
+const char* goss_gpu_object_last_error(const goss_gpu_object* obj);
+int goss_gpu_object_info(const goss_gpu_object* obj, goss_gpu_object_desc* out);
+int goss_gpu_object_rank(goss_gpu_object* obj, const void* d_keys, uint64_t n, uint32_t flags, uint64_t* d_rank,
+                         uint8_t* d_present);
+int goss_gpu_object_select(goss_gpu_object* obj, const uint64_t* d_ranks, uint64_t n, void* d_keys);
+int goss_gpu_object_multiplicity(goss_gpu_object* obj, const uint64_t* d_ranks, uint64_t n, uint32_t* d_counts);
+int goss_gpu_object_lookup(goss_gpu_object* obj, const void* d_keys, uint64_t n, uint32_t flags, uint32_t* d_counts);
+int goss_gpu_object_node_ranks(goss_gpu_object* obj, const void* d_nodes, uint64_t n, uint32_t flags, uint64_t* d_begin,
+                               uint64_t* d_end);
+
 #ifdef __cplusplus
 }
 #endif

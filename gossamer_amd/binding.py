@@ -32,6 +32,7 @@ SYMBOLS = [
     "goss_gpu_object_open", "goss_gpu_object_open_emitted", "goss_gpu_object_close", "goss_gpu_object_last_error",
     "goss_gpu_object_info", "goss_gpu_object_rank", "goss_gpu_object_select", "goss_gpu_object_multiplicity",
     "goss_gpu_object_lookup", "goss_gpu_object_node_ranks",
+    "goss_gpu_prune_tips",
 ]
 
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
@@ -44,6 +45,10 @@ def record_bytes(k, mode=0):
 
 
 RELEASE_FN = C.CFUNCTYPE(None, C.c_void_p)
+
+# goss_gpu_tips_report, in the order of its fields
+TIPS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "tips", "zapped", "too_long", "both_joined", "isolated",
+                      "outweighed", "joined_at_begin", "joined_at_end")
 
 
 def pack_bases(text):
@@ -567,6 +572,18 @@ class Context:
         self._check(self._L.goss_gpu_lint(self._h, 1 if asymmetric else 0, C.byref(rep)))
         return {"missing_rc": rep.missing_rc, "count_mismatch": rep.count_mismatch, "zero_count": rep.zero_count,
                 "order_violation": rep.order_violation}
+
+    def prune_tips(self, iterations=1):
+        """Between finish and emit, graph mode: `iterations` rounds of prune-tips on the device (goss_gpu_prune_tips).
+        The context's result becomes the pruned graph; returns one report dict per iteration."""
+        class TipsReport(C.Structure):
+            _fields_ = [(name, C.c_uint64) for name in TIPS_REPORT_FIELDS]
+        reps = (TipsReport * max(1, iterations))()
+        self._L.goss_gpu_prune_tips.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(TipsReport)]
+        self._check(self._L.goss_gpu_prune_tips(self._h, iterations, reps))
+        if iterations and getattr(self, "counts", None) is not None:
+            self.counts.distinct = int(reps[iterations - 1].edges_after)       # what result() copies
+        return [{name: int(getattr(reps[i], name)) for name in TIPS_REPORT_FIELDS} for i in range(iterations)]
 
     def check_index(self, files, base=""):
         """goss_gpu_check_index on a SparseArray given as {suffix: bytes} (files[base + ".header"]

@@ -225,6 +225,8 @@ struct goss_gpu_ctx {
     void* res_keys = nullptr;
     uint32_t* res_counts = nullptr;
     uint64_t M = 0;
+    void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
+    uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -350,6 +352,7 @@ bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
     };
     for (auto& r : c->runs) { rebase(r.keys); rebase(r.counts); }
     rebase(c->res_keys); rebase(c->res_counts);
+    rebase(c->tips_keys); rebase(c->tips_counts);
     for (auto& f : c->files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
     (void)hipFree(a.base);
     a.base = nb; a.hi = target - top; a.size = target;
@@ -5038,6 +5041,7 @@ int goss_gpu_reset(goss_gpu_ctx* c)
         c->finished = c->emitted = false;
         c->broken = false;
         c->res_keys = nullptr; c->res_counts = nullptr; c->M = 0;
+        c->tips_keys = nullptr; c->tips_counts = nullptr;
         c->arena.lo = 0; c->arena.hi = c->arena.size;
         if (c->copy_stream) HIP_TRY(hipStreamSynchronize(c->copy_stream));
         c->stage_cur = 0; c->stage = c->stage_buf[0]; c->stage_fill = 0;          // (the staging buffers stay)
@@ -5650,6 +5654,149 @@ int goss_gpu_lint(goss_gpu_ctx* c, int asymmetric, goss_gpu_lint_report* out)
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
         if (out->nexamples > 32) out->nexamples = 32;
+    });
+}
+
+extern "C++" {
+// Temporaries of one call, given back on every way out (an exception included).
+struct ArenaScope {
+    Arena& a;
+    uint64_t mark;
+    explicit ArenaScope(Arena& arena) : a(arena), mark(arena.mark()) {}
+    ~ArenaScope() { a.release(mark); }
+    ArenaScope(const ArenaScope&) = delete;
+    ArenaScope& operator=(const ArenaScope&) = delete;
+};
+
+// Bits of the link pass's bucket table for n edges of len bases: about one edge per bucket, at most 2^26 entries
+// (256 MB).  GOSS_GPU_TIPS_BUCKET_BITS overrides it (0 = plain binary search; the probe's A/B).
+static uint32_t tips_bucket_bits(uint64_t n, uint32_t len)
+{
+    uint32_t bits = 0;
+    while (bits < 26u && (2ULL << bits) <= n) ++bits;
+    if (const char* e = std::getenv("GOSS_GPU_TIPS_BUCKET_BITS")) bits = (uint32_t)std::min<long>(26, std::max<long>(0, std::atol(e)));
+    return std::min(bits, 2u * len);
+}
+
+// One iteration of prune-tips over the result (GossCmdPruneTips.cc:279-319).  Nothing of the context changes
+// before the survivors are complete: a failure leaves the result as it was.
+template <class K>
+static void prune_tips_once(goss_gpu_ctx* c, goss_gpu_tips_report* out)
+{
+    static_assert(sizeof(goss_gpu_tips_report) == 11 * 8 && sizeof(TipsReport) == 13 * 8, "tips report layout");
+    goss_gpu_tips_report rep{};
+    const uint64_t n64 = c->M;
+    rep.edges_before = rep.edges_after = n64;
+    if (out) *out = rep;
+    if (n64 == 0) return;
+    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "prune_tips: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
+    const uint32_t n = (uint32_t)n64;
+    const uint32_t bits = tips_bucket_bits(n, c->len);
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    const uint64_t zap_words = ntiles * (kRedTile / 32), cand_words = (n64 + 63) / 64;
+    {
+        // rcr + nxt + info + the two bitmaps + the table, and the survivors once more while they are compacted
+        const uint64_t need = n64 * 9 + zap_words * 4 + cand_words * 8 + (bits ? ((1ULL << bits) + 1) * 4 : 0)
+                              + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);       // (no temporary is live between two entry points)
+    }
+    ArenaScope scope(c->arena);
+    const K* keys = (const K*)c->res_keys;
+    const uint32_t* counts = c->res_counts;
+    uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
+    uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
+    uint8_t* info = (uint8_t*)c->arena.temp(n64);
+    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
+    uint64_t* cand = (uint64_t*)c->arena.temp(cand_words * 8);
+    uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
+    TipsReport* d_rep = (TipsReport*)c->arena.temp(sizeof(TipsReport));
+    TipsReport* h = (TipsReport*)c->h_pinned;
+    static_assert(sizeof(TipsReport) <= 256, "pinned scratch");
+
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(TipsReport), c->stream));
+    HIP_TRY(hipMemsetAsync(&d_rep->missing_rc, 0xFF, 8, c->stream));
+    HIP_TRY(hipMemsetAsync(zap, 0, zap_words * 4, c->stream));
+    const dim3 grid(grid_for(n64, kTB)), block(kTB);
+    if (bits)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
+                       (const uint32_t*)table, rcr, nxt, info, d_rep);
+    const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kTipsGridBlocks));
+    hipLaunchKernelGGL(tips_flag_kernel, few, block, 0, c->stream, (const uint32_t*)rcr, (const uint8_t*)info, n, cand, d_rep);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    if (h->missing_rc != ~0ULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "prune_tips: edge " + std::to_string(h->missing_rc) +
+                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
+    const uint64_t ncand = h->candidates;
+    rep.candidates = ncand;
+    if (ncand == 0) { if (out) *out = rep; return; }
+
+    uint32_t* list = (uint32_t*)c->arena.temp(ncand * 4);
+    HIP_TRY(hipMemsetAsync(list, 0xFF, ncand * 4, c->stream));
+    const uint64_t words_per_block = (cand_words + kTipsGridBlocks - 1) / kTipsGridBlocks;
+    hipLaunchKernelGGL(tips_gather_kernel, dim3(grid_for(cand_words, (uint32_t)std::max<uint64_t>(words_per_block, 1))), block, 0, c->stream,
+                       (const uint64_t*)cand, cand_words, words_per_block, list, ncand, d_rep);
+    hipLaunchKernelGGL(tips_walk_kernel, dim3(grid_for(ncand, kTB)), block, 0, c->stream, (const uint32_t*)list, ncand, n, c->k,
+                       (const uint32_t*)rcr, (const uint32_t*)nxt, (const uint8_t*)info, counts, zap, d_rep);
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), block, 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
+    HIP_TRY(hipMemsetAsync(tile_counts + ntiles, 0, 8, c->stream));
+    exclusive_scan_u64(c, tile_counts, ntiles + 1);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
+    uint64_t* hm = (uint64_t*)((uint8_t*)c->h_pinned + 128);
+    HIP_TRY(hipMemcpyAsync(hm, tile_counts + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    rep.tips = h->tips; rep.zapped = h->zapped;
+    rep.too_long = h->too_long; rep.both_joined = h->both_joined; rep.isolated = h->isolated; rep.outweighed = h->outweighed;
+    rep.joined_at_begin = h->joined_at_begin; rep.joined_at_end = h->joined_at_end;
+    const uint64_t m = hm[0];
+    rep.edges_after = m;
+    if (m != n64)
+    {
+        const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
+        const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
+        // a result this entry point allocated is compacted beside itself and copied back (five iterations take the
+        // permanent room of one); anybody else's arrays (a run, select_counts) are left alone
+        K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
+        uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), block, 0, c->stream, keys, counts, n64,
+                           (const uint32_t*)zap, (const uint64_t*)tile_counts, okeys, ocounts);
+        if (own)
+        {
+            if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+            if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
+        c->M = m;
+    }
+    if (out) *out = rep;
+}
+}  // extern "C++"
+
+int goss_gpu_prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_report* reports)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "prune_tips works on a graph"; return GOSS_ERR_STATE; }
+    if (!c->finished || c->emitted) { c->last_error = "prune_tips belongs between finish and emit"; return GOSS_ERR_STATE; }
+    if (reports && iterations) std::memset(reports, 0, sizeof(goss_gpu_tips_report) * (size_t)iterations);
+    if (!c->res_big.empty())
+    {
+        c->last_error = "prune_tips: the graph has multiplicities of 2^32 - 1 or more";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    return guarded(c, [&]() {
+        for (uint32_t it = 0; it < iterations; ++it)
+        {
+            PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+            goss_gpu_tips_report* r = reports ? reports + it : nullptr;
+            if (c->words == 1) prune_tips_once<Key1>(c, r); else prune_tips_once<Key2>(c, r);
+            t.stop();
+        }
     });
 }
 

@@ -20,3 +20,4 @@
 #include "kernels_merge.hpp"
 #include "kernels_emit.hpp"
 #include "kernels_query.hpp"
+#include "kernels_tips.hpp"

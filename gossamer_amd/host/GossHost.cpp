@@ -1922,7 +1922,9 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  merge-graphs     create a new graph by merging zero or more existing graphs\n"
               << "  merge-kmer-sets  create a new graph by merging zero or more existing graphs\n"
               << "  subtract-kmer-set  subtract the second k-mer set from the first\n"
-              << "  graph-to-kmer-set  generate a graph's k-mer set\n";
+              << "  graph-to-kmer-set  generate a graph's k-mer set\n"
+              << "  trim-graph       create a new graph by trimming low frequency edges\n"
+              << "  prune-tips       create a new graph by removing low frequency tips\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -1951,7 +1953,8 @@ int gossMain(int argc, char* argv[])
         const bool isToKmerSet = cmdName == "graph-to-kmer-set";
         const bool isDump = cmdName == "dump-kmer-set" || cmdName == "dump-graph";
         const bool isRestore = cmdName == "restore-graph", isLint = cmdName == "lint-graph";
-        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet)
+        const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
+        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune)
         {
             // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
             // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
@@ -1959,7 +1962,16 @@ int gossMain(int argc, char* argv[])
             // GossCmdFactoryIntersectKmerSets::create (GossCmdIntersectKmerSets.cc:131-150),
             // GossCmdFactorySubtractKmerSet::create (GossCmdSubtractKmerSet.cc:88-113),
             // GossCmdFactoryMergeAndAnnotateKmerSets::create (GossCmdMergeAndAnnotateKmerSets.cc:209-224),
-            // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378)
+            // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378),
+            // GossCmdFactoryTrimGraph::create (GossCmdTrimGraph.cc:130-172), GossCmdFactoryPruneTips::create
+            // (GossCmdPruneTips.cc:347-373)
+            static const OptDef kTrimPrune[] = {
+                {"cutoff", "C", kU64, "coverage cutoff"},
+                {"estimate-only", "", kFlag, "only estimate the coverage cutoff (trim-graph)"},
+                {"scale-cutoff-by-k", "", kU64, "scale the coverage cutoff by k-mer size"},
+                {"relative-cutoff", "", kString, "relative coverage cutoff"},
+                {"iterate", "", kU64, "number of passes to perform"},
+            };
             static const OptDef kMerge[] = {
                 {"graph-in", "G", kStrings, "name of the input graph object"},
                 {"graphs-in", "", kStrings, "read graph names (one per line) from the given file."},
@@ -1972,6 +1984,7 @@ int gossMain(int argc, char* argv[])
             OptTable t;
             for (auto& d : kGlobal) t.defs.push_back(d);
             for (auto& d : kMerge) t.defs.push_back(d);
+            if (isTrim || isPrune) for (auto& d : kTrimPrune) t.defs.push_back(d);
             for (auto& d : kGpuSpecific) t.defs.push_back(d);
             Parsed opts; std::string bad;
             parseArgs(argc, argv, 2, t, opts, bad);
@@ -1994,6 +2007,8 @@ int gossMain(int argc, char* argv[])
             uint64_t maxMerge = 8;
             std::string outName;
             std::string textName = "-";
+            uint64_t cutoff = 0, iterations = 1;
+            std::string notOffered;                 // a part of trim-graph / prune-tips that this build refuses
             if (isDump || isLint)
             {
                 // getRepeatingOnce("graph-in") (GossOptionChecker.hh:235-254)
@@ -2031,6 +2046,35 @@ int gossMain(int argc, char* argv[])
                 if (!opts.count("graph-out")) { chk.errors += "mandatory option graph-out was not given.\n"; chk.suggestUsage = true; }
                 else outName = opts.str("graph-out");
             }
+            else if (isTrim || isPrune)
+            {
+                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+                else if (opts.strs("graph-in").size() != 1)
+                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+                else ins = opts.strs("graph-in");
+                chk.mandatoryOut("graph-out", outName);
+                if (isTrim)
+                {
+                    const bool inferCutoff = !chk.optionalU64("cutoff", cutoff);
+                    if (opts.count("estimate-only") && !inferCutoff)
+                        throw Error::Usage("cannot estimate cutoff unless it is also being inferred");
+                    if (inferCutoff && opts.count("scale-cutoff-by-k")) throw Error::Usage("cannot scale an inferred cutoff");
+                    // the inferred cutoff (EstimateGraphStatistics, a Levenberg-Marquardt fit of the multiplicity histogram)
+                    // and what hangs on it are not part of this build
+                    if (inferCutoff || opts.count("scale-cutoff-by-k"))
+                        notOffered = ("not implemented: give -C (the cutoff is not inferred by this build; --estimate-only and "
+                                           "--scale-cutoff-by-k are not offered)\n");
+                }
+                else
+                {
+                    // the reference reads both optionals whether given or not (GossCmdPruneTips.cc:79-80) and compares
+                    // the count with the relative cutoff (:172): defined only when both are given -- neither is offered
+                    if (opts.count("cutoff") || opts.count("relative-cutoff"))
+                        notOffered = ("not implemented: --cutoff and --relative-cutoff (the reference reads them unset "
+                                           "unless both are given, so their behaviour is undefined)\n");
+                    chk.optionalU64("iterate", iterations);
+                }
+            }
             else if (isAnnotate)
             {
                 if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
@@ -2052,6 +2096,7 @@ int gossMain(int argc, char* argv[])
             }
             if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
             chk.throwIfNecessary();
+            if (!notOffered.empty()) throw Error::Usage(notOffered);
             GossCmdContext cxt{*logger, cmdName};
             uint64_t dev = 0, budgetGb = 0;
             if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
@@ -2068,6 +2113,8 @@ int gossMain(int argc, char* argv[])
                 else if (isRestore) { GossCmdRestoreGraph cmd(textName, outName); cmd(cxt); }
                 else if (isLint) { GossCmdLintGraph cmd(ins[0], opts.count("dump-properties") != 0); cmd(cxt); }
                 else if (isToKmerSet) { GossCmdGraphToKmerSet cmd(ins[0], outName); cmd(cxt); }
+                else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
+                else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
                 else { GossCmdMergeAndAnnotateKmerSets cmd(ins[0], ins[1], outName); cmd(cxt); }
             }
             catch (Error& e) { e.cmd = cmdName; throw; }

@@ -255,6 +255,24 @@ private:
     const std::string mIn; const bool mDumpProperties; uint64_t mProblems = 0;
 };
 
+// GossCmdTrimGraph (GossCmdTrimGraph.{hh,cc}) with an explicit cutoff: the edges of multiplicity > cutoff.
+class GossCmdTrimGraph {
+public:
+    GossCmdTrimGraph(const std::string& pIn, const std::string& pOut, uint64_t pCutoff) : mIn(pIn), mOut(pOut), mCutoff(pCutoff) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const uint64_t mCutoff;
+};
+
+// GossCmdPruneTips (GossCmdPruneTips.{hh,cc}) without its two cutoffs: pIterations rounds of tip removal.
+class GossCmdPruneTips {
+public:
+    GossCmdPruneTips(const std::string& pIn, const std::string& pOut, uint64_t pIterations) : mIn(pIn), mOut(pOut), mIterations(pIterations) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const uint64_t mIterations;
+};
+
 }  // namespace gosshost
 struct goss_gpu_ctx;
 namespace gosshost {

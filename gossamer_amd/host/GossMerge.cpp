@@ -895,6 +895,60 @@ void GossCmdLintGraph::operator()(const GossCmdContext& pCxt)
                      + num(rep.order_violation) + " out of order); the first " + num(rep.nexamples) + " found are shown");
 }
 
+// GossCmdTrimGraph::operator() (GossCmdTrimGraph.cc:31-127) with the cutoff given (-C): the edges whose multiplicity
+// exceeds it, built with their exact number as the estimate.  (The inferred cutoff, EstimateGraphStatistics, is not
+// part of this build: the factory refuses the command without -C.)
+void GossCmdTrimGraph::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    uint64_t z = 0, n = 0;
+    g.check(goss_gpu_result(g.h, nullptr, nullptr, &z), "counting");
+    // multiplicities are u32: a cutoff of 2^32 - 1 or more keeps nothing
+    if (mCutoff >= 0xFFFFFFFFULL) g.check(goss_gpu_select_counts(g.h, 0, 0), "trimming");
+    else g.check(goss_gpu_select_counts(g.h, (uint32_t)mCutoff + 1, 0xFFFFFFFFu), "trimming");
+    g.check(goss_gpu_result(g.h, nullptr, nullptr, &n), "counting");
+    log(info, "scanning to trim edges");
+    log(info, mIn + " had " + num(z));
+    log(info, mOut + " will have " + num(n));
+    g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, elapsed(t0));
+}
+
+// GossCmdPruneTips::operator() (GossCmdPruneTips.cc:261-344): the iterations run on the device
+// (goss_gpu_prune_tips), the survivors are built with their exact number as the estimate.
+void GossCmdPruneTips::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    uint64_t tc = 0, zc = 0;
+    for (uint64_t it = 0; it < mIterations; ++it)
+    {
+        log(info, "locating tips (iteration " + num(it + 1) + ")");
+        goss_gpu_tips_report rep;
+        g.check(goss_gpu_prune_tips(g.h, 1, &rep), "pruning tips");
+        log(info, "number of tips removed: " + num(rep.tips));
+        log(info, "number of edges removed: " + num(rep.zapped));
+        tc += rep.tips;
+        zc += rep.zapped;
+    }
+    log(info, "writing out graph.");
+    g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, elapsed(t0));
+    log(info, "total number of tips removed: " + num(tc));
+    log(info, "total number of edges removed: " + num(zc));
+}
+
 void GossCmdMergeKmerSets::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, false, mIns, mMaxMerge, mOut); }
 void GossCmdMergeGraphs::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, true, mIns, mMaxMerge, mOut); }
 

@@ -522,6 +522,42 @@ typedef struct {
 int goss_gpu_lint(goss_gpu_ctx* ctx, int asymmetric, goss_gpu_lint_report* out);
 
 /*
+ * Between finish and emit, graph mode: `iterations` rounds of prune-tips over the edge list held by
+ * the context (GossCmdPruneTips.cc:82-225,276-333; the walk is Graph::linearPath, Graph.tcc:19-46;
+ * the removal Graph::remove).  One round, decided against the graph as it stands at its start: for
+ * every edge `beg` whose from-node has no incoming edge, follow the path while the node reached has
+ * exactly one edge in and one out; a path of at most 2K edges that is joined to the rest of the graph
+ * at exactly one end, and whose joining edge no edge out of the attaching node undercuts in
+ * multiplicity, is a tip: its edges and their reverse complements are removed together after all
+ * decisions are taken.  Where the reference answers each degree with rank/select calls on the
+ * Elias-Fano index behind one mutex, a link pass here stores, per edge, the rank of its reverse
+ * complement, the rank of the first edge out of its to-node and the degrees (9 bytes per edge), and
+ * one thread per candidate walks those arrays.
+ *
+ * Afterwards the context's result is the pruned graph: goss_gpu_result, goss_gpu_emit (the exact
+ * surviving count is the size estimate, as Graph::Builder(k, out, fac, g.count()) has it),
+ * goss_gpu_emit_dump, goss_gpu_lint and goss_gpu_object_open_emitted work on it unchanged.
+ * reports: one entry per iteration, or NULL.  iterations == 0 does nothing.
+ *
+ * GOSS_ERR_STATE: a k-mer-set context, before finish, after emit.  GOSS_ERR_INVALID_ARG: an edge
+ * without its reverse complement in the list (last_error names its index); more than 2^32 - 2 edges.
+ * GOSS_ERR_OOM: the working arrays do not fit the context's arena.  In each case the result is what
+ * it was before the failing iteration.  The --cutoff / --relative-cutoff options of the reference
+ * read unset optionals unless both are given (GossCmdPruneTips.cc:79-80,172) and are not offered.
+ *
+ * trim-graph -C c (GossCmdTrimGraph.cc:97-124) needs no entry point of its own:
+ * goss_gpu_select_counts(ctx, c + 1, UINT32_MAX).
+ */
+typedef struct {
+    uint64_t edges_before, edges_after;            /* distinct edges; before - after = really removed */
+    uint64_t candidates;                           /* edges with in(from) == 0 */
+    uint64_t tips, zapped;                         /* as the reference logs them: zapped = sum of 2 * path length */
+    uint64_t too_long, both_joined, isolated, outweighed;   /* why the other candidates stayed */
+    uint64_t joined_at_begin, joined_at_end;       /* tips by kind; sum = tips */
+} goss_gpu_tips_report;
+int goss_gpu_prune_tips(goss_gpu_ctx* ctx, uint32_t iterations, goss_gpu_tips_report* reports);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "goss_gpu_object_info", "goss_gpu_object_rank", "goss_gpu_object_select", "goss_gpu_object_multiplicity",
     "goss_gpu_object_lookup", "goss_gpu_object_node_ranks",
     "goss_gpu_prune_tips",
+    "goss_gpu_segments_build", "goss_gpu_segments_table", "goss_gpu_segments_text", "goss_gpu_segments_release",
 ]
 
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
@@ -49,6 +50,37 @@ RELEASE_FN = C.CFUNCTYPE(None, C.c_void_p)
 # goss_gpu_tips_report, in the order of its fields
 TIPS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "tips", "zapped", "too_long", "both_joined", "isolated",
                       "outweighed", "joined_at_begin", "joined_at_end")
+
+
+# goss_gpu_segments_info and goss_gpu_segment, in the order of their fields
+SEGMENTS_INFO_FIELDS = (("segments", C.c_uint64), ("text_bytes", C.c_uint64), ("paths", C.c_uint64), ("taken_paths", C.c_uint64),
+                        ("cycle_edges", C.c_uint64), ("longest_path", C.c_uint64), ("rounds", C.c_uint32),
+                        ("walk_steps", C.c_uint32), ("ms_link", C.c_float), ("ms_rank", C.c_float),
+                        ("ms_figures", C.c_float), ("ms_text", C.c_float))
+SEGMENT_DTYPE = [("s", "<u8"), ("s2", "<u8"), ("text_offset", "<u8"), ("text_bytes", "<u8"), ("len", "<u8"),
+                 ("first_rank", "<u4"), ("edges", "<u4"), ("min", "<u4"), ("max", "<u4"), ("flags", "<u4"), ("end_rank", "<u4")]
+SEGMENTS_NO_LINE_BREAKS = 1
+SEGMENT_INCLUDE_FIRST, SEGMENT_INCLUDE_LAST = 1, 2
+
+
+class SegmentsInfo(C.Structure):
+    _fields_ = list(SEGMENTS_INFO_FIELDS)
+
+
+def format_double(x):
+    """a double as a C++ ostream prints it by default (six significant digits, %g)"""
+    return "%g" % x
+
+
+def segment_stats(row, k):
+    """(L, min, max, mean, sd) of one row of the segment table as print-contigs prints them: L = edges + K, the mean
+    and the deviation from the 64-bit sums in doubles, in the reference's order of operations"""
+    import math
+    m = int(row["edges"])
+    a = float(int(row["s"])) / m
+    rad = float(int(row["s2"])) / m - a * a
+    sd = format_double(math.sqrt(rad)) if rad >= 0.0 else "-nan"
+    return m + k, int(row["min"]), int(row["max"]), format_double(a), sd
 
 
 def pack_bases(text):
@@ -584,6 +616,62 @@ class Context:
         if iterations and getattr(self, "counts", None) is not None:
             self.counts.distinct = int(reps[iterations - 1].edges_after)       # what result() copies
         return [{name: int(getattr(reps[i], name)) for name in TIPS_REPORT_FIELDS} for i in range(iterations)]
+
+    def segments_build(self, min_length=0, min_coverage=0, line_breaks=True):
+        """Between finish and emit, graph mode: build the linear segments on the device (goss_gpu_segments_build) and
+        hold them; returns the info dict.  segments_table / segments_text read them, segments_release gives them back."""
+        inf = SegmentsInfo()
+        self._L.goss_gpu_segments_build.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SegmentsInfo)]
+        self._check(self._L.goss_gpu_segments_build(self._h, min_length, min_coverage,
+                                                    0 if line_breaks else SEGMENTS_NO_LINE_BREAKS, C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in SEGMENTS_INFO_FIELDS}
+
+    def segments_table(self, first, count):
+        import numpy as np
+        out = np.zeros(count, dtype=SEGMENT_DTYPE)
+        self._L.goss_gpu_segments_table.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_segments_table(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def segments_text(self, offset, nbytes):
+        buf = C.create_string_buffer(max(1, nbytes))
+        self._L.goss_gpu_segments_text.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p]
+        self._check(self._L.goss_gpu_segments_text(self._h, offset, nbytes, buf))
+        return buf.raw[:nbytes]
+
+    def segments_release(self):
+        self._L.goss_gpu_segments_release.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_segments_release(self._h))
+
+    def linear_segments(self, min_length=0, min_coverage=0, line_breaks=True):
+        """The linear segments of the graph, as `goss print-contigs` numbers them: (table, text, info).  table is a
+        numpy structured array (SEGMENT_DTYPE), one row per segment in printing order; text holds the bodies back to
+        back, row["text_offset"] / row["text_bytes"] say where.  The context's result is untouched."""
+        info = self.segments_build(min_length, min_coverage, line_breaks)
+        try:
+            table = self.segments_table(0, info["segments"])
+            text = self.segments_text(0, info["text_bytes"])
+        finally:
+            self.segments_release()
+        return table, text, info
+
+    def contigs(self, min_length=0, min_coverage=0, line_breaks=True, verbose_headers=False, sequence=True):
+        """Exactly the bytes `goss print-contigs` writes for the graph the context holds."""
+        table, text, _ = self.linear_segments(min_length, min_coverage, line_breaks)
+        out = []
+        if not sequence:
+            out.append(b"Number\tLength\tMinCov\tMaxCov\tMeanCov\tStdDevCov\n")
+        for no, row in enumerate(table, 1):
+            if not sequence:
+                out.append(("%d\t%d\t%d\t%d\t%s\t%s\n" % ((no,) + segment_stats(row, self.k))).encode())
+                continue
+            head = ">%d" % no
+            if verbose_headers:
+                head += " %d:%d:%d:%s:%s" % segment_stats(row, self.k)
+            out.append(head.encode() + b"\n")
+            o = int(row["text_offset"])
+            out.append(text[o:o + int(row["text_bytes"])])
+        return b"".join(out)
 
     def check_index(self, files, base=""):
         """goss_gpu_check_index on a SparseArray given as {suffix: bytes} (files[base + ".header"]

@@ -227,6 +227,13 @@ struct goss_gpu_ctx {
     uint64_t M = 0;
     void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
     uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
+    // goss_gpu_segments_build: the segment table and the text, permanent room above everything else, held until
+    // goss_gpu_segments_release or the next call that may allocate (guarded() gives it back first)
+    void* seg_recs = nullptr;
+    uint8_t* seg_text = nullptr;
+    uint64_t seg_count = 0, seg_text_bytes = 0, seg_lo = 0;
+    bool seg_live = false;
+    bool seg_hold = false;                // the entry point that runs now only reads: what is held stays
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -353,6 +360,7 @@ bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
     for (auto& r : c->runs) { rebase(r.keys); rebase(r.counts); }
     rebase(c->res_keys); rebase(c->res_counts);
     rebase(c->tips_keys); rebase(c->tips_counts);
+    rebase(c->seg_recs); rebase(c->seg_text);
     for (auto& f : c->files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
     (void)hipFree(a.base);
     a.base = nb; a.hi = target - top; a.size = target;
@@ -3522,6 +3530,10 @@ int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
         // poll of the host process): from here on an error is ours
         (void)hipGetLastError();
         if (c && wait_bg) wait_background_thread(c);
+        // segments held by goss_gpu_segments_build lie on top of the permanent room: whatever may allocate there, or
+        // change the result they were read from, gives them back first
+        if (c && c->seg_live && !c->seg_hold) { c->arena.lo = c->seg_lo; c->seg_live = false; }
+        if (c) c->seg_hold = false;
         f();
         // a refused kernel launch raises no exception by itself and leaves its outputs untouched:
         // no entry point returns success over one
@@ -4219,6 +4231,7 @@ int goss_gpu_result_copy(goss_gpu_ctx* c, uint64_t first, uint64_t n, uint64_t* 
     if (!c) return GOSS_ERR_INVALID_ARG;
     if (!c->finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
     if (first > c->M || n > c->M - first) return GOSS_ERR_INVALID_ARG;
+    c->seg_hold = true;
     return guarded(c, [&]() {
         const uint64_t ksz = c->words * 8;
         if (h_keys && n) HIP_TRY(hipMemcpyAsync(h_keys, (const uint8_t*)c->res_keys + first * ksz, n * ksz, hipMemcpyDeviceToHost, c->stream));
@@ -4969,6 +4982,7 @@ int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, 
     if (offset > f.size || n > f.size - offset) return GOSS_ERR_INVALID_ARG;
     if (n == 0) return GOSS_OK;
     if (!f.dev) { std::memcpy(dst, f.host.data() + offset, n); return GOSS_OK; }
+    c->seg_hold = true;
     return guarded(c, [&]() {
         HIP_TRY(hipMemcpyAsync(dst, f.dev + offset, n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4978,6 +4992,7 @@ int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, 
 int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 {
     if (!c || !out) return GOSS_ERR_INVALID_ARG;
+    c->seg_hold = true;
     int rc = guarded(c, [&]() { resolve_timing(c); });
     *out = c->timing;
     return rc;
@@ -4986,6 +5001,7 @@ int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 int goss_gpu_timing_reset(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
+    c->seg_hold = true;
     int rc = guarded(c, [&]() { resolve_timing(c); });
     c->timing = goss_gpu_timing{};
     return rc;
@@ -5042,6 +5058,7 @@ int goss_gpu_reset(goss_gpu_ctx* c)
         c->broken = false;
         c->res_keys = nullptr; c->res_counts = nullptr; c->M = 0;
         c->tips_keys = nullptr; c->tips_counts = nullptr;
+        c->seg_live = false; c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
         c->arena.lo = 0; c->arena.hi = c->arena.size;
         if (c->copy_stream) HIP_TRY(hipStreamSynchronize(c->copy_stream));
         c->stage_cur = 0; c->stage = c->stage_buf[0]; c->stage_fill = 0;          // (the staging buffers stay)
@@ -5640,6 +5657,7 @@ int goss_gpu_lint(goss_gpu_ctx* c, int asymmetric, goss_gpu_lint_report* out)
     if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "lint checks a graph"; return GOSS_ERR_STATE; }
     std::memset(out, 0, sizeof *out);
     if (c->M == 0) return GOSS_OK;
+    c->seg_hold = true;
     return guarded(c, [&]() {
         uint64_t mark = c->arena.mark();
         LintReport* rep = (LintReport*)c->arena.temp(sizeof(LintReport));
@@ -5798,6 +5816,242 @@ int goss_gpu_prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_repo
             t.stop();
         }
     });
+}
+
+extern "C++" {
+// Pointers the first ranking launch follows per lane before doubling takes over: kContigsWalkSteps, or
+// GOSS_GPU_CONTIGS_WALK=<steps> (1 = doubling alone; the probe's A/B).
+static uint32_t contigs_walk_steps()
+{
+    long v = kContigsWalkSteps;
+    if (const char* e = std::getenv("GOSS_GPU_CONTIGS_WALK")) v = std::atol(e);
+    return (uint32_t)std::min<long>(4096, std::max<long>(1, v));
+}
+
+struct EventPair {
+    hipEvent_t e[5] = {};
+    EventPair() { for (auto& x : e) HIP_TRY(hipEventCreate(&x)); }
+    ~EventPair() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// Linear segments of the result (GossCmdPrintContigs.cc:49-193).  Temporaries under an ArenaScope; the table and the
+// text are permanent room on top of everything else (c->seg_lo marks where it began).
+template <class K>
+static void segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
+{
+    static_assert(sizeof(goss_gpu_segment) == sizeof(SegRec) && sizeof(SegRec) == 64, "segment layout");
+    static_assert(sizeof(ContigsReport) <= 128, "pinned scratch");
+    goss_gpu_segments_info inf{};
+    const uint64_t n64 = c->M;
+    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = 0; c->seg_text_bytes = 0;
+    if (n64 == 0) { *out = inf; return; }
+    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "segments: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
+    const uint32_t n = (uint32_t)n64;
+    const uint32_t bits = tips_bucket_bits(n, c->len);
+    const uint32_t steps = contigs_walk_steps();
+    const uint32_t Kn = c->k;
+    const uint32_t line = (flags & GOSS_SEGMENTS_NO_LINE_BREAKS) ? 0u : 60u;
+    inf.walk_steps = steps;
+    {
+        // rcr, nxt, pred, two arrays of pairs, the scan (4 + 4 + 4 + 8 + 8 + 8), info, flag, st, the table; then a
+        // record per taken path and about half a byte of text per edge
+        const uint64_t need = n64 * 39 + (bits ? ((1ULL << bits) + 1) * 4 : 0) + n64 + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+        c->seg_lo = c->arena.lo;
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    const K* keys = (const K*)c->res_keys;
+    const uint32_t* counts = c->res_counts;
+    uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
+    uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
+    uint8_t* info = (uint8_t*)c->arena.temp(n64);
+    uint8_t* flag = (uint8_t*)c->arena.temp(n64);
+    uint8_t* st = (uint8_t*)c->arena.temp(n64);
+    uint32_t* pred = (uint32_t*)c->arena.temp(n64 * 4);
+    uint2* cur = (uint2*)c->arena.temp(n64 * 8);
+    uint2* oth = (uint2*)c->arena.temp(n64 * 8);
+    uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+    uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
+    ContigsReport* d_rep = (ContigsReport*)c->arena.temp(sizeof(ContigsReport));
+    TipsReport* d_tips = (TipsReport*)c->arena.temp(sizeof(TipsReport));
+    ContigsReport* h = (ContigsReport*)c->h_pinned;
+    uint64_t* hx = (uint64_t*)((uint8_t*)c->h_pinned + 128);
+
+    // ---- the link pass of prune-tips, as it is
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(ContigsReport), c->stream));
+    HIP_TRY(hipMemsetAsync(d_tips, 0, sizeof(TipsReport), c->stream));
+    HIP_TRY(hipMemsetAsync(&d_tips->missing_rc, 0xFF, 8, c->stream));
+    HIP_TRY(hipMemsetAsync(pred, 0, n64 * 4, c->stream));
+    const dim3 grid(grid_for(n64, kTB)), block(kTB);
+    const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kContigsGridBlocks));
+    if (bits)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
+                       (const uint32_t*)table, rcr, nxt, info, d_tips);
+    HIP_TRY(hipMemcpyAsync(hx, &d_tips->missing_rc, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    if (hx[0] != ~0ULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "segments: edge " + std::to_string(hx[0]) +
+                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
+
+    // ---- starts, predecessors, list ranking
+    hipLaunchKernelGGL(contigs_mark_kernel, grid, block, 0, c->stream, (const uint32_t*)rcr, (const uint32_t*)nxt,
+                       (const uint8_t*)info, n, flag, pred);
+    hipLaunchKernelGGL(contigs_walk_kernel, few, block, 0, c->stream, (const uint32_t*)pred, (const uint8_t*)flag, n, steps,
+                       cur, oth, st, d_rep);
+    uint32_t rounds = 1;
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    uint64_t open = h->open, resolved = 0;
+    while (open && rounds < 64)
+    {
+        hipLaunchKernelGGL(contigs_double_kernel, few, block, 0, c->stream, (const uint2*)cur, oth, (const uint8_t*)flag, st, n, d_rep);
+        std::swap(cur, oth);
+        ++rounds;
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        const uint64_t fresh = h->resolved - resolved;
+        resolved = h->resolved;
+        if (fresh == 0) break;                          // what is open now lies on cycles without a start
+        open -= fresh;
+    }
+    inf.rounds = rounds;
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+
+    // ---- ends, the rule per path, the layout of the taken paths
+    uint32_t* end_of = pred;                            // (the predecessors are no longer needed)
+    uint32_t* len_of = (uint32_t*)oth;                  // (nor the pairs of the round before the last)
+    uint32_t* ord = len_of + n64;
+    hipLaunchKernelGGL(contigs_ends_kernel, few, block, 0, c->stream, (const uint2*)cur, (const uint8_t*)flag, (const uint8_t*)st, n,
+                       end_of, len_of, d_rep);
+    hipLaunchKernelGGL(contigs_decide_kernel, few, block, 0, c->stream, flag, (const uint32_t*)rcr, (const uint32_t*)end_of,
+                       (const uint32_t*)len_of, n, sc, d_rep);
+    HIP_TRY(hipMemsetAsync(sc + n64, 0, 8, c->stream));
+    exclusive_scan_u64(c, sc, n64 + 1);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hx, sc + n64, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    inf.paths = h->paths; inf.taken_paths = h->taken; inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
+    const uint64_t npaths = hx[0] >> 32, nslots = hx[0] & 0xFFFFFFFFULL;
+    uint64_t nsegs = 0, total = 0;
+    SegRec* segs = nullptr;
+    uint8_t* text = nullptr;
+    if (npaths)
+    {
+        SegRec* recs = (SegRec*)c->arena.temp(npaths * sizeof(SegRec));
+        uint64_t* pass = (uint64_t*)c->arena.temp((npaths + 1) * 8);
+        uint64_t* bytes = (uint64_t*)c->arena.temp((npaths + 1) * 8);
+        hipLaunchKernelGGL(contigs_paths_kernel, grid, block, 0, c->stream, (const uint8_t*)flag, (const uint64_t*)sc,
+                           (const uint32_t*)end_of, (const uint32_t*)len_of, n, recs);
+        hipLaunchKernelGGL(contigs_order_kernel, grid, block, 0, c->stream, (const uint2*)cur, (const uint8_t*)flag, (const uint8_t*)st,
+                           (const uint64_t*)sc, n, ord);
+        hipLaunchKernelGGL(contigs_figures_kernel, dim3(grid_for(nslots, kTB * kContigsFigSteps)), block, 0, c->stream,
+                           (const uint32_t*)ord, (uint32_t)nslots, counts, (const uint2*)cur, (const uint64_t*)sc, recs);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_select_kernel<K>), dim3(grid_for(npaths, kTB)), block, 0, c->stream, keys,
+                           (const uint32_t*)rcr, (const uint8_t*)info, recs, npaths, Kn, min_length, min_coverage, line, pass, bytes);
+        HIP_TRY(hipMemsetAsync(pass + npaths, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(bytes + npaths, 0, 8, c->stream));
+        exclusive_scan_u64(c, pass, npaths + 1);
+        exclusive_scan_u64(c, bytes, npaths + 1);
+        HIP_TRY(hipMemcpyAsync(hx, pass + npaths, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hx + 1, bytes + npaths, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        nsegs = hx[0]; total = hx[1];
+        if (nsegs)
+        {
+            segs = (SegRec*)c->arena.perm(nsegs * sizeof(SegRec));
+            text = (uint8_t*)c->arena.perm(((total + 15) & ~15ULL) + 16);
+            uint32_t* base = (uint32_t*)c->arena.temp(nsegs * 4);
+            hipLaunchKernelGGL(contigs_compact_kernel, dim3(grid_for(npaths, kTB)), block, 0, c->stream, (const SegRec*)recs, npaths,
+                               (const uint64_t*)pass, (const uint64_t*)bytes, segs, base);
+            if (total)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_text_kernel<K>), dim3(grid_for(total, kTB * kContigsTextRun)), block, 0,
+                                   c->stream, keys, (const uint32_t*)ord, (const SegRec*)segs, (const uint32_t*)base, nsegs, total, Kn,
+                                   line, text);
+        }
+    }
+    else HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_figures, &inf.ms_text};
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    inf.segments = nsegs; inf.text_bytes = total;
+    c->seg_recs = segs; c->seg_text = text; c->seg_count = nsegs; c->seg_text_bytes = total;
+    *out = inf;
+}
+}  // extern "C++"
+
+int goss_gpu_segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
+{
+    if (!c || !out || (flags & ~(uint32_t)GOSS_SEGMENTS_NO_LINE_BREAKS)) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "segments are read from a graph"; return GOSS_ERR_STATE; }
+    if (!c->finished || c->emitted) { c->last_error = "segments belong between finish and emit"; return GOSS_ERR_STATE; }
+    if (!c->res_big.empty())
+    {
+        c->last_error = "segments: the graph has multiplicities of 2^32 - 1 or more";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    bool began = false;
+    int rc = guarded(c, [&]() {                          // (gives back what an earlier build holds)
+        c->seg_lo = c->arena.lo;
+        began = true;
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        if (c->words == 1) segments_build<Key1>(c, min_length, min_coverage, flags, out);
+        else segments_build<Key2>(c, min_length, min_coverage, flags, out);
+        t.stop();
+        c->seg_live = true;
+    });
+    if (rc != GOSS_OK)
+    {
+        // nothing is held after a failure; the result was only read
+        if (began) c->arena.lo = c->seg_lo;
+        c->seg_live = false; c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+        std::memset(out, 0, sizeof *out);
+    }
+    return rc;
+}
+
+int goss_gpu_segments_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, goss_gpu_segment* out)
+{
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (!c->seg_live) { c->last_error = "segments_table needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
+    if (first > c->seg_count || count > c->seg_count - first) { c->last_error = "segments_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    c->seg_hold = true;
+    return guarded(c, [&]() {
+        if (count) HIP_TRY(hipMemcpyAsync(out, (const SegRec*)c->seg_recs + first, count * sizeof(SegRec), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+int goss_gpu_segments_text(goss_gpu_ctx* c, uint64_t text_offset, uint64_t bytes, char* dst)
+{
+    if (!c || (bytes && !dst)) return GOSS_ERR_INVALID_ARG;
+    if (!c->seg_live) { c->last_error = "segments_text needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
+    if (text_offset > c->seg_text_bytes || bytes > c->seg_text_bytes - text_offset) { c->last_error = "segments_text: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    c->seg_hold = true;
+    return guarded(c, [&]() {
+        if (bytes) HIP_TRY(hipMemcpyAsync(dst, c->seg_text + text_offset, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+int goss_gpu_segments_release(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->seg_live) { c->arena.lo = c->seg_lo; c->seg_live = false; }
+    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+    return GOSS_OK;
 }
 
 int goss_gpu_emit_count_bits(goss_gpu_ctx* c, uint32_t mask, const char* suffix)

@@ -21,3 +21,4 @@
 #include "kernels_emit.hpp"
 #include "kernels_query.hpp"
 #include "kernels_tips.hpp"
+#include "kernels_contigs.hpp"

@@ -1924,7 +1924,8 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  subtract-kmer-set  subtract the second k-mer set from the first\n"
               << "  graph-to-kmer-set  generate a graph's k-mer set\n"
               << "  trim-graph       create a new graph by trimming low frequency edges\n"
-              << "  prune-tips       create a new graph by removing low frequency tips\n";
+              << "  prune-tips       create a new graph by removing low frequency tips\n"
+              << "  print-contigs    print all the non-branching paths in the given assembly graph\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -1954,7 +1955,8 @@ int gossMain(int argc, char* argv[])
         const bool isDump = cmdName == "dump-kmer-set" || cmdName == "dump-graph";
         const bool isRestore = cmdName == "restore-graph", isLint = cmdName == "lint-graph";
         const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
-        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune)
+        const bool isContigs = cmdName == "print-contigs";
+        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs)
         {
             // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
             // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
@@ -1972,6 +1974,19 @@ int gossMain(int argc, char* argv[])
                 {"relative-cutoff", "", kString, "relative coverage cutoff"},
                 {"iterate", "", kU64, "number of passes to perform"},
             };
+            // GossCmdFactoryPrintContigs (GossCmdPrintContigs.cc:226-289).  The reference registers
+            // include-entailed-contigs and reads print-entailed-contigs (:260, :285); both belong to the supergraph form
+            static const OptDef kContigs[] = {
+                {"min-length", "", kU64, "minimum length of a printed sequence"},
+                {"min-coverage", "", kU64, "minimum coverage"},
+                {"no-sequence", "", kFlag, "print a table of the segments' figures instead of their sequence"},
+                {"print-linear-segments", "", kFlag, "Only print individual linear paths, even if a supergraph is present."},
+                {"verbose-headers", "", kFlag, "Print additional information in contig headers"},
+                {"no-line-breaks", "", kFlag, "Print contig sequences without line breaks"},
+                {"include-entailed-contigs", "", kFlag, "not offered (supergraph contigs)"},
+                {"print-entailed-contigs", "", kFlag, "not offered (supergraph contigs)"},
+                {"print-rcs", "", kFlag, "Include each sequence's reverse complement."},
+            };
             static const OptDef kMerge[] = {
                 {"graph-in", "G", kStrings, "name of the input graph object"},
                 {"graphs-in", "", kStrings, "read graph names (one per line) from the given file."},
@@ -1985,6 +2000,7 @@ int gossMain(int argc, char* argv[])
             for (auto& d : kGlobal) t.defs.push_back(d);
             for (auto& d : kMerge) t.defs.push_back(d);
             if (isTrim || isPrune) for (auto& d : kTrimPrune) t.defs.push_back(d);
+            if (isContigs) for (auto& d : kContigs) t.defs.push_back(d);
             for (auto& d : kGpuSpecific) t.defs.push_back(d);
             Parsed opts; std::string bad;
             parseArgs(argc, argv, 2, t, opts, bad);
@@ -2009,14 +2025,25 @@ int gossMain(int argc, char* argv[])
             std::string textName = "-";
             uint64_t cutoff = 0, iterations = 1;
             std::string notOffered;                 // a part of trim-graph / prune-tips that this build refuses
-            if (isDump || isLint)
+            uint64_t minLength = 0, minCoverage = 0;
+            if (isDump || isLint || isContigs)
             {
                 // getRepeatingOnce("graph-in") (GossOptionChecker.hh:235-254)
                 if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
                 else if (opts.strs("graph-in").size() != 1)
                 { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
                 else ins = opts.strs("graph-in");
-                if (isDump && opts.count("output-file"))
+                if (isContigs)
+                {
+                    uint64_t ignoredThreads = 1;
+                    chk.optionalU64("num-threads", ignoredThreads);
+                    chk.optionalU64("min-coverage", minCoverage);
+                    chk.optionalU64("min-length", minLength);
+                    if (opts.count("include-entailed-contigs") || opts.count("print-entailed-contigs"))
+                        notOffered = ("not implemented: --print-entailed-contigs / --include-entailed-contigs (they belong to "
+                                      "supergraph contigs; this build prints linear segments only)\n");
+                }
+                if ((isDump || isContigs) && opts.count("output-file"))
                 {
                     textName = opts.str("output-file");
                     if (textName != "-")
@@ -2097,6 +2124,14 @@ int gossMain(int argc, char* argv[])
             if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
             chk.throwIfNecessary();
             if (!notOffered.empty()) throw Error::Usage(notOffered);
+            if (isContigs && !opts.count("print-linear-segments") && ::access((ins[0] + "-supergraph.header").c_str(), F_OK) == 0)
+            {
+                // the reference would print the supergraph's contigs here (GossCmdPrintContigs.cc:208-221)
+                Error e = Error::General("\t'" + ins[0] + "' has a supergraph: supergraph contigs are not implemented by this build; "
+                                         "give --print-linear-segments to print the graph's linear segments\n");
+                e.cmd = cmdName;
+                throw e;
+            }
             GossCmdContext cxt{*logger, cmdName};
             uint64_t dev = 0, budgetGb = 0;
             if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
@@ -2115,6 +2150,12 @@ int gossMain(int argc, char* argv[])
                 else if (isToKmerSet) { GossCmdGraphToKmerSet cmd(ins[0], outName); cmd(cxt); }
                 else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
                 else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
+                else if (isContigs)
+                {
+                    GossCmdPrintContigs cmd(ins[0], minCoverage, minLength, opts.count("no-sequence") != 0, opts.count("verbose-headers") != 0,
+                                            opts.count("no-line-breaks") != 0, textName);
+                    cmd(cxt);
+                }
                 else { GossCmdMergeAndAnnotateKmerSets cmd(ins[0], ins[1], outName); cmd(cxt); }
             }
             catch (Error& e) { e.cmd = cmdName; throw; }

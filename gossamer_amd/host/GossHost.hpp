@@ -273,6 +273,19 @@ private:
     const std::string mIn, mOut; const uint64_t mIterations;
 };
 
+// GossCmdPrintContigs (GossCmdPrintContigs.{hh,cc}) in its linear-segments form: the non-branching paths of a graph
+// as FASTA (or, with pOmitSequence, as a table of their figures).  Supergraph contigs are not part of this build.
+class GossCmdPrintContigs {
+public:
+    GossCmdPrintContigs(const std::string& pIn, uint64_t pC, uint64_t pL, bool pOmitSequence, bool pVerboseHeaders,
+                        bool pNoLineBreaks, const std::string& pOut)
+        : mIn(pIn), mOut(pOut), mC(pC), mL(pL), mOmitSequence(pOmitSequence), mVerboseHeaders(pVerboseHeaders),
+          mNoLineBreaks(pNoLineBreaks) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const uint64_t mC, mL; const bool mOmitSequence, mVerboseHeaders, mNoLineBreaks;
+};
+
 }  // namespace gosshost
 struct goss_gpu_ctx;
 namespace gosshost {

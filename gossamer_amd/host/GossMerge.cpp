@@ -14,6 +14,7 @@
 #include <cctype>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -947,6 +948,82 @@ void GossCmdPruneTips::operator()(const GossCmdContext& pCxt)
     log(info, elapsed(t0));
     log(info, "total number of tips removed: " + num(tc));
     log(info, "total number of edges removed: " + num(zc));
+}
+
+// GossCmdPrintContigs::operator() -> printLinearSegments (GossCmdPrintContigs.cc:49-193).  The device finds the
+// segments, their figures and the bodies (goss_gpu_segments_build); the header lines are formatted here, doubles
+// through the stream as the reference prints them.  The table is read 64 K segments at a time and the text in pieces
+// of at most 16 MB, so the host never holds the whole output.
+void GossCmdPrintContigs::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    goss_gpu_segments_info inf;
+    g.check(goss_gpu_segments_build(g.h, mL, mC, mNoLineBreaks ? GOSS_SEGMENTS_NO_LINE_BREAKS : 0u, &inf), "finding the linear segments");
+    log(info, "linear paths: " + num(inf.paths) + ", printed segments: " + num(inf.segments) + ", edges on cycles: "
+                  + num(inf.cycle_edges) + ", longest path: " + num(inf.longest_path) + " edges");
+    FILE* fp = mOut == "-" ? stdout : fopen(mOut.c_str(), "wb");
+    if (!fp) throw Error::Errno(mOut, errno);
+    auto put = [&](const char* p, size_t n) {
+        if (n && fwrite(p, 1, n, fp) != n) { if (fp != stdout) fclose(fp); throw Error::Write(mOut); }
+    };
+    if (mOmitSequence)
+    {
+        const std::string head = "Number\tLength\tMinCov\tMaxCov\tMeanCov\tStdDevCov\n";
+        put(head.data(), head.size());
+    }
+    const uint64_t rows = 1u << 16, piece = 16u << 20;
+    std::vector<goss_gpu_segment> table;
+    std::vector<char> buf;
+    uint64_t bufAt = 0, bufLen = 0;                      // the piece of the text in `buf`
+    for (uint64_t first = 0; first < inf.segments; first += rows)
+    {
+        const uint64_t cnt = std::min(rows, inf.segments - first);
+        table.resize((size_t)cnt);
+        g.check(goss_gpu_segments_table(g.h, first, cnt, table.data()), "reading the segment table");
+        std::ostringstream line;
+        for (uint64_t j = 0; j < cnt; ++j)
+        {
+            const goss_gpu_segment& sg = table[(size_t)j];
+            const uint64_t n = sg.edges;
+            const double a = static_cast<double>(sg.s) / n;
+            const double d = sqrt(static_cast<double>(sg.s2) / n - a * a);
+            line.str(std::string());
+            if (mOmitSequence)
+                line << (first + j + 1) << '\t' << (n + o.K) << '\t' << sg.min << '\t' << sg.max << '\t' << a << '\t' << d << '\n';
+            else
+            {
+                line << '>' << (first + j + 1);
+                if (mVerboseHeaders) line << ' ' << (n + o.K) << ':' << sg.min << ':' << sg.max << ':' << a << ':' << d;
+                line << '\n';
+            }
+            const std::string text = line.str();
+            put(text.data(), text.size());
+            if (mOmitSequence) continue;
+            uint64_t at = sg.text_offset, left = sg.text_bytes;
+            while (left)
+            {
+                if (at < bufAt || at >= bufAt + bufLen)
+                {
+                    bufAt = at;
+                    bufLen = std::min(piece, inf.text_bytes - at);
+                    buf.resize((size_t)bufLen);
+                    g.check(goss_gpu_segments_text(g.h, bufAt, bufLen, buf.data()), "reading the text");
+                }
+                const uint64_t take = std::min(left, bufAt + bufLen - at);
+                put(buf.data() + (at - bufAt), (size_t)take);
+                at += take; left -= take;
+            }
+        }
+    }
+    g.check(goss_gpu_segments_release(g.h), "releasing the segments");
+    if (fp == stdout) fflush(stdout);
+    else if (fclose(fp) != 0) throw Error::Write(mOut);
+    log(info, elapsed(t0));
 }
 
 void GossCmdMergeKmerSets::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, false, mIns, mMaxMerge, mOut); }

@@ -558,6 +558,61 @@ typedef struct {
 int goss_gpu_prune_tips(goss_gpu_ctx* ctx, uint32_t iterations, goss_gpu_tips_report* reports);
 
 /*
+ * Between finish and emit, graph mode: the linear segments of the graph the context holds, as
+ * `goss print-contigs` prints them (printLinearSegments, GossCmdPrintContigs.cc:49-193; the walk is
+ * Graph::linearPath, Graph.tcc:21-46).  An edge starts a path unless its from-node has exactly one
+ * edge in and one out; the path goes on while the node reached has exactly one edge in and one out.
+ * Of a path and its mirror image on the other strand the one whose start ranks lower is taken (a path
+ * that is its own mirror image once); cycles without a start are never printed.  The ends' K bases
+ * are printed or not by the canonical form of the end nodes, then min_length (on the printed length)
+ * and min_coverage (on the smallest multiplicity) filter, and what remains is numbered from 1 in rank
+ * order of the starts.
+ *
+ * The link pass of goss_gpu_prune_tips gives the successor of every edge; the position of every edge
+ * on its path is found by list ranking (a bounded walk, then pointer doubling: `rounds` launches, no
+ * more than ceil(log2(longest_path)) + 2), the figures by a reduction over the edges ordered by (path,
+ * position), and the text -- the bodies of all segments back to back, 60 bases per line, every line
+ * ended by '\n', nothing for a segment of length 0 -- is written on the device.  The header lines are
+ * the caller's (doubles printed by its stream).
+ *
+ * build: any number of times; the context's result is only read.  The table and the text are held in
+ * the context's arena (about 39 bytes per edge of working room while building, 64 bytes per segment
+ * and the text afterwards) until goss_gpu_segments_release, the next build, or any other entry point
+ * except goss_gpu_segments_table / _text, goss_gpu_result, goss_gpu_result_copy, goss_gpu_lint,
+ * goss_gpu_file_read and the stat / timing getters: a call that may change the result or allocate
+ * gives them back first.
+ * table / text: any sub-range, so that a large output is streamed in pieces.
+ *
+ * GOSS_ERR_STATE: a k-mer-set context, before finish, after emit; table / text without a build.
+ * GOSS_ERR_INVALID_ARG: an edge without its reverse complement (last_error names its index); 2^32 - 1
+ * edges or more; multiplicities of 2^32 - 1 or more; a range past the end; an unknown flag.
+ * GOSS_ERR_OOM: it does not fit the arena; nothing is held afterwards and the result is intact.
+ */
+#define GOSS_SEGMENTS_NO_LINE_BREAKS 1u
+#define GOSS_SEGMENT_INCLUDE_FIRST 1u          /* goss_gpu_segment.flags: the first node's K bases are printed */
+#define GOSS_SEGMENT_INCLUDE_LAST 2u           /* ... the last node's */
+typedef struct {
+    uint64_t segments, text_bytes;                 /* what table / text hold */
+    uint64_t paths, taken_paths;                   /* starts; of them taken by the mirror rule (before the filters) */
+    uint64_t cycle_edges;                          /* edges on cycles without a start */
+    uint64_t longest_path;                         /* edges */
+    uint32_t rounds;                               /* ranking launches: the bounded walk and the doubling rounds */
+    uint32_t walk_steps;                           /* pointers the walk followed per lane (GOSS_GPU_CONTIGS_WALK) */
+    float ms_link, ms_rank, ms_figures, ms_text;   /* HIP-event time of the four parts */
+} goss_gpu_segments_info;
+typedef struct {
+    uint64_t s, s2;                                /* sum and sum of squares of the multiplicities (mod 2^64) */
+    uint64_t text_offset, text_bytes;              /* the body within the text */
+    uint64_t len;                                  /* bases printed */
+    uint32_t first_rank, edges, min, max, flags, end_rank;
+} goss_gpu_segment;
+int goss_gpu_segments_build(goss_gpu_ctx* ctx, uint64_t min_length, uint64_t min_coverage, uint32_t flags,
+                            goss_gpu_segments_info* info);
+int goss_gpu_segments_table(goss_gpu_ctx* ctx, uint64_t first, uint64_t count, goss_gpu_segment* out);
+int goss_gpu_segments_text(goss_gpu_ctx* ctx, uint64_t text_offset, uint64_t bytes, char* dst);
+int goss_gpu_segments_release(goss_gpu_ctx* ctx);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */

@@ -36,6 +36,9 @@ SYMBOLS = [
     "goss_gpu_segments_build", "goss_gpu_segments_table", "goss_gpu_segments_text", "goss_gpu_segments_release",
 ]
 
+# every symbol include/goss_gpu_match.h declares (reads against an object)
+MATCH_SYMBOLS = ["goss_gpu_object_match_reads", "goss_gpu_object_match_reads_host"]
+
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
 
@@ -750,6 +753,8 @@ class Context:
 
 OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY = 0, 1, 2
 QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
+MATCH_NORMALIZE, MATCH_ANY = 1, 4
+ERR_BUFFER = -9
 
 
 def encode_kmers(strings, k):
@@ -787,6 +792,14 @@ class NamedFile(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("bytes", C.c_uint64)]
 
 
+class MatchInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64), ("matched_reads", C.c_uint64),
+                ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def _declare_object(L):
     if getattr(L, "_object_declared", False):
         return
@@ -803,6 +816,7 @@ def _declare_object(L):
     L.goss_gpu_object_multiplicity.argtypes = [P, P, U64, P]
     L.goss_gpu_object_lookup.argtypes = [P, P, U64, C.c_uint32, P]
     L.goss_gpu_object_node_ranks.argtypes = [P, P, U64, C.c_uint32, P, P]
+    L.goss_gpu_object_match_reads.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(MatchInfo)]
     L._object_declared = True
 
 
@@ -952,3 +966,39 @@ class Object:
         flags = (QUERY_INCOMING if incoming else 0) | (QUERY_NORMALIZE if normalize else 0)
         self._check(self._L.goss_gpu_object_node_ranks(self._h, t.data_ptr(), n, flags, b.data_ptr(), e.data_ptr()))
         return self._back(b, staged, np.uint64), self._back(e, staged, np.uint64)
+
+    def match_reads(self, bases, normalize=False, any=False, starts=False, flags=0, max_reads=None):
+        """(windows, hits[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_match_reads.
+        windows[r]: valid L-windows of read r; hits[r]: how many are in the object, or with any=True 1 / 0.
+        bases: bytes or numpy uint8 (staged; numpy comes back) or a device uint8 tensor (used in place; tensors
+        come back).  The outputs are sized by counting the newlines; max_reads overrides that."""
+        import numpy as np
+        import torch
+        if isinstance(bases, torch.Tensor):
+            if not bases.is_cuda or bases.element_size() != 1:
+                raise ValueError("torch inputs must be device tensors of bytes")
+            t, staged = bases.contiguous().reshape(-1), False
+            _torch_ready()
+        else:
+            arr = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1)
+            t, staged = torch.from_numpy(arr.copy()).to("cuda:%d" % self.device), True
+        n = t.numel()
+        flags |= (MATCH_NORMALIZE if normalize else 0) | (MATCH_ANY if any else 0)
+        info = MatchInfo()
+        call = self._L.goss_gpu_object_match_reads
+        ptr = t.data_ptr() if n else None
+        if max_reads is None:
+            max_reads = int((t == 10).sum()) + (1 if n and int(t[-1]) != 10 else 0)
+        w = self._out(t, max_reads, torch.int32)
+        h = self._out(t, max_reads, torch.int32)
+        s = self._out(t, max_reads + 1, torch.int64) if starts else None
+        rc = call(self._h, ptr, n, flags, max_reads, w.data_ptr(), h.data_ptr(), s.data_ptr() if starts else None, C.byref(info))
+        if rc == ERR_BUFFER:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), "needs max_reads = %d" % info.reads)
+        self._check(rc)
+        r = info.reads
+        out = [self._back(w[:r], staged, np.uint32), self._back(h[:r], staged, np.uint32)]
+        if starts:
+            out.append(self._back(s[:r + 1], staged, np.uint64))
+        return tuple(out) + (info.as_dict(),)

@@ -6125,6 +6125,16 @@ struct goss_gpu_object {
     unsigned long long* h_bad = nullptr;    // (page-locked)
     QueryObj q{};
     std::string last_error;
+    // goss_gpu_object_match_reads: grow-only working memory (tile counts and their scan; outputs the caller left out),
+    // a page-locked block for what comes back, the events that time the kernels
+    uint8_t* match_mem = nullptr;
+    uint64_t match_bytes = 0;
+    uint8_t* match_tmp = nullptr;
+    uint64_t match_tmp_bytes = 0;
+    uint8_t* match_stage = nullptr;         // goss_gpu_object_match_reads_host: the batch and its answers on the device
+    uint64_t match_stage_bytes = 0;
+    unsigned long long* h_match = nullptr;
+    hipEvent_t match_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -6311,6 +6321,11 @@ void object_free(goss_gpu_object* o)
     if (o->stream) (void)hipStreamSynchronize(o->stream);
     if (o->mem) (void)hipFree(o->mem);
     if (o->h_bad) (void)hipHostFree(o->h_bad);
+    if (o->match_mem) (void)hipFree(o->match_mem);
+    if (o->match_tmp) (void)hipFree(o->match_tmp);
+    if (o->match_stage) (void)hipFree(o->match_stage);
+    if (o->h_match) (void)hipHostFree(o->h_match);
+    for (hipEvent_t e : o->match_ev) if (e) (void)hipEventDestroy(e);
     if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }
@@ -6466,3 +6481,167 @@ int goss_gpu_object_node_ranks(goss_gpu_object* o, const void* d_nodes, uint64_t
 }
 
 }  // extern "C"
+
+// ============================================================================================
+// Reads against an object (goss_gpu_object_match_reads): kernels_match.hpp
+// ============================================================================================
+
+namespace {
+
+// at least `bytes` of device memory in a buffer that only grows
+uint8_t* match_room(uint8_t*& mem, uint64_t& have, uint64_t bytes)
+{
+    if (bytes > have)
+    {
+        if (mem) { HIP_TRY(hipFree(mem)); mem = nullptr; have = 0; }
+        const uint64_t want = (bytes + (bytes >> 2) + 4095) & ~4095ULL;
+        if (hipMalloc((void**)&mem, want) != hipSuccess) { (void)hipGetLastError(); mem = nullptr; throw StatusError{GOSS_ERR_OOM, "no device memory for the working arrays of match_reads"}; }
+        have = want;
+    }
+    return mem;
+}
+
+// exclusive scan of a[0..n) in place; `partial` holds the chunk sums of every level
+void match_scan(hipStream_t st, uint64_t* a, uint64_t n, uint64_t* partial)
+{
+    const uint64_t nchunks = (n + kScanChunk - 1) / kScanChunk;
+    if (nchunks <= 1)
+    {
+        hipLaunchKernelGGL(scan_apply_kernel, dim3(1), dim3(kTB), 0, st, a, n, (const uint64_t*)nullptr);
+        return;
+    }
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, st, (const uint64_t*)a, n, partial);
+    match_scan(st, partial, nchunks, partial + nchunks);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, st, a, n, (const uint64_t*)partial);
+}
+
+template <class K>
+void match_launch(goss_gpu_object* o, bool any, uint64_t ntiles, const uint8_t* bases, uint64_t nbytes, const uint64_t* tile_read,
+                  uint32_t flags, uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad)
+{
+    if (any)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, true>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
+                           tile_read, flags, aligned, w, h, starts, bad);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, false>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
+                           tile_read, flags, aligned, w, h, starts, bad);
+}
+
+}  // namespace
+
+extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                           uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, goss_gpu_match_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)(GOSS_MATCH_NORMALIZE | GOSS_MATCH_ANY)) { o->last_error = "match_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    if (o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "match_reads needs a KmerSet or a Graph: a bare SparseArray has no key length"; return GOSS_ERR_INVALID_ARG; }
+    if (nbytes == 0)
+    {
+        if (!d_read_starts) return GOSS_OK;
+        return obj_guarded(o->device, o->last_error, [&]() {
+            HIP_TRY(hipMemsetAsync(d_read_starts, 0, 8, o->stream));
+            HIP_TRY(hipStreamSynchronize(o->stream));
+        });
+    }
+    return obj_guarded(o->device, o->last_error, [&]() {
+        const uint8_t* bases = (const uint8_t*)d_bases;
+        const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
+        // working memory: [0, 64) sums[3], bad[2]; then the tiles' newline counts (+ 1: the total) and the scan's partial sums
+        const uint64_t npartial = 2 * ((ntiles + 1 + kScanChunk - 1) / kScanChunk) + 64;
+        uint8_t* mem = match_room(o->match_mem, o->match_bytes, 64 + (ntiles + 1 + npartial) * 8);
+        unsigned long long* sums = (unsigned long long*)mem;
+        unsigned long long* bad = sums + 4;
+        uint64_t* tiles = (uint64_t*)(mem + 64);
+        uint64_t* partial = tiles + ntiles + 1;
+        if (!o->h_match) HIP_TRY(hipHostMalloc((void**)&o->h_match, 64, hipHostMallocDefault));
+        for (hipEvent_t& e : o->match_ev) if (!e) HIP_TRY(hipEventCreate(&e));
+        const uint32_t aligned = ((uintptr_t)bases & 7u) == 0;
+
+        // reads: one '\n' count per tile, scanned; the last byte decides whether a read is left open
+        HIP_TRY(hipMemsetAsync(mem, 0, 32, o->stream));
+        HIP_TRY(hipMemsetAsync(bad, 0xFF, 16, o->stream));
+        HIP_TRY(hipMemsetAsync(tiles + ntiles, 0, 8, o->stream));
+        HIP_TRY(hipEventRecord(o->match_ev[0], o->stream));
+        hipLaunchKernelGGL(match_count_newlines_kernel, unit_grid((ntiles + kWaves - 1) / kWaves), dim3(kTB), 0, o->stream, bases, nbytes, ntiles, tiles, aligned);
+        match_scan(o->stream, tiles, ntiles + 1, partial);
+        HIP_TRY(hipEventRecord(o->match_ev[1], o->stream));
+        HIP_TRY(hipMemcpyAsync(&o->h_match[0], tiles + ntiles, 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipMemcpyAsync(&o->h_match[1], bases + nbytes - 1, 1, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        check_launch("match_reads: counting the reads");
+        const bool open_end = (uint8_t)(o->h_match[1] & 0xFF) != (uint8_t)'\n';
+        const uint64_t reads = o->h_match[0] + (open_end ? 1 : 0);
+        if (info) info->reads = reads;
+        if ((d_windows || d_hits || d_read_starts) && reads > max_reads)
+            throw StatusError{GOSS_ERR_BUFFER, "match_reads: the input holds " + std::to_string(reads) + " reads, the output arrays " + std::to_string(max_reads)};
+
+        // outputs the caller left out are still the kernel's counters
+        uint32_t* w = d_windows;
+        uint32_t* h = d_hits;
+        if (!w || !h)
+        {
+            const uint64_t each = (reads * 4 + 255) & ~255ULL;
+            uint8_t* tmp = match_room(o->match_tmp, o->match_tmp_bytes, 2 * each + 256);
+            if (!w) w = (uint32_t*)tmp;
+            if (!h) h = (uint32_t*)(tmp + each);
+        }
+        if (reads)
+        {
+            HIP_TRY(hipMemsetAsync(w, 0, reads * 4, o->stream));
+            HIP_TRY(hipMemsetAsync(h, 0, reads * 4, o->stream));
+        }
+        HIP_TRY(hipEventRecord(o->match_ev[2], o->stream));
+        if (o->key_words == 1) match_launch<Key1>(o, flags & GOSS_MATCH_ANY, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad);
+        else match_launch<Key2>(o, flags & GOSS_MATCH_ANY, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad);
+        hipLaunchKernelGGL(match_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256 + 1, 2048)), dim3(kTB), 0, o->stream,
+                           (const uint32_t*)w, (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
+        HIP_TRY(hipEventRecord(o->match_ev[3], o->stream));
+        HIP_TRY(hipMemcpyAsync(o->h_match, mem, 48, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        check_launch("match_reads: matching");
+        if (o->h_match[4] != ~0ULL)
+            throw StatusError{GOSS_ERR_INVALID_ARG, "match_reads: the window at byte " + std::to_string(o->h_match[4] >> 2) + ": the index walk cannot answer (damaged object)"};
+        if (o->h_match[5] != ~0ULL)
+            throw StatusError{GOSS_ERR_INVALID_ARG, "match_reads: read " + std::to_string(o->h_match[5]) + " has 2^32 - 1 windows or more"};
+        if (info)
+        {
+            float a = 0, b = 0;
+            HIP_TRY(hipEventElapsedTime(&a, o->match_ev[0], o->match_ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, o->match_ev[2], o->match_ev[3]));
+            info->windows = o->h_match[0]; info->hits = o->h_match[1]; info->matched_reads = o->h_match[2];
+            info->ms = a + b;
+        }
+    });
+}
+
+extern "C" int goss_gpu_object_match_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                                uint32_t* windows, uint32_t* hits, uint64_t* read_starts, goss_gpu_match_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (nbytes == 0)
+    {
+        if (read_starts) read_starts[0] = 0;
+        return goss_gpu_object_match_reads(o, nullptr, 0, flags, max_reads, nullptr, nullptr, nullptr, info);
+    }
+    uint32_t* dw = nullptr; uint32_t* dh = nullptr; uint64_t* ds = nullptr;
+    int rc = obj_guarded(o->device, o->last_error, [&]() {
+        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL;
+        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, b0 + 2 * each + (max_reads + 1) * 8);
+        dw = (uint32_t*)(mem + b0); dh = (uint32_t*)(mem + b0 + each); ds = (uint64_t*)(mem + b0 + 2 * each);
+        HIP_TRY(hipMemcpyAsync(mem, bases, nbytes, hipMemcpyHostToDevice, o->stream));
+    });
+    if (rc != GOSS_OK) return rc;
+    goss_gpu_match_info mine;
+    rc = goss_gpu_object_match_reads(o, o->match_stage, nbytes, flags, max_reads, windows ? dw : nullptr, hits ? dh : nullptr,
+                                     read_starts ? ds : nullptr, &mine);
+    if (info) *info = mine;
+    if (rc != GOSS_OK) return rc;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        if (windows && mine.reads) HIP_TRY(hipMemcpyAsync(windows, dw, mine.reads * 4, hipMemcpyDeviceToHost, o->stream));
+        if (hits && mine.reads) HIP_TRY(hipMemcpyAsync(hits, dh, mine.reads * 4, hipMemcpyDeviceToHost, o->stream));
+        if (read_starts) HIP_TRY(hipMemcpyAsync(read_starts, ds, (mine.reads + 1) * 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    });
+}

@@ -22,3 +22,4 @@
 #include "kernels_query.hpp"
 #include "kernels_tips.hpp"
 #include "kernels_contigs.hpp"
+#include "kernels_match.hpp"

@@ -1,0 +1,252 @@
+// kernels_match.hpp -- reads against one KmerSet / Graph resident in HBM (goss_gpu_object_match_reads): from base
+// bytes to per-read window and hit counts in one pass, the window keys never leaving the registers.
+//
+// The input is cut into tiles of 2,048 byte positions, one workgroup each, whatever the reads are: a read is the
+// stretch between two '\n', so the read a position belongs to is the number of '\n' before it -- a count per tile
+// (match_count_newlines_kernel), one device scan, and inside the tile a popcount over a 64-bit mask.  A read of a
+// million bases is 489 tiles on 489 workgroups like any other million bytes.
+//
+// A tile is staged once: every lane turns 8 bytes into 16 bits of 2-bit codes, 8 non-base flags and 8 newline flags
+// (base_codes: the extraction kernels' decoder) and stores them into three LDS bit arrays, the tile's 2,048 positions
+// plus a halo of 64 (>= L - 1).  The window that starts at a position is then a funnel shift of two or three LDS
+// words, valid when L flag bits are clear (a '\n' is a non-base, so a valid window lies inside one read).  Stored
+// with the first base in the LOW bits, the shifted words are the window's reverse complement once inverted
+// (GossReadBaseString.hh:133-188 wants the first base on top): normalising costs one more base-4 reversal, no loop
+// over L.  What is left is the walk, rd_sparse_access_rank on the object's k-mers / edges only: the multiplicity
+// arrays are never touched.
+//
+// A wave takes 8 consecutive runs of 64 positions.  The reads inside a run are lane intervals between newline bits:
+// ballots of "valid" and "present" are cut by each interval's first lane (popcount under the interval's mask) and
+// added to per-read counters in LDS; after the tile, the non-zero counters go to the output arrays with one vector
+// atomic each (a read that spans tiles receives several).  Integer sums: the result does not depend on the order.
+//
+// GOSS_MATCH_ANY: a lane skips its walk when its read's LDS counter is already non-zero (earlier runs of this tile;
+// for the tile's first read also what earlier tiles left in hits[]), and inside a run every eighth window walks
+// first -- the other seven follow only where their read is still unmatched after that ballot.
+//
+// A walk that cannot answer (damaged image) leaves the lowest such byte position in bad[0]; a read whose window
+// count reaches 2^32 - 1 leaves its index in bad[1].
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "goss_key.hpp"
+#include "goss_reader.hpp"
+#include "kernels_common.hpp"
+#include "kernels_query.hpp"
+
+namespace goss {
+
+enum : uint32_t { kMatchNormalize = 1, kMatchAny = 4 };
+constexpr uint32_t kMatchTile = 2048;                    // positions per workgroup: 256 lanes x 8 bytes
+constexpr uint32_t kMatchRuns = kMatchTile / 64;         // runs of 64 positions, 8 per wave
+constexpr uint32_t kMatchGroups = kMatchTile / 8 + 8;    // 8-byte groups staged: the tile and a halo of 64 positions
+
+// 0x80 in every byte of w that is '\n'
+__device__ __forceinline__ uint32_t newline_flags(uint32_t w)
+{
+    const uint32_t v = w ^ 0x0A0A0A0Au;
+    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u;
+}
+
+// bytes [pos, pos + 8) of the input, 0 (no base, no newline) at and beyond nbytes
+__device__ __forceinline__ uint64_t match_load8(const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t pos, bool aligned)
+{
+    if (aligned && pos + 8 <= nbytes) return *reinterpret_cast<const uint64_t*>(bases + pos);
+    uint64_t w = 0;
+    for (uint32_t j = 0; j < 8; ++j)
+        if (pos + j < nbytes) w |= (uint64_t)bases[pos + j] << (8 * j);
+    return w;
+}
+
+// tiles[t] = number of '\n' in tile t; one wave per tile
+__global__ __launch_bounds__(256) void match_count_newlines_kernel(const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t ntiles,
+                                                                   uint64_t* __restrict__ tiles, uint32_t aligned)
+{
+    const uint64_t t = (uint64_t)unit_block() * kWaves + wave_id();
+    if (t >= ntiles) return;
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t it = 0; it < kMatchTile / 512; ++it)
+    {
+        const uint64_t pos = t * kMatchTile + it * 512 + lane_id() * 8;
+        if (pos >= nbytes) continue;
+        const uint64_t w = match_load8(bases, nbytes, pos, aligned);
+        n += __popc(newline_flags((uint32_t)w)) + __popc(newline_flags((uint32_t)(w >> 32)));
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+    if (lane_id() == 0) tiles[t] = n;
+}
+
+// the window of L bases whose first base is `v` bit 0..1 (2-bit codes, first base lowest): its key and, for
+// normalising, the key of its reverse complement
+template <class K> __device__ __forceinline__ void match_keys(uint64_t v0, uint64_t v1, uint32_t L, K* fwd, K* rc);
+template <> __device__ __forceinline__ void match_keys<Key1>(uint64_t v0, uint64_t, uint32_t L, Key1* fwd, Key1* rc)
+{
+    *rc = Key1{~v0 & ((1ULL << (2 * L)) - 1)};
+    *fwd = Key1{rev64(v0) >> (64 - 2 * L)};
+}
+template <> __device__ __forceinline__ void match_keys<Key2>(uint64_t v0, uint64_t v1, uint32_t L, Key2* fwd, Key2* rc)
+{
+    *rc = Key2{~v0, ~v1 & ((1ULL << (2 * L - 64)) - 1)};               // (32 <= L <= 63)
+    *fwd = revcomp(*rc, L);
+}
+
+// out[0..2] += sums over the reads: windows, hits, reads with a hit; starts[reads] = end
+__global__ __launch_bounds__(256) void match_sums_kernel(const uint32_t* __restrict__ windows, const uint32_t* __restrict__ hits, uint64_t reads,
+                                                         unsigned long long* __restrict__ out, uint64_t* __restrict__ starts, uint64_t end)
+{
+    unsigned long long w = 0, h = 0, m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < reads; i += (uint64_t)gridDim.x * blockDim.x)
+    {
+        w += windows[i];
+        h += hits[i];
+        m += hits[i] ? 1 : 0;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1)
+    {
+        w += __shfl_xor(w, d, 64);
+        h += __shfl_xor(h, d, 64);
+        m += __shfl_xor(m, d, 64);
+    }
+    if (lane_id() == 0)
+    {
+        if (w) atomicAdd(&out[0], w);
+        if (h) atomicAdd(&out[1], h);
+        if (m) atomicAdd(&out[2], m);
+    }
+    if (starts && blockIdx.x == 0 && threadIdx.x == 0) starts[reads] = end;
+}
+
+template <class K, bool ANY>
+__global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t ntiles,
+                                                          const uint64_t* __restrict__ tile_read, uint32_t flags, uint32_t aligned,
+                                                          uint32_t* __restrict__ windows, uint32_t* __restrict__ hits,
+                                                          uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad)
+{
+    __shared__ uint64_t s_codes[kMatchGroups / 4];       // 32 bases per word, first base lowest
+    __shared__ uint64_t s_inv[kMatchGroups / 8];         // bit = not one of ACGTacgt (or beyond the input)
+    __shared__ uint64_t s_nl[kMatchRuns];                // bit = '\n'
+    __shared__ uint32_t s_pre[kMatchRuns + 1];           // newlines before each run; [kMatchRuns] = in the tile
+    __shared__ uint32_t s_win[kMatchTile + 1], s_hit[kMatchTile + 1];      // per read that touches the tile
+    __shared__ uint32_t s_prev_nl;                       // the byte before the tile is '\n'
+
+    const uint64_t tile = unit_block();
+    if (tile >= ntiles) return;
+    const uint64_t t0 = tile * kMatchTile;
+    const uint64_t read0 = tile_read[tile];              // the read the tile's first position belongs to
+    const uint32_t L = o.len;
+    const uint32_t lane = lane_id();
+
+    // stage: group g = 8 bytes -> 16 bits of codes, 8 + 8 flags
+    for (uint32_t g = threadIdx.x; g < kMatchGroups; g += kTB)
+    {
+        const uint64_t w = match_load8(bases, nbytes, t0 + 8ULL * g, aligned);
+        uint32_t bad0, bad1;
+        const uint32_t x0 = base_codes((uint32_t)w, bad0), x1 = base_codes((uint32_t)(w >> 32), bad1);
+        reinterpret_cast<uint16_t*>(s_codes)[g] = (uint16_t)(pack_codes(x0) | (pack_codes(x1) << 8));
+        reinterpret_cast<uint8_t*>(s_inv)[g] = (uint8_t)(pack_flags(bad0) | (pack_flags(bad1) << 4));
+        if (g < kMatchTile / 8)
+            reinterpret_cast<uint8_t*>(s_nl)[g] = (uint8_t)(pack_flags(newline_flags((uint32_t)w)) | (pack_flags(newline_flags((uint32_t)(w >> 32))) << 4));
+    }
+    if (threadIdx.x == 0) s_prev_nl = t0 && bases[t0 - 1] == '\n';
+    __syncthreads();
+    if (threadIdx.x < 64)
+    {
+        const uint32_t v = lane < kMatchRuns ? (uint32_t)__popcll(s_nl[lane]) : 0;
+        const uint32_t inc = wave_incl_scan_u32(v);
+        if (lane < kMatchRuns) s_pre[lane] = inc - v;
+        if (lane == kMatchRuns - 1) s_pre[kMatchRuns] = inc;
+    }
+    __syncthreads();
+    const uint32_t nloc = s_pre[kMatchRuns] + 1;         // reads with a position in the tile
+    for (uint32_t i = threadIdx.x; i < nloc; i += kTB)
+    {
+        s_win[i] = 0;
+        s_hit[i] = ANY && i == 0 ? __atomic_load_n(&hits[read0], __ATOMIC_RELAXED) : 0;
+    }
+    __syncthreads();
+
+    const uint64_t lmask = (1ULL << L) - 1;              // (L <= 63)
+    for (uint32_t it = 0; it < kMatchRuns / kWaves; ++it)
+    {
+        const uint32_t run = wave_id() * (kMatchRuns / kWaves) + it;
+        const uint32_t q = run * 64 + lane;
+        const uint64_t p = t0 + q;
+        const uint64_t nlw = s_nl[run];
+        const uint64_t below = nlw & ((1ULL << lane) - 1), rest = nlw >> lane;
+        const uint32_t local = s_pre[run] + (uint32_t)__popcll(below);
+        // the lanes of this lane's read inside the run: after the last newline below, up to the next newline
+        const uint32_t first = below ? 64u - (uint32_t)__clzll((long long)below) : 0u;
+        const uint32_t last = rest ? lane + (uint32_t)__ffsll((long long)rest) - 1u : 63u;
+        const uint64_t seg = (~0ULL >> (63u - last)) & (~0ULL << first);
+
+        if (starts && p < nbytes)
+        {
+            const bool begins = lane ? ((nlw >> (lane - 1)) & 1) : run ? (s_nl[run - 1] >> 63) : (t0 == 0 || s_prev_nl);
+            if (begins) starts[read0 + local] = p;
+        }
+
+        const uint64_t iv = (s_inv[run] >> lane) | (lane ? s_inv[run + 1] << (64 - lane) : 0);
+        const bool valid = (iv & lmask) == 0;
+        const uint64_t vb = __ballot(valid);
+        if (!vb) continue;
+
+        bool done = ANY && __atomic_load_n(&s_hit[local], __ATOMIC_RELAXED) != 0;
+        uint64_t hb = 0;
+#pragma unroll
+        for (uint32_t ph = 0; ph < (ANY ? 2u : 1u); ++ph)
+        {
+            const bool go = valid && !done && (!ANY || ((lane & 7u) == 0) == (ph == 0));
+            bool hit = false;
+            if (go)
+            {
+                const uint32_t cw = q >> 5, co = 2 * (q & 31);
+                const uint64_t c0 = s_codes[cw], c1 = s_codes[cw + 1];
+                const uint64_t v0 = co ? (c0 >> co) | (c1 << (64 - co)) : c0;
+                uint64_t v1 = 0;
+                if (K::kWords == 2)
+                {
+                    const uint64_t c2 = s_codes[cw + 2];
+                    v1 = co ? (c1 >> co) | (c2 << (64 - co)) : c1;
+                }
+                K x, rc;
+                match_keys<K>(v0, v1, L, &x, &rc);
+                if (flags & kMatchNormalize) x = canonical(x, rc);
+                uint64_t r;
+                if (!rd_sparse_access_rank<K>(o.s, x, &r, &hit)) { q_fail(bad, p, kQBadWalk); hit = false; }
+            }
+            const uint64_t b = __ballot(hit);
+            hb |= b;
+            if (ANY) done = done || (b & seg) != 0;
+        }
+
+        if (lane == first)
+        {
+            const uint32_t nw = (uint32_t)__popcll(vb & seg), nh = (uint32_t)__popcll(hb & seg);
+            if (nw) atomicAdd(&s_win[local], nw);
+            if (nh) atomicAdd(&s_hit[local], nh);
+        }
+    }
+    __syncthreads();
+
+    for (uint32_t i = threadIdx.x; i < nloc; i += kTB)
+    {
+        const uint32_t nw = s_win[i], nh = s_hit[i];
+        if (nw)
+        {
+            const uint32_t old = atomicAdd(&windows[read0 + i], nw);
+            if ((uint64_t)old + nw >= 0xFFFFFFFFULL) atomicMin(&bad[1], (unsigned long long)(read0 + i));
+        }
+        if (nh)
+        {
+            if (ANY) atomicOr(&hits[read0 + i], 1u);
+            else atomicAdd(&hits[read0 + i], nh);
+        }
+    }
+}
+
+}  // namespace goss

@@ -1925,7 +1925,9 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  graph-to-kmer-set  generate a graph's k-mer set\n"
               << "  trim-graph       create a new graph by trimming low frequency edges\n"
               << "  prune-tips       create a new graph by removing low frequency tips\n"
-              << "  print-contigs    print all the non-branching paths in the given assembly graph\n";
+              << "  print-contigs    print all the non-branching paths in the given assembly graph\n"
+              << "  extract-reads    extract reads which map on to a graph\n"
+              << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -2157,6 +2159,97 @@ int gossMain(int argc, char* argv[])
                     cmd(cxt);
                 }
                 else { GossCmdMergeAndAnnotateKmerSets cmd(ins[0], ins[1], outName); cmd(cxt); }
+            }
+            catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "extract-reads" || cmdName == "filter-reads")
+        {
+            // GossCmdFactoryExtractReads::create (GossCmdExtractReads.cc:113-139), GossCmdFactoryFilterReads::create
+            // (GossCmdFilterReads.cc:312-349)
+            const bool isFilter = cmdName == "filter-reads";
+            static const OptDef kReads[] = {
+                {"graph-in", "G", kStrings, "name of the input graph object"},
+                {"fasta-in", "I", kStrings, "input file in FASTA format"},
+                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
+                {"line-in", "", kStrings, "input file with one sequence per line"},
+            };
+            static const OptDef kExtract[] = {
+                {"output-file", "o", kString, "output file name ('-' for standard output)"},
+            };
+            static const OptDef kFilter[] = {
+                {"match-file", "", kString, "a file to put matching reads into"},
+                {"non-match-file", "", kString, "a file to put non-matching reads into"},
+                {"pairs", "", kFlag, "treat reads as pairs"},
+                {"count", "", kFlag, "generate histogram of matching kmers per read"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            for (auto& d : kReads) t.defs.push_back(d);
+            if (isFilter) for (auto& d : kFilter) t.defs.push_back(d);
+            else for (auto& d : kExtract) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            std::string in;
+            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+            else if (opts.strs("graph-in").size() != 1)
+            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+            else in = opts.str("graph-in");
+            strings fastas, fastqs, lines;
+            chk.repeatingIn("fasta-in", fastas);
+            chk.repeatingIn("fastq-in", fastqs);
+            chk.repeatingIn("line-in", lines);
+            std::string outName = "-", matchName, nonMatchName;
+            uint64_t T = 4;
+            if (isFilter)
+            {
+                if (opts.count("match-file")) matchName = opts.str("match-file");
+                if (opts.count("non-match-file")) nonMatchName = opts.str("non-match-file");
+                chk.optionalU64("num-threads", T);
+            }
+            else if (opts.count("output-file"))
+            {
+                outName = opts.str("output-file");
+                if (outName != "-")
+                {
+                    FILE* fp = fopen(outName.c_str(), "wb");      // FileCreateCheck(fac, false)
+                    if (!fp)
+                    {
+                        chk.errors += "The given value of the option output-file was invalid.\n";
+                        chk.errors += "\tcannot create file '" + outName + "'\n";
+                    }
+                    else fclose(fp);
+                }
+            }
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            try
+            {
+                if (isFilter)
+                {
+                    GossCmdFilterReads cmd(in, fastas, fastqs, lines, opts.count("pairs") != 0, opts.count("count") != 0, T, matchName, nonMatchName);
+                    cmd(cxt);
+                }
+                else { GossCmdExtractReads cmd(in, fastas, fastqs, lines, outName); cmd(cxt); }
             }
             catch (Error& e) { e.cmd = cmdName; throw; }
             return 0;

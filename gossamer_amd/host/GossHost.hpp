@@ -286,6 +286,39 @@ private:
     const std::string mIn, mOut; const uint64_t mC, mL; const bool mOmitSequence, mVerboseHeaders, mNoLineBreaks;
 };
 
+// GossCmdExtractReads (GossCmdExtractReads.{hh,cc}): the reads with at least one (K + 1)-mer that is an edge of the graph, as
+// parsed, one per line, in input order (line files, then FASTA, then FASTQ).
+class GossCmdExtractReads {
+public:
+    GossCmdExtractReads(const std::string& pIn, const strings& pFastas, const strings& pFastqs, const strings& pLines, const std::string& pOut)
+        : mIn(pIn), mOut(pOut), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const strings mFastas, mFastqs, mLines;
+};
+
+// GossCmdFilterReads (GossCmdFilterReads.{hh,cc}): the reads (or, pPairs, the pairs of reads of files 2i and 2i + 1) go to
+// the match file when either strand of one of their K-mers is in the k-mer set, else to the non-match file; with pPairs the
+// two mates go to <pre>_1<suf> and <pre>_2<suf> (pairFiles).  pCount and pNumThreads are accepted and unused, as in the
+// reference.  Two deliberate departures, both defects there and not behaviour to copy: its unpaired path cuts (K + 1)-windows
+// against a K-mer set, keys outside the set's universe (GossCmdFilterReads.cc:48), and its pair path computes the normalised
+// k-mer and then looks up the un-normalised one (:142-146); what both evidently intend -- either strand of a K-mer -- is what
+// is built.  The reference writes in the order its threads finish; here the order is the input's.  An odd number of files
+// with pPairs makes the reference throw the integer 42 (ReadPairSequenceFileSequence.hh:88-91); here it is an error that says so.
+class GossCmdFilterReads {
+public:
+    GossCmdFilterReads(const std::string& pIn, const strings& pFastas, const strings& pFastqs, const strings& pLines, bool pPairs,
+                       bool pCount, uint64_t pNumThreads, const std::string& pMatch, const std::string& pNonMatch)
+        : mIn(pIn), mMatch(pMatch), mNonMatch(pNonMatch), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines), mPairs(pPairs),
+          mCount(pCount), mNumThreads(pNumThreads) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mMatch, mNonMatch; const strings mFastas, mFastqs, mLines; const bool mPairs, mCount; const uint64_t mNumThreads;
+};
+
+// pairFiles (GossCmdFilterReads.cc:164-172): "a.b.fq" -> "a.b_1.fq", "a.b_2.fq"
+void pairFiles(const std::string& pBaseName, std::string& pName1, std::string& pName2);
+
 }  // namespace gosshost
 struct goss_gpu_ctx;
 namespace gosshost {

@@ -1,0 +1,297 @@
+// GossMatch.cpp -- `goss extract-reads` (GossCmdExtractReads.cc) and `goss filter-reads` (GossCmdFilterReads.cc): the
+// reads that share an edge with a graph, or a k-mer with a k-mer set.
+//
+// The object is opened on the device as it lies on disk (goss_gpu_object_open).  The reads are parsed in order, batched
+// ('\n' after each), and each batch is answered by goss_gpu_object_match_reads_host with GOSS_MATCH_ANY; what comes back
+// is one word per read, and the reads are written from the host's copy of the batch, in input order.
+#include <fcntl.h>
+#include <glob.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cerrno>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/goss_gpu.h"
+#include "GossHost.hpp"
+
+namespace gosshost {
+
+namespace {
+
+std::string num(uint64_t v) { return std::to_string(v); }
+
+// An object's files, mapped, under the names they have on disk.
+struct ObjectFiles {
+    std::vector<std::string> names;
+    std::vector<std::pair<const void*, size_t>> maps;
+    ~ObjectFiles() { for (auto& m : maps) if (m.first && m.second) munmap((void*)m.first, m.second); }
+    void add(const std::string& name)
+    {
+        int fd = ::open(name.c_str(), O_RDONLY);
+        if (fd < 0) throw Error::Errno(name, errno);
+        struct stat st;
+        if (fstat(fd, &st) != 0) { int e = errno; ::close(fd); throw Error::Errno(name, e); }
+        const void* p = nullptr;
+        if (S_ISREG(st.st_mode) && st.st_size)
+        {
+            void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) { int e = errno; ::close(fd); throw Error::Errno(name, e); }
+            p = m;
+        }
+        ::close(fd);
+        if (!S_ISREG(st.st_mode)) return;
+        names.push_back(name);
+        maps.emplace_back(p, (size_t)st.st_size);
+    }
+};
+
+struct Object {
+    goss_gpu_object* h = nullptr;
+    goss_gpu_object_desc desc{};
+    ~Object() { if (h) goss_gpu_object_close(h); }
+    void check(int rc, const char* what) const
+    {
+        if (rc == GOSS_OK) return;
+        std::string msg = std::string(what) + ": " + goss_gpu_strerror(rc);
+        const char* d = goss_gpu_object_last_error(h);
+        if (d && *d) msg += std::string(" (") + d + ")";
+        throw Error::General(msg + "\n");
+    }
+    // Graph::open(name, fac) / KmerSet(name, fac): every file "<name>." or "<name>-" something
+    void open(const GossCmdContext& cxt, const std::string& name, bool graph)
+    {
+        ObjectFiles files;
+        glob_t g{};
+        std::string pat;
+        for (char c : name) { if (c == '*' || c == '?' || c == '[' || c == '\\') pat += '\\'; pat += c; }
+        pat += "[.-]*";
+        if (::glob(pat.c_str(), 0, nullptr, &g) == 0)
+            for (size_t i = 0; i < g.gl_pathc; ++i)
+            {
+                const std::string f = g.gl_pathv[i];
+                if (f.size() >= 4 && f.compare(f.size() - 4, 4, ".txt") == 0) continue;
+                files.add(f);
+            }
+        globfree(&g);
+        std::vector<goss_gpu_named_file> nf(files.names.size());
+        for (size_t i = 0; i < nf.size(); ++i) nf[i] = goss_gpu_named_file{files.names[i].c_str(), files.maps[i].first, files.maps[i].second};
+        int rc = goss_gpu_object_open(&h, cxt.device, nullptr, graph ? GOSS_OBJECT_GRAPH : GOSS_OBJECT_KMER_SET, name.c_str(), nf.data(), (uint32_t)nf.size());
+        if (rc != GOSS_OK)
+        {
+            std::string msg = "\tunable to open graph '" + name + "'\n\t" + goss_gpu_strerror(rc);
+            const char* d = goss_gpu_object_last_error(nullptr);
+            if (d && *d) msg += std::string(" (") + d + ")";
+            throw Error::General(msg + "\n");
+        }
+        check(goss_gpu_object_info(h, &desc), "describing the object");
+    }
+};
+
+size_t matchBatchBytes(const GossCmdContext& cxt)
+{
+    if (const char* e = std::getenv("GOSS_MATCH_BATCH"))
+    {
+        char* end = nullptr;
+        unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && *end == 0 && v > 0) return (size_t)v;
+    }
+    return cxt.batchBytes;
+}
+
+// Reads in, one verdict per read out, in order: batches end at read boundaries and hold `cap` bytes (one read more than
+// that is a batch of its own).
+class Matcher {
+public:
+    typedef std::function<void(const char* seq, size_t len, bool hit)> Verdict;
+    Matcher(const Object& obj, uint32_t flags, size_t cap, Verdict v) : mObj(obj), mFlags(flags), mCap(cap), mVerdict(std::move(v)) {}
+    void push(const char* seq, size_t len)
+    {
+        if (!mBuf.empty() && mBuf.size() + len + 1 > mCap) flush();
+        mStart.push_back(mBuf.size());
+        mBuf.insert(mBuf.end(), seq, seq + len);
+        mBuf.push_back('\n');
+    }
+    void flush()
+    {
+        if (mStart.empty()) return;
+        const uint64_t n = mStart.size();
+        mHits.resize(n);
+        goss_gpu_match_info info;
+        mObj.check(goss_gpu_object_match_reads_host(mObj.h, mBuf.data(), mBuf.size(), mFlags, n, nullptr, mHits.data(), nullptr, &info),
+                   "matching a batch of reads");
+        if (info.reads != n) throw Error::General("matching a batch of reads: " + num(n) + " reads sent, " + num(info.reads) + " answered\n");
+        mStart.push_back(mBuf.size());
+        for (uint64_t r = 0; r < n; ++r) mVerdict(mBuf.data() + mStart[r], mStart[r + 1] - mStart[r] - 1, mHits[r] != 0);
+        mBuf.clear();
+        mStart.clear();
+        ++mBatches;
+    }
+    uint64_t batches() const { return mBatches; }
+private:
+    const Object& mObj;
+    const uint32_t mFlags;
+    const size_t mCap;
+    Verdict mVerdict;
+    std::vector<char> mBuf;
+    std::vector<uint64_t> mStart;
+    std::vector<uint32_t> mHits;
+    uint64_t mBatches = 0;
+};
+
+// FileFactory::out(name): "-" is standard output
+struct OutFile {
+    std::string name;
+    FILE* fp = nullptr;
+    std::string pending;
+    void open(const std::string& n)
+    {
+        name = n;
+        fp = n == "-" ? stdout : fopen(n.c_str(), "wb");
+        if (!fp) throw Error::Errno(n, errno);
+    }
+    // GossReadBaseString::print (GossReadBaseString.hh:115-118): the bases as parsed, then '\n'
+    void print(const char* seq, size_t len)
+    {
+        pending.append(seq, len);
+        pending += '\n';
+        if (pending.size() >= (4u << 20)) drain();
+    }
+    void drain()
+    {
+        if (!pending.empty() && fwrite(pending.data(), 1, pending.size(), fp) != pending.size()) throw Error::Write(name);
+        pending.clear();
+    }
+    void close()
+    {
+        if (!fp) return;
+        drain();
+        if (fp == stdout) fflush(stdout);
+        else if (fclose(fp) != 0) { fp = nullptr; throw Error::Write(name); }
+        fp = nullptr;
+    }
+    ~OutFile() { if (fp && fp != stdout) fclose(fp); }
+};
+
+enum Format { kLine, kFasta, kFastq };
+struct Item { std::string name; Format fmt; };
+
+// the reference's item order: all line files, then all FASTA files, then all FASTQ files
+// (GossCmdExtractReads.cc:64-88, GossCmdFilterReads.cc:186-212)
+std::vector<Item> itemsOf(const strings& fastas, const strings& fastqs, const strings& lines)
+{
+    std::vector<Item> items;
+    for (auto& f : lines) items.push_back(Item{f, kLine});
+    for (auto& f : fastas) items.push_back(Item{f, kFasta});
+    for (auto& f : fastqs) items.push_back(Item{f, kFastq});
+    return items;
+}
+
+uint64_t parseItem(const Item& it, const ReadSink& sink)
+{
+    return it.fmt == kLine ? parseLines(it.name, sink) : it.fmt == kFasta ? parseFasta(it.name, sink) : parseFastq(it.name, sink);
+}
+
+}  // namespace
+
+void pairFiles(const std::string& pBaseName, std::string& pName1, std::string& pName2)
+{
+    // (find_last_of = npos when there is no dot: substr(0, npos) is the whole name, substr(npos) throws in the
+    // reference; here such a name gets the numbers at its end)
+    const size_t lastDot = pBaseName.find_last_of('.');
+    const std::string pre = pBaseName.substr(0, lastDot);
+    const std::string suf = lastDot == std::string::npos ? std::string() : pBaseName.substr(lastDot);
+    pName1 = pre + "_1" + suf;
+    pName2 = pre + "_2" + suf;
+}
+
+void GossCmdExtractReads::operator()(const GossCmdContext& pCxt)
+{
+    Logger& log(pCxt.log);
+    Object g;
+    g.open(pCxt, mIn, true);
+    if (g.desc.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    OutFile out;
+    out.open(mOut);
+    uint64_t n = 0, m = 0;
+    Matcher matcher(g, GOSS_MATCH_ANY, matchBatchBytes(pCxt), [&](const char* seq, size_t len, bool hit) {
+        ++n;
+        if (hit) { out.print(seq, len); ++m; }
+    });
+    for (auto& it : itemsOf(mFastas, mFastqs, mLines))
+        parseItem(it, [&](const char* seq, size_t len) { matcher.push(seq, len); });
+    matcher.flush();
+    out.close();
+    log(info, "extracted " + num(m) + " reads, out of " + num(n));
+}
+
+void GossCmdFilterReads::operator()(const GossCmdContext& pCxt)
+{
+    Logger& log(pCxt.log);
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<Item> items = itemsOf(mFastas, mFastqs, mLines);
+    if (mPairs && items.size() % 2) throw Error::General("filter-reads --pairs: an even number of input files is required (" + num(items.size()) + " given)\n");
+    Object g;
+    g.open(pCxt, mIn, false);
+    const uint32_t flags = GOSS_MATCH_ANY | GOSS_MATCH_NORMALIZE;
+    const size_t cap = matchBatchBytes(pCxt);
+    log(info, "Filtering reads....");
+    uint64_t n = 0, m = 0;
+    if (!mPairs)
+    {
+        OutFile match, nonMatch;
+        if (!mMatch.empty()) match.open(mMatch);
+        if (!mNonMatch.empty()) nonMatch.open(mNonMatch);
+        Matcher matcher(g, flags, cap, [&](const char* seq, size_t len, bool hit) {
+            ++n;
+            if (hit) ++m;
+            OutFile& o = hit ? match : nonMatch;
+            if (o.fp) o.print(seq, len);
+        });
+        for (auto& it : items) parseItem(it, [&](const char* seq, size_t len) { matcher.push(seq, len); });
+        matcher.flush();
+        match.close();
+        nonMatch.close();
+    }
+    else
+    {
+        // files 2i and 2i + 1 read in lockstep: the verdict of every read of both files first (one byte per read), then
+        // both files once more, each read going where its pair belongs
+        OutFile match[2], nonMatch[2];
+        std::string a, b;
+        if (!mMatch.empty()) { pairFiles(mMatch, a, b); match[0].open(a); match[1].open(b); }
+        if (!mNonMatch.empty()) { pairFiles(mNonMatch, a, b); nonMatch[0].open(a); nonMatch[1].open(b); }
+        for (size_t i = 0; i + 1 < items.size(); i += 2)
+        {
+            std::vector<uint8_t> verdict[2];
+            for (int s = 0; s < 2; ++s)
+            {
+                Matcher matcher(g, flags, cap, [&](const char*, size_t, bool hit) { verdict[s].push_back(hit ? 1 : 0); });
+                parseItem(items[i + s], [&](const char* seq, size_t len) { matcher.push(seq, len); });
+                matcher.flush();
+            }
+            if (verdict[0].size() != verdict[1].size())
+                throw Error::General("filter-reads --pairs: '" + items[i].name + "' holds " + num(verdict[0].size()) + " reads, '" + items[i + 1].name
+                                     + "' " + num(verdict[1].size()) + "\n");
+            for (size_t r = 0; r < verdict[0].size(); ++r) { verdict[0][r] |= verdict[1][r]; ++n; m += verdict[0][r]; }
+            for (int s = 0; s < 2; ++s)
+            {
+                if (!match[s].fp && !nonMatch[s].fp) continue;
+                uint64_t r = 0;
+                parseItem(items[i + s], [&](const char* seq, size_t len) {
+                    if (r >= verdict[0].size()) throw Error::General("filter-reads --pairs: '" + items[i + s].name + "' changed while it was read\n");
+                    OutFile& o = verdict[0][r++] ? match[s] : nonMatch[s];
+                    if (o.fp) o.print(seq, len);
+                });
+            }
+        }
+        for (int s = 0; s < 2; ++s) { match[s].close(); nonMatch[s].close(); }
+    }
+    log(info, std::string("matched ") + num(m) + (mPairs ? " pairs, out of " : " reads, out of ") + num(n));
+    log(info, "total elapsed time: " + std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()));
+}
+
+}  // namespace gosshost

@@ -792,6 +792,10 @@ int goss_gpu_object_lookup(goss_gpu_object* obj, const void* d_keys, uint64_t n,
 int goss_gpu_object_node_ranks(goss_gpu_object* obj, const void* d_nodes, uint64_t n, uint32_t flags, uint64_t* d_begin,
                                uint64_t* d_end);
 
+/* Reads against an object (goss_gpu_object_match_reads, goss_gpu_object_match_reads_host): a part of this ABI kept
+ * in a header of its own. */
+#include "goss_gpu_match.h"
+
 #ifdef __cplusplus
 }
 #endif

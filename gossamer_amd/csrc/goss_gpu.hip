@@ -81,6 +81,15 @@ struct Run { void* keys; uint32_t* counts; uint64_t m; int big = -1; bool rep = 
 
 struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
 
+// Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
+// itself (goss_gpu_ctx::canon_l1 == 1).
+// (0.05: re-ordering M distinct pairs into the canonical order costs 53 ms per 10^9 of them, two FNV hashes per window
+// 34 ms per 12.6 G windows -- even at M = 0.051 x windows, and the counting of canonical keys is the faster above that
+// (C2 with 0.3 % / 0.5 % errors: 160 -> 148 / 216 -> 170 ms); 0.10 until the end of round 5)
+constexpr double kCanonL1At = 0.05;
+// At most 2^kBigRoundsMax workgroups share a 16-bit segment counted in the big table.
+constexpr int kBigRoundsMax = 2;
+
 }  // namespace
 
 struct goss_gpu_ctx {
@@ -118,19 +127,13 @@ struct goss_gpu_ctx {
     std::vector<hipEvent_t> pend_pool;  // events of `pending` (the counting thread has event_pool to itself)
     uint8_t* stage = nullptr;           // the staging buffer being filled (= stage_buf[stage_cur])
     uint64_t stage_cap = 0, stage_fill = 0;
-    bool cursor_pass0 = true;           // GOSS_GPU_NO_CURSOR_PASS0=1: look-back chain in every pass
     bool mute_timing = false;           // set around auxiliary launches (the distinct-count estimate)
     uint32_t segment_retries = 0;       // segment path attempts that overflowed an LDS table
     uint32_t extract_hist_shift = 0xFFFFFFFFu;   // digits histogrammed by the last extraction (or none)
     bool extract_rep = false;           // the next one-word k-mer extraction stores strand representatives (fused path's sample)
     uint32_t rep_chunks = 0;            // chunks counted in strand-representative space and mapped to canonical order afterwards
-    bool ef_by_words = false;           // GOSS_GPU_EF_BY_WORDS=1: the high-bits bitmap by a binary search per word (round 1's kernel)
     bool graph_rep = true;              // GOSS_GPU_NO_GRAPH_REP=1: the fused path of a graph build counts both strands of every window (round 3's form)
-    int canon_l1 = 1;                   // GOSS_GPU_CANON_L1=0|1|2: the fused first level computes gossamer's canonical form itself never / from canon_l1_at distinct keys per window on / always
-    // (0.05: re-ordering M distinct pairs into the canonical order costs 53 ms per 10^9 of them, two FNV hashes per window
-    // 34 ms per 12.6 G windows -- even at M = 0.051 x windows, and the counting of canonical keys is the faster above that
-    // (C2 with 0.3 % / 0.5 % errors: 160 -> 148 / 216 -> 170 ms); 0.10 until the end of round 5)
-    double canon_l1_at = 0.05;          // GOSS_GPU_CANON_L1_AT=<fraction>
+    int canon_l1 = 1;                   // GOSS_GPU_CANON_L1=0|1|2: the fused first level computes gossamer's canonical form itself never / from kCanonL1At distinct keys per window on / always
     // more of the same input is known to follow the push being counted (a staging buffer that filled up while the caller
     // keeps pushing): its runs will be merged with the runs of the others
     // in representative space and the re-ordering into canonical order paid ONCE, on the merged run -- the chunk's own
@@ -142,7 +145,6 @@ struct goss_gpu_ctx {
     uint64_t expect_bases = 0;          // goss_gpu_expect_bases: bases the caller means to push in all (0: not said)
     int space_choice = -1;              // the key space the build's fused chunks count in once one has chosen: 0 representatives, 1 canonical forms (-1: none yet)
     uint32_t canon_chunks = 0;          // chunks counted that way
-    bool extract_v1 = false;            // GOSS_GPU_EXTRACT_V1=1: per-base LDS extraction kernel for one-word keys
     bool fused = true;                  // GOSS_GPU_NO_FUSED=1: never fuse the first partition pass into the extraction
     uint64_t fused_min = 32u << 20;     // GOSS_GPU_FUSED_MIN=<window starts>: smallest chunk the fused path takes
     uint32_t fused_overflows = 0;       // fused chunks redone because a bucket region was too small
@@ -156,8 +158,6 @@ struct goss_gpu_ctx {
     std::thread arena_thread;           // goss_gpu_prepare: the arena is being mapped in the background
     int arena_status = GOSS_OK;         // ... and how that went
     std::string arena_error;
-    uint32_t fused_grid = 0;            // GOSS_GPU_FUSED_GRID: workgroups of the fused extraction kernel (0 = 1024)
-    bool seg_merge = true;              // GOSS_GPU_NO_SEG_MERGE=1: merge runs by sorting their concatenation
     uint32_t seg_merges = 0;            // merges done by segments
     uint32_t hash_merges = 0;           // ... of them through the counting table (seg_hash_merge96_kernel)
     uint64_t hash_merge_min = 1u << 20; // GOSS_GPU_HASH_MERGE_MIN=<entries>: smallest merge that goes that way (65 536 workgroups)
@@ -166,11 +166,8 @@ struct goss_gpu_ctx {
     bool rem32 = true;                  // GOSS_GPU_NO_REM32=1: never take the 32-bit-remainder form of the second level and the counting
     int rem32_slots = 0;                // GOSS_GPU_REM32_SLOTS=2048|4096|8192|16384: counting table of that form (0 = by the distinct-key estimate)
     uint32_t narrow_capg = 656;         // GOSS_GPU_NARROW_CAPG (tests): granules a tile of the narrow form may lay out before it sends its carried granules off short
-    bool ds_parts = true;               // GOSS_GPU_DS_PARTS=0: a range builds no DenseSelect blocks of its own (round 4: the assembler builds them all)
     bool narrow = true;                 // GOSS_GPU_NARROW=0: 8-byte keys between the two levels of the 32-bit-remainder form (rounds 3-4)
-    int r32_form = 1;                   // GOSS_GPU_R32_FORM=0: the pair layout of rounds 3-4 (seg_hash_reduce32_kernel), 1: buckets of four (round 5)
     uint32_t r32_small_max = 0;         // distinct keys per segment up to which the 2048-slot table is taken (GOSS_GPU_R32_SMALL_MAX; 0 = the form's default)
-    bool big_r32 = true;                // GOSS_GPU_R32_BIG=0: no 8 192- / 16 384-slot tables of remainders (a third partition level instead, as before)
     bool overflow_by_sort = true;       // GOSS_GPU_OVERFLOW_BY_SORT=0: a table that overflows sends the whole chunk up the ladder of forms (rounds 1-5)
     uint64_t overflow_units = 0;        // segments counted by sort because their table overflowed
     uint32_t rem32_chunks = 0;          // chunks counted in that form
@@ -192,7 +189,6 @@ struct goss_gpu_ctx {
     uint32_t table96_chunks = 0;
     bool wide_table = true;             // GOSS_GPU_NO_WIDE_TABLE=1: never count two-word keys in the 6144-slot table
     bool big_table = true;              // GOSS_GPU_NO_BIG_TABLE=1: never count 16-bit segments in the 8192-slot table
-    int big_rounds_max = 2;             // GOSS_GPU_BIG_ROUNDS=<r>: at most 2^r workgroups share a segment of that form
     int big_rounds_min = 0;             // GOSS_GPU_BIG_ROUNDS_MIN=<r>: at least 2^r (tests)
     uint32_t big_table_chunks = 0;      // chunks counted that way
     uint32_t wide_table_chunks = 0;     // ... of them, two-word keys in the 6144-slot table
@@ -470,7 +466,7 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
         if (lookback)
         {
             // pass 0 may place tiles in any order: atomic bucket cursors instead of the chain
-            unsigned long long* cur = (di == 0 && c->cursor_pass0) ? cursors : nullptr;
+            unsigned long long* cur = di == 0 ? cursors : nullptr;
             if (cur) HIP_TRY(hipMemsetAsync(cursors, 0, 256 * kCursorStride * 8, c->stream));
             else HIP_TRY(hipMemsetAsync(status, 0, ntiles * 256 * 8, c->stream));
             {
@@ -648,14 +644,6 @@ static const uint8_t* pk_unpack_temp(goss_gpu_ctx* c, const uint8_t* p, uint64_t
     return out;
 }
 
-template <class K, int MODE, int P>
-void launch_extract(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, K* out)
-{
-    constexpr int T = kTB * P;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract_kernel<K, MODE, P>), dim3(grid_for(nstarts, T)), dim3(kTB), 0, c->stream,
-                       aligned, mis, nstarts, navail, c->len, out, c->d_ctr);
-}
-
 template <class K>
 void extract_dispatch(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, K* out);
 template <class K> bool use_segment_path(const goss_gpu_ctx* c);
@@ -738,12 +726,6 @@ void extract_dispatch<Key1>(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mi
         launch_extract_records(c, (const SkRec*)aligned, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, c->extract_rep);
         return;
     }
-    if (c->extract_v1)
-    {
-        if (c->mode == GOSS_MODE_KMER_SET) launch_extract<Key1, 0, 16>(c, aligned, mis, nstarts, navail, out);
-        else launch_extract<Key1, 1, 8>(c, aligned, mis, nstarts, navail, out);
-        return;
-    }
     // (extract_rep in graph mode: one strand representative per window -- the fused path's key space for graphs)
     if (c->mode == GOSS_MODE_KMER_SET || c->extract_rep) launch_extract1<0, 16, 8>(c, aligned, mis, nstarts, navail, out);
     else launch_extract1<1, 8, 8>(c, aligned, mis, nstarts, navail, out);
@@ -791,12 +773,6 @@ void extract_dispatch<Key2>(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mi
         launch_extract_records2(c, (const SkRec2*)aligned, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, c->extract_rep);
         return;
     }
-    if (c->extract_v1)
-    {
-        if (c->mode == GOSS_MODE_KMER_SET) launch_extract<Key2, 0, 8>(c, aligned, mis, nstarts, navail, out);
-        else launch_extract<Key2, 1, 4>(c, aligned, mis, nstarts, navail, out);
-        return;
-    }
     if (c->mode == GOSS_MODE_KMER_SET || c->extract_rep) launch_extract2<0, 8, 8>(c, aligned, mis, nstarts, navail, out, 0, 0, 0, c->extract_rep);
     else launch_extract2<1, 4, 8>(c, aligned, mis, nstarts, navail, out);
 }
@@ -834,14 +810,23 @@ inline void check_launch(const char* what)
     if (e != hipSuccess) throw StatusError{GOSS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)};
 }
 
+// The counting table of segment_reduce.
+enum class SegTable {
+    Small,               // 4096 slots, one workgroup of 256 threads per segment
+    Big,                 // one-word keys: 8192 slots, two-word keys: 4096 slots; 1024 threads, 2^rounds workgroups share a segment
+    Wide,                // two-word keys: 6144 slots, one workgroup per segment
+    Rem96,               // two-word keys: 8192 slots of 96-bit remainders, one workgroup per segment
+    Rem96Packed          // ... fed the 12-byte records of the remainders that the second level wrote
+};
+struct SegCount { SegTable table = SegTable::Small; uint32_t rounds = 0; };
+
 inline void launch_seg_hash(goss_gpu_ctx* c, uint32_t nseg, const Key1* keys, const uint64_t* seg_off, const uint64_t* seg_end,
-                            SegOut* so, uint64_t* seg_pos, uint64_t* seg_cnt, Key1* sk, uint32_t* sc, uint32_t rem_bits, int big)
+                            SegOut* so, uint64_t* seg_pos, uint64_t* seg_cnt, Key1* sk, uint32_t* sc, uint32_t rem_bits, SegCount how)
 {
-    // big: 0 = the 4096-slot table; 1 + r = the 8192-slot table, every segment shared by 2^r workgroups
-    if (big > 1)
-        hipLaunchKernelGGL(seg_hash_reduce_shared_kernel, unit_grid((uint64_t)nseg << (big - 1)), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end,
-                           so, seg_pos, seg_cnt, sk, sc, rem_bits, (uint32_t)(big - 1));
-    else if (big)
+    if (how.table == SegTable::Big && how.rounds)
+        hipLaunchKernelGGL(seg_hash_reduce_shared_kernel, unit_grid((uint64_t)nseg << how.rounds), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end,
+                           so, seg_pos, seg_cnt, sk, sc, rem_bits, how.rounds);
+    else if (how.table == SegTable::Big)
         hipLaunchKernelGGL(seg_hash_reduce_big_kernel, unit_grid(nseg), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end,
                            so, seg_pos, seg_cnt, sk, sc, rem_bits, 0u);
     else
@@ -849,22 +834,20 @@ inline void launch_seg_hash(goss_gpu_ctx* c, uint32_t nseg, const Key1* keys, co
                            rem_bits);
 }
 inline void launch_seg_hash(goss_gpu_ctx* c, uint32_t nseg, const Key2* keys, const uint64_t* seg_off, const uint64_t* seg_end,
-                            SegOut* so, uint64_t* seg_pos, uint64_t* seg_cnt, Key2* sk, uint32_t* sc, uint32_t rem_bits, int big)
+                            SegOut* so, uint64_t* seg_pos, uint64_t* seg_cnt, Key2* sk, uint32_t* sc, uint32_t rem_bits, SegCount how)
 {
-    // big: -2 = the 8192-slot table of 96-bit remainders, -1 = the 6144-slot table, one workgroup per segment each;
-    // 1 + r = the 4096-slot table, 2^r workgroups per segment
-    if (big == -3)      // the 96-bit-remainder table fed 12-byte records by the second level
+    if (how.table == SegTable::Rem96Packed)
         hipLaunchKernelGGL(seg_hash_reduce96p_kernel, unit_grid(nseg), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end, so,
                            seg_pos, seg_cnt, sk, sc, rem_bits);
-    else if (big == -2)
+    else if (how.table == SegTable::Rem96)
         hipLaunchKernelGGL(seg_hash_reduce96_kernel, unit_grid(nseg), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end, so,
                            seg_pos, seg_cnt, sk, sc, rem_bits);
-    else if (big < 0)
+    else if (how.table == SegTable::Wide)
         hipLaunchKernelGGL(seg_hash_reduce2_wide_kernel, unit_grid(nseg), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end, so,
                            seg_pos, seg_cnt, sk, sc, rem_bits);
-    else if (big)
-        hipLaunchKernelGGL(seg_hash_reduce2_big_kernel, unit_grid((uint64_t)nseg << (big - 1)), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end, so,
-                           seg_pos, seg_cnt, sk, sc, rem_bits, (uint32_t)(big - 1));
+    else if (how.table == SegTable::Big)
+        hipLaunchKernelGGL(seg_hash_reduce2_big_kernel, unit_grid((uint64_t)nseg << how.rounds), dim3(kSegBigThreads), 0, c->stream, keys, seg_off, seg_end, so,
+                           seg_pos, seg_cnt, sk, sc, rem_bits, how.rounds);
     else
         hipLaunchKernelGGL(seg_hash_reduce2_kernel, unit_grid(nseg), dim3(kTB), 0, c->stream, keys, seg_off, seg_end, so, seg_pos, seg_cnt, sk, sc,
                            rem_bits);
@@ -1010,7 +993,7 @@ uint64_t estimate_distinct(goss_gpu_ctx* c, const K* keys, uint64_t n)
 // permuted, in ka or kb (*in_b_out).
 template <class K>
 int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segbits, Run* out, const uint64_t* seg_beg = nullptr,
-                   const uint64_t* seg_end = nullptr, int big = 0);
+                   const uint64_t* seg_end = nullptr, SegCount how = {});
 
 template <class K>
 int segment_count(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n, uint32_t segbits, bool* in_b_out, Run* out)
@@ -1118,12 +1101,12 @@ int count_overflowed_units(goss_gpu_ctx* c, uint32_t nunit, const uint64_t* d_be
 // the bounds are found by binary search in the dense, partitioned array.
 template <class K>
 int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segbits, Run* out, const uint64_t* seg_beg,
-                   const uint64_t* seg_end, int big)
+                   const uint64_t* seg_end, SegCount how)
 {
     const uint32_t keybits = 2 * c->len;
     const uint32_t shift = keybits - segbits;
     const uint32_t nseg = 1u << segbits;
-    const uint32_t nunit = big > 1 ? nseg << (big - 1) : nseg;      // (segment, round) units of the staging area
+    const uint32_t nunit = nseg << how.rounds;      // (segment, round) units of the staging area
     uint64_t mark = c->arena.mark();
     PhaseTimer t(c, GOSS_T_REDUCE, n);
     uint64_t* seg_off = (uint64_t*)c->arena.temp(((uint64_t)nseg + 1) * 8);
@@ -1144,12 +1127,12 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
                            (const K*)part, n, shift, nseg, seg_off);
         seg_beg = seg_off; seg_end = seg_off + 1;
     }
-    launch_seg_hash(c, nseg, (const K*)part, seg_beg, seg_end, so, seg_pos, seg_cnt, stage_keys, stage_counts, shift, big);
+    launch_seg_hash(c, nseg, (const K*)part, seg_beg, seg_end, so, seg_pos, seg_cnt, stage_keys, stage_counts, shift, how);
     check_launch("segment counting kernel");
     SegOut* h = (SegOut*)c->h_pinned;
     HIP_TRY(hipMemcpyAsync(h, so, sizeof(SegOut), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h->overflow == 1u && big <= 1 && c->overflow_by_sort)
+    if (h->overflow == 1u && how.rounds == 0 && c->overflow_by_sort)
     {
         // (tables that overflowed, nothing else: those segments by sort -- not the forms in which several workgroups
         // share a segment, whose units are not ranges of `part`)
@@ -1158,7 +1141,7 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
             [&](uint32_t u, uint64_t first, uint64_t cnt_u, K* dst) {
                 if constexpr (std::is_same<K, Key2>::value)
                 {
-                    if (big == -3)          // (12-byte records of the remainders: the second level's packed form)
+                    if (how.table == SegTable::Rem96Packed)          // (12-byte records of the remainders: the second level's packed form)
                     {
                         hipLaunchKernelGGL(expand_rem96_kernel, dim3(grid_for(cnt_u, kTB)), dim3(kTB), 0, c->stream,
                                            reinterpret_cast<const Rem96*>(part) + first, cnt_u, (uint64_t)u, shift, dst);
@@ -1201,7 +1184,7 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
 }
 
 // The same for the 32-bit-remainder form (subpart32_kernel's output): nseg = 2^17 .. 2^20 segments of u32 remainders, counted by
-// seg_hash_reduce32_kernel in tables of `slots` slots; `spare` (n one-word keys) is the staging area.
+// seg_hash_reduce32b_kernel in tables of `slots` slots; `spare` (n one-word keys) is the staging area.
 // Returns 0, 1 (a table overflowed) or 2 (staging area too small) like segment_reduce.
 int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_t n, Run* out, const uint64_t* seg_beg,
                      const uint64_t* seg_end, int slots, bool squeeze, uint32_t rbits, uint32_t sqbit, uint32_t nseg, uint32_t split_bits)
@@ -1218,23 +1201,14 @@ int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_
     SegOut hso{};
     hso.stage_cap = cap;
     HIP_TRY(hipMemcpyAsync(so, &hso, sizeof(SegOut), hipMemcpyHostToDevice, c->stream));
-#define GOSS_LAUNCH_R32(KERNEL, SLOTS, SQ)                                                                               \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<SLOTS, SQ>), unit_grid(nseg), dim3(SLOTS <= 4096 ? kTB : SLOTS / 4096 * kTB), 0, c->stream, rems, seg_beg, \
+#define GOSS_LAUNCH_R32(SLOTS, SQ)                                                                                       \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_hash_reduce32b_kernel<SLOTS, SQ>), unit_grid(nseg), dim3(SLOTS <= 4096 ? kTB : SLOTS / 4096 * kTB), 0, c->stream, rems, seg_beg, \
                        seg_end, so, seg_pos, seg_cnt, stage_keys, stage_counts, rbits, sqbit, split_bits)
-    // (round 5: buckets of four remainders, home bucket only in the fast path; GOSS_GPU_R32_FORM=0: the pair layout, whose
-    // largest table has 4 096 slots)
-    if (c->r32_form)
-    {
-        if (slots == 2048) { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 2048, true); else GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 2048, false); }
-        else if (slots == 8192) { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 8192, true); else GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 8192, false); }
-        else if (slots == 16384) { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 16384, true); else GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 16384, false); }
-        else { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 4096, true); else GOSS_LAUNCH_R32(seg_hash_reduce32b_kernel, 4096, false); }
-    }
-    else
-    {
-        if (slots == 2048) { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32_kernel, 2048, true); else GOSS_LAUNCH_R32(seg_hash_reduce32_kernel, 2048, false); }
-        else { if (squeeze) GOSS_LAUNCH_R32(seg_hash_reduce32_kernel, 4096, true); else GOSS_LAUNCH_R32(seg_hash_reduce32_kernel, 4096, false); }
-    }
+    // (buckets of four remainders, home bucket only in the fast path)
+    if (slots == 2048) { if (squeeze) GOSS_LAUNCH_R32(2048, true); else GOSS_LAUNCH_R32(2048, false); }
+    else if (slots == 8192) { if (squeeze) GOSS_LAUNCH_R32(8192, true); else GOSS_LAUNCH_R32(8192, false); }
+    else if (slots == 16384) { if (squeeze) GOSS_LAUNCH_R32(16384, true); else GOSS_LAUNCH_R32(16384, false); }
+    else { if (squeeze) GOSS_LAUNCH_R32(4096, true); else GOSS_LAUNCH_R32(4096, false); }
 #undef GOSS_LAUNCH_R32
     check_launch("32-bit segment counting kernel");
     SegOut* h = (SegOut*)c->h_pinned;
@@ -1328,22 +1302,6 @@ Run count_keys(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n)
     if (c->debug) std::fprintf(stderr, "libgossgpu: count_keys: full sort of %llu keys -> %llu distinct\n", (unsigned long long)n, (unsigned long long)r.m);
     return r;
 }
-
-// ---- fused extraction + first partition pass (one-word canonical keys) ----------------------
-// Returns true when it counted the chunk (run appended, counters updated); false = not
-// applicable or a region overflowed / a later stage asked for a retry: the caller then runs the
-// unfused sequence on the same (untouched) input.
-//
-// Two forms.  LSD (any number of partition digits): the fused kernel partitions on the lowest
-// partition digit into 256 bucket regions, the remaining digits are look-back passes (the first
-// of them reads the regions).  MSD (exactly two digits, the common case): the fused kernel
-// partitions on the HIGH digit and the second pass places the keys of region b by their LOW digit
-// into 65 536 sub-regions -- the segments of the counting kernel -- with atomic cursors: no
-// look-back chain and no digit histograms at all.  Region and sub-region sizes come from a sample
-// of the input (the whole chunk when it is small), with 5 / 6 standard deviations of slack.
-template <class K>
-int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segbits, Run* out, const uint64_t* seg_beg,
-                   const uint64_t* seg_end, int big);
 
 // A run counted in strand-representative space (extract1_part_kernel, MODE 0) -> the run the rest of
 // the library expects: every key replaced by gossamer's canonical form (the strand with the smaller
@@ -1490,814 +1448,8 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
     if (c->debug) std::fprintf(stderr, "libgossgpu: %llu strand pairs expanded (%llu palindromes)\n", (unsigned long long)m, (unsigned long long)npads);
 }
 
-// Returns kFusedDone, kFusedDeclined (the caller runs the unfused sequence) or kFusedNeedFull (the
-// key buffers were sized for fewer valid windows than the sample shows: the caller retries with
-// buffers of one key per window start).
-enum { kFusedDeclined = 0, kFusedDone = 1, kFusedNeedFull = 2 };
-constexpr uint32_t kFusedGrid = 256 * GOSS_E1_OCC;                         // workgroups of extract1_part_kernel: 3 per CU (52 KB of LDS each)
-#ifndef GOSS_FUSED_NKEYS2
-#define GOSS_FUSED_NKEYS2 14          // keys per thread of extract2_part_kernel (tile of 3584 keys + carry = 70 KB of LDS)
-#endif
-#ifndef GOSS_FUSED_GRID2
-#define GOSS_FUSED_GRID2 512
-#endif
-constexpr uint32_t kFusedGrid2 = GOSS_FUSED_GRID2;                        // ... of extract2_part_kernel: 2 per CU (75 KB)
-constexpr double kValidSlackA = 1.06, kValidSlackB = 1.17;   // key buffer slots per expected key (bucket regions; sub-regions with their six sigma each: 1.149 measured on C4's two-word keys)
-constexpr uint64_t kValidSizingMin = 640u << 20;             // window starts: smaller chunks are sampled whole into a full buffer
-
-template <class K>
-int process_chunk_fused(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, uint64_t navail, K* ka, uint64_t ka_slots,
-                        K* kb, uint64_t kb_slots)
-{
-    constexpr bool kOne = std::is_same<K, Key1>::value;          // one-word keys
-    const uint32_t keybits = 2 * c->len;
-    if (c->rec_mode && !kOne && c->mode == GOSS_MODE_GRAPH && !c->graph_rep) return kFusedDeclined;          // (the record form extracts one key per window)
-    // Graph mode wants both strands of every window (ReverseComplementAdapter.hh:34-55), and both always come together:
-    // the fused path counts ONE strand representative per window -- half the keys through the partition and the tables
-    // -- and the run is expanded into both strands after counting (expand_graph_run).  Inside this function such a chunk
-    // is a k-mer-set chunk of (k+1)-mers in representative space.
-    const bool rep_graph = c->mode == GOSS_MODE_GRAPH && c->graph_rep;
-    const bool rep_kmer = c->mode != GOSS_MODE_GRAPH && kOne;    // (one-word k-mer sets: representatives, canonical forms after counting)
-    const bool use_rep = rep_graph || rep_kmer;
-    if (!c->fused || c->path != 0 || !c->lookback || c->ordered_tiles ||
-        c->extract_v1 || nstarts < c->fused_min || keybits < (uint32_t)kSegBits + 8)
-        return kFusedDeclined;
-    constexpr int kTile = SortCfg<K, false>::kTile;
-    uint64_t mark = c->arena.mark();
-    struct Release { goss_gpu_ctx* c; uint64_t m; ~Release() { c->arena.release(m); } } release{c, mark};
-    auto decline = [&](const char* why) {
-        if (c->debug) std::fprintf(stderr, "libgossgpu: fused path declined (%s), %llu window starts\n", why, (unsigned long long)nstarts);
-        return (int)kFusedDeclined;
-    };
-
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!c->debug) return;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::fprintf(stderr, "libgossgpu: fused path: %-28s at %8.3f ms\n", what,
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
-
-    // 1. a sample of the keys: slices spread evenly over the chunk, extracted with the plain
-    //    kernel.  The two-level form needs the joint histogram of two digits (65 536 bins), hence
-    //    a larger sample: 1/64 of the chunk but at least 160 M window starts; a chunk of up to 640 M
-    //    window starts is sampled whole (exact sizes, +4 % extraction work at most).
-    const bool want_msd = c->fused_msd;
-    uint64_t sample_starts = nstarts <= (16u << 20) ? nstarts : (4u << 20);
-    if (want_msd) sample_starts = nstarts <= (640u << 20) ? nstarts : std::max<uint64_t>(160u << 20, nstarts / 64);
-    // keys that the 32-bit-remainder forms take (by their width): half the sample -- their sub-regions are 4-byte slots,
-    // which have the room for the wider six-sigma margins of a smaller sample (22 % instead of 15 % on C2), and the
-    // sample's extraction, spectrum and joint histogram are 3 ms of a 97 ms step
-    {
-        bool width_ok = false;
-        if (kOne && c->rem32 && keybits >= 8 + 9 + 8)
-            for (uint32_t b2 = kSub32BitsMin; b2 <= (uint32_t)kSub32BitsMax; ++b2)
-            {
-                const uint32_t rb = keybits - 8 - b2;
-                const bool sq = (rep_kmer || rep_graph) && (c->len & 1u) && rb == 33;
-                width_ok = width_ok || rb - (sq ? 1u : 0u) <= 32;
-            }
-        if (want_msd && width_ok && nstarts > (640u << 20)) sample_starts = std::max<uint64_t>(80u << 20, nstarts / 128);
-    }
-    // slices are whole super-tiles of the plain kernel (32 768 window starts) and lie a multiple
-    // of 16 bytes apart, so that ONE strided launch extracts them all
-    const bool graph_mode = c->mode == GOSS_MODE_GRAPH && !rep_graph;
-    // window starts per super-tile of the plain kernels: extract1_kernel<0,16,8> / <1,8,8>, extract2_kernel<0,8,8> / <1,4,8>
-    const uint64_t kPlainSuper = 8ULL * kTB * (kOne ? (graph_mode ? 8 : 16) : (graph_mode ? 4 : 8));
-    // a slice is ONE super-tile (~217 reads of 150 bp): thousands of slices follow a drifting
-    // k-mer distribution (sorted inputs) far better than a few long ones
-    const uint64_t nslices = sample_starts >= nstarts ? 1 : std::max<uint64_t>(64, sample_starts / kPlainSuper);
-    const uint64_t slice_starts = sample_starts >= nstarts ? nstarts : kPlainSuper;
-    if (nslices > 1 && nstarts < 4 * nslices * slice_starts) return decline("chunk smaller than the sample");
-    // key buffers sized from the estimated share of valid windows (process_chunk): they must hold
-    // the sample whatever it contains
-    const uint64_t kps = graph_mode ? 2 : 1;
-    const bool reduced = ka_slots < nstarts * kps || kb_slots < nstarts * kps;
-    if (reduced && (nslices == 1 || nslices * slice_starts * kps > std::min(ka_slots, kb_slots))) return (int)kFusedNeedFull;
-    const uint64_t slice_stride = nslices > 1 ? ((nstarts - slice_starts) / (nslices - 1)) & ~15ULL : 0;
-    // rep: one-word k-mer sets in strand-representative space (what the fused kernel counts in, unless canon_l1 below)
-    auto extract_sample = [&](bool rep) {
-    c->mute_timing = true;
-    HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(ExtractCounters), c->stream));
-    {
-        const uintptr_t addr0 = (uintptr_t)d_bases;
-        const uint32_t mis0 = c->rec_mode ? 0u : (uint32_t)(addr0 & 15u);          // (records are taken where they lie)
-        // (a packed string whose sample is the whole chunk: the slice kernels below, told to take every tile in turn --
-        // they have a packed form, the plain kernels behind extract_dispatch read bytes)
-        const bool whole_pk = nslices == 1 && c->pk.on && !c->rec_mode;
-        if (nslices == 1 && !whole_pk)
-        {
-            c->extract_rep = use_rep && rep;
-            extract_dispatch<K>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka);
-            c->extract_rep = false;
-        }
-        else if (!kOne && c->rec_mode)
-        {
-            // slices of kPlainSuper window slots of two-word records
-            const uint64_t P = rec_slots(c);
-            const uint64_t slice_groups = std::max<uint64_t>(1, slice_starts / P / kRecGroup);
-            launch_extract_records2(c, (const SkRec2*)d_bases, nstarts / P, (Key2*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
-                                    rep_graph && rep);
-        }
-        else if constexpr (!kOne)
-        {
-            const uint64_t slice_tiles = whole_pk ? 0 : slice_starts / kPlainSuper, nsuper = whole_pk ? (nstarts + kPlainSuper - 1) / kPlainSuper : slice_tiles * nslices;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper, 2048);
-            (void)grid;
-            if (graph_mode) launch_extract2<1, 4, 8>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka, slice_tiles, slice_stride, nsuper);
-            else launch_extract2<0, 8, 8>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka, slice_tiles, slice_stride, nsuper, rep_graph && rep);
-        }
-        else if (c->rec_mode)
-        {
-            // slices of kPlainSuper window slots = 2048 records each, in strand-representative space for k-mer sets
-            const uint64_t P = rec_slots(c);
-            const uint64_t slice_groups = slice_starts / P / kRecGroup;
-            launch_extract_records(c, (const SkRec*)d_bases, nstarts / P, (Key1*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
-                                   use_rep && rep);
-        }
-        else
-        {
-            const uint64_t slice_tiles = whole_pk ? 0 : slice_starts / kPlainSuper, nsuper = whole_pk ? (nstarts + kPlainSuper - 1) / kPlainSuper : slice_tiles * nslices;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper, 2048);
-            const uint8_t* src = (const uint8_t*)(addr0 - mis0); const uint16_t* pbad = nullptr;
-            if (c->pk.on) pk_ptrs(c, src, &src, &pbad);
-#define GOSS_LAUNCH_SAMPLE1(MODE, P, REP, PK)                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, 8, 8, REP, PK>), dim3(grid), dim3(kTB), 0, c->stream, src, mis0, nstarts, navail, \
-                       c->len, ka, c->d_ctr, 0xFFFFFFFFu, nsuper, slice_tiles, slice_stride, pbad)
-            if (graph_mode) { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(1, 8, false, true); else GOSS_LAUNCH_SAMPLE1(1, 8, false, false); }
-            else if (rep)      // strand representatives: the key space the fused kernel counts in
-            { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(0, 16, true, true); else GOSS_LAUNCH_SAMPLE1(0, 16, true, false); }
-            else { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(0, 16, false, true); else GOSS_LAUNCH_SAMPLE1(0, 16, false, false); }
-#undef GOSS_LAUNCH_SAMPLE1
-        }
-    }
-    c->extract_hist_shift = 0xFFFFFFFFu;
-    ExtractCounters* hcs = (ExtractCounters*)c->h_pinned;
-    HIP_TRY(hipMemcpyAsync(hcs, c->d_ctr, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->mute_timing = false;
-    return (uint64_t)hcs->keys_out;
-    };
-    const uint64_t ns = extract_sample(true);
-    if (ns < (1u << 20)) return decline("mostly non-bases");
-    lap("sample extracted");
-    const bool exact = nslices == 1;                                   // the sample is the chunk
-    const double scale = (double)nstarts / (double)(nslices * slice_starts);
-    const uint64_t n_exp = (uint64_t)((double)ns * scale);          // expected number of keys
-    uint64_t m_rare = 0;
-    uint64_t m_est = spectrum_estimate<K>(c, ka, ns, (double)n_exp, &m_rare);
-    if (c->est_scale != 1.0) m_est = (uint64_t)((double)m_est * c->est_scale);      // tests: a wrong estimate on purpose
-    m_rare = std::min(m_rare, m_est);
-    lap("distinct keys estimated");
-    if (m_est == 0 || m_est > n_exp / 3) return decline("too little duplication for the segment path");
-    // One-word k-mer sets are counted as strand representatives and mapped to gossamer's canonical form afterwards -- a
-    // re-ordering of the DISTINCT keys (0.06 ms per million), cheap beside two FNV hashes per WINDOW in the first level
-    // (+ ~2.4 ms per 10^9 windows) while distinct keys are few.  Reads with many errors turn that round (2e9 distinct
-    // 25-mers of 12.6e9 windows: 116 ms of re-ordering against ~30 ms of hashing): from 5 % distinct keys per window on
-    // (canon_l1_at) the first level computes the canonical form itself and the run needs no re-ordering.
-    // A chunk that is ONE OF SEVERAL shares the re-ordering with the others -- the runs are merged in representative
-    // space and re-ordered once -- so what counts is the whole build: its windows W (what the caller said it will push,
-    // goss_gpu_expect_bases; else what has been counted plus this chunk, times four when more is known to follow) and
-    // its distinct keys D = the chunk's frequent keys (more of the same input mostly brings THEM again) + its keys of
-    // multiplicity ~1 scaled to W (every chunk brings its own).  C2 from FASTQ: thirteen chunks of 0.8 G windows each
-    // see all 10^8 k-mers of the genome (12 % of their windows) -- per chunk that read "canonical", 67 ms of first
-    // level where representatives take 31, ten second-level bits, a re-ordering per run; of the build's 12.6 G windows
-    // they are 0.8 %.  Once a chunk has chosen, the chunks that follow count in the same space while its run waits:
-    // a run in canonical space among runs of representatives sends every one of those through a re-ordering of its own.
-    bool canon_auto = (double)m_est > c->canon_l1_at * (double)n_exp;
-    if (rep_kmer && c->canon_l1 == 1)
-    {
-        if (c->space_choice >= 0 && !c->runs.empty()) canon_auto = c->space_choice == 1;
-        else
-        {
-            const double w_c = (double)n_exp;
-            // (what follows: known for the rest of the push being counted; a guess -- three times as much again -- when
-            // that push is a staging buffer that filled up under a caller who goes on pushing)
-            const double w_push = w_c + (double)c->more_starts * std::min(1.0, c->valid_frac);          // this push, from this chunk on
-            double w_all = (double)c->windows + w_push * (c->more_follows ? 4.0 : 1.0);
-            if (c->expect_bases) w_all = std::max(w_all, (double)c->expect_bases * std::min(1.0, c->valid_frac));
-            const double d_all = (double)(m_est - m_rare) + (double)m_rare * (w_all / w_c);
-            canon_auto = d_all > c->canon_l1_at * w_all;
-            if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: %.0f distinct keys (%.0f of multiplicity ~1) of %.0f windows here, %.0f of %.0f in all: %s\n",
-                                       (double)m_est, (double)m_rare, w_c, d_all, w_all, canon_auto ? "canonical forms in the first level" : "strand representatives");
-        }
-    }
-    const bool canon_l1 = rep_kmer && (c->canon_l1 == 2 || (c->canon_l1 == 1 && canon_auto));
-    if (rep_kmer && c->canon_l1 == 1) c->space_choice = canon_l1 ? 1 : 0;
-    if (canon_l1)
-    {
-        // (the regions are sized from the sample: it must be in the key space the first level writes)
-        const uint64_t ns2 = extract_sample(false);
-        if (ns2 != ns) throw StatusError{GOSS_ERR_HIP, "fused path: the sample changed between two extractions"};
-        lap("sample extracted again (canonical forms)");
-    }
-    // buffers sized from the estimated share of valid windows must hold what the sample promises
-    {
-        if (reduced && ((double)n_exp * 1.035 + 262144.0 > (double)ka_slots || (double)n_exp * 1.02 + 6.0e6 > (double)kb_slots))
-        {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: %llu keys expected, buffers of %llu / %llu slots too small\n",
-                                       (unsigned long long)n_exp, (unsigned long long)ka_slots, (unsigned long long)kb_slots);
-            return (int)kFusedNeedFull;
-        }
-    }
-    const uint64_t limit = SegCfg<K>::kLimit;
-    uint32_t segbits = kSegBits;
-    while (segbits < (uint32_t)kSegBitsMax && (m_est >> segbits) > limit * 3 / 4) segbits += 4;
-    // one-word keys: between 3/4 of the small table and 3/4 of the big one per 16-bit segment, the
-    // two-level form with the big counting table saves the third partition digit
-    // (up to 4 workgroups sharing a segment, each counting the keys of one value of the next bits)
-    int big_table = 0;
-    if (kOne && c->fused_msd && c->big_table && segbits > (uint32_t)kSegBits && keybits >= (uint32_t)kSegBits + 8 + 2)
-        for (int r = std::max(0, c->big_rounds_min); r <= c->big_rounds_max; ++r)
-            if ((m_est >> (kSegBits + r)) <= (uint64_t)kSegBigLimit * 17 / 20) { segbits = kSegBits; big_table = 1 + r; break; }   // (an overflow costs one more counting pass, no more)
-    // two-word keys: the 4096-slot table, up to two workgroups per segment (a pass over 16-byte
-    // keys costs more than one over 8-byte keys)
-    // two-word keys whose bits below a 16-bit prefix fit 96: 16-byte slots, 8192 of them
-    if (!kOne && c->fused_msd && c->big_table && c->table96 && segbits > (uint32_t)kSegBits && keybits - kSegBits <= 96 &&
-        c->big_rounds_min == 0 && (m_est >> kSegBits) <= (uint64_t)kSeg96Limit * 3 / 4)
-    { segbits = kSegBits; big_table = -2; }
-    if (!kOne && !big_table && c->fused_msd && c->big_table && segbits > (uint32_t)kSegBits)
-        for (int r = std::max(0, c->big_rounds_min); r <= std::min(1, c->big_rounds_max); ++r)
-        {
-            if ((m_est >> (kSegBits + r)) <= (uint64_t)kSegBigLimit2 * 3 / 4) { segbits = kSegBits; big_table = 1 + r; break; }
-            // between the two: the 6144-slot table, still one workgroup (and one read) per segment
-            if (r == 0 && c->wide_table && (m_est >> kSegBits) <= (uint64_t)kSegWideLimit2 * 3 / 4) { segbits = kSegBits; big_table = -1; break; }
-        }
-    // one-word keys whose bits below a 17- to 20-bit prefix fit 32 (an odd-length k-mer's strand representative has one
-    // bit that is always clear): 9 to 12 bits at the second level, which then writes -- and the counting kernel reads --
-    // 4-byte remainders instead of 8-byte keys (kernels_partition.hpp: subpart32_kernel).  The fewest bits whose
-    // segments hold the estimated distinct keys in an LDS table (2048 slots at 9 bits when they do, else 4096).
-    uint32_t r32_bits = 0, rbits32 = 0, r32_split = 0;
-    bool squeeze = false;
-    const uint32_t sqbit32 = c->len - 1;
-    int r32_slots = 0;
-    if (kOne && c->rem32 && c->fused_msd && c->big_rounds_min == 0)
-    {
-        // (second-level bits, third-level bits) in the order of what they cost on C2's 12.6 G keys: the second level 31 ms
-        // with 9 bits and 46 with 10 (shorter runs), the third level ~30 ms whatever it splits into -- so ten bits before a
-        // third level, and nine bits + a third level before ten + a third level.  The first pair whose remainder fits 32
-        // bits and whose segments hold the estimated distinct keys in an LDS table (2048 slots at (9, 0) when they
-        // do, else 4096 with a quarter to spare).
-        // Reads with errors (round 5): where ten bits and the 4 096-slot table do not do, the tables of 8 192 and 16 384 slots
-        // (512 / 1 024 threads) come BEFORE a third level -- that level is a pass over all keys (~30 ms on C2's 12.6 G), the
-        // larger table the same counting on fewer, longer segments.  Third element: the largest table of the candidate.
-        static const uint32_t order[][3] = {{9, 0, 4096}, {10, 0, 4096}, {10, 0, 8192}, {10, 0, 16384}, {9, 1, 4096}, {9, 2, 4096}, {9, 3, 4096}, {9, 4, 4096},
-                                            {10, 1, 4096}, {10, 2, 4096}, {10, 3, 4096}, {10, 4, 4096}};
-        for (const auto& cand : order)
-        {
-            const uint32_t b2 = cand[0], b3 = cand[1], table = cand[2];
-            if (table > 4096u && !(c->r32_form && c->big_r32 && !c->rem32_slots)) continue;
-            if (b2 < c->rem32_bits_min || b3 < c->rem32_split_min) continue;
-            if (keybits < 8 + b2 + 8) continue;
-            const uint32_t rb = keybits - 8 - b2;
-            const bool sq = !graph_mode && !canon_l1 && (c->len & 1u) && rb == 33;
-            if (rb - (sq ? 1u : 0u) > 32 || rb - (sq ? 1u : 0u) < b3 + 8) continue;
-            const uint64_t per = m_est >> (8 + b2 + b3);
-            int slots = 0;
-            if (c->rem32_slots) slots = per <= (uint64_t)(c->rem32_slots / 4 * 3) || (b2 == 10 && b3 == (uint32_t)kSub32SplitMax) ? c->rem32_slots : 0;
-            // (buckets of four: what is not at home costs a second look, and at a load of 0.37 that is 1.5 % of the keys, at
-            // 0.19 a per-mille -- the small table only where it stays that empty)
-            else if (per <= (c->r32_small_max ? c->r32_small_max : c->r32_form ? 400u : 2048u / 4 * 3 * 3 / 4) && b3 == 0 && b2 == (uint32_t)kSub32BitsMin) slots = 2048;
-            else if (per <= (uint64_t)table / 4 * 3 * 3 / 4) slots = (int)table;
-            if (!slots) continue;
-            r32_slots = slots; r32_bits = b2; rbits32 = rb; squeeze = sq; r32_split = b3;
-            break;
-        }
-    }
-    if (r32_slots) { segbits = kSegBits; big_table = 0; }
-    const uint32_t r32_digits = 1u << r32_bits, r32_regions = 256u << r32_bits;
-    if ((!big_table && !r32_slots && (m_est >> segbits) > limit) || segbits + 8 > keybits)
-        return decline("too many distinct keys per segment");
-    const uint32_t shift = keybits - segbits;
-    const uint32_t npass = (segbits + 7) / 8;
-
-    // 2. histograms of the sample: joint over both digits for the two-level form, else of the
-    //    first partition digit only
-    std::vector<unsigned long long> hh(256, 0);          // the fused kernel's digit
-    std::vector<uint64_t> joint;                         // [high*256 + low], two-level form only
-    std::vector<uint64_t> joint17;                       // [high*512 + low9], 32-bit-remainder form
-    bool msd = want_msd && segbits == 16;
-    if (!msd) r32_slots = 0;
-    if (msd)
-    {
-        // the sample's joint histogram of both digits (kept out of the per-kernel timing): one pass over the sample
-        // with the bins in LDS (a 16-bit partition of the sample + segment bounds took 2.4 ms on C2, this 0.9);
-        // 17 bits (four sweeps) for the 32-bit-remainder form, whose pairs of bins are the 16-bit form's
-        const uint32_t jbins = r32_slots ? r32_regions : 65536u;
-        c->mute_timing = true;
-        unsigned long long* jh = (unsigned long long*)c->arena.temp((uint64_t)jbins * 8);
-        HIP_TRY(hipMemsetAsync(jh, 0, (uint64_t)jbins * 8, c->stream));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(joint_hist_kernel<K>), dim3(256), dim3(kJointThreads), 0, c->stream, (const K*)ka, ns,
-                           r32_slots ? rbits32 : shift, jh, jbins / 32768u);
-        c->mute_timing = false;
-        std::vector<uint64_t> ho(jbins);
-        HIP_TRY(hipMemcpyAsync(ho.data(), jh, (uint64_t)jbins * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        joint.resize(65536);
-        if (r32_slots)
-        {
-            joint17.swap(ho);
-            const uint32_t fold = r32_regions / 65536u;          // bins of this form per bin of the 16-bit form
-            for (uint32_t i = 0; i < 65536; ++i) { uint64_t a = 0; for (uint32_t j = 0; j < fold; ++j) a += joint17[i * fold + j]; joint[i] = a; }
-        }
-        else joint.swap(ho);
-        for (uint32_t i = 0; i < 65536; ++i) hh[i >> 8] += joint[i];
-    }
-    else
-    {
-        unsigned long long* shist = (unsigned long long*)c->arena.temp(256 * 8);
-        HIP_TRY(hipMemsetAsync(shist, 0, 256 * 8, c->stream));
-        c->mute_timing = true;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(global_hist_kernel<K>), dim3(256), dim3(kTB), 0, c->stream, (const K*)ka, ns, shift, 1u, shist);
-        c->mute_timing = false;
-        HIP_TRY(hipMemcpyAsync(hh.data(), shist, 256 * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-
-    // sub-regions of the second buffer (two-level form): expected size + six standard deviations
-    // of the sample count; they must fit, else the one-level form is used
-    std::vector<SubTable> hsub;
-    std::vector<uint64_t> hsub32_start;          // 32-bit-remainder form: first slot and capacity of every sub-region
-    std::vector<uint32_t> hsub32_cap;
-    if (msd && r32_slots)
-    {
-        // 2^17 .. 2^20 sub-regions of 4-byte slots in the second key buffer; every start a multiple of four slots (the
-        // counting kernel loads 16 bytes per lane)
-        hsub32_start.resize(r32_regions);
-        hsub32_cap.resize(r32_regions);
-        uint64_t at = 0;
-        bool fits = true;
-        for (uint32_t i = 0; i < r32_regions; ++i)
-        {
-            const double h = (double)joint17[i];
-            const uint64_t cap = exact ? (((uint64_t)(h * c->fused_capscale)) + 3) & ~3ULL
-                                       : (((uint64_t)(((h + 6.0 * std::sqrt(h + 1.0) + 4.0) * scale + 64.0) * c->fused_capscale) + 15) & ~15ULL);
-            if (cap > 0xFFFF0000ULL) fits = false;
-            hsub32_start[i] = at; hsub32_cap[i] = (uint32_t)cap;
-            at += cap;
-            // (the second level addresses a region's sub-regions with 32-bit offsets from the region's first)
-            if ((i & (r32_digits - 1u)) == r32_digits - 1u && at - hsub32_start[i - (r32_digits - 1u)] > 0xFFFF0000ULL) fits = false;
-        }
-        if (!fits || at > 2 * kb_slots || (r32_split && at > 2 * ka_slots))          // (the third level writes the remainders into the first buffer)
-        {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: 32-bit sub-regions need %llu slots of %llu: 8-byte form\n",
-                                       (unsigned long long)at, (unsigned long long)(2 * kb_slots));
-            r32_slots = 0;
-            hsub32_start.clear(); hsub32_cap.clear();
-            if ((m_est >> segbits) > limit) return decline("too many distinct keys per segment");
-        }
-    }
-    if (msd && !r32_slots)
-    {
-        hsub.resize(1);
-        uint64_t at = 0;
-        for (uint32_t i = 0; i < 65536; ++i)
-        {
-            const double h = (double)joint[i];
-            // exact counts need no slack (and a small chunk cannot afford 65 536 paddings)
-            const uint64_t cap = exact ? (uint64_t)(h * c->fused_capscale)
-                                       : (((uint64_t)(((h + 6.0 * std::sqrt(h + 1.0) + 4.0) * scale + 64.0) * c->fused_capscale) + 15) & ~15ULL);
-            hsub[0].start[i] = at; hsub[0].cap[i] = cap;
-            at += cap;
-        }
-        if (at > kb_slots && reduced)
-        {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu\n", (unsigned long long)at, (unsigned long long)kb_slots);
-            return (int)kFusedNeedFull;
-        }
-        if (at > kb_slots)
-        {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu: one-level form\n",
-                                       (unsigned long long)at, (unsigned long long)kb_slots);
-            if (big_table) return decline("sub-regions do not fit and the big table needs them");
-            msd = false;
-            // the one-level form partitions on the LOW digit: its marginal histogram
-            std::fill(hh.begin(), hh.end(), 0ULL);
-            for (uint32_t i = 0; i < 65536; ++i) hh[i & 255u] += joint[i];
-            hsub.clear();
-        }
-    }
-    const uint32_t part_shift = msd ? keybits - 8 : shift;           // the fused kernel's digit
-    const bool narrow = kOne && msd && r32_slots && c->narrow;       // remainder + digit between the two levels, 5.33 bytes a key
-    lap("sample histograms");
-
-    // bucket regions of the first buffer: expected size of every bucket plus five standard
-    // deviations of the sample count; whatever room the key buffer has beyond that (up to 25 %)
-    // is handed out proportionally, so that a mildly non-stationary input still fits
-    // Every workgroup of the fused kernel appends to a private block of B slots per bucket and pads the
-    // unused tail of its last blocks, so a region also needs one block per workgroup; B is the largest
-    // power of two (one 64-byte granule .. 256 slots) that keeps that padding within 3 % of the keys: a small
-    // chunk gets fewer workgroups, then smaller blocks.  Workgroups per CU: 3 for one-word keys (52 KB of
-    // LDS each), 2 for two-word keys (75 KB).
-    const uint32_t kGranule = kOne ? 8 : 4;                       // keys per 64 bytes
-    const uint64_t kSuperFused = kOne ? (uint64_t)kTB * (graph_mode ? GOSS_E1_NK / 2 : GOSS_E1_NK)
-                                      : (uint64_t)kTB * (graph_mode ? GOSS_FUSED_NKEYS2 / 2 : GOSS_FUSED_NKEYS2);
-    const double pad_budget = 0.03 * (double)n_exp;
-    uint32_t fgrid = (uint32_t)std::min<uint64_t>((nstarts + kSuperFused - 1) / kSuperFused, (uint64_t)(kOne ? kFusedGrid : kFusedGrid2));
-    if (c->fused_grid) fgrid = std::min(fgrid, c->fused_grid);
-    fgrid = (uint32_t)std::max(16.0, std::min((double)fgrid, pad_budget / (256.0 * kGranule)));
-    uint32_t blk_log2 = kOne ? 3 : 2;
-    while (blk_log2 < 8 && (double)fgrid * 256.0 * (double)(2u << blk_log2) <= pad_budget) ++blk_log2;
-    if (c->blk_log2_max) blk_log2 = std::min(blk_log2, std::max(c->blk_log2_max, kOne ? 3u : 2u));
-    const uint64_t B = 1ULL << blk_log2;
-    // (a workgroup also holds a reserved block per bucket that it may never open)
-    const double blk_extra = (double)fgrid * (double)B * 2.0;
-    GapTable gt{};
-    double base[256], base_sum = 0;
-    for (int d = 0; d < 256; ++d)
-    {
-        const double h = (double)hh[d];
-        base[d] = exact ? h + 64.0 : (h + 5.0 * std::sqrt(h + 1.0) + 16.0) * scale + 1024.0;    // exact counts need no slack
-        base_sum += base[d];
-    }
-    double slack = std::min(1.25, ((double)ka_slots - 256.0 * ((double)B + blk_extra)) / base_sum);
-    if (slack < (exact ? 1.0 : 1.02))
-    {
-        // buffers sized from the share of valid windows: the caller retries with one slot per window start
-        if (reduced) return (int)kFusedNeedFull;
-        return decline("bucket regions do not fit the key buffer");
-    }
-    slack *= c->fused_capscale;
-    uint64_t at = 0;
-    for (int d = 0; d < 256; ++d)
-    {
-        uint64_t cap = ((uint64_t)(base[d] * slack + blk_extra * c->fused_capscale) + B - 1) & ~(B - 1);
-        gt.reg_start[d] = at; gt.reg_cap[d] = cap;
-        at += cap;
-    }
-
-    // 3. extraction that partitions
-    GapTable* dgt = (GapTable*)c->arena.temp(sizeof(GapTable));
-    PartCounters* pc = (PartCounters*)c->arena.temp(sizeof(PartCounters));
-    HIP_TRY(hipMemcpyAsync(dgt, &gt, sizeof(GapTable), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(pc, 0, sizeof(PartCounters), c->stream));
-    const uintptr_t addr = (uintptr_t)d_bases;
-    const uint32_t mis = (uint32_t)(addr & 15u);
-    const uint8_t* aligned = (const uint8_t*)(addr - mis);
-    const uint8_t* pk_src = nullptr; const uint16_t* pk_bad = nullptr;          // (a packed string: the group `aligned` stands for)
-    if (c->pk.on && !c->rec_mode) { pk_ptrs(c, aligned, &pk_src, &pk_bad); c->pk_fused_chunks++; }
-    {
-#ifndef GOSS_FUSED_G
-#define GOSS_FUSED_G 1
-#endif
-        const bool graph = graph_mode;
-        const uint64_t kSuper = kOne ? (uint64_t)kTB * (graph ? GOSS_E1_NK / 2 : GOSS_E1_NK)
-                                     : (uint64_t)kTB * (graph ? GOSS_FUSED_NKEYS2 / 2 : GOSS_FUSED_NKEYS2);
-        const uint64_t nsuper = (nstarts + kSuper - 1) / kSuper;
-        uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper, 1024);
-        if (c->fused_grid) grid = std::min(grid, c->fused_grid);      // experiments: leave room for a second context's kernels
-        grid = fgrid;                                                  // the regions were sized for this many workgroups
-        const int nh = msd ? 0 : (npass > 2 ? 2 : 1);
-        PhaseTimer t(c, GOSS_T_EXTRACT, nstarts);
-        if constexpr (kOne)
-        {
-            // the 32-bit forms of the kernel: the partition digit is the key's top eight bits (msd) and lies at bit 34 or above
-            const bool fastk = nh == 0 && 2 * c->len >= 32 && part_shift >= 34 && !c->no_fast32;
-            // (round 5: ahead of the 32-bit-remainder form of the second level the keys leave as remainder + digit, twelve
-            // to a granule -- kernels_extract.hpp, NARROW)
-            const uint32_t nr_rbits = rbits32, nr_sqbit = squeeze ? sqbit32 : 0u, nr_dmask = (1u << r32_bits) - 1u;
-            const uint32_t nr_capg = std::min(656u, std::max(576u, c->narrow_capg));          // (granules of the kernel's LDS layout: kernels_extract.hpp, kSlots)
-#define GOSS_LAUNCH_EP5(MODE, NH, ODD, FAST, NRW)                                                                     \
-    do {                                                                                                              \
-        if (c->rec_mode)                                                                                              \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, ODD, true, FAST, NRW>), dim3(grid), dim3(kTB), 0, c->stream, \
-                               d_bases, 0u, nstarts, nstarts / rec_slots(c), c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2, \
-                               nr_rbits, nr_sqbit, nr_dmask, nr_capg);                                                \
-        else if (c->pk.on)                                                                                            \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, ODD, false, FAST, NRW, true>), dim3(grid), dim3(kTB), 0, c->stream, \
-                               pk_src, mis, nstarts, navail, c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2, \
-                               nr_rbits, nr_sqbit, nr_dmask, nr_capg, pk_bad);                                        \
-        else                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, ODD, false, FAST, NRW>), dim3(grid), dim3(kTB), 0, c->stream, \
-                               aligned, mis, nstarts, navail, c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2, \
-                               nr_rbits, nr_sqbit, nr_dmask, nr_capg, (const uint16_t*)nullptr);                      \
-    } while (0)
-#define GOSS_LAUNCH_EP4(MODE, NH, ODD, FAST)                                                                          \
-    do {                                                                                                              \
-        if (narrow) GOSS_LAUNCH_EP5(MODE, NH, ODD, FAST, (NH == 0));                                                  \
-        else GOSS_LAUNCH_EP5(MODE, NH, ODD, FAST, false);                                                             \
-    } while (0)
-#define GOSS_LAUNCH_EP3(MODE, NH, ODD)                                                                                \
-    do {                                                                                                              \
-        if (fastk) GOSS_LAUNCH_EP4(MODE, NH, ODD, (NH == 0));                                                         \
-        else GOSS_LAUNCH_EP4(MODE, NH, ODD, false);                                                                   \
-    } while (0)
-            if (graph)
-            {
-                if (nh == 0) GOSS_LAUNCH_EP3(1, 0, 0);
-                else if (nh == 1) GOSS_LAUNCH_EP3(1, 1, 0);
-                else GOSS_LAUNCH_EP3(1, 2, 0);
-            }
-            else if (canon_l1)
-            {
-                // gossamer's canonical form computed per window (many distinct keys: above)
-                if (nh == 0) GOSS_LAUNCH_EP3(0, 0, 2);
-                else if (nh == 1) GOSS_LAUNCH_EP3(0, 1, 2);
-                else GOSS_LAUNCH_EP3(0, 2, 2);
-            }
-            else if (c->len & 1u)
-            {
-                // k-mer sets are counted as strand representatives and mapped to the canonical form
-                // afterwards (canonicalize_run); odd k: the central base picks the strand
-                if (nh == 0) GOSS_LAUNCH_EP3(0, 0, 1);
-                else if (nh == 1) GOSS_LAUNCH_EP3(0, 1, 1);
-                else GOSS_LAUNCH_EP3(0, 2, 1);
-            }
-            else
-            {
-                if (nh == 0) GOSS_LAUNCH_EP3(0, 0, 0);
-                else if (nh == 1) GOSS_LAUNCH_EP3(0, 1, 0);
-                else GOSS_LAUNCH_EP3(0, 2, 0);
-            }
-#undef GOSS_LAUNCH_EP3
-#undef GOSS_LAUNCH_EP4
-#undef GOSS_LAUNCH_EP5
-        }
-        else
-        {
-#define GOSS_LAUNCH_E2P(MODE, NH, NBH)                                                                                \
-    do {                                                                                                              \
-        if constexpr (MODE == 0)                                                                                      \
-        {                                                                                                             \
-            if (c->rec_mode)                                                                                          \
-            {                                                                                                         \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<0, NH, GOSS_FUSED_NKEYS2, NBH, true>), dim3(grid), dim3(kTB), 0, c->stream, \
-                                   d_bases, 0u, nstarts, nstarts / rec_slots(c), c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2); \
-                break;                                                                                                \
-            }                                                                                                         \
-        }                                                                                                             \
-        if (c->pk.on)                                                                                                 \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<MODE, NH, GOSS_FUSED_NKEYS2, NBH, false, true>), dim3(grid), dim3(kTB), 0, c->stream, \
-                               pk_src, mis, nstarts, navail, c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2, pk_bad); \
-        else                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<MODE, NH, GOSS_FUSED_NKEYS2, NBH>), dim3(grid), dim3(kTB), 0, c->stream, \
-                               aligned, mis, nstarts, navail, c->len, ka, pc, (const GapTable*)dgt, part_shift, nsuper, blk_log2, (const uint16_t*)nullptr); \
-    } while (0)
-#define GOSS_LAUNCH_E2N(MODE, NBH)                                                                                    \
-    do { if (nh == 0) GOSS_LAUNCH_E2P(MODE, 0, NBH); else if (nh == 1) GOSS_LAUNCH_E2P(MODE, 1, NBH); else GOSS_LAUNCH_E2P(MODE, 2, NBH); } while (0)
-            if (graph) GOSS_LAUNCH_E2N(1, 8);
-            else if (rep_graph) GOSS_LAUNCH_E2N(0, 0);          // (NBH 0: strand representatives)
-            else
-                switch (key2_nbh(c))
-                {
-                    case 2: GOSS_LAUNCH_E2N(0, 2); break;
-                    case 4: GOSS_LAUNCH_E2N(0, 4); break;
-                    case 6: GOSS_LAUNCH_E2N(0, 6); break;
-                    default: GOSS_LAUNCH_E2N(0, 8); break;
-                }
-#undef GOSS_LAUNCH_E2N
-#undef GOSS_LAUNCH_E2P
-        }
-        t.stop();
-    }
-    std::vector<unsigned long long> hpc(sizeof(PartCounters) / 8);
-    HIP_TRY(hipMemcpyAsync(hpc.data(), pc, sizeof(PartCounters), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const PartCounters* hp = (const PartCounters*)hpc.data();
-    if (hp->overflow) { c->fused_overflows++; return decline("a bucket region overflowed"); }
-    lap("extraction + first level");
-#if defined(GOSS_STAMPS)
-    // (timing build: wave 0's cycles per phase and tile, averaged over the workgroups)
-    if (hp->hist[505])
-        std::fprintf(stderr, "libgossgpu: stamps per tile (cycles): A %.0f  B %.0f  C %.0f  scatter %.0f  D %.0f   (%llu tiles)\n",
-                     (double)hp->hist[500] / hp->hist[505], (double)hp->hist[501] / hp->hist[505], (double)hp->hist[502] / hp->hist[505],
-                     (double)hp->hist[503] / hp->hist[505], (double)hp->hist[504] / hp->hist[505], (unsigned long long)hp->hist[505]);
-    if (hp->hist[505] && hp->hist[506])
-        std::fprintf(stderr, "libgossgpu: stamps, finer: C = scan %.0f + bookkeeping %.0f + barrier; scatter = LDS %.0f + encoder %.0f + barrier; D = stores %.0f + absorb %.0f + barrier %.0f\n",
-                     (double)hp->hist[506] / hp->hist[505], (double)hp->hist[507] / hp->hist[505], (double)hp->hist[510] / hp->hist[505],
-                     (double)hp->hist[511] / hp->hist[505], (double)hp->hist[508] / hp->hist[505], (double)hp->hist[509] / hp->hist[505],
-                     (double)hp->hist[504] / hp->hist[505]);
-#endif
-    const uint64_t n = hp->keys_out;
-    if (n == 0) return kFusedDeclined;
-    if (n > ka_slots || n > kb_slots) return decline("more keys than the buffers hold");
-    uint64_t tiles = 0, sum = 0;
-    const uint64_t tile_keys = narrow ? (uint64_t)(r32_bits == 9 ? Sub32N<9>::kTileSlots : Sub32N<10>::kTileSlots) : (msd && r32_slots) ? (uint64_t)kSub32Tile : msd ? (uint64_t)SubCfg<K>::kTile : (uint64_t)kTile;      // of the pass that reads the regions
-    for (int d = 0; d < 256; ++d)
-    {
-        // one-word keys: slots handed out in whole blocks, padding included (the next pass skips it)
-        gt.cnt[d] = hp->cursors[d * kCursorStride];
-        gt.tile_first[d] = tiles;
-        tiles += (gt.cnt[d] + tile_keys - 1) / tile_keys;
-        sum += gt.cnt[d];
-    }
-    gt.tile_first[256] = tiles;
-    // (the 8-byte slots handed out hold the keys: one each, or -- narrow form -- twelve to a granule of eight)
-    const uint64_t n_slots = narrow ? n / 3 * 2 : n;
-    if (sum < n_slots || sum > n_slots + 8 + (uint64_t)fgrid * 256 * (2 * B + 8))
-        throw StatusError{GOSS_ERR_HIP, "fused extraction: bucket counts do not add up"};
-    HIP_TRY(hipMemcpyAsync(dgt, &gt, sizeof(GapTable), hipMemcpyHostToDevice, c->stream));
-
-    LookbackCtl* ctl = (LookbackCtl*)c->arena.temp(sizeof(LookbackCtl));
-    LookbackCtl* hctl = (LookbackCtl*)((uint8_t*)c->h_pinned + 128);
-    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(LookbackCtl), c->stream));
-    Run r{nullptr, nullptr, 0};
-    if (msd && r32_slots)
-    {
-        // 4a'. second level, 32-bit-remainder form: keys of region b go to sub-region (b, next 9 bits) as u32 remainders
-        SubTable32* dsub = (SubTable32*)c->arena.temp(sizeof(SubTable32));
-        unsigned long long* cur2 = (unsigned long long*)c->arena.temp((uint64_t)r32_regions * 4);     // pairs of 32-bit cursors
-        uint64_t* seg_beg = (uint64_t*)c->arena.temp((uint64_t)r32_regions * 8);
-        uint64_t* seg_end = (uint64_t*)c->arena.temp((uint64_t)r32_regions * 8);
-        Tile32* tdesc = (Tile32*)c->arena.temp(std::max<uint64_t>(tiles, 1) * sizeof(Tile32));
-        // (only the used part of the table travels: the starts, then the capacities)
-        HIP_TRY(hipMemcpyAsync(dsub->start, hsub32_start.data(), (uint64_t)r32_regions * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dsub->cap, hsub32_cap.data(), (uint64_t)r32_regions * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(cur2, 0, (uint64_t)r32_regions * 4, c->stream));
-        if (narrow && r32_bits == 9)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tiles32_kernel<Sub32N<9>::kTileSlots>), dim3(grid_for(tiles, 256)), dim3(256), 0, c->stream,
-                               (const GapTable*)dgt, tdesc, (uint32_t)tiles);
-        else if (narrow)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tiles32_kernel<Sub32N<10>::kTileSlots>), dim3(grid_for(tiles, 256)), dim3(256), 0, c->stream,
-                               (const GapTable*)dgt, tdesc, (uint32_t)tiles);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tiles32_kernel<kSub32Tile>), dim3(grid_for(tiles, 256)), dim3(256), 0, c->stream,
-                               (const GapTable*)dgt, tdesc, (uint32_t)tiles);
-        {
-            PhaseTimer t(c, GOSS_T_SCATTER, n);
-            const dim3 g2((uint32_t)((tiles + 7) / 8 * 8));
-#define GOSS_LAUNCH_S32N(SQ, B2, NRW)                                                                                    \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(subpart32_kernel<SQ, B2, NRW>), g2, dim3(kTB), 0, c->stream, (const Key1*)ka, (uint32_t*)kb, rbits32, \
-                       sqbit32, cur2, (const Tile32*)tdesc, (uint32_t)tiles, (const SubTable32*)dsub, ctl)
-#define GOSS_LAUNCH_S32(SQ, B2) do { if (narrow) GOSS_LAUNCH_S32N(SQ, B2, true); else GOSS_LAUNCH_S32N(SQ, B2, false); } while (0)
-            if (squeeze) GOSS_LAUNCH_S32(true, 9);          // (only the 9-bit form of an odd k-mer set needs the squeeze)
-            else if (r32_bits == 9) GOSS_LAUNCH_S32(false, 9);
-            else GOSS_LAUNCH_S32(false, 10);
-#undef GOSS_LAUNCH_S32
-#undef GOSS_LAUNCH_S32N
-            t.stop();
-        }
-        hipLaunchKernelGGL(sub_bounds32_kernel, dim3(r32_regions / 256), dim3(256), 0, c->stream, (const SubTable32*)dsub,
-                           (const uint32_t*)cur2, r32_regions, seg_beg, seg_end);
-        HIP_TRY(hipMemcpyAsync(hctl, ctl, sizeof(LookbackCtl), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hctl->error) { c->fused_overflows++; return decline("a 32-bit sub-region overflowed"); }
-        lap("second level (32-bit remainders)");
-        // third level: every segment split into 2^r32_split sub-segments, from kb into ka (same offsets); the counts are
-        // then staged in kb
-        const uint32_t* rems = (const uint32_t*)kb;
-        Key1* spare32 = (Key1*)ka;
-        uint32_t nseg32 = r32_regions;
-        if (r32_split)
-        {
-            nseg32 = r32_regions << r32_split;
-            uint64_t* sub_beg = (uint64_t*)c->arena.temp((uint64_t)nseg32 * 8);
-            uint64_t* sub_end = (uint64_t*)c->arena.temp((uint64_t)nseg32 * 8);
-            {
-                PhaseTimer t(c, GOSS_T_SCATTER, n);
-                hipLaunchKernelGGL(subsplit32_kernel, unit_grid(r32_regions), dim3(kTB), 0, c->stream, (const uint32_t*)kb, (uint32_t*)ka,
-                                   (const uint64_t*)seg_beg, (const uint64_t*)seg_end, rbits32 - (squeeze ? 1u : 0u), r32_split, sub_beg, sub_end);
-                t.stop();
-            }
-            check_launch("third-level split kernel");
-            seg_beg = sub_beg; seg_end = sub_end;
-            rems = (const uint32_t*)ka;
-            spare32 = (Key1*)kb;
-            lap("third level (sub-segments)");
-        }
-        int rc;
-        for (;;)
-        {
-            rc = segment_reduce32(c, rems, spare32, n, &r, seg_beg, seg_end, r32_slots, squeeze, rbits32, sqbit32, nseg32, r32_split);
-            const int top_slots = c->r32_form && c->big_r32 ? 16384 : 4096;
-            if (rc != 1 || r32_slots >= top_slots || c->rem32_slots) break;
-            // the remainders are still in their sub-regions: only the counting is redone, in the next larger table
-            c->segment_retries++;
-            r32_slots = r32_slots < 4096 ? 4096 : 2 * r32_slots;
-        }
-        if (rc != 0)
-        {
-            // more distinct keys per segment than this form takes: the chunk again in the 8-byte form and its ladder of tables
-            c->segment_retries++;
-            // more second-level bits while the remainder allows them (the chunk's first level is redone: the staging of
-            // the counts has overwritten its regions), else the 8-byte form and its ladder of tables
-            if (rc == 1 && r32_split < (uint32_t)kSub32SplitMax) c->rem32_split_min = r32_split + 1;
-            else c->rem32 = false;
-            if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: 32-bit form with %u + %u bits overflowed (%d), redoing the chunk %s\n", r32_bits, r32_split, rc,
-                                       c->rem32 ? "with more sub-segments" : "in the 8-byte form");
-            c->arena.release(mark);
-            return process_chunk_fused<K>(c, d_bases, nstarts, navail, ka, ka_slots, kb, kb_slots);
-        }
-        c->fused_msd_chunks++;
-        c->rem32_chunks++;
-        if (narrow) c->narrow_chunks++;
-        c->rem32_bits_last = r32_bits;
-        c->rem32_split_last = r32_split;
-    }
-    else if (msd)
-    {
-        // 4a. second level: keys of region b go to sub-region (b, low digit) by atomic cursors
-        SubTable* dsub = (SubTable*)c->arena.temp(sizeof(SubTable));
-        unsigned long long* cur2 = (unsigned long long*)c->arena.temp(65536ULL * kSubCursorStride * 8);
-        uint64_t* seg_beg = (uint64_t*)c->arena.temp(65536 * 8);
-        uint64_t* seg_end = (uint64_t*)c->arena.temp(65536 * 8);
-        HIP_TRY(hipMemcpyAsync(dsub, hsub.data(), sizeof(SubTable), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(cur2, 0, 65536ULL * kSubCursorStride * 8, c->stream));
-        {
-            PhaseTimer t(c, GOSS_T_SCATTER, n);
-            // (a multiple of 8 workgroups: the kernel deals the tiles out by XCD)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_onesweep_kernel<K, false, false, true, SubCfg<K>::kItems>), dim3((uint32_t)((tiles + 7) / 8 * 8)), dim3(kTB), 0,
-                               c->stream, (const K*)ka, (const uint32_t*)nullptr, kb, (uint32_t*)nullptr, n, shift, shift,
-                               (const unsigned long long*)nullptr, (unsigned long long*)nullptr, ctl, cur2,
-                               (const GapTable*)dgt, (const SubTable*)dsub, big_table == -2 ? 1u : 0u);
-            t.stop();
-        }
-        hipLaunchKernelGGL(sub_bounds_kernel, dim3(256), dim3(256), 0, c->stream, (const SubTable*)dsub,
-                           (const unsigned long long*)cur2, seg_beg, seg_end);
-        HIP_TRY(hipMemcpyAsync(hctl, ctl, sizeof(LookbackCtl), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hctl->error) { c->fused_overflows++; return decline("a sub-region overflowed"); }
-        lap("second level");
-        // (-3: the second level wrote 12-byte remainders for the 96-bit table)
-        int rc;
-        for (;;)
-        {
-            rc = segment_reduce<K>(c, kb, ka, n, segbits, &r, seg_beg, seg_end, big_table == -2 ? -3 : big_table);
-            // a table that overflowed (one-word keys): the keys are still in their sub-regions, so only the counting
-            // is redone, with the next larger form -- 8192 slots, then 2 and 4 workgroups per segment -- instead of
-            // the whole chunk with the unfused kernels
-            if (rc != 1 || !kOne || !c->big_table || big_table < 0 || big_table >= 1 + c->big_rounds_max) break;
-            c->segment_retries++;
-            ++big_table;
-            if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: a counting table overflowed, next form %d\n", big_table);
-        }
-        if (rc != 0)
-        {
-            c->segment_retries++;
-            // this input is too skewed for it: the next smaller form from now on
-            if (big_table == -2) c->table96 = false;
-            else if (big_table < 0) c->wide_table = false;
-            else if (big_table) c->big_table = false;
-            return decline("a segment table overflowed");
-        }
-        c->fused_msd_chunks++;
-        if (big_table) c->big_table_chunks++;
-        if (big_table == -1) c->wide_table_chunks++;
-        if (big_table == -2) c->table96_chunks++;
-    }
-    else
-    {
-        // 4b. remaining partition passes: the first reads the bucket regions, the others are dense
-        const uint64_t ntiles_dense = (n + kTile - 1) / kTile;
-        unsigned long long* status = (unsigned long long*)c->arena.temp(256ULL * std::max(tiles, ntiles_dense) * 8);
-        {
-            PhaseTimer t(c, GOSS_T_SCAN, 512);
-            hipLaunchKernelGGL(scan_rows256_kernel, dim3(2), dim3(kTB), 0, c->stream, pc->hist);
-            t.stop();
-        }
-        K* src = ka; K* dst = kb;
-        for (uint32_t di = 1; di < npass; ++di)
-        {
-            const uint32_t d = shift + 8 * di;
-            const bool gapped = di == 1;
-            const uint64_t nt = gapped ? tiles : ntiles_dense;
-            HIP_TRY(hipMemsetAsync(status, 0, nt * 256 * 8, c->stream));
-            {
-                PhaseTimer t(c, GOSS_T_SCATTER, n);
-                if (gapped)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_onesweep_kernel<K, false, false, true>), dim3((uint32_t)nt), dim3(kTB), 0,
-                                       c->stream, (const K*)src, (const uint32_t*)nullptr, dst, (uint32_t*)nullptr, n, d, shift,
-                                       (const unsigned long long*)(pc->hist + (di - 1) * 256), status, ctl,
-                                       (unsigned long long*)nullptr, (const GapTable*)dgt, (const SubTable*)nullptr);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_onesweep_kernel<K, false, false, false>), dim3((uint32_t)nt), dim3(kTB), 0,
-                                       c->stream, (const K*)src, (const uint32_t*)nullptr, dst, (uint32_t*)nullptr, n, d, shift,
-                                       (const unsigned long long*)(pc->hist + (di - 1) * 256), status, ctl,
-                                       (unsigned long long*)nullptr, (const GapTable*)nullptr, (const SubTable*)nullptr);
-                t.stop();
-            }
-            HIP_TRY(hipMemcpyAsync(hctl, ctl, sizeof(LookbackCtl), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (hctl->error)
-            {
-                std::fprintf(stderr, "libgossgpu: radix look-back chain gave up in the fused path; redoing the chunk unfused\n");
-                c->lookback_failures++;
-                c->ordered_tiles = true;
-                return kFusedDeclined;
-            }
-            std::swap(src, dst);
-        }
-        // src = partitioned keys (dense: npass >= 2), dst = spare
-        c->arena.release(mark); release.m = c->arena.mark();
-        const int rc = segment_reduce<K>(c, src, dst, n, segbits, &r, nullptr, nullptr, false);
-        if (rc != 0) { c->segment_retries++; return decline("a segment table overflowed"); }
-    }
-    lap("segments counted");
-    if (canon_l1) c->canon_chunks++;
-    if (use_rep && !canon_l1)
-    {
-        // the run stays in representative space: it is mapped to gossamer's canonical forms when it meets a run
-        // that is not, or at finish -- a build of several chunks pays for the re-ordering once, on the merged run
-        r.rep = true;
-        c->rep_chunks++;
-    }
-    c->runs.push_back(r);
-    c->windows += hp->windows;
-    c->keys_total += rep_graph ? 2 * n : n;          // (the adapter's key stream: two keys per window of a graph)
-    c->fused_chunks++;
-    if (c->rec_mode) c->rec_chunks++;
-    return kFusedDone;
-}
+// ---- fused extraction + first partition pass, and the counting behind it -----------------------
+#include "fused_path.hpp"
 
 // Process window starts [0, nstarts) of a device-resident byte string (navail readable bytes,
 // navail >= nstarts): extract -> sort -> reduce -> append a run.
@@ -2447,7 +1599,7 @@ void merge_runs(goss_gpu_ctx* c)
     if constexpr (std::is_same<K, Key2>::value)
     {
         const uint32_t keybits = 2 * c->len;
-        if (c->seg_merge && c->table96 && keybits >= 16 + 8 && keybits - 16 <= 96 && nruns <= (uint32_t)kMergeRuns && total >= c->hash_merge_min)
+        if (c->table96 && keybits >= 16 + 8 && keybits - 16 <= 96 && nruns <= (uint32_t)kMergeRuns && total >= c->hash_merge_min)
         {
             const uint32_t nseg = 65536, shift = keybits - 16;
             uint64_t m2 = c->arena.mark();
@@ -2498,7 +1650,7 @@ void merge_runs(goss_gpu_ctx* c)
 
     // Merge by segments (seg_merge_kernel): every entry read once, written once.  Needs every
     // segment's entries of all runs to fit kMergeCap; else the concatenation is sorted again.
-    if (c->seg_merge && nruns <= (uint32_t)kMergeRuns && total >= 1024)
+    if (nruns <= (uint32_t)kMergeRuns && total >= 1024)
     {
         const uint32_t keybits = 2 * c->len;
         uint32_t segbits = 8;
@@ -3060,9 +2212,9 @@ void emit_sparse_index(goss_gpu_ctx* c, const K* keys, uint64_t m, uint32_t D, u
     const uint64_t nwords = (nd + m + 3) / 64 + 1;
     uint64_t* words = built ? built : (uint64_t*)c->arena.perm(nwords * 8);
     if (built) {}                                // (assembled from the ranges' spans: emit_assemble)
-    else if (m >= (1u << 16) && !c->ef_by_words)
+    else if (m >= (1u << 16))
     {
-        // from the keys' side: one coalesced pass over the keys (GOSS_GPU_EF_BY_WORDS=1: the per-word binary search)
+        // from the keys' side: one coalesced pass over the keys (below 65 536 keys: the per-word binary search)
         HIP_TRY(hipMemsetAsync(words, 0, nwords * 8, c->stream));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(ef_high_bits_keys_kernel<K>), dim3(grid_for(m, kEfChunk)), dim3(kTB), 0, c->stream,
                            keys, m, D, (uint64_t)0, nwords, (unsigned long long*)words, (uint64_t)0);
@@ -3307,13 +2459,13 @@ void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t e
         const uint64_t count1 = total, count0 = nd + 2;
         DsPlan p1, p0;
         const DsSrc<K> src1{keys, m, D, 0, first_index, nullptr, 0}, src0{keys, m, D, 1, first_index, nullptr, 0};
-        if (m && c->ds_parts)
+        if (m)
         {
             const uint64_t b0 = (first_index + 8191) >> 13;
             const uint64_t e = last_range ? (count1 + 8191) >> 13 : (first_index + m) >> 13;
             if (e > b0) p1 = ds_plan<K>(c, src1, count1, b0, e - b0);
         }
-        if (have_prev && c->ds_parts && m)
+        if (have_prev && m)
         {
             const uint64_t z0 = prev_high, z1 = last_range ? count0 : last_high;
             const uint64_t b0 = (z0 + 8191) >> 13;
@@ -3622,34 +2774,24 @@ int goss_gpu_create(goss_gpu_ctx** out, int device, uint32_t k, int mode, uint64
     { const char* e = std::getenv("GOSS_GPU_ORDERED_TILES"); if (e && *e == '1') c->ordered_tiles = true; }
     { const char* e = std::getenv("GOSS_GPU_EST_SCALE"); if (e && std::atof(e) > 0) c->est_scale = std::atof(e); }
     { const char* e = std::getenv("GOSS_GPU_ORDER_BITS"); if (e && std::atoi(e) >= 16 && std::atoi(e) <= 24) c->order_bits = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_EXTRACT_V1"); if (e && *e == '1') c->extract_v1 = true; }
-    { const char* e = std::getenv("GOSS_GPU_NO_CURSOR_PASS0"); if (e && *e == '1') c->cursor_pass0 = false; }
     { const char* e = std::getenv("GOSS_GPU_NO_FUSED"); if (e && *e == '1') c->fused = false; }
-    { const char* e = std::getenv("GOSS_GPU_FUSED_GRID"); if (e && *e) c->fused_grid = (uint32_t)std::strtoul(e, nullptr, 10); }
-    { const char* e = std::getenv("GOSS_GPU_NO_SEG_MERGE"); if (e && *e == '1') c->seg_merge = false; }
     { const char* e = std::getenv("GOSS_GPU_NO_MSD"); if (e && *e == '1') c->fused_msd = false; }
-    { const char* e = std::getenv("GOSS_GPU_EF_BY_WORDS"); if (e && *e && *e != '0') c->ef_by_words = true; }
     { const char* e = std::getenv("GOSS_GPU_NO_GRAPH_REP"); if (e && *e && *e != '0') c->graph_rep = false; }
     { const char* e = std::getenv("GOSS_GPU_CANON_L1"); if (e && *e >= '0' && *e <= '2') c->canon_l1 = *e - '0'; }
-    { const char* e = std::getenv("GOSS_GPU_CANON_L1_AT"); if (e && std::atof(e) > 0) c->canon_l1_at = std::atof(e); }
     { const char* e = std::getenv("GOSS_GPU_NO_REM32"); if (e && *e && *e != '0') c->rem32 = false; }
     { const char* e = std::getenv("GOSS_GPU_REM32_BITS"); if (e && std::atoi(e) >= 9 && std::atoi(e) <= 10) c->rem32_bits_min = (uint32_t)std::atoi(e); }
     { const char* e = std::getenv("GOSS_GPU_REM32_SPLIT"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 4) c->rem32_split_min = (uint32_t)std::atoi(e); }
     { const char* e = std::getenv("GOSS_GPU_REM32_SLOTS"); if (e && (std::atoi(e) == 2048 || std::atoi(e) == 4096 || std::atoi(e) == 8192 || std::atoi(e) == 16384)) c->rem32_slots = std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_R32_FORM"); if (e) c->r32_form = std::atoi(e) ? 1 : 0; }
     { const char* e = std::getenv("GOSS_GPU_NARROW"); if (e) c->narrow = std::atoi(e) != 0; }
     { const char* e = std::getenv("GOSS_GPU_OVERFLOW_BY_SORT"); if (e) c->overflow_by_sort = std::atoi(e) != 0; }
-    { const char* e = std::getenv("GOSS_GPU_DS_PARTS"); if (e) c->ds_parts = std::atoi(e) != 0; }
     { const char* e = std::getenv("GOSS_GPU_NARROW_CAPG"); if (e && std::atoi(e) > 0) c->narrow_capg = (uint32_t)std::atoi(e); }
     { const char* e = std::getenv("GOSS_GPU_R32_SMALL_MAX"); if (e) c->r32_small_max = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_R32_BIG"); if (e && *e == '0') c->big_r32 = false; }
     { const char* e = std::getenv("GOSS_GPU_NO_BIG_TABLE"); if (e && *e && *e != '0') c->big_table = false; }
     { const char* e = std::getenv("GOSS_GPU_HASH_MERGE_MIN"); if (e && *e) c->hash_merge_min = std::strtoull(e, nullptr, 10); }
     { const char* e = std::getenv("GOSS_GPU_BLK_LOG2"); if (e && *e) c->blk_log2_max = (uint32_t)std::atoi(e); }
     { const char* e = std::getenv("GOSS_GPU_NO_FAST32"); if (e && *e == '1') c->no_fast32 = true; }
     { const char* e = std::getenv("GOSS_GPU_NO_TABLE96"); if (e && *e && *e != '0') c->table96 = false; }
     { const char* e = std::getenv("GOSS_GPU_NO_WIDE_TABLE"); if (e && *e && *e != '0') c->wide_table = false; }
-    { const char* e = std::getenv("GOSS_GPU_BIG_ROUNDS"); if (e && *e) c->big_rounds_max = std::min(3, std::max(0, std::atoi(e))); }
     { const char* e = std::getenv("GOSS_GPU_BIG_ROUNDS_MIN"); if (e && *e) c->big_rounds_min = std::min(3, std::max(0, std::atoi(e))); }
     { const char* e = std::getenv("GOSS_GPU_NO_VALID_SIZING"); if (e && *e && *e != '0') c->size_by_valid = false; }
     { const char* e = std::getenv("GOSS_GPU_FUSED_MIN"); if (e && *e) c->fused_min = std::strtoull(e, nullptr, 10); }

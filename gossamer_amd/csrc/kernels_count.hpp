@@ -594,346 +594,26 @@ __global__ __launch_bounds__(kSegBigThreads) void seg_hash_reduce_shared_kernel(
 }
 
 // --------------------------------------------------------------------------------------
-// Counting of 32-bit remainders (subpart32_kernel's output): 131 072 segments, one workgroup each
+// Counting of 32-bit remainders (subpart32_kernel's output): 2^17 .. 2^20 segments, one workgroup each
 // --------------------------------------------------------------------------------------
 //
-// A slot is two 32-bit words, remainder and count; count 0 = empty.  A bucket is two slots = 16 bytes, read with one
-// LDS load.  A key has a home bucket and an independent second one (both from one 32-bit mix; second = home ^ an odd
-// field of the mix, so never the home); behind the second the buckets that follow it.  A key is inserted with its first
-// occurrence counted (64-bit CAS of {marker, 0} -> {rem, 1}); a hit adds 1 to the count word (32-bit LDS atomic).
+// The table is an array of SLOTS remainders with the SLOTS counts at the same offsets of a count array behind it.  A
+// bucket is FOUR remainders = 16 bytes, read with one LDS load.  A key has a home bucket and an independent second one
+// (both from one 32-bit mix; second = home ^ an odd field of the mix, so never the home); behind the second the buckets
+// that follow it.  A slot is claimed by a 32-bit CAS on its key word (marker -> key); counts are only ever added to
+// (32-bit LDS atomic).
 //
 // Every 32-bit pattern is a remainder, so "empty" cannot be a key value -- but it can be a value that never MATCHES:
 // the empty slots of bucket b hold the key E_b whose home is b ^ 1 and whose second bucket is b ^ 2.  The fast path
-// compares a key only with the slots of its own two buckets, so it can never take an empty slot for its key, and
-// needs no look at the counts: four compares pick the address of the count word to bump (or a word of the lane's own
-// behind the table, for a miss), one unconditional LDS add does the rest.  ~28 vector instructions per key where the
-// 8-byte form takes 56 -- these kernels are bound by what they issue, not by what they read (profiles/r04).
-// Misses wait in the lane's bit mask for the slow path, which looks at counts and starts at the home bucket.
-// The table is a quarter (SLOTS = 2048: 16 KB) or half (4096) of the 8-byte form's, the keys half the bytes.
-// Remainders are loaded four per lane (16 bytes); a sub-region starts on a 16-byte boundary and its capacity is a
-// multiple of four, so the last vector may be read whole.
+// compares a key only with the slots of its home bucket, and a key that is not at home only with those of its second,
+// so neither can take an empty slot for its key and neither needs a look at the counts; the slow path's chain can reach
+// b with that very key, and skips the bucket.
+// The remainders are loaded four per lane (16 bytes); a sub-region starts on a 16-byte boundary and its capacity is a
+// multiple of four, so the last vector may be read whole.  The table is a quarter (SLOTS = 2048: 16 KB) or half (4096)
+// of the 8-byte form's, the keys half the bytes.
 constexpr uint32_t kR32Mul = 0x9E3779B1u, kR32MulInv = 0x0E8B2F51u;          // kR32Mul * kR32MulInv = 1 mod 2^32
 __host__ __device__ __forceinline__ uint32_t r32_mix(uint32_t k) { return (k ^ (k >> 15)) * kR32Mul; }
 __host__ __device__ __forceinline__ uint32_t r32_unmix(uint32_t f) { const uint32_t y = f * kR32MulInv; return y ^ (y >> 15) ^ (y >> 30); }
-
-#ifndef GOSS_R32_OCC
-#define GOSS_R32_OCC 5
-#endif
-#ifndef GOSS_R32_G
-#define GOSS_R32_G 4
-#endif
-template <int SLOTS, bool SQ>
-__global__ __launch_bounds__(kTB, SLOTS == 2048 ? GOSS_R32_OCC : 4) void seg_hash_reduce32_kernel(const uint32_t* __restrict__ rems, const uint64_t* __restrict__ seg_off,
-                                                                const uint64_t* __restrict__ seg_end, SegOut* __restrict__ so,
-                                                                uint64_t* __restrict__ seg_pos, uint64_t* __restrict__ seg_cnt,
-                                                                Key1* __restrict__ stage_keys, uint32_t* __restrict__ stage_counts,
-                                                                uint32_t rbits, uint32_t sqbit, uint32_t split_bits)
-{
-    // split_bits: the segments are the sub-segments of subsplit32_kernel -- 2^split_bits per second-level segment, told
-    // apart by the top split_bits bits of the remainder (which they keep) and starting anywhere, not on a 16-byte boundary
-    constexpr int NT = kTB;
-    constexpr int kLimit = SLOTS / 4 * 3;
-    constexpr int BB = SLOTS == 4096 ? 11 : SLOTS == 2048 ? 10 : -1;       // log2(buckets)
-    constexpr uint32_t NB = SLOTS / 2;
-    static_assert(BB > 0, "table size");
-    // the table, then a bucket per lane (64 x 16 bytes) for the accesses that must not land in the table
-    __shared__ __attribute__((aligned(16))) unsigned long long tab[SLOTS + 128];
-    __shared__ uint32_t ndist, ovf;
-    __shared__ unsigned long long sh_base;
-    const uint32_t s = unit_block(), tid = threadIdx.x;
-    const uint64_t b = seg_off[s], e = seg_end[s];
-    if (b == e)
-    {
-        if (tid == 0) { seg_pos[s] = 0; seg_cnt[s] = 0; }
-        return;
-    }
-    if (e - b > 0xFFFFFFF0ULL)
-    {
-        if (tid == 0) { atomicOr(&so->overflow, 2u); seg_pos[s] = 0; seg_cnt[s] = 0; }
-        return;
-    }
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) uint8_t* lds_bytes;
-    typedef const __attribute__((address_space(3))) u32x4* lds_bucket_plain;
-    typedef const volatile __attribute__((address_space(3))) u32x4* lds_bucket_ptr;
-    typedef __attribute__((address_space(3))) uint32_t* lds_word;
-    const lds_bytes tb = (lds_bytes)tab;
-    // (f of the marker: home b ^ 1, odd field 3 -> second bucket b ^ 2)
-    auto marker = [](uint32_t bkt) -> uint32_t { return r32_unmix(((bkt ^ 1u) << (32 - BB)) | (3u << (32 - 2 * BB))); };
-    for (uint32_t i = tid; i < NB; i += NT)
-    {
-        const uint32_t m = marker(i);
-        *(__attribute__((address_space(3))) u32x4*)(tb + 16 * i) = u32x4{m, 0u, m, 0u};
-    }
-    if (tid < 128) tab[SLOTS + tid] = 0;
-    if (tid == 0) { ndist = 0; ovf = 0; }
-    __syncthreads();
-
-    lds_vu32 vovf = (lds_vu32)&ovf;
-    // behind the table: a bucket (16 bytes) per lane that nobody else touches -- its second word takes the lane's misses
-    const uint32_t own16 = 8u * (uint32_t)SLOTS + 16u * (tid & 63u);
-    const uint32_t dummy = own16 + 4u;
-    auto home_of = [](uint32_t f) -> uint32_t { return f >> (32 - BB); };
-    auto second_of = [](uint32_t f, uint32_t h) -> uint32_t { return h ^ (((f >> (32 - 2 * BB)) & (NB - 1u)) | 1u); };
-
-    constexpr int kVec = 4;                                  // 16-byte loads in flight per lane
-    constexpr int kG = GOSS_R32_G;                           // keys whose buckets are read together
-    // (vectors from the 16-byte boundary at or below the segment's start: the first `head` elements are not its own)
-    const uint32_t head = (uint32_t)(b & 3ULL);
-    const u32x4* const v4 = reinterpret_cast<const u32x4*>(rems + (b - head));
-    const uint32_t n = (uint32_t)(e - b) + head;
-    const uint32_t nvec = (n + 3u) >> 2, nfull = n >> 2;      // vectors, and vectors of four live remainders
-    u32x4 nxt[kVec];
-#pragma unroll
-    for (int u = 0; u < kVec; ++u)
-    {
-        const uint32_t i = (uint32_t)u * NT + tid;
-        nxt[u] = __builtin_nontemporal_load(&v4[i < nvec ? i : nvec - 1]);
-    }
-    for (uint32_t i0 = 0; i0 < nvec; i0 += (uint32_t)NT * kVec)
-    {
-        u32x4 cur[kVec];
-#pragma unroll
-        for (int u = 0; u < kVec; ++u) cur[u] = nxt[u];
-        // software pipeline: the next batch's loads are in flight while this one is inserted
-#pragma unroll
-        for (int u = 0; u < kVec; ++u)
-        {
-            const uint32_t i = i0 + (uint32_t)(kVec + u) * NT + tid;
-            nxt[u] = __builtin_nontemporal_load(&v4[i < nvec ? i : nvec - 1]);
-        }
-#if defined(GOSS_R32_EXP) && GOSS_R32_EXP == 1
-        // (timing experiment: the loads alone)
-#pragma unroll
-        for (int u = 0; u < kVec; ++u) asm volatile("" ::"v"(cur[u].x), "v"(cur[u].y), "v"(cur[u].z), "v"(cur[u].w));
-        continue;
-#endif
-        // every vector of the batch whole?  (all but a segment's last batch: no validity arithmetic in the fast path)
-        const bool whole = i0 + (uint32_t)NT * kVec <= nfull && (i0 != 0 || head == 0);
-        uint32_t pend = 0;                                   // bit 4 u + j: remainder j of vector u missed
-#pragma unroll
-        for (int u = 0; u < kVec; ++u)
-        {
-            const uint32_t kk[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-            uint32_t live = 0xFu;
-            if (!whole)
-            {
-                const uint32_t i = i0 + (uint32_t)u * NT + tid;
-                const uint32_t have = i < nvec ? (n - 4u * i >= 4u ? 4u : n - 4u * i) : 0u;
-                live = (1u << have) - 1u;
-                if (i == 0) live &= ~((1u << head) - 1u);
-            }
-            // kG keys at a time: their home buckets read and looked at; the second bucket only by the lanes whose key
-            // was not at home (6 % at a load of 0.37): a 16-byte LDS read costs what its busiest bank takes, and with a
-            // few lanes active that is one cycle per lane group instead of three -- the LDS pipe is this kernel's bound
-#pragma unroll
-            for (int g0 = 0; g0 < 4; g0 += kG)
-            {
-                uint32_t a1[kG], a2[kG], at[kG];
-                u32x4 q[kG];
-#pragma unroll
-                for (int j = 0; j < kG; ++j)
-                {
-                    const uint32_t f = r32_mix(kk[g0 + j]);
-                    const uint32_t h = home_of(f);
-                    a1[j] = h << 4;
-                    a2[j] = second_of(f, h) << 4;
-                    q[j] = *(lds_bucket_plain)(tb + a1[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < kG; ++j)
-                {
-                    // the count word of the slot that holds the key, else the lane's own word
-                    const uint32_t k1 = kk[g0 + j];
-                    uint32_t t = dummy;
-                    t = q[j].z == k1 ? a1[j] + 12u : t;
-                    t = q[j].x == k1 ? a1[j] + 4u : t;
-                    at[j] = t;
-                }
-                {
-                    // (a lane whose key was at home reads a bucket of its own behind the table instead: 64 such reads
-                    // are one conflict-free sweep, so the instruction costs what the few lanes that missed make it cost)
-                    u32x4 q2[kG];
-#pragma unroll
-                    for (int j = 0; j < kG; ++j)
-                    {
-#if !defined(GOSS_R32_BOTH)
-                        a2[j] = at[j] == dummy ? a2[j] : own16;
-#endif
-                        q2[j] = *(lds_bucket_plain)(tb + a2[j]);
-                    }
-#pragma unroll
-                    for (int j = 0; j < kG; ++j)
-                    {
-                        const uint32_t k1 = kk[g0 + j];
-                        uint32_t t = dummy;
-                        t = q2[j].z == k1 ? a2[j] + 12u : t;
-                        t = q2[j].x == k1 ? a2[j] + 4u : t;
-                        at[j] = at[j] == dummy ? t : at[j];
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < kG; ++j)
-                {
-                    uint32_t t = at[j];
-                    uint32_t miss = t == dummy ? 1u : 0u;
-                    if (!whole) { const uint32_t lv = (live >> (g0 + j)) & 1u; t = lv ? t : dummy; miss &= lv; }
-                    __hip_atomic_fetch_add((lds_word)(tb + t), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    pend |= miss << (4 * u + g0 + j);
-                }
-            }
-        }
-        // slow path: every lane walks its own queue of leftover keys, one probe per wave iteration
-        if (__ballot(pend != 0))
-        {
-            uint32_t key = 0, bk = 0, st = 0;
-            bool busy = false;
-            for (;;)
-            {
-                if (!busy && pend)
-                {
-                    const uint32_t u = __ffs(pend) - 1;
-                    pend &= pend - 1;
-#pragma unroll
-                    for (int uu = 0; uu < kVec; ++uu)
-                        if ((u >> 2) == (uint32_t)uu)
-                        {
-                            const uint32_t j = u & 3u;
-                            key = j == 0 ? cur[uu].x : j == 1 ? cur[uu].y : j == 2 ? cur[uu].z : cur[uu].w;
-                        }
-                    bk = home_of(r32_mix(key));
-                    st = 0;
-                    busy = true;
-                }
-                if (!__ballot(busy)) break;
-                if (busy)
-                {
-                    const u32x4 q01 = *(lds_bucket_ptr)(tb + 16u * bk);
-                    uint32_t hit = ~0u;                       // slot that holds the key
-                    if (q01.y != 0u && q01.x == key) hit = 2 * bk;
-                    else if (q01.w != 0u && q01.z == key) hit = 2 * bk + 1;
-                    else if (q01.y == 0u || q01.w == 0u)
-                    {
-                        const uint32_t slot = 2 * bk + (q01.y == 0u ? 0u : 1u);
-                        const unsigned long long old = atomicCAS(&tab[slot], (unsigned long long)marker(bk), (unsigned long long)key | (1ULL << 32));
-                        if (old == (unsigned long long)marker(bk))
-                        {
-                            const uint32_t nd = atomicAdd(&ndist, 1u);
-                            if (nd + 1 > (uint32_t)kLimit) *vovf = 1;
-                            busy = false;                     // (counted by the insertion itself)
-                        }
-                        else if ((uint32_t)old == key && (old >> 32) != 0) hit = slot;
-                        // else: somebody else took the slot; look at this bucket again
-                    }
-                    else if (st == 0) { bk = second_of(r32_mix(key), bk); st = 1; }
-                    else bk = (bk + 1) & (NB - 1u);
-                    if (hit != ~0u) { atomicAdd(reinterpret_cast<uint32_t*>(tab) + 2 * hit + 1, 1u); busy = false; }
-                }
-                if (*vovf) break;
-            }
-        }
-        if (*vovf) break;
-    }
-    __syncthreads();
-    if (ovf)
-    {
-        if (tid == 0) { atomicOr(&so->overflow, 1u); seg_pos[s] = 0; seg_cnt[s] = kSegOverflowed; }
-        return;
-    }
-
-    // Order the occupied slots on the remainder: every thread takes its slots into registers, a bucket sort on the top
-    // bits of the remainder (rank inside the bin by an LDS atomic, scan of the bin sizes, scatter as remainder << 32 |
-    // count so that a 64-bit compare orders by remainder), an insertion sort of every bin (1.5 entries on average at
-    // half the limit); a bin of more than 24 entries (skewed low bits) -> bitonic sort of the compacted entries.
-    constexpr int kPer = SLOTS / NT;
-    constexpr int kBins = SLOTS / 4, kBinsPer = kBins / NT, kBinBits = BB - 1;
-    __shared__ uint32_t bins[kBins];
-    __shared__ uint32_t sh_scan2[NT / 64 + 1];
-    __shared__ uint32_t big;
-    unsigned long long ck[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) ck[j] = tab[tid * kPer + j];
-    for (uint32_t i = tid; i < kBins; i += NT) bins[i] = 0;
-    if (tid == 0) big = 0;
-    __syncthreads();
-    const uint32_t rem_bits = rbits - (SQ ? 1u : 0u);
-    // (the top split_bits bits are the same for the whole sub-segment: the bins are cut below them)
-    const uint32_t bsh = rem_bits > (uint32_t)kBinBits + split_bits ? rem_bits - split_bits - kBinBits : 0;
-    uint32_t rnk[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-        if ((ck[j] >> 32) != 0) rnk[j] = atomicAdd(&bins[((uint32_t)ck[j] >> bsh) & (kBins - 1)], 1u);
-    __syncthreads();
-    uint32_t bn[kBinsPer], bs[kBinsPer], mine = 0;
-#pragma unroll
-    for (int q = 0; q < kBinsPer; ++q) { bn[q] = bins[tid * kBinsPer + q]; mine += bn[q]; }
-    uint32_t tot_occ;
-    uint32_t at = block_excl_scan_n<uint32_t, NT / 64>(mine, sh_scan2, &tot_occ);
-    lds_vu32 vbig = (lds_vu32)&big;
-#pragma unroll
-    for (int q = 0; q < kBinsPer; ++q)
-    {
-        bs[q] = at; bins[tid * kBinsPer + q] = at; at += bn[q];
-        if (bn[q] > 24) *vbig = 1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-        if ((ck[j] >> 32) != 0)
-            tab[bins[((uint32_t)ck[j] >> bsh) & (kBins - 1)] + rnk[j]] = (ck[j] << 32) | (ck[j] >> 32);
-    __syncthreads();
-    if (!big)
-    {
-#pragma unroll
-        for (int q = 0; q < kBinsPer; ++q)
-            for (uint32_t i = 1; i < bn[q]; ++i)
-            {
-                const unsigned long long kk = tab[bs[q] + i];
-                uint32_t j = i;
-                while (j > 0 && tab[bs[q] + j - 1] > kk) { tab[bs[q] + j] = tab[bs[q] + j - 1]; --j; }
-                tab[bs[q] + j] = kk;
-            }
-        __syncthreads();
-    }
-    else
-    {
-        uint32_t nsort = 512;
-        while (nsort < tot_occ) nsort <<= 1;
-        for (uint32_t i = tot_occ + tid; i < nsort; i += NT) tab[i] = ~0ULL;
-        __syncthreads();
-        for (uint32_t k2 = 2; k2 <= nsort; k2 <<= 1)
-            for (uint32_t j = k2 >> 1; j > 0; j >>= 1)
-            {
-                for (uint32_t t = tid; t < nsort / 2; t += NT)
-                {
-                    const uint32_t i = 2 * t - (t & (j - 1));
-                    const uint32_t p = i + j;
-                    const bool up = (i & k2) == 0;
-                    const unsigned long long a = tab[i], c2 = tab[p];
-                    if ((a > c2) == up) { tab[i] = c2; tab[p] = a; }
-                }
-                __syncthreads();
-            }
-    }
-    const uint32_t d = ndist;
-    if (tid == 0)
-    {
-        sh_base = atomicAdd(&so->cursor, (unsigned long long)d);
-        if (sh_base + d > so->stage_cap) { atomicOr(&so->overflow, 2u); sh_base = ~0ULL; }
-        seg_pos[s] = sh_base;
-        seg_cnt[s] = d;
-    }
-    __syncthreads();
-    const uint64_t ob = sh_base;
-    if (ob == ~0ULL) return;
-    const uint64_t prefix = (uint64_t)(s >> split_bits) << rbits;
-    for (uint32_t i = tid; i < d; i += NT)
-    {
-        const unsigned long long v = tab[i];
-        stage_keys[ob + i].lo = prefix | rem32_unpack<SQ>((uint32_t)(v >> 32), sqbit);
-        stage_counts[ob + i] = (uint32_t)v;
-    }
-}
 
 // Which of a bucket's four slots holds the key: the byte offset of the slot (0, 4, 8, 12), or 16 for none.  Four compares
 // into four scalar masks, then four selects: written out because the compiler runs every compare and its select through
@@ -972,17 +652,14 @@ __device__ __forceinline__ void r32b_pick4(uint32_t (&t)[4], const uint32_t (&of
         : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(dummy));
 }
 
-// The same counting with what round 5's look at the instruction stream took out (profiles/r05/SUMMARY.md): the kernel
-// above issues 51 vector instructions and three LDS operations per key -- two 16-byte bucket reads and the add -- for a
-// table whose LDS pipe is 70-85 % busy.  Here a bucket is FOUR remainders = 16 bytes of a key array, with the four
-// counts at the same offset of a count array: one 16-byte read shows a key four candidates where the pair layout
-// shows two, so at the same table size far fewer keys live outside their home bucket (load 0.19: 0.13 % of them
-// against 1.8 %) and the fast path looks at the home bucket ONLY: mix, one read, four compare-selects for the offset of
-// the count word, one add.  A key that is not at home (that per-mille, and every first occurrence) looks at its second
-// bucket under a wave-level branch and otherwise waits for the slow path, which walks home, second, second + 1, ...
-// Empty slots of bucket b hold a key that never looks at b in either of those two places (home b ^ 1, second b ^ 2), so
-// neither needs a look at the counts; the slow path's chain can reach b with that very key, and skips the bucket.
-// A slot is claimed by a 32-bit CAS on its key word (marker -> key); counts are only ever added to.
+// The counting kernel.  These kernels are bound by what they issue, not by what they read (profiles/r04), and their LDS
+// pipe is 70-85 % busy (profiles/r05/SUMMARY.md), so the fast path is as short as it gets: mix, ONE 16-byte read of the
+// home bucket, four compare-selects for the offset of the count word (or of a word of the lane's own behind the table,
+// for a miss), one unconditional add.  A bucket shows a key four candidates, so few keys live outside their home bucket
+// (load 0.19: 0.13 % of them; the pair layout of rounds 3-4, two candidates a bucket and two buckets read per key,
+// had 1.8 % and 51 vector instructions and three LDS operations per key).  A key that is not at home (that per-mille,
+// and every first occurrence) looks at its second bucket under a wave-level branch and otherwise waits in the lane's bit
+// mask for the slow path, which walks home, second, second + 1, ...
 #ifndef GOSS_R32B_VEC
 #define GOSS_R32B_VEC 4
 #endif
@@ -1076,12 +753,6 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
             const uint32_t i = i0 + (uint32_t)(kVec + u) * NT + tid;
             nxt[u] = __builtin_nontemporal_load(&v4[i < nvec ? i : nvec - 1]);
         }
-#if defined(GOSS_R32_EXP) && GOSS_R32_EXP == 1
-        // (timing experiment: the loads alone)
-#pragma unroll
-        for (int u = 0; u < kVec; ++u) asm volatile("" ::"v"(cur[u].x), "v"(cur[u].y), "v"(cur[u].z), "v"(cur[u].w));
-        continue;
-#endif
         GOSS_STAMP(1);
         // four keys at a time: their home buckets read together and looked at; a key that is not at home looks at its
         // second bucket under a wave-level branch of its own (a per-mille of the keys once the table is filled: the branch

@@ -15,14 +15,11 @@ namespace goss {
 // K2: rolling / canonical k-mer extraction straight from ASCII bases
 // --------------------------------------------------------------------------------------
 //
-// One workgroup handles a tile of T = 256*P window starts.  Phase A loads T+80 bytes with
-// 16-byte vector loads and writes one code byte (0..3, 4 = not a base) per position to LDS.
-// Phase B1: every thread derives the validity mask of its P windows; block scan gives the
-// compacted slot of each thread.  Phase B2: threads roll the forward and reverse-complement
-// key together, hash both (FNV-1a, in registers) for valid windows only and store the
-// canonical key (or both strands) into an LDS staging buffer at the compacted slot.
-// Phase C: one atomicAdd per tile reserves dense output space; staged keys are written with
-// fully coalesced stores.
+// The plain kernels take the window starts [0, nstarts) of a 16-byte aligned byte string (`mis` bytes of it lie before
+// the first window, `navail` bytes are readable) and write one key per valid window -- a window is valid when all its
+// `len` positions are bases -- densely to `out`: a tile's keys are compacted in LDS, one atomicAdd per tile on
+// ExtractCounters::keys_out reserves the output space, and the staged keys leave with fully coalesced stores.  The keys'
+// order in `out` is that of the tiles' reservations, not of the input.
 //
 // MODE 0: canonical key per window.  MODE 1: forward key and its reverse complement.
 
@@ -217,170 +214,11 @@ __device__ __forceinline__ Key2 strand_rep2(const Key2& f, const Key2& rc, uint3
 __device__ __forceinline__ bool is_pad_key(const Key1& k) { return k.lo == ~0ULL; }
 __device__ __forceinline__ bool is_pad_key(const Key2& k) { return (k.lo & k.hi) == ~0ULL; }
 
-template <class K> struct KeyOps;
-template <> struct KeyOps<Key1> {
-    static __device__ __forceinline__ Key1 zero() { return Key1{0}; }
-    static __device__ __forceinline__ void push(Key1& f, Key1& r, uint32_t c, uint64_t mask_lo, uint64_t, uint32_t topshift)
-    {
-        f.lo = ((f.lo << 2) | c) & mask_lo;
-        r.lo = (r.lo >> 2) | ((uint64_t)(3u - c) << topshift);
-    }
-};
-template <> struct KeyOps<Key2> {
-    static __device__ __forceinline__ Key2 zero() { return Key2{0, 0}; }
-    static __device__ __forceinline__ void push(Key2& f, Key2& r, uint32_t c, uint64_t mask_lo, uint64_t mask_hi, uint32_t topshift)
-    {
-        f.hi = ((f.hi << 2) | (f.lo >> 62)) & mask_hi;
-        f.lo = ((f.lo << 2) | c) & mask_lo;
-        r.lo = (r.lo >> 2) | (r.hi << 62);
-        r.hi >>= 2;
-        uint64_t cc = (uint64_t)(3u - c);
-        if (topshift >= 64) r.hi |= cc << (topshift - 64);
-        else r.lo |= cc << topshift;
-    }
-};
-
-template <class K, int MODE, int P, bool PACKED = false>
-__global__ __launch_bounds__(kTB) void extract_kernel(const uint8_t* __restrict__ bases_aligned, uint32_t mis,
-                                                      uint64_t nstarts, uint64_t navail, uint32_t len,
-                                                      K* __restrict__ out, ExtractCounters* __restrict__ ctr,
-                                                      const uint16_t* __restrict__ pbad = nullptr)
-{
-    constexpr int T = kTB * P;
-    constexpr int NVEC = T / 16 + 5;
-    constexpr int S = MODE == 1 ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) uint8_t code[NVEC * 16];
-    __shared__ K stage[T * S];
-    __shared__ uint32_t sh_scan[kWaves + 1];
-    __shared__ unsigned long long sh_base;
-
-    const uint64_t tile_base = (uint64_t)blockIdx.x * T;   // first window start of the tile
-    const uint32_t tid = threadIdx.x;
-
-    // ---- phase A: ASCII -> code bytes -------------------------------------------------
-    // LDS index a corresponds to byte (tile_base + a) of the aligned stream, i.e. window
-    // position (tile_base + a - mis).  Bytes whose position is >= navail are invalid.
-    for (uint32_t v = tid; v < NVEC; v += kTB)
-    {
-        uint64_t byte0 = tile_base + (uint64_t)v * 16;            // aligned-stream offset
-        if constexpr (PACKED)
-        {
-            // (a packed string: the group's codes and flags spread out to the code bytes this kernel works on)
-            uint32_t cd, bd, o[4];
-            load_group16<true>(bases_aligned, pbad, byte0, navail + mis, cd, bd);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-            {
-                uint32_t x = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    x |= (((bd >> (4 * i + j)) & 1u) ? 4u : ((cd >> (2 * (4 * i + j))) & 3u)) << (8 * j);
-                o[i] = x;
-            }
-            *reinterpret_cast<uint4*>(&code[v * 16]) = make_uint4(o[0], o[1], o[2], o[3]);
-            continue;
-        }
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        // positions byte0-mis .. byte0-mis+15 ; fully in range?
-        if (byte0 + 16 <= navail + mis)
-        {
-            uint4 q = *reinterpret_cast<const uint4*>(bases_aligned + byte0);
-            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        }
-        else if (byte0 < navail + mis)
-        {
-            for (int j = 0; j < 16; ++j)
-            {
-                uint64_t b = byte0 + j;
-                uint32_t c = b < navail + mis ? bases_aligned[b] : 0x0Au;
-                w[j >> 2] = (w[j >> 2] & ~(0xFFu << (8 * (j & 3)))) | (c << (8 * (j & 3)));
-            }
-        }
-        uint32_t o[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-            // SWAR over 4 bytes: 2-bit code per byte, 0x80 where the byte is no base
-            uint32_t bad;
-            const uint32_t x = base_codes(w[i], bad);
-            // bad byte -> code 4
-            uint32_t badm = (bad >> 7) * 0xFFu;      // 0xFF in bad bytes
-            o[i] = (x & ~badm) | ((bad >> 5) & 0x04040404u);
-        }
-        *reinterpret_cast<uint4*>(&code[v * 16]) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    __syncthreads();
-
-    // ---- phase B1: validity of this thread's P windows --------------------------------
-    const uint32_t q0 = tid * P + mis;               // LDS index of the first base of window 0
-    const uint64_t p0 = tile_base + (uint64_t)tid * P;   // global window start
-    uint32_t vmask = 0;
-    {
-        uint32_t run = 0;
-        const uint32_t steps = P + len - 1;
-        for (uint32_t j = 0; j < steps; ++j)
-        {
-            uint32_t c = code[q0 + j];
-            run = c < 4 ? run + 1 : 0;
-            if (j + 1 >= len && run >= len) vmask |= 1u << (j + 1 - len);
-        }
-        // windows starting at or beyond nstarts do not belong to this launch
-        if (p0 + P > nstarts)
-        {
-            uint32_t keep = p0 >= nstarts ? 0u : (uint32_t)(nstarts - p0);
-            vmask &= keep >= 32 ? 0xFFFFFFFFu : ((1u << keep) - 1u);
-        }
-    }
-    uint32_t cnt = __popc(vmask);
-    uint32_t tile_cnt;
-    uint32_t slot = block_excl_scan<uint32_t>(cnt, sh_scan, &tile_cnt);
-
-    // ---- phase B2: roll keys, canonicalise valid windows ------------------------------
-    if (cnt)
-    {
-        const uint32_t bits = 2 * len;
-        uint64_t mask_lo, mask_hi;
-        if (bits >= 128) { mask_lo = ~0ULL; mask_hi = ~0ULL; }
-        else if (bits >= 64) { mask_lo = ~0ULL; mask_hi = bits == 64 ? 0 : ((1ULL << (bits - 64)) - 1); }
-        else { mask_lo = (1ULL << bits) - 1; mask_hi = 0; }
-        const uint32_t topshift = bits - 2;
-        K f = KeyOps<K>::zero(), r = KeyOps<K>::zero();
-        const uint32_t steps = P + len - 1;
-        uint32_t s = slot * S;
-        for (uint32_t j = 0; j < steps; ++j)
-        {
-            uint32_t c = code[q0 + j] & 3u;
-            KeyOps<K>::push(f, r, c, mask_lo, mask_hi, topshift);
-            if (j + 1 >= len && ((vmask >> (j + 1 - len)) & 1u))
-            {
-                if (MODE == 0) stage[s++] = canonical(f, r);
-                else { stage[s++] = f; stage[s++] = r; }
-            }
-        }
-    }
-    if (tid == 0)
-    {
-        unsigned long long b = 0;
-        if (tile_cnt)
-        {
-            b = atomicAdd(&ctr->keys_out, (unsigned long long)tile_cnt * S);
-            atomicAdd(&ctr->windows, (unsigned long long)tile_cnt);
-        }
-        sh_base = b;
-    }
-    __syncthreads();
-
-    // ---- phase C: coalesced dense store -----------------------------------------------
-    const uint64_t ob = sh_base;
-    const uint32_t total = tile_cnt * S;
-    for (uint32_t i = tid; i < total; i += kTB) out[ob + i] = stage[i];
-}
-
 // --------------------------------------------------------------------------------------
 // K2, one-word keys: windows cut out of packed registers
 // --------------------------------------------------------------------------------------
 //
-// Same contract as extract_kernel<Key1,...>.  Phase A packs every 16 loaded bytes into a
+// Phase A packs every 16 loaded bytes into a
 // 32-bit word of 2-bit codes (base j at bits 2j) and a 16-bit mask of non-bases.  A thread then
 // holds the 128 code bits + 64 mask bits that cover its P windows in registers: the window
 // starting at base i is the field E_i = bits [2i, 2i+2len), its reverse complement is simply

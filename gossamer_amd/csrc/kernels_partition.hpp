@@ -562,7 +562,7 @@ __global__ __launch_bounds__(kTB) void radix_onesweep_kernel(const K* __restrict
 // bits are implied.  With NINE bits at the second level -- 256 x 512 = 131 072 sub-regions -- a k-mer of k = 25 has
 // 33 bits left, and the strand representative of an odd-length k-mer has one bit that is always clear (bit len - 1,
 // the low bit of its middle base: extract1_part_kernel picks the strand by it), which is squeezed out: 32 bits.
-// This kernel reads 8-byte keys and writes 4-byte remainders; seg_hash_reduce32_kernel counts those: 12 + 4 bytes per
+// This kernel reads 8-byte keys and writes 4-byte remainders; seg_hash_reduce32b_kernel counts those: 12 + 4 bytes per
 // key behind the first level instead of 16 + 8.  Applies while 2 len - 17 - (odd k-mer set ? 1 : 0) <= 32.
 // Ten bits at the second level (2^18 sub-regions) where nine leave 33 bits and there is no bit to squeeze out (graphs of
 // k = 24, k-mer sets of k = 26 would need twelve: not served).  More distinct keys than the tables of 2^17 / 2^18 segments

@@ -1,5 +1,5 @@
 """The 32-bit-remainder form of the second partition level and of the counting stage (kernels_partition.hpp:
-subpart32_kernel, kernels_count.hpp: seg_hash_reduce32_kernel; role: BackyardHash.cc:115-242 insert + count,
+subpart32_kernel, kernels_count.hpp: seg_hash_reduce32b_kernel; role: BackyardHash.cc:115-242 insert + count,
 BlendedSort.hh:68-167 order).  One-word keys whose bits below a 17-bit prefix fit 32 -- k <= 24, and k = 25 k-mer sets,
 whose strand representative has one bit that is always clear -- are written as 4-byte remainders into 131 072
 sub-regions and counted there.  Files / (key, count) lists against the oracle and against the 8-byte form."""
@@ -166,7 +166,7 @@ def test_rem32_gives_way_to_the_8_byte_form(oracle):
 
 def test_rem32_skewed_low_bits(oracle):
     """Keys of one segment that agree on the bits the ordering pass bins on: hundreds of entries in one bin, the bitonic
-    fallback of seg_hash_reduce32_kernel.  One fixed prefix + 5 random bases (1 024 distinct forward keys, fewer than
+    fallback of seg_hash_reduce32b_kernel.  One fixed prefix + 5 random bases (1 024 distinct forward keys, fewer than
     a table takes), 1.1 M reads; k = 25 (squeezed remainders) and graph k = 20."""
     rng = random.Random(8)
     for k, mode, prefix in ((25, 0, "ACGTTGCAAGCTGAGGCATC"), (20, 1, "ACGTTGCAAGCTTAGG")):

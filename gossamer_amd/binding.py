@@ -34,6 +34,7 @@ SYMBOLS = [
     "goss_gpu_object_lookup", "goss_gpu_object_node_ranks",
     "goss_gpu_prune_tips",
     "goss_gpu_segments_build", "goss_gpu_segments_table", "goss_gpu_segments_text", "goss_gpu_segments_release",
+    "goss_gpu_entries_build", "goss_gpu_entries_release", "goss_gpu_entries_length", "goss_gpu_entries_end_rank",
 ]
 
 # every symbol include/goss_gpu_match.h declares (reads against an object)
@@ -68,6 +69,16 @@ SEGMENT_INCLUDE_FIRST, SEGMENT_INCLUDE_LAST = 1, 2
 
 class SegmentsInfo(C.Structure):
     _fields_ = list(SEGMENTS_INFO_FIELDS)
+
+
+# goss_gpu_entries_info, in the order of its fields
+ENTRIES_INFO_FIELDS = (("entries", C.c_uint64), ("cycle_edges", C.c_uint64), ("longest_path", C.c_uint64),
+                       ("hist_size", C.c_uint64), ("rounds", C.c_uint32), ("walk_steps", C.c_uint32),
+                       ("ms_link", C.c_float), ("ms_rank", C.c_float), ("ms_paths", C.c_float), ("ms_emit", C.c_float))
+
+
+class EntriesInfo(C.Structure):
+    _fields_ = list(ENTRIES_INFO_FIELDS)
 
 
 def format_double(x):
@@ -676,6 +687,30 @@ class Context:
             out.append(text[o:o + int(row["text_bytes"])])
         return b"".join(out)
 
+    def entries_build(self):
+        """Between finish and emit, graph mode: build the graph's EntryEdgeSet on the device (goss_gpu_entries_build)
+        and hold its images as the context's file list ("-entries.*"); returns the info dict.  files() / read_file()
+        read them, Object.from_context opens them, entries_release gives them back."""
+        inf = EntriesInfo()
+        self._L.goss_gpu_entries_build.argtypes = [C.c_void_p, C.POINTER(EntriesInfo)]
+        self._check(self._L.goss_gpu_entries_build(self._h, C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in ENTRIES_INFO_FIELDS}
+
+    def entries_release(self):
+        self._L.goss_gpu_entries_release.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_entries_release(self._h))
+
+    def entry_edge_set(self):
+        """The EntryEdgeSet of the graph, as `goss build-entry-edge-set` writes it: ({name: bytes}, info), the names
+        as on disk less the graph's name ("-entries.header", "-entries.edges.high-bits", ...).  The context's result
+        is untouched."""
+        info = self.entries_build()
+        try:
+            files = self.files()
+        finally:
+            self.entries_release()
+        return files, info
+
     def check_index(self, files, base=""):
         """goss_gpu_check_index on a SparseArray given as {suffix: bytes} (files[base + ".header"]
         ...): the context must hold the array's decoded elements (push_run + finish).  Returns a
@@ -751,7 +786,7 @@ class Context:
 
 # ---- objects opened for queries (goss_gpu_object_*) ------------------------------------------
 
-OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY = 0, 1, 2
+OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY, OBJECT_ENTRY_EDGE_SET = 0, 1, 2, 3
 QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
 MATCH_NORMALIZE, MATCH_ANY = 1, 4
 ERR_BUFFER = -9
@@ -817,11 +852,13 @@ def _declare_object(L):
     L.goss_gpu_object_lookup.argtypes = [P, P, U64, C.c_uint32, P]
     L.goss_gpu_object_node_ranks.argtypes = [P, P, U64, C.c_uint32, P, P]
     L.goss_gpu_object_match_reads.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(MatchInfo)]
+    L.goss_gpu_entries_length.argtypes = [P, P, U64, P]
+    L.goss_gpu_entries_end_rank.argtypes = [P, P, U64, P]
     L._object_declared = True
 
 
 class Object:
-    """One KmerSet, Graph or bare SparseArray resident in HBM, with batched queries (goss_gpu_object_*).
+    """One KmerSet, Graph, bare SparseArray or EntryEdgeSet resident in HBM, with batched queries (goss_gpu_object_*).
 
     Every query takes device torch tensors (used in place; results come back as torch tensors on the same device)
     or numpy arrays (staged through the device; results come back as numpy).  Keys: uint64 values when
@@ -860,7 +897,8 @@ class Object:
 
     @classmethod
     def from_context(cls, ctx):
-        """What the context has just emitted, device to device (goss_gpu_object_open_emitted)."""
+        """What the context has just emitted -- or built with entries_build --, device to device
+        (goss_gpu_object_open_emitted)."""
         L = load()
         _declare_object(L)
         h = C.c_void_p()
@@ -966,6 +1004,24 @@ class Object:
         flags = (QUERY_INCOMING if incoming else 0) | (QUERY_NORMALIZE if normalize else 0)
         self._check(self._L.goss_gpu_object_node_ranks(self._h, t.data_ptr(), n, flags, b.data_ptr(), e.data_ptr()))
         return self._back(b, staged, np.uint64), self._back(e, staged, np.uint64)
+
+    def length(self, ranks):
+        """EntryEdgeSet::length of every entry rank: the edges of the path that starts there (u32; torch: int32)"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(ranks, 1)
+        c = self._out(t, n, torch.int32)
+        self._check(self._L.goss_gpu_entries_length(self._h, t.data_ptr(), n, c.data_ptr()))
+        return self._back(c, staged, np.uint32)
+
+    def end_rank(self, ranks):
+        """EntryEdgeSet::endRank of every entry rank: the entry at which the mirror path starts (u64; torch: int64)"""
+        import numpy as np
+        import torch
+        t, n, staged = self._input(ranks, 1)
+        e = self._out(t, n, torch.int64)
+        self._check(self._L.goss_gpu_entries_end_rank(self._h, t.data_ptr(), n, e.data_ptr()))
+        return self._back(e, staged, np.uint64)
 
     def match_reads(self, bases, normalize=False, any=False, starts=False, flags=0, max_reads=None):
         """(windows, hits[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_match_reads.

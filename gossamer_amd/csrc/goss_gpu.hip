@@ -230,6 +230,10 @@ struct goss_gpu_ctx {
     uint64_t seg_count = 0, seg_text_bytes = 0, seg_lo = 0;
     bool seg_live = false;
     bool seg_hold = false;                // the entry point that runs now only reads: what is held stays
+    // goss_gpu_entries_build: the images of the EntryEdgeSet are the file list, in permanent room above everything else
+    // from ent_lo on, held exactly as the segments are (at most one of the two is live)
+    uint64_t ent_lo = 0;
+    bool ent_live = false;
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -2275,8 +2279,10 @@ void add_host_file(goss_gpu_ctx* c, const std::string& suffix, const void* p, si
     c->files.push_back(std::move(f));
 }
 
-// VariableByteArray + counts histogram (VariableByteArray.hh:76-118, Graph.cc:115-134).
-void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t num_items, const std::string& out_counts, const std::string& out_hist)
+// VariableByteArray + counts histogram (VariableByteArray.hh:76-118, Graph.cc:115-134) of any u32 column on the
+// device.  out_hist empty: no histogram file; hist_lines: the number of distinct values the histogram lists.
+void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t num_items, const std::string& out_counts, const std::string& out_hist,
+                 uint64_t* hist_lines = nullptr)
 {
     uint64_t mark = c->arena.mark();
     uint8_t* ord0 = (uint8_t*)c->arena.perm(std::max<uint64_t>(m, 8));
@@ -2326,7 +2332,8 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
 
     // histogram of counts: sort the counts as keys, run-length them, format on the host
     std::string text;
-    if (m)
+    if (hist_lines) *hist_lines = 0;
+    if (m && !out_hist.empty())
     {
         Key1* ka = (Key1*)c->arena.temp(m * 8);
         Key1* kb = (Key1*)c->arena.temp(m * 8);
@@ -2361,6 +2368,7 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
                 if (it != hist.end() && --it->second == 0) hist.erase(it);
                 hist[kv.second] += 1;
             }
+        if (hist_lines) *hist_lines = hist.size();
         char line[64];
         for (auto& kv : hist)
         {
@@ -2368,7 +2376,7 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
             text.append(line, (size_t)l);
         }
     }
-    add_host_file(c, out_hist, text.data(), text.size());
+    if (!out_hist.empty()) add_host_file(c, out_hist, text.data(), text.size());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->arena.release(mark);
 }
@@ -2685,6 +2693,7 @@ int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
         // segments held by goss_gpu_segments_build lie on top of the permanent room: whatever may allocate there, or
         // change the result they were read from, gives them back first
         if (c && c->seg_live && !c->seg_hold) { c->arena.lo = c->seg_lo; c->seg_live = false; }
+        if (c && c->ent_live && !c->seg_hold) { c->arena.lo = c->ent_lo; c->ent_live = false; c->files.clear(); }
         if (c) c->seg_hold = false;
         f();
         // a refused kernel launch raises no exception by itself and leaves its outputs untouched:
@@ -5196,6 +5205,204 @@ int goss_gpu_segments_release(goss_gpu_ctx* c)
     return GOSS_OK;
 }
 
+extern "C++" {
+// The EntryEdgeSet of the result (EntryEdgeSet::build, EntryEdgeSet.cc:154-287).  Working arrays under an ArenaScope;
+// the compacted columns and the file images are permanent room on top of everything else (c->ent_lo marks where it
+// began), and the images are the context's file list under names that begin with "-entries".
+template <class K>
+static void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
+{
+    static_assert(sizeof(ContigsReport) <= 128, "pinned scratch");
+    goss_gpu_entries_info inf{};
+    const uint64_t n64 = c->M;
+    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "entries: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
+    const uint32_t n = (uint32_t)n64;
+    const uint32_t bits = n ? tips_bucket_bits(n, c->len) : 0;
+    const uint32_t steps = contigs_walk_steps();
+    inf.walk_steps = steps;
+    {
+        // rcr, nxt, pred (4 + 4 + 4), two arrays of pairs and two of weights (4 x 8), the scan (8), info, flag, st: 55
+        // bytes per edge and the table; then per entry the key, two columns, the images and what the emit kernels sort
+        const uint64_t need = n64 * 55 + (bits ? ((1ULL << bits) + 1) * 4 : 0) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+        c->ent_lo = c->arena.lo;
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    const K* keys = (const K*)c->res_keys;
+    const uint32_t* counts = c->res_counts;
+    ContigsReport* h = (ContigsReport*)c->h_pinned;
+    uint64_t* hx = (uint64_t*)((uint8_t*)c->h_pinned + 128);
+    uint64_t nent = 0;
+    K* ekeys = nullptr;
+    uint32_t *elen = nullptr, *ecnt = nullptr, *lwr = nullptr;
+    uint8_t* upr = nullptr;
+    auto columns = [&]() {
+        ekeys = (K*)c->arena.perm(std::max<uint64_t>(nent * sizeof(K), 16));
+        elen = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+        ecnt = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+        upr = (uint8_t*)c->arena.perm(std::max<uint64_t>(nent, 16));
+        lwr = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+    };
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (n == 0)
+    {
+        columns();
+        for (int i = 1; i < 4; ++i) HIP_TRY(hipEventRecord(ev.e[i], c->stream));
+    }
+    else
+    {
+        uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
+        uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
+        uint8_t* info = (uint8_t*)c->arena.temp(n64);
+        uint8_t* flag = (uint8_t*)c->arena.temp(n64);
+        uint8_t* st = (uint8_t*)c->arena.temp(n64);
+        uint32_t* pred = (uint32_t*)c->arena.temp(n64 * 4);
+        uint2* cur = (uint2*)c->arena.temp(n64 * 8);
+        uint2* oth = (uint2*)c->arena.temp(n64 * 8);
+        uint64_t* wcur = (uint64_t*)c->arena.temp(n64 * 8);
+        uint64_t* woth = (uint64_t*)c->arena.temp(n64 * 8);
+        uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+        uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
+        ContigsReport* d_rep = (ContigsReport*)c->arena.temp(sizeof(ContigsReport));
+        TipsReport* d_tips = (TipsReport*)c->arena.temp(sizeof(TipsReport));
+
+        // ---- the link pass of prune-tips, as it is
+        HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(ContigsReport), c->stream));
+        HIP_TRY(hipMemsetAsync(d_tips, 0, sizeof(TipsReport), c->stream));
+        HIP_TRY(hipMemsetAsync(&d_tips->missing_rc, 0xFF, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(pred, 0, n64 * 4, c->stream));
+        const dim3 grid(grid_for(n64, kTB)), block(kTB);
+        const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kContigsGridBlocks));
+        if (bits)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
+                           (const uint32_t*)table, rcr, nxt, info, d_tips);
+        HIP_TRY(hipMemcpyAsync(hx, &d_tips->missing_rc, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        if (hx[0] != ~0ULL)
+            throw StatusError{GOSS_ERR_INVALID_ARG, "entries: edge " + std::to_string(hx[0]) +
+                                                        " has no reverse complement in the graph (lint-graph reports such edges)"};
+
+        // ---- starts, predecessors, list ranking with the weights; the numbering of the starts
+        hipLaunchKernelGGL(contigs_mark_kernel, grid, block, 0, c->stream, (const uint32_t*)rcr, (const uint32_t*)nxt,
+                           (const uint8_t*)info, n, flag, pred);
+        hipLaunchKernelGGL(entries_flags_kernel, grid, block, 0, c->stream, (const uint8_t*)flag, n, sc);
+        HIP_TRY(hipMemsetAsync(sc + n64, 0, 8, c->stream));
+        exclusive_scan_u64(c, sc, n64 + 1);
+        HIP_TRY(hipMemcpyAsync(hx, sc + n64, 8, hipMemcpyDeviceToHost, c->stream));
+        hipLaunchKernelGGL(entries_walk_kernel, few, block, 0, c->stream, (const uint32_t*)pred, (const uint8_t*)flag, counts, n, steps,
+                           cur, oth, wcur, woth, st, d_rep);
+        uint32_t rounds = 1;
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        nent = hx[0];
+        uint64_t open = h->open, resolved = 0;
+        while (open && rounds < 64)
+        {
+            hipLaunchKernelGGL(entries_double_kernel, few, block, 0, c->stream, (const uint2*)cur, oth, (const uint64_t*)wcur, woth,
+                               (const uint8_t*)flag, st, n, d_rep);
+            std::swap(cur, oth);
+            std::swap(wcur, woth);
+            ++rounds;
+            HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            check_launch("a kernel launch was refused");
+            const uint64_t fresh = h->resolved - resolved;
+            resolved = h->resolved;
+            if (fresh == 0) break;                          // what is open now lies on cycles without a start
+            open -= fresh;
+        }
+        inf.rounds = rounds;
+        HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+
+        // ---- the records, compacted: every path's last edge writes where the path's start goes
+        columns();
+        if (nent)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(entries_keys_kernel<K>), grid, block, 0, c->stream, keys, (const uint8_t*)flag,
+                               (const uint64_t*)sc, n, ekeys);
+        hipLaunchKernelGGL(entries_paths_kernel, few, block, 0, c->stream, (const uint2*)cur, (const uint64_t*)wcur, (const uint8_t*)flag,
+                           (const uint8_t*)st, (const uint32_t*)rcr, counts, (const uint64_t*)sc, n, elen, ecnt, upr, lwr, d_rep);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        check_launch("a kernel launch was refused");
+        inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
+    }
+    inf.entries = nent;
+
+    // ---- the images (EntryEdgeSet.cc:203-286): SparseArray::Builder(.edges, z, n) ... end(z) with z = 4^(K+1), two
+    // VariableByteArrays of n items, the histogram of the counts, the 40-bit IntegerArray, the header
+    const std::string base = "-entries";
+    const uint32_t ubits = 2 * c->k + 2;
+    const uint64_t zlo = ubits < 64 ? (1ULL << ubits) : 0, zhi = ubits >= 64 ? (1ULL << (ubits - 64)) : 0;
+    emit_sparse_array<K>(c, ekeys, nent, zlo, zhi, nent, zlo, zhi, base + ".edges");
+    uint64_t lines = 0;
+    emit_counts(c, ecnt, nent, nent, base + ".counts", base + ".counts-hist.txt", &lines);
+    emit_counts(c, elen, nent, nent, base + ".lengths", std::string());
+    inf.hist_size = lines;
+    {
+        std::vector<IaCol> cols;                          // RankBits = 40 (EntryEdgeSet.hh:41): ".upr" u8, ".lwr" u32
+        ia_layout(40, base + ".ends", 0, cols);
+        const uint8_t* img[2] = {upr, (const uint8_t*)lwr};
+        for (size_t i = 0; i < cols.size() && i < 2; ++i)
+        {
+            OutFile f; f.suffix = cols[i].suffix; f.size = nent * cols[i].bytes; f.dev = img[i];
+            c->files.push_back(std::move(f));
+        }
+    }
+    const uint64_t hdr[2] = {2011041901ULL, c->k};
+    add_host_file(c, base + ".header", hdr, sizeof hdr);
+    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_paths, &inf.ms_emit};
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    *out = inf;
+}
+}  // extern "C++"
+
+int goss_gpu_entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
+{
+    if (!c || !out) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "an entry edge set is built from a graph"; return GOSS_ERR_STATE; }
+    if (!c->finished || c->emitted) { c->last_error = "entries belong between finish and emit"; return GOSS_ERR_STATE; }
+    if (!c->res_big.empty())
+    {
+        c->last_error = "entries: the graph has multiplicities of 2^32 - 1 or more";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    bool began = false;
+    int rc = guarded(c, [&]() {                          // (gives back what an earlier build holds)
+        c->files.clear();
+        c->ent_lo = c->arena.lo;
+        began = true;
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        if (c->words == 1) entries_build<Key1>(c, out); else entries_build<Key2>(c, out);
+        t.stop();
+        c->ent_live = true;
+    });
+    if (rc != GOSS_OK)
+    {
+        // nothing is held after a failure; the result was only read
+        if (began) { c->arena.lo = c->ent_lo; c->files.clear(); }
+        c->ent_live = false;
+        std::memset(out, 0, sizeof *out);
+    }
+    return rc;
+}
+
+int goss_gpu_entries_release(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->ent_live) { c->arena.lo = c->ent_lo; c->ent_live = false; c->files.clear(); }
+    return GOSS_OK;
+}
+
 int goss_gpu_emit_count_bits(goss_gpu_ctx* c, uint32_t mask, const char* suffix)
 {
     if (!c || !suffix || !mask) return GOSS_ERR_INVALID_ARG;
@@ -5266,6 +5473,7 @@ struct goss_gpu_object {
     unsigned long long* d_bad = nullptr;
     unsigned long long* h_bad = nullptr;    // (page-locked)
     QueryObj q{};
+    QueryEntries qe{};                      // an EntryEdgeSet's lengths and ends
     std::string last_error;
     // goss_gpu_object_match_reads: grow-only working memory (tile counts and their scan; outputs the caller left out),
     // a page-locked block for what comes back, the events that time the kernels
@@ -5370,10 +5578,52 @@ void open_object(goss_gpu_object* o, int kind, const std::string& base, const Ob
     ObjPlan pl{files};
     QueryObj& q = o->q;
     o->kind = kind;
+    // VariableByteArray(base, fac) (VariableByteArray.hh:120-160) of `items` values
+    auto plan_vba = [&](const std::string& vb, RdVba& v, uint64_t items) {
+        const ObjSrc& o0 = pl.need(vb + ".ord0");
+        if (o0.n < items) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord0 is shorter than the item count"};
+        pl.place(o0, items, (const void**)&v.ord0);
+        plan_sparse(pl, vb + ".ord1p", v.p1);
+        plan_sparse(pl, vb + ".ord2p", v.p2);
+        if (v.p1.size_hi || v.p2.size_hi) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ": presence arrays wider than 64 bits"};
+        const ObjSrc& o1 = pl.need(vb + ".ord1");
+        const ObjSrc& o2 = pl.need(vb + ".ord2");
+        if (o1.n < v.p1.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord1 is shorter than the ord1p count"};
+        if (o2.n / 2 < v.p2.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord2 is shorter than the ord2p count"};
+        pl.place(o1, v.p1.count, (const void**)&v.ord1);
+        pl.place(o2, v.p2.count * 2, (const void**)&v.ord2);
+    };
     if (kind == GOSS_OBJECT_SPARSE_ARRAY)
     {
         plan_sparse(pl, base, q.s);
         o->key_words = q.s.size_hi ? 2 : 1;
+    }
+    else if (kind == GOSS_OBJECT_ENTRY_EDGE_SET)
+    {
+        // EntryEdgeSet(baseName, fac) (EntryEdgeSet.cc:139-152, 299-306): header, .edges, .counts, .lengths, .ends
+        const ObjSrc& hs = pl.need(base + ".header");
+        if (hs.n < 16) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header is too short"};
+        uint64_t h[2];
+        std::memcpy(h, pl.head(hs, 16).data(), 16);
+        if (h[0] != 2011041901ULL) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: EntryEdgeSet version mismatch"};
+        if (h[1] == 0 || h[1] > 62u) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: K out of range"};
+        o->K = (uint32_t)h[1];
+        q.len = o->K + 1;
+        q.graph = 1;                                              // (a count per element: lookup answers it)
+        o->key_words = 2 * q.len <= 62 ? 1 : 2;
+        o->node_words = 2 * o->K <= 62 ? 1 : 2;
+        plan_sparse(pl, base + ".edges", q.s);
+        uint64_t nhi, nlo = pow4(q.len, &nhi);
+        if (q.s.size_lo != nlo || q.s.size_hi != nhi) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".edges.header: the universe is not 4^len"};
+        plan_vba(base + ".counts", q.v, q.s.count);
+        plan_vba(base + ".lengths", o->qe.lengths, q.s.count);
+        o->qe.count = q.s.count;
+        const ObjSrc& up = pl.need(base + ".ends.upr");
+        const ObjSrc& lw = pl.need(base + ".ends.lwr");
+        if (up.n < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".ends.upr is shorter than the entry count"};
+        if (lw.n / 4 < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".ends.lwr is shorter than the entry count"};
+        pl.place(up, q.s.count, (const void**)&o->qe.ends_upr);
+        pl.place(lw, q.s.count * 4, (const void**)&o->qe.ends_lwr);
     }
     else
     {
@@ -5398,20 +5648,7 @@ void open_object(goss_gpu_object* o, int kind, const std::string& base, const Ob
         if (!graph && h[2] != q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: count differs from " + sa};
         if (graph)
         {
-            // VariableByteArray(base, fac) (VariableByteArray.hh:120-160)
-            const std::string vb = base + "-counts";
-            const ObjSrc& o0 = pl.need(vb + ".ord0");
-            if (o0.n < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord0 is shorter than the edge count"};
-            pl.place(o0, q.s.count, (const void**)&q.v.ord0);
-            plan_sparse(pl, vb + ".ord1p", q.v.p1);
-            plan_sparse(pl, vb + ".ord2p", q.v.p2);
-            if (q.v.p1.size_hi || q.v.p2.size_hi) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ": presence arrays wider than 64 bits"};
-            const ObjSrc& o1 = pl.need(vb + ".ord1");
-            const ObjSrc& o2 = pl.need(vb + ".ord2");
-            if (o1.n < q.v.p1.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord1 is shorter than the ord1p count"};
-            if (o2.n / 2 < q.v.p2.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord2 is shorter than the ord2p count"};
-            pl.place(o1, q.v.p1.count, (const void**)&q.v.ord1);
-            pl.place(o2, q.v.p2.count * 2, (const void**)&q.v.ord2);
+            plan_vba(base + "-counts", q.v, q.s.count);
         }
     }
     // one allocation: the images, then the failure word
@@ -5520,7 +5757,8 @@ int goss_gpu_object_open(goss_gpu_object** out, int device, void* stream, int ki
     if (!out) return GOSS_ERR_INVALID_ARG;
     *out = nullptr;
     t_open_error.clear();
-    if (kind != GOSS_OBJECT_KMER_SET && kind != GOSS_OBJECT_GRAPH && kind != GOSS_OBJECT_SPARSE_ARRAY) return GOSS_ERR_INVALID_ARG;
+    if (kind != GOSS_OBJECT_KMER_SET && kind != GOSS_OBJECT_GRAPH && kind != GOSS_OBJECT_SPARSE_ARRAY && kind != GOSS_OBJECT_ENTRY_EDGE_SET)
+        return GOSS_ERR_INVALID_ARG;
     if (!base || (!files && nfiles)) return GOSS_ERR_INVALID_ARG;
     if (int rc = usable_device(device)) return rc;
     ObjFiles fs;
@@ -5540,14 +5778,17 @@ int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* c)
     ObjFiles fs;
     for (auto& f : c->files) fs[f.suffix] = ObjSrc{f.dev ? f.dev : f.host.data(), f.size, f.dev != nullptr};
     int kind = -1;
+    std::string base;
     if (fs.count(".kmers.header")) kind = GOSS_OBJECT_KMER_SET;
     else if (fs.count("-edges.header")) kind = GOSS_OBJECT_GRAPH;
     else if (fs.count(".high-bits")) kind = GOSS_OBJECT_SPARSE_ARRAY;
-    if (kind < 0) { t_open_error = "the context holds no emitted KmerSet, Graph or SparseArray"; return GOSS_ERR_STATE; }
-    // what the context's stream still writes into its files
+    else if (fs.count("-entries.header")) { kind = GOSS_OBJECT_ENTRY_EDGE_SET; base = "-entries"; }
+    if (kind < 0) { t_open_error = "the context holds no emitted KmerSet, Graph, SparseArray or EntryEdgeSet"; return GOSS_ERR_STATE; }
+    // what the context's stream still writes into its files (the call only reads: what is held stays)
+    c->seg_hold = true;
     int rc = guarded(c, [&]() { HIP_TRY(hipStreamSynchronize(c->stream)); });
     if (rc != GOSS_OK) { t_open_error = c->last_error; return rc; }
-    return object_open(out, c->device, nullptr, kind, "", fs);
+    return object_open(out, c->device, nullptr, kind, base, fs);
 }
 
 void goss_gpu_object_close(goss_gpu_object* o) { object_free(o); }
@@ -5590,7 +5831,7 @@ int goss_gpu_object_select(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t
 int goss_gpu_object_multiplicity(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t n, uint32_t* d_counts)
 {
     if (!o || ((!d_ranks || !d_counts) && n)) return GOSS_ERR_INVALID_ARG;
-    if (o->kind != GOSS_OBJECT_GRAPH) { o->last_error = "multiplicity needs a Graph"; return GOSS_ERR_INVALID_ARG; }
+    if (o->kind != GOSS_OBJECT_GRAPH && o->kind != GOSS_OBJECT_ENTRY_EDGE_SET) { o->last_error = "multiplicity needs a Graph or an EntryEdgeSet"; return GOSS_ERR_INVALID_ARG; }
     return object_query(o, n, [&](dim3 grid) {
         hipLaunchKernelGGL(query_multiplicity_kernel, grid, dim3(256), 0, o->stream, o->q, d_ranks, n, d_counts, o->d_bad);
     });
@@ -5619,6 +5860,24 @@ int goss_gpu_object_node_ranks(goss_gpu_object* o, const void* d_nodes, uint64_t
             hipLaunchKernelGGL(HIP_KERNEL_NAME(query_node_ranks_kernel<Key1, Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key1*)d_nodes, n, flags, d_begin, d_end, o->d_bad);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(query_node_ranks_kernel<Key2, Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key2*)d_nodes, n, flags, d_begin, d_end, o->d_bad);
+    });
+}
+
+int goss_gpu_entries_length(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t n, uint32_t* d_lengths)
+{
+    if (!o || ((!d_ranks || !d_lengths) && n)) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_ENTRY_EDGE_SET) { o->last_error = "length needs an EntryEdgeSet"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        hipLaunchKernelGGL(query_length_kernel, grid, dim3(256), 0, o->stream, o->qe, d_ranks, n, d_lengths, o->d_bad);
+    });
+}
+
+int goss_gpu_entries_end_rank(goss_gpu_object* o, const uint64_t* d_ranks, uint64_t n, uint64_t* d_ends)
+{
+    if (!o || ((!d_ranks || !d_ends) && n)) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_ENTRY_EDGE_SET) { o->last_error = "end_rank needs an EntryEdgeSet"; return GOSS_ERR_INVALID_ARG; }
+    return object_query(o, n, [&](dim3 grid) {
+        hipLaunchKernelGGL(query_end_rank_kernel, grid, dim3(256), 0, o->stream, o->qe, d_ranks, n, d_ends, o->d_bad);
     });
 }
 

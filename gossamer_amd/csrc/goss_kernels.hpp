@@ -22,4 +22,5 @@
 #include "kernels_query.hpp"
 #include "kernels_tips.hpp"
 #include "kernels_contigs.hpp"
+#include "kernels_entries.hpp"
 #include "kernels_match.hpp"

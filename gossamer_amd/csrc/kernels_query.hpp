@@ -1,5 +1,6 @@
 // kernels_query.hpp -- batched queries against one KmerSet / Graph / SparseArray resident in HBM
-// (goss_gpu_object_*): rank / presence, select, multiplicity, the fused lookup and a node's edge range.
+// (goss_gpu_object_*): rank / presence, select, multiplicity, the fused lookup and a node's edge range; for an
+// EntryEdgeSet also a path's length and the entry of its mirror path.
 // One lane per query, grid-stride; no LDS.  A query is a chain of dependent global loads through the
 // structure (d0 rank + index arrays, the sample, high-bits words, the low-bits columns of a group of one
 // or two elements, and for a graph's count ord0 plus two more rank walks over ord1p / ord2p): latency,
@@ -130,6 +131,41 @@ __global__ __launch_bounds__(256) void query_lookup_kernel(QueryObj o, const K* 
         uint32_t c = p ? 1u : 0u;
         if (p && o.graph && !rd_vba_get(o.v, r, &c)) { q_fail(bad, i, kQBadWalk); continue; }
         out[i] = c;
+    }
+}
+
+// What an EntryEdgeSet holds beside its edges and counts (EntryEdgeSet.hh:100-125): the paths' lengths and, as the
+// two columns of a 40-bit IntegerArray, the entry at which each path's mirror image starts.
+struct QueryEntries {
+    RdVba lengths;
+    const uint8_t* ends_upr;
+    const uint32_t* ends_lwr;
+    uint64_t count;
+};
+
+// EntryEdgeSet::length(rank) (EntryEdgeSet.hh:113-118)
+__global__ __launch_bounds__(256) void query_length_kernel(QueryEntries e, const uint64_t* __restrict__ ranks, uint64_t n,
+                                                           uint32_t* __restrict__ out, unsigned long long* bad)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    {
+        const uint64_t r = ranks[i];
+        if (r >= e.count) { q_fail(bad, i, kQBadRank); continue; }
+        uint32_t l;
+        if (!rd_vba_get(e.lengths, r, &l)) { q_fail(bad, i, kQBadWalk); continue; }
+        out[i] = l;
+    }
+}
+
+// EntryEdgeSet::endRank(rank) (EntryEdgeSet.hh:120-125)
+__global__ __launch_bounds__(256) void query_end_rank_kernel(QueryEntries e, const uint64_t* __restrict__ ranks, uint64_t n,
+                                                             uint64_t* __restrict__ out, unsigned long long* bad)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    {
+        const uint64_t r = ranks[i];
+        if (r >= e.count) { q_fail(bad, i, kQBadRank); continue; }
+        out[i] = ((uint64_t)e.ends_upr[r] << 32) | e.ends_lwr[r];
     }
 }
 

@@ -1926,6 +1926,7 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  trim-graph       create a new graph by trimming low frequency edges\n"
               << "  prune-tips       create a new graph by removing low frequency tips\n"
               << "  print-contigs    print all the non-branching paths in the given assembly graph\n"
+              << "  build-entry-edge-set  build an entry edge set for a graph\n"
               << "  extract-reads    extract reads which map on to a graph\n"
               << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n";
     if (t)
@@ -1957,8 +1958,8 @@ int gossMain(int argc, char* argv[])
         const bool isDump = cmdName == "dump-kmer-set" || cmdName == "dump-graph";
         const bool isRestore = cmdName == "restore-graph", isLint = cmdName == "lint-graph";
         const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
-        const bool isContigs = cmdName == "print-contigs";
-        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs)
+        const bool isContigs = cmdName == "print-contigs", isEntries = cmdName == "build-entry-edge-set";
+        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
         {
             // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
             // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
@@ -1968,7 +1969,7 @@ int gossMain(int argc, char* argv[])
             // GossCmdFactoryMergeAndAnnotateKmerSets::create (GossCmdMergeAndAnnotateKmerSets.cc:209-224),
             // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378),
             // GossCmdFactoryTrimGraph::create (GossCmdTrimGraph.cc:130-172), GossCmdFactoryPruneTips::create
-            // (GossCmdPruneTips.cc:347-373)
+            // (GossCmdPruneTips.cc:347-373), GossCmdFactoryBuildEntryEdgeSet::create (GossCmdBuildEntryEdgeSet.cc:68-84)
             static const OptDef kTrimPrune[] = {
                 {"cutoff", "C", kU64, "coverage cutoff"},
                 {"estimate-only", "", kFlag, "only estimate the coverage cutoff (trim-graph)"},
@@ -2028,13 +2029,18 @@ int gossMain(int argc, char* argv[])
             uint64_t cutoff = 0, iterations = 1;
             std::string notOffered;                 // a part of trim-graph / prune-tips that this build refuses
             uint64_t minLength = 0, minCoverage = 0;
-            if (isDump || isLint || isContigs)
+            if (isDump || isLint || isContigs || isEntries)
             {
                 // getRepeatingOnce("graph-in") (GossOptionChecker.hh:235-254)
                 if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
                 else if (opts.strs("graph-in").size() != 1)
                 { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
                 else ins = opts.strs("graph-in");
+                if (isEntries)
+                {
+                    uint64_t ignoredThreads = 4;            // (the walk is the device's)
+                    chk.optionalU64("num-threads", ignoredThreads);
+                }
                 if (isContigs)
                 {
                     uint64_t ignoredThreads = 1;
@@ -2152,6 +2158,7 @@ int gossMain(int argc, char* argv[])
                 else if (isToKmerSet) { GossCmdGraphToKmerSet cmd(ins[0], outName); cmd(cxt); }
                 else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
                 else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
+                else if (isEntries) { GossCmdBuildEntryEdgeSet cmd(ins[0]); cmd(cxt); }
                 else if (isContigs)
                 {
                     GossCmdPrintContigs cmd(ins[0], minCoverage, minLength, opts.count("no-sequence") != 0, opts.count("verbose-headers") != 0,

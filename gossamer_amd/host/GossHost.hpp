@@ -286,6 +286,16 @@ private:
     const std::string mIn, mOut; const uint64_t mC, mL; const bool mOmitSequence, mVerboseHeaders, mNoLineBreaks;
 };
 
+// GossCmdBuildEntryEdgeSet (GossCmdBuildEntryEdgeSet.{hh,cc}): the EntryEdgeSet of a graph, written beside it as
+// <graph>-entries.*.
+class GossCmdBuildEntryEdgeSet {
+public:
+    explicit GossCmdBuildEntryEdgeSet(const std::string& pIn) : mIn(pIn) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn;
+};
+
 // GossCmdExtractReads (GossCmdExtractReads.{hh,cc}): the reads with at least one (K + 1)-mer that is an edge of the graph, as
 // parsed, one per line, in input order (line files, then FASTA, then FASTQ).
 class GossCmdExtractReads {

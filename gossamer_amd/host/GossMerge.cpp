@@ -1026,6 +1026,31 @@ void GossCmdPrintContigs::operator()(const GossCmdContext& pCxt)
     log(info, elapsed(t0));
 }
 
+// GossCmdBuildEntryEdgeSet::operator() (GossCmdBuildEntryEdgeSet.cc:48-66) -> EntryEdgeSet::build
+// (EntryEdgeSet.cc:154-287).  The device finds the entry edges and their figures and builds every image
+// (goss_gpu_entries_build); the images are the context's file list under "-entries.*", written beside the graph.
+void GossCmdBuildEntryEdgeSet::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    log(info, "Loading graph");
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    log(info, "Locating entry edges");
+    goss_gpu_entries_info inf;
+    g.check(goss_gpu_entries_build(g.h, &inf), "building the entry edge set");
+    log(info, "entry edges: " + num(inf.entries) + ", edges on cycles: " + num(inf.cycle_edges) + ", longest path: "
+                  + num(inf.longest_path) + " edges");
+    log(info, "Writing entry edges");
+    log(info, "Writing counts histogram");
+    log(info, "Writing end edges");
+    writeOut(g, mIn);
+    g.check(goss_gpu_entries_release(g.h), "releasing the entry edge set");
+    log(info, elapsed(t0));
+}
+
 void GossCmdMergeKmerSets::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, false, mIns, mMaxMerge, mOut); }
 void GossCmdMergeGraphs::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, true, mIns, mMaxMerge, mOut); }
 

@@ -613,6 +613,52 @@ int goss_gpu_segments_text(goss_gpu_ctx* ctx, uint64_t text_offset, uint64_t byt
 int goss_gpu_segments_release(goss_gpu_ctx* ctx);
 
 /*
+ * Between finish and emit, graph mode: the EntryEdgeSet of the graph the context holds, as
+ * `goss build-entry-edge-set` writes it beside the graph (EntryEdgeSet::build, EntryEdgeSet.cc:154-287,
+ * called by GossCmdBuildEntryEdgeSet.cc:48-66 with the base name <graph> + "-entries").  An edge is an
+ * entry edge unless its from-node has exactly one edge in and one out (EntryEdgeSet.cc:76-80); entry j,
+ * in rank order, holds the number of edges of the linear path that starts there (Graph::linearPath,
+ * Graph.tcc:19-46), the mean of the path's own multiplicities rounded half away from zero
+ * (boost::math::round, EntryEdgeSet.cc:85-86) and, as `ends`, the number among the entries of the
+ * reverse complement of the path's last edge: the start of the mirror path (j itself for a path that is
+ * its own mirror image).  Cycles whose nodes are all one-in-one-out start nothing.
+ *
+ * The link pass of goss_gpu_prune_tips and the list ranking of goss_gpu_segments_build find every
+ * edge's start and position (`rounds` launches, no more than ceil(log2(longest_path)) + 2); a u64
+ * weight carried through the same rounds gives every path's sum at its last edge, so no edge is sorted
+ * by (path, position).  A prefix sum over the start flags numbers the entries.
+ *
+ * build: any number of times; the context's result is only read.  The images replace the context's
+ * file list and are read with goss_gpu_file_count / _info / _read / _device under the names
+ *   -entries.edges.header / .high-bits / -d0 / -d1 / .low-bits*   SparseArray, N = 4^(K+1), M = entries
+ *   -entries.counts.* , -entries.lengths.*                        VariableByteArrays of `entries` items
+ *   -entries.counts-hist.txt                                      "<cnt>\t<entries>\n", ascending
+ *   -entries.ends.upr / .lwr                                      40-bit IntegerArray (EntryEdgeSet.hh:41)
+ *   -entries.header                                               {u64 2011041901, u64 K}
+ * (SparseArray.cc:47-170, VariableByteArray.cc:32-43, IntegerArray.cc:259-357); goss_gpu_object_open_emitted
+ * opens them as a GOSS_OBJECT_ENTRY_EDGE_SET.  They are held in the context's arena (about 55 bytes per
+ * edge of working room while building) until goss_gpu_entries_release, the next build, or any other entry
+ * point that may change the result or allocate -- the rule of goss_gpu_segments_build, whose segments
+ * they replace and are replaced by.
+ *
+ * GOSS_ERR_STATE: a k-mer-set context, before finish, after emit.
+ * GOSS_ERR_INVALID_ARG: an edge without its reverse complement (last_error names its index); 2^32 - 1
+ * edges or more; multiplicities of 2^32 - 1 or more.
+ * GOSS_ERR_OOM: it does not fit the arena; nothing is held afterwards and the result is intact.
+ */
+typedef struct {
+    uint64_t entries;                              /* entry edges = items of every image */
+    uint64_t cycle_edges;                          /* edges on cycles without a start */
+    uint64_t longest_path;                         /* edges */
+    uint64_t hist_size;                            /* lines of -entries.counts-hist.txt */
+    uint32_t rounds;                               /* ranking launches: the bounded walk and the doubling rounds */
+    uint32_t walk_steps;                           /* pointers the walk followed per lane (GOSS_GPU_CONTIGS_WALK) */
+    float ms_link, ms_rank, ms_paths, ms_emit;     /* HIP-event time of the four parts */
+} goss_gpu_entries_info;
+int goss_gpu_entries_build(goss_gpu_ctx* ctx, goss_gpu_entries_info* info);
+int goss_gpu_entries_release(goss_gpu_ctx* ctx);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */
@@ -729,13 +775,17 @@ int goss_synth_reads_host(char* out, uint64_t nreads, uint32_t read_len,
  *   graph         <base>.header, <base>-edges.*, <base>-counts.ord0 / .ord1 / .ord2, <base>-counts.ord1p.*,
  *                 <base>-counts.ord2p.* (the -counts-hist.txt is not needed)
  *   sparse array  <base>.header, <base>.high-bits, <base>-d0, <base>-d1, <base>.low-bits*
+ *   entry edge set  <base>.header, <base>.edges.*, <base>.counts.* and <base>.lengths.* (ord0 / ord1 / ord2 / ord1p.* /
+ *                 ord2p.*), <base>.ends.upr, <base>.ends.lwr (EntryEdgeSet(baseName, fac), EntryEdgeSet.cc:299-306; the
+ *                 .counts-hist.txt is not needed); base is the graph's name + "-entries"
  * The library parses every header itself (KmerSet / Graph: K, count, the asymmetric flag; SparseArray: D, qD,
  * N, count; DenseSelect: offsets and block counts), derives the low-bits columns from qD (IntegerArray.cc:259-357)
  * and checks every file's size against its header before anything runs: a missing or short file is
  * GOSS_ERR_INVALID_ARG naming the file.  Every image is copied into ONE device allocation of the object's own.
  * stream: the stream every call of the object runs on (NULL: a stream of its own).
  * goss_gpu_object_open_emitted: the same, device to device, from what a context has just emitted
- * (goss_gpu_emit, goss_gpu_emit_sparse_array, goss_gpu_group_emit's contexts[0]); the object stays valid when
+ * (goss_gpu_emit, goss_gpu_emit_sparse_array, goss_gpu_group_emit's contexts[0]) or built with
+ * goss_gpu_entries_build; the object stays valid when
  * the context is reset or destroyed.  GOSS_ERR_STATE when the context holds no emitted object.
  * goss_gpu_object_last_error(NULL): why the calling thread's last open failed.
  *
@@ -752,16 +802,20 @@ int goss_synth_reads_host(char* out, uint64_t nreads, uint32_t read_len,
  *   rank          SparseArray::accessAndRank (SparseArray.hh:262-276) / rank (:296-309): u64 rank and u8 presence
  *                 per key; either output may be NULL.
  *   select        SparseArray::select (SparseArray.hh:311-325): the key of each rank (< count).
- *   multiplicity  Graph only: Graph::multiplicity(rank) (Graph.hh:425-428), VariableByteArray::operator[]
+ *   multiplicity  Graph (an EntryEdgeSet: the rounded mean of each entry's path, from .counts): Graph::multiplicity(rank) (Graph.hh:425-428), VariableByteArray::operator[]
  *                 (VariableByteArray.hh:227-247); an opened graph has no removed edges, originalRank is the identity.
  *   lookup        rank, then multiplicity, in one kernel: the count of each key, 0 when absent (1 / 0 in a KmerSet
  *                 or a bare array).
+ *   goss_gpu_entries_length    EntryEdgeSet only: EntryEdgeSet::length (EntryEdgeSet.hh:113-118), the edges of the path that starts at
+ *                 each entry (u32), from .lengths.
+ *   goss_gpu_entries_end_rank  EntryEdgeSet only: EntryEdgeSet::endRank (EntryEdgeSet.hh:120-125), the entry at which the mirror path
+ *                 starts (u64), from .ends.
  *   node_ranks    Graph only: GraphEssentials::beginEndRank (GraphEssentials.hh:88-96) of each node (K bases):
  *                 out-degree = end - begin; GOSS_QUERY_INCOMING: of the node's reverse complement, i.e. inDegree
  *                 (GraphEssentials.hh:74-77).  Either output may be NULL.
  */
 typedef struct goss_gpu_object goss_gpu_object;
-enum { GOSS_OBJECT_KMER_SET = 0, GOSS_OBJECT_GRAPH = 1, GOSS_OBJECT_SPARSE_ARRAY = 2 };
+enum { GOSS_OBJECT_KMER_SET = 0, GOSS_OBJECT_GRAPH = 1, GOSS_OBJECT_SPARSE_ARRAY = 2, GOSS_OBJECT_ENTRY_EDGE_SET = 3 };
 enum { GOSS_QUERY_NORMALIZE = 1, GOSS_QUERY_INCOMING = 2 };
 typedef struct {
     const char* name;           /* e.g. "gr.header", "gr-edges.low-bits.lwr" */
@@ -791,6 +845,8 @@ int goss_gpu_object_multiplicity(goss_gpu_object* obj, const uint64_t* d_ranks, 
 int goss_gpu_object_lookup(goss_gpu_object* obj, const void* d_keys, uint64_t n, uint32_t flags, uint32_t* d_counts);
 int goss_gpu_object_node_ranks(goss_gpu_object* obj, const void* d_nodes, uint64_t n, uint32_t flags, uint64_t* d_begin,
                                uint64_t* d_end);
+int goss_gpu_entries_length(goss_gpu_object* obj, const uint64_t* d_ranks, uint64_t n, uint32_t* d_lengths);
+int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uint64_t n, uint64_t* d_ends);
 
 /* Reads against an object (goss_gpu_object_match_reads, goss_gpu_object_match_reads_host): a part of this ABI kept
  * in a header of its own. */

@@ -1,0 +1,410 @@
+"""build-entry-edge-set on the device (goss_gpu_entries_*, Context.entry_edge_set, Object.length / end_rank,
+`goss build-entry-edge-set`) against the pure-Python model of entries_model.py: every file byte for byte, the read side
+of the object, the command, the refusals."""
+import functools
+import math
+import os
+import random
+import subprocess
+from bisect import bisect_left
+
+import numpy as np
+import pytest
+
+import entries_model as em
+import gossamer_amd as g
+import tips_cases
+import tips_model as tm
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOSS = os.path.join(ROOT, "gossamer_amd", "goss")
+BUDGET = 512 << 20
+READS = dict(genome_len=3000, coverage=20, error_rate=0.01, seed=3)
+# Ranking launches, as in test_gpu_contigs.py: one bounded walk, then doubling round r resolves every edge up to 2^r
+# from its start, and one more launch may find that nothing new resolves.
+WALK_LAUNCHES = 1
+
+
+def max_rounds(longest):
+    return WALK_LAUNCHES + math.ceil(math.log2(max(longest, 2))) + 1
+
+
+def run_goss(*args):
+    p = subprocess.run([GOSS] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    return p.returncode, p.stdout, p.stderr.decode()
+
+
+def graph_files(oracle, edges, counts, K):
+    return {n[1:]: b for n, b in oracle.write_graph(edges, counts, K, out="x").items()}
+
+
+def loaded(oracle, edges, counts, K, budget=BUDGET):
+    ctx = g.Context(K, g.MODE_GRAPH, hbm_budget=budget)
+    ctx.push_run_graph(graph_files(oracle, edges, counts, K), 2 * (K + 1))
+    ctx.finish()
+    return ctx
+
+
+def current(ctx):
+    ctx.counts.distinct = ctx.result_ptrs()[2]
+    keys, counts = ctx.result()
+    return keys, [int(c) for c in counts]
+
+
+def same_files(got, want):
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name
+
+
+def check_against_model(oracle, ctx, edges, counts, K, model=None, want=None):
+    """every file of the context's entry edge set equals the model's, and so do the figures of the info"""
+    if model is None:
+        model, want = em.expected(oracle, edges, counts, K)
+    files, info = ctx.entry_edge_set()
+    same_files(files, want)
+    assert info["entries"] == len(model["starts"])
+    assert info["cycle_edges"] == model["cycle_edges"] and info["longest_path"] == model["longest"]
+    assert info["hist_size"] == len(model["hist"])
+    if edges:
+        assert 1 <= info["rounds"] <= max_rounds(info["longest_path"])
+    assert ctx.files() == {}                                     # given back
+    return model, info
+
+
+def _rc_text(s):
+    return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
+
+
+def _keys_of(text, K):
+    """the (K+1)-mers of a text as Python ints, in text order"""
+    codes = np.frombuffer(text.encode(), dtype=np.uint8)
+    codes = ((codes >> 1) & 3) ^ (((codes >> 1) & 3) >> 1)            # A C G T -> 0 1 2 3
+    vals = [0] * (len(text) - K)
+    v = 0
+    mask = (1 << (2 * (K + 1))) - 1
+    for i, c in enumerate(codes.tolist()):
+        v = ((v << 2) | c) & mask
+        if i >= K:
+            vals[i - K] = v
+    return vals
+
+
+def graph_with_counts(strings, K):
+    """sorted (edges, counts) of (text, multiplicities of the forward strand's edges, of the other strand's, each a
+    number or a list in that strand's path order)"""
+    got = {}
+    for text, fwd, bwd in strings:
+        for t, c in ((text, fwd), (_rc_text(text), bwd)):
+            ks = _keys_of(t, K)
+            cs = c if isinstance(c, list) else [c] * len(ks)
+            assert len(cs) == len(ks)
+            for k, x in zip(ks, cs):
+                assert got.setdefault(k, x) == x
+    edges = sorted(got)
+    return edges, [got[e] for e in edges]
+
+
+@functools.lru_cache(maxsize=None)
+def reads_case(oracle, K):
+    """(reads, edges, counts, model, files) of the graph of the reads with errors: computed once, shared"""
+    reads = tips_cases.error_reads(**READS)
+    edges, counts, _, _ = oracle.count([(oracle.LINE, "r", reads)], K + 1, 1)
+    model, want = em.expected(oracle, edges, counts, K)
+    return reads, edges, counts, model, want
+
+
+# ---- 1: the hand-made graphs -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K", [15, 27, 30, 31, 55, 33, 62])
+def test_hand_made_graphs(oracle, K):
+    edges, counts, _ = tips_cases.combined_graph(K)
+    with loaded(oracle, edges, counts, K) as ctx:
+        model, info = check_against_model(oracle, ctx, edges, counts, K)
+        assert current(ctx) == (edges, counts)
+    n = len(model["starts"])
+    assert n > 10 and len(set(model["len"])) > 3
+    assert all(model["ends"][e] == j for j, e in enumerate(model["ends"]))
+    own_mirror = sum(1 for j, e in enumerate(model["ends"]) if e == j)
+    assert own_mirror == (2 if (K + 1) % 2 == 0 else 0)          # lone_palindrome and hairpin
+
+
+def test_pure_cycle(oracle):
+    K = 27
+    rng = random.Random(5)
+    ring = "".join(rng.choice("ACGT") for _ in range(300))
+    edges, counts = graph_with_counts([(ring + ring[:K], 3, 3)], K)
+    assert len(edges) == 600
+    with loaded(oracle, edges, counts, K) as ctx:
+        model, info = check_against_model(oracle, ctx, edges, counts, K)
+        assert info["entries"] == 0 and info["cycle_edges"] == 600 and info["hist_size"] == 0
+        assert current(ctx) == (edges, counts)
+    assert model["starts"] == []
+
+
+# ---- 2: the paths' own multiplicities, the rounding, the classes of the byte arrays ---------------------------------------
+
+def test_own_multiplicities(oracle):
+    K = 27
+    rng = random.Random(6)
+    text = "".join(rng.choice("ACGT") for _ in range(K + 40))
+    fwd = [rng.randint(1, 9) for _ in range(40)]
+    bwd = [rng.randint(20, 90) for _ in range(40)]
+    edges, counts = graph_with_counts([(text, fwd, bwd)], K)
+    with loaded(oracle, edges, counts, K) as ctx:
+        model, _ = check_against_model(oracle, ctx, edges, counts, K)
+    assert model["len"] == [40, 40] and model["ends"] == [1, 0]
+    want = sorted(em.round_half_away(sum(c) / 40.0) for c in (fwd, bwd))
+    assert sorted(model["cnt"]) == want and want[0] < 10 < want[1]
+
+
+def test_rounding(oracle):
+    """means of exactly x.5 for x = 1 .. 16, odd and even: always x + 1"""
+    K = 27
+    rng = random.Random(7)
+    strings, means = [], {}
+    for a in range(1, 16, 2):
+        text = "".join(rng.choice("ACGT") for _ in range(K + 2))
+        strings.append((text, [a, a + 1], [a + 2, a + 1]))             # a + 0.5 and a + 1.5
+        means[tm.encode(text[:K + 1])] = a + 1
+        means[tm.encode(_rc_text(text)[:K + 1])] = a + 2
+    text = "".join(rng.choice("ACGT") for _ in range(K + 4))
+    strings.append((text, [2, 3, 2, 3], [6, 7, 6, 7]))                  # 2.5 and 6.5 over four edges
+    means[tm.encode(text[:K + 1])] = 3
+    means[tm.encode(_rc_text(text)[:K + 1])] = 7
+    edges, counts = graph_with_counts(strings, K)
+    with loaded(oracle, edges, counts, K) as ctx:
+        model, _ = check_against_model(oracle, ctx, edges, counts, K)
+    assert {edges[r]: c for r, c in zip(model["starts"], model["cnt"])} == means
+
+
+def test_byte_array_classes_and_a_long_path(oracle):
+    """cnt and len above 255 and above 65,535 (the ord1 and ord2 levels of both VariableByteArrays); the long path also
+    takes the doubling rounds"""
+    K = 27
+    rng = random.Random(8)
+    rnd = lambda m: "".join(rng.choice("ACGT") for _ in range(m))
+    n = 70000
+    strings = [(rnd(n + K), 3, 5), (rnd(K + 300), 300, 301), (rnd(K + 9), 70000, 0xFFFFFFF0), (rnd(K + 2), [65535, 65536], 255)]
+    edges, counts = graph_with_counts(strings, K)
+    assert len(edges) == 2 * (n + 300 + 9 + 2)
+    with loaded(oracle, edges, counts, K) as ctx:
+        model, info = check_against_model(oracle, ctx, edges, counts, K)
+        assert info["longest_path"] == n and info["rounds"] >= 10
+    assert sorted(model["len"]) == [2, 2, 9, 9, 300, 300, n, n]
+    assert sorted(model["cnt"]) == [3, 5, 255, 300, 301, 65536, 70000, 0xFFFFFFF0]
+
+
+def test_dense_select_blocks(oracle):
+    """more than 8,192 and fewer than 16,384 entries: a full block and a last partial one in the -d1 of .edges"""
+    K = 27
+    rng = random.Random(9)
+    strings = [("".join(rng.choice("ACGT") for _ in range(K + rng.randint(1, 3))), rng.randint(1, 600), rng.randint(1, 600))
+               for _ in range(5000)]
+    edges, counts = graph_with_counts(strings, K)
+    model, want = em.expected(oracle, edges, counts, K)
+    assert 8192 < len(model["starts"]) < 16384
+    with loaded(oracle, edges, counts, K) as ctx:
+        check_against_model(oracle, ctx, edges, counts, K, model, want)
+
+
+# ---- 3: reads with substituted bases, raw and cleaned in the same context ---------------------------------------------
+
+@pytest.mark.parametrize("K", [27, 33])
+def test_reads_with_errors(oracle, K):
+    reads, edges, counts, model, want = reads_case(oracle, K)
+    assert len(model["starts"]) > 1000
+    ce, cc, _ = tm.prune(edges, counts, K, 2)[-1]
+    with g.Context(K, g.MODE_GRAPH, hbm_budget=BUDGET) as ctx:
+        ctx.push_host(reads.encode())
+        ctx.finish()
+        check_against_model(oracle, ctx, edges, counts, K, model, want)
+        assert current(ctx) == (edges, counts)
+        ctx.prune_tips(2)
+        assert current(ctx) == (ce, cc)
+        cmodel, _ = check_against_model(oracle, ctx, ce, cc, K)
+        assert 0 < len(cmodel["starts"]) < len(model["starts"])
+        assert current(ctx) == (ce, cc)
+        files = ctx.emit()
+    same_files(files, graph_files(oracle, ce, cc, K))
+
+
+# ---- 4: the read side ---------------------------------------------------------------------------------------------------
+
+def to_keys(vals, words):
+    if words == 1:
+        return np.asarray(vals, dtype=np.uint64)
+    m = (1 << 64) - 1
+    return np.asarray([[v & m, v >> 64] for v in vals], dtype=np.uint64).reshape(-1, 2)
+
+
+def from_keys(arr, words):
+    if words == 1:
+        return [int(v) for v in arr]
+    return [int(lo) | (int(hi) << 64) for lo, hi in arr.reshape(-1, 2)]
+
+
+def check_object(obj, K, edges, model, rng):
+    n = len(model["starts"])
+    ekeys = [edges[r] for r in model["starts"]]
+    info = obj.info()
+    assert (info["kind"], info["K"], info["count"], info["N"]) == (g.OBJECT_ENTRY_EDGE_SET, K, n, 1 << (2 * (K + 1)))
+    words = obj.key_words
+    ranks = np.arange(n, dtype=np.uint64)
+    assert from_keys(obj.select(ranks), words) == ekeys
+    assert obj.multiplicity(ranks).tolist() == model["cnt"]
+    assert obj.length(ranks).tolist() == model["len"]
+    ends = obj.end_rank(ranks)
+    assert ends.tolist() == model["ends"]
+    assert obj.end_rank(ends).tolist() == list(range(n))
+    # 10^4 keys: entries, edges that are no entries, values off the graph
+    keys = [rng.choice(ekeys) for _ in range(4000)] + [rng.choice(edges) for _ in range(3000)]
+    keys += [rng.getrandbits(2 * (K + 1)) for _ in range(3000)]
+    at = {e: j for j, e in enumerate(ekeys)}
+    r, p = obj.rank(to_keys(keys, words))
+    assert p.tolist() == [k in at for k in keys]
+    assert r.tolist() == [bisect_left(ekeys, k) for k in keys]
+    assert obj.lookup(to_keys(keys, words)).tolist() == [model["cnt"][at[k]] if k in at else 0 for k in keys]
+    for fn in (obj.length, obj.end_rank, obj.multiplicity):
+        with pytest.raises(g.GossGpuError) as e:
+            fn(np.asarray([0, n], dtype=np.uint64))
+        assert e.value.status == -1 and "query 1" in str(e.value)
+
+
+@pytest.mark.parametrize("K", [27, 33])
+def test_read_side(oracle, K):
+    reads, edges, counts, model, want = reads_case(oracle, K)
+    rng = random.Random(40 + K)
+    with loaded(oracle, edges, counts, K) as ctx:
+        info = ctx.entries_build()
+        assert info["entries"] == len(model["starts"])
+        with g.Object.from_context(ctx) as obj:                  # straight from the build, device to device
+            got = ctx.files()                                    # (reading keeps what is held)
+            ctx.entries_release()
+            check_object(obj, K, edges, model, rng)
+    same_files(got, want)
+    for files in (got, want):
+        with g.Object.open({"x" + n: b for n, b in files.items()}, "x-entries", g.OBJECT_ENTRY_EDGE_SET) as obj:
+            check_object(obj, K, edges, model, rng)
+    # a Graph answers no length; a file that is missing is named
+    with g.Object.open({"x" + n: b for n, b in graph_files(oracle, edges, counts, K).items()}, "x", g.OBJECT_GRAPH) as gr:
+        with pytest.raises(g.GossGpuError) as e:
+            gr.length(np.zeros(1, dtype=np.uint64))
+        assert e.value.status == -1
+    short = {"x" + n: b for n, b in want.items() if n != "-entries.ends.lwr"}
+    with pytest.raises(g.GossGpuError) as e:
+        g.Object.open(short, "x-entries", g.OBJECT_ENTRY_EDGE_SET)
+    assert e.value.status == -1 and "x-entries.ends.lwr" in str(e.value)
+
+
+# ---- 5: the command, end to end -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K", [27, 33])
+def test_cli(oracle, tmp_path, K):
+    reads, edges, counts, model, want = reads_case(oracle, K)
+    for name, data in oracle.write_graph(edges, counts, K, out="x").items():
+        (tmp_path / name).write_bytes(data)
+    before = set(os.listdir(tmp_path))
+    rc, out, err = run_goss("build-entry-edge-set", "-G", tmp_path / "x", "-T", 2, "-v")
+    assert rc == 0 and out == b"", err
+    at = [err.index(line) for line in ("Loading graph", "Locating entry edges", "Writing entry edges", "Writing counts histogram",
+                                       "Writing end edges", "total elapsed time: ")]
+    assert at == sorted(at)
+    made = set(os.listdir(tmp_path)) - before
+    assert made == {"x" + n for n in want}
+    for n in want:
+        assert (tmp_path / ("x" + n)).read_bytes() == want[n], n
+    rc, out, err = run_goss("build-entry-edge-set", "-G", tmp_path / "x")            # quiet without -v
+    assert rc == 0 and out == b"" and err == ""
+    # the asymmetric flag of a graph's header: refused with the reference's text
+    hdr = bytearray((tmp_path / "x.header").read_bytes())
+    hdr[16] |= 1
+    (tmp_path / "x.header").write_bytes(bytes(hdr))
+    rc, out, err = run_goss("build-entry-edge-set", "-G", tmp_path / "x")
+    assert rc == 1 and out == b"" and err.endswith("Asymmetric graphs not yet handled")
+
+
+# ---- 6: refusals and memory ---------------------------------------------------------------------------------------------
+
+def _status(fn):
+    with pytest.raises(g.GossGpuError) as e:
+        fn()
+    return e.value.status, str(e.value)
+
+
+def test_refusals(oracle):
+    K = 15
+    edges, counts, _ = tips_cases.combined_graph(K)
+    with g.Context(K, g.MODE_KMER_SET, hbm_budget=BUDGET) as ctx:
+        ctx.push_host(b"ACGTACGTACGTACGTACGTAAACCCGGGTTT\n")
+        ctx.finish()
+        assert _status(lambda: ctx.entries_build())[0] == -5
+    with g.Context(K, g.MODE_GRAPH, hbm_budget=BUDGET) as ctx:
+        assert _status(lambda: ctx.entries_build())[0] == -5
+        ctx.push_run_graph(graph_files(oracle, edges, counts, K), 2 * (K + 1))
+        assert _status(lambda: ctx.entries_build())[0] == -5            # before finish
+        ctx.finish()
+        info = ctx.entries_build()
+        assert info["entries"] > 0 and "-entries.header" in ctx.files()
+        # reading the result and linting keep what is held; a call that changes the result gives it back
+        assert current(ctx) == (edges, counts) and ctx.lint()["missing_rc"] == 0
+        held = ctx.files()
+        assert "-entries.ends.lwr" in held
+        ctx.prune_tips(1)
+        assert ctx.files() == {}
+        ctx.entries_build()
+        ctx.segments_build()                                             # the segments take the entries' place
+        assert ctx.files() == {}
+        ctx.entries_build()                                              # ... and the other way round
+        assert _status(lambda: ctx.segments_table(0, 0))[0] == -5
+        ctx.entries_release()
+        ctx.entries_release()                                            # twice is harmless
+        assert ctx.files() == {}
+        ctx.emit()
+        assert _status(lambda: ctx.entries_build())[0] == -5            # after emit
+    # one reverse complement deleted: refused, naming the edge; nothing changed; the context goes on working
+    beg = next(e for e in edges if tm.revcomp(e, K + 1) != e)
+    i = edges.index(tm.revcomp(beg, K + 1))
+    be, bc = edges[:i] + edges[i + 1:], counts[:i] + counts[i + 1:]
+    with loaded(oracle, be, bc, K) as ctx:
+        st, msg = _status(lambda: ctx.entries_build())
+        assert st == -1 and ("edge %d has no reverse complement" % be.index(beg)) in msg
+        assert ctx.files() == {}
+        assert current(ctx) == (be, bc)
+        assert ctx.lint()["missing_rc"] == 1
+
+
+def test_out_of_memory(oracle):
+    """Working memory that does not fit: GOSS_ERR_OOM, nothing held, the result intact.  The working arrays take more
+    room than the edge list itself, so below some arena size the graph still loads and the entries no longer fit:
+    walk the size down in steps of 256 KB until the graph itself is refused."""
+    K = 27
+    reads, edges, counts, model, want = reads_case(oracle, K)
+    files = graph_files(oracle, edges, counts, K)
+    refused = fitted = 0
+    for kb in range(8192, 256, -256):
+        ctx = g.Context(K, g.MODE_GRAPH, hbm_budget=kb << 10)
+        try:
+            try:
+                ctx.push_run_graph(files, 2 * (K + 1))
+                ctx.finish()
+            except g.GossGpuError as e:
+                assert e.status == -3
+                break
+            try:
+                got, info = ctx.entry_edge_set()
+                fitted += 1
+                if fitted == 1:
+                    same_files(got, want)
+                assert info["entries"] == len(model["starts"])
+            except g.GossGpuError as e:
+                assert e.status == -3, str(e)
+                refused += 1
+                assert ctx.files() == {}
+                assert current(ctx) == (edges, counts)
+                assert ctx.lint()["missing_rc"] == 0
+        finally:
+            ctx.close()
+    assert refused > 0 and fitted > 0

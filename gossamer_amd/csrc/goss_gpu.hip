@@ -81,6 +81,11 @@ struct Run { void* keys; uint32_t* counts; uint64_t m; int big = -1; bool rep = 
 
 struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
 
+// What a build entry point left on top of the permanent room for later calls to read (graph_passes.hpp): the segment
+// table and text of goss_gpu_segments_build, or the images of goss_gpu_entries_build.  One record: at most one is held.
+enum class Held : uint8_t { None, Segments, Entries };
+struct HeldResult { Held kind = Held::None; uint64_t lo = 0; };          // lo: the permanent top before the build
+
 // Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
 // itself (goss_gpu_ctx::canon_l1 == 1).
 // (0.05: re-ordering M distinct pairs into the canonical order costs 53 ms per 10^9 of them, two FNV hashes per window
@@ -223,17 +228,14 @@ struct goss_gpu_ctx {
     uint64_t M = 0;
     void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
     uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
-    // goss_gpu_segments_build: the segment table and the text, permanent room above everything else, held until
-    // goss_gpu_segments_release or the next call that may allocate (guarded() gives it back first)
+    // the held result: permanent room above everything else from held.lo on, held until its release entry point or
+    // the next call that may allocate (guarded() gives it back first).  goss_gpu_segments_build: the segment table and
+    // the text (seg_*); goss_gpu_entries_build: the images of the EntryEdgeSet, which are the file list
+    HeldResult held;
+    bool keep_held = false;               // the entry point that runs now only reads: what is held stays
     void* seg_recs = nullptr;
     uint8_t* seg_text = nullptr;
-    uint64_t seg_count = 0, seg_text_bytes = 0, seg_lo = 0;
-    bool seg_live = false;
-    bool seg_hold = false;                // the entry point that runs now only reads: what is held stays
-    // goss_gpu_entries_build: the images of the EntryEdgeSet are the file list, in permanent room above everything else
-    // from ent_lo on, held exactly as the segments are (at most one of the two is live)
-    uint64_t ent_lo = 0;
-    bool ent_live = false;
+    uint64_t seg_count = 0, seg_text_bytes = 0;
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -2677,6 +2679,15 @@ void emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_bytes, ui
 
 void wait_background_thread(goss_gpu_ctx* c);
 
+// Give back what the context holds (segments or an entry edge set), if anything: the permanent room from held.lo on.
+void release_held(goss_gpu_ctx* c)
+{
+    if (c->held.kind != Held::None) c->arena.lo = c->held.lo;
+    if (c->held.kind == Held::Entries) c->files.clear();
+    c->held = HeldResult();
+    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+}
+
 // wait_bg: the call works on the arena or the runs -- the thread that counts a full staging buffer must have ended
 // (its failure becomes this call's).  Only the host pushes, which touch nothing but the other staging buffer, go on
 // beside it.
@@ -2690,11 +2701,10 @@ int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
         // poll of the host process): from here on an error is ours
         (void)hipGetLastError();
         if (c && wait_bg) wait_background_thread(c);
-        // segments held by goss_gpu_segments_build lie on top of the permanent room: whatever may allocate there, or
-        // change the result they were read from, gives them back first
-        if (c && c->seg_live && !c->seg_hold) { c->arena.lo = c->seg_lo; c->seg_live = false; }
-        if (c && c->ent_live && !c->seg_hold) { c->arena.lo = c->ent_lo; c->ent_live = false; c->files.clear(); }
-        if (c) c->seg_hold = false;
+        // a held result lies on top of the permanent room: whatever may allocate there, or change the result it was
+        // read from, gives it back first
+        if (c && !c->keep_held) release_held(c);
+        if (c) c->keep_held = false;
         f();
         // a refused kernel launch raises no exception by itself and leaves its outputs untouched:
         // no entry point returns success over one
@@ -2728,6 +2738,9 @@ int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
         return GOSS_ERR_STATE;
     }
 }
+
+// ---- prune-tips, print-contigs, build-entry-edge-set: the passes over a finished graph ---------
+#include "graph_passes.hpp"
 
 }  // namespace
 
@@ -3382,7 +3395,7 @@ int goss_gpu_result_copy(goss_gpu_ctx* c, uint64_t first, uint64_t n, uint64_t* 
     if (!c) return GOSS_ERR_INVALID_ARG;
     if (!c->finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
     if (first > c->M || n > c->M - first) return GOSS_ERR_INVALID_ARG;
-    c->seg_hold = true;
+    c->keep_held = true;
     return guarded(c, [&]() {
         const uint64_t ksz = c->words * 8;
         if (h_keys && n) HIP_TRY(hipMemcpyAsync(h_keys, (const uint8_t*)c->res_keys + first * ksz, n * ksz, hipMemcpyDeviceToHost, c->stream));
@@ -4133,7 +4146,7 @@ int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, 
     if (offset > f.size || n > f.size - offset) return GOSS_ERR_INVALID_ARG;
     if (n == 0) return GOSS_OK;
     if (!f.dev) { std::memcpy(dst, f.host.data() + offset, n); return GOSS_OK; }
-    c->seg_hold = true;
+    c->keep_held = true;
     return guarded(c, [&]() {
         HIP_TRY(hipMemcpyAsync(dst, f.dev + offset, n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4143,7 +4156,7 @@ int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, 
 int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 {
     if (!c || !out) return GOSS_ERR_INVALID_ARG;
-    c->seg_hold = true;
+    c->keep_held = true;
     int rc = guarded(c, [&]() { resolve_timing(c); });
     *out = c->timing;
     return rc;
@@ -4152,7 +4165,7 @@ int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 int goss_gpu_timing_reset(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    c->seg_hold = true;
+    c->keep_held = true;
     int rc = guarded(c, [&]() { resolve_timing(c); });
     c->timing = goss_gpu_timing{};
     return rc;
@@ -4209,7 +4222,7 @@ int goss_gpu_reset(goss_gpu_ctx* c)
         c->broken = false;
         c->res_keys = nullptr; c->res_counts = nullptr; c->M = 0;
         c->tips_keys = nullptr; c->tips_counts = nullptr;
-        c->seg_live = false; c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+        release_held(c);
         c->arena.lo = 0; c->arena.hi = c->arena.size;
         if (c->copy_stream) HIP_TRY(hipStreamSynchronize(c->copy_stream));
         c->stage_cur = 0; c->stage = c->stage_buf[0]; c->stage_fill = 0;          // (the staging buffers stay)
@@ -4808,7 +4821,7 @@ int goss_gpu_lint(goss_gpu_ctx* c, int asymmetric, goss_gpu_lint_report* out)
     if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "lint checks a graph"; return GOSS_ERR_STATE; }
     std::memset(out, 0, sizeof *out);
     if (c->M == 0) return GOSS_OK;
-    c->seg_hold = true;
+    c->keep_held = true;
     return guarded(c, [&]() {
         uint64_t mark = c->arena.mark();
         LintReport* rep = (LintReport*)c->arena.temp(sizeof(LintReport));
@@ -4826,359 +4839,29 @@ int goss_gpu_lint(goss_gpu_ctx* c, int asymmetric, goss_gpu_lint_report* out)
     });
 }
 
-extern "C++" {
-// Temporaries of one call, given back on every way out (an exception included).
-struct ArenaScope {
-    Arena& a;
-    uint64_t mark;
-    explicit ArenaScope(Arena& arena) : a(arena), mark(arena.mark()) {}
-    ~ArenaScope() { a.release(mark); }
-    ArenaScope(const ArenaScope&) = delete;
-    ArenaScope& operator=(const ArenaScope&) = delete;
-};
-
-// Bits of the link pass's bucket table for n edges of len bases: about one edge per bucket, at most 2^26 entries
-// (256 MB).  GOSS_GPU_TIPS_BUCKET_BITS overrides it (0 = plain binary search; the probe's A/B).
-static uint32_t tips_bucket_bits(uint64_t n, uint32_t len)
-{
-    uint32_t bits = 0;
-    while (bits < 26u && (2ULL << bits) <= n) ++bits;
-    if (const char* e = std::getenv("GOSS_GPU_TIPS_BUCKET_BITS")) bits = (uint32_t)std::min<long>(26, std::max<long>(0, std::atol(e)));
-    return std::min(bits, 2u * len);
-}
-
-// One iteration of prune-tips over the result (GossCmdPruneTips.cc:279-319).  Nothing of the context changes
-// before the survivors are complete: a failure leaves the result as it was.
-template <class K>
-static void prune_tips_once(goss_gpu_ctx* c, goss_gpu_tips_report* out)
-{
-    static_assert(sizeof(goss_gpu_tips_report) == 11 * 8 && sizeof(TipsReport) == 13 * 8, "tips report layout");
-    goss_gpu_tips_report rep{};
-    const uint64_t n64 = c->M;
-    rep.edges_before = rep.edges_after = n64;
-    if (out) *out = rep;
-    if (n64 == 0) return;
-    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "prune_tips: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t bits = tips_bucket_bits(n, c->len);
-    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
-    const uint64_t zap_words = ntiles * (kRedTile / 32), cand_words = (n64 + 63) / 64;
-    {
-        // rcr + nxt + info + the two bitmaps + the table, and the survivors once more while they are compacted
-        const uint64_t need = n64 * 9 + zap_words * 4 + cand_words * 8 + (bits ? ((1ULL << bits) + 1) * 4 : 0)
-                              + n64 * (sizeof(K) + 4) + (16u << 20);
-        if (c->arena.avail() < need) grow_arena(c, need);       // (no temporary is live between two entry points)
-    }
-    ArenaScope scope(c->arena);
-    const K* keys = (const K*)c->res_keys;
-    const uint32_t* counts = c->res_counts;
-    uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
-    uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
-    uint8_t* info = (uint8_t*)c->arena.temp(n64);
-    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
-    uint64_t* cand = (uint64_t*)c->arena.temp(cand_words * 8);
-    uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
-    TipsReport* d_rep = (TipsReport*)c->arena.temp(sizeof(TipsReport));
-    TipsReport* h = (TipsReport*)c->h_pinned;
-    static_assert(sizeof(TipsReport) <= 256, "pinned scratch");
-
-    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(TipsReport), c->stream));
-    HIP_TRY(hipMemsetAsync(&d_rep->missing_rc, 0xFF, 8, c->stream));
-    HIP_TRY(hipMemsetAsync(zap, 0, zap_words * 4, c->stream));
-    const dim3 grid(grid_for(n64, kTB)), block(kTB);
-    if (bits)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
-                       (const uint32_t*)table, rcr, nxt, info, d_rep);
-    const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kTipsGridBlocks));
-    hipLaunchKernelGGL(tips_flag_kernel, few, block, 0, c->stream, (const uint32_t*)rcr, (const uint8_t*)info, n, cand, d_rep);
-    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    if (h->missing_rc != ~0ULL)
-        throw StatusError{GOSS_ERR_INVALID_ARG, "prune_tips: edge " + std::to_string(h->missing_rc) +
-                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
-    const uint64_t ncand = h->candidates;
-    rep.candidates = ncand;
-    if (ncand == 0) { if (out) *out = rep; return; }
-
-    uint32_t* list = (uint32_t*)c->arena.temp(ncand * 4);
-    HIP_TRY(hipMemsetAsync(list, 0xFF, ncand * 4, c->stream));
-    const uint64_t words_per_block = (cand_words + kTipsGridBlocks - 1) / kTipsGridBlocks;
-    hipLaunchKernelGGL(tips_gather_kernel, dim3(grid_for(cand_words, (uint32_t)std::max<uint64_t>(words_per_block, 1))), block, 0, c->stream,
-                       (const uint64_t*)cand, cand_words, words_per_block, list, ncand, d_rep);
-    hipLaunchKernelGGL(tips_walk_kernel, dim3(grid_for(ncand, kTB)), block, 0, c->stream, (const uint32_t*)list, ncand, n, c->k,
-                       (const uint32_t*)rcr, (const uint32_t*)nxt, (const uint8_t*)info, counts, zap, d_rep);
-    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
-    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), block, 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
-    HIP_TRY(hipMemsetAsync(tile_counts + ntiles, 0, 8, c->stream));
-    exclusive_scan_u64(c, tile_counts, ntiles + 1);
-    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
-    uint64_t* hm = (uint64_t*)((uint8_t*)c->h_pinned + 128);
-    HIP_TRY(hipMemcpyAsync(hm, tile_counts + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    rep.tips = h->tips; rep.zapped = h->zapped;
-    rep.too_long = h->too_long; rep.both_joined = h->both_joined; rep.isolated = h->isolated; rep.outweighed = h->outweighed;
-    rep.joined_at_begin = h->joined_at_begin; rep.joined_at_end = h->joined_at_end;
-    const uint64_t m = hm[0];
-    rep.edges_after = m;
-    if (m != n64)
-    {
-        const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
-        const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
-        // a result this entry point allocated is compacted beside itself and copied back (five iterations take the
-        // permanent room of one); anybody else's arrays (a run, select_counts) are left alone
-        K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
-        uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), block, 0, c->stream, keys, counts, n64,
-                           (const uint32_t*)zap, (const uint64_t*)tile_counts, okeys, ocounts);
-        if (own)
-        {
-            if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
-            if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
-        c->M = m;
-    }
-    if (out) *out = rep;
-}
-}  // extern "C++"
-
 int goss_gpu_prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_report* reports)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "prune_tips works on a graph"; return GOSS_ERR_STATE; }
-    if (!c->finished || c->emitted) { c->last_error = "prune_tips belongs between finish and emit"; return GOSS_ERR_STATE; }
-    if (reports && iterations) std::memset(reports, 0, sizeof(goss_gpu_tips_report) * (size_t)iterations);
-    if (!c->res_big.empty())
-    {
-        c->last_error = "prune_tips: the graph has multiplicities of 2^32 - 1 or more";
-        return GOSS_ERR_INVALID_ARG;
-    }
-    return guarded(c, [&]() {
-        for (uint32_t it = 0; it < iterations; ++it)
-        {
-            PhaseTimer t(c, GOSS_T_REDUCE, c->M);
-            goss_gpu_tips_report* r = reports ? reports + it : nullptr;
-            if (c->words == 1) prune_tips_once<Key1>(c, r); else prune_tips_once<Key2>(c, r);
-            t.stop();
-        }
-    });
+    const int st = graph_pass_state(c, "prune_tips", "prune_tips works on a graph", "prune_tips belongs between finish and emit");
+    if (st != GOSS_ERR_STATE && reports && iterations) std::memset(reports, 0, sizeof(goss_gpu_tips_report) * (size_t)iterations);
+    if (st != GOSS_OK) return st;
+    return guarded(c, [&]() { prune_tips(c, iterations, reports); });
 }
-
-extern "C++" {
-// Pointers the first ranking launch follows per lane before doubling takes over: kContigsWalkSteps, or
-// GOSS_GPU_CONTIGS_WALK=<steps> (1 = doubling alone; the probe's A/B).
-static uint32_t contigs_walk_steps()
-{
-    long v = kContigsWalkSteps;
-    if (const char* e = std::getenv("GOSS_GPU_CONTIGS_WALK")) v = std::atol(e);
-    return (uint32_t)std::min<long>(4096, std::max<long>(1, v));
-}
-
-struct EventPair {
-    hipEvent_t e[5] = {};
-    EventPair() { for (auto& x : e) HIP_TRY(hipEventCreate(&x)); }
-    ~EventPair() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-// Linear segments of the result (GossCmdPrintContigs.cc:49-193).  Temporaries under an ArenaScope; the table and the
-// text are permanent room on top of everything else (c->seg_lo marks where it began).
-template <class K>
-static void segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
-{
-    static_assert(sizeof(goss_gpu_segment) == sizeof(SegRec) && sizeof(SegRec) == 64, "segment layout");
-    static_assert(sizeof(ContigsReport) <= 128, "pinned scratch");
-    goss_gpu_segments_info inf{};
-    const uint64_t n64 = c->M;
-    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = 0; c->seg_text_bytes = 0;
-    if (n64 == 0) { *out = inf; return; }
-    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "segments: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t bits = tips_bucket_bits(n, c->len);
-    const uint32_t steps = contigs_walk_steps();
-    const uint32_t Kn = c->k;
-    const uint32_t line = (flags & GOSS_SEGMENTS_NO_LINE_BREAKS) ? 0u : 60u;
-    inf.walk_steps = steps;
-    {
-        // rcr, nxt, pred, two arrays of pairs, the scan (4 + 4 + 4 + 8 + 8 + 8), info, flag, st, the table; then a
-        // record per taken path and about half a byte of text per edge
-        const uint64_t need = n64 * 39 + (bits ? ((1ULL << bits) + 1) * 4 : 0) + n64 + (16u << 20);
-        if (c->arena.avail() < need) grow_arena(c, need);
-        c->seg_lo = c->arena.lo;
-    }
-    ArenaScope scope(c->arena);
-    EventPair ev;
-    const K* keys = (const K*)c->res_keys;
-    const uint32_t* counts = c->res_counts;
-    uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
-    uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
-    uint8_t* info = (uint8_t*)c->arena.temp(n64);
-    uint8_t* flag = (uint8_t*)c->arena.temp(n64);
-    uint8_t* st = (uint8_t*)c->arena.temp(n64);
-    uint32_t* pred = (uint32_t*)c->arena.temp(n64 * 4);
-    uint2* cur = (uint2*)c->arena.temp(n64 * 8);
-    uint2* oth = (uint2*)c->arena.temp(n64 * 8);
-    uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
-    uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
-    ContigsReport* d_rep = (ContigsReport*)c->arena.temp(sizeof(ContigsReport));
-    TipsReport* d_tips = (TipsReport*)c->arena.temp(sizeof(TipsReport));
-    ContigsReport* h = (ContigsReport*)c->h_pinned;
-    uint64_t* hx = (uint64_t*)((uint8_t*)c->h_pinned + 128);
-
-    // ---- the link pass of prune-tips, as it is
-    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(ContigsReport), c->stream));
-    HIP_TRY(hipMemsetAsync(d_tips, 0, sizeof(TipsReport), c->stream));
-    HIP_TRY(hipMemsetAsync(&d_tips->missing_rc, 0xFF, 8, c->stream));
-    HIP_TRY(hipMemsetAsync(pred, 0, n64 * 4, c->stream));
-    const dim3 grid(grid_for(n64, kTB)), block(kTB);
-    const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kContigsGridBlocks));
-    if (bits)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
-                       (const uint32_t*)table, rcr, nxt, info, d_tips);
-    HIP_TRY(hipMemcpyAsync(hx, &d_tips->missing_rc, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    if (hx[0] != ~0ULL)
-        throw StatusError{GOSS_ERR_INVALID_ARG, "segments: edge " + std::to_string(hx[0]) +
-                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
-
-    // ---- starts, predecessors, list ranking
-    hipLaunchKernelGGL(contigs_mark_kernel, grid, block, 0, c->stream, (const uint32_t*)rcr, (const uint32_t*)nxt,
-                       (const uint8_t*)info, n, flag, pred);
-    hipLaunchKernelGGL(contigs_walk_kernel, few, block, 0, c->stream, (const uint32_t*)pred, (const uint8_t*)flag, n, steps,
-                       cur, oth, st, d_rep);
-    uint32_t rounds = 1;
-    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    uint64_t open = h->open, resolved = 0;
-    while (open && rounds < 64)
-    {
-        hipLaunchKernelGGL(contigs_double_kernel, few, block, 0, c->stream, (const uint2*)cur, oth, (const uint8_t*)flag, st, n, d_rep);
-        std::swap(cur, oth);
-        ++rounds;
-        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        const uint64_t fresh = h->resolved - resolved;
-        resolved = h->resolved;
-        if (fresh == 0) break;                          // what is open now lies on cycles without a start
-        open -= fresh;
-    }
-    inf.rounds = rounds;
-    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
-
-    // ---- ends, the rule per path, the layout of the taken paths
-    uint32_t* end_of = pred;                            // (the predecessors are no longer needed)
-    uint32_t* len_of = (uint32_t*)oth;                  // (nor the pairs of the round before the last)
-    uint32_t* ord = len_of + n64;
-    hipLaunchKernelGGL(contigs_ends_kernel, few, block, 0, c->stream, (const uint2*)cur, (const uint8_t*)flag, (const uint8_t*)st, n,
-                       end_of, len_of, d_rep);
-    hipLaunchKernelGGL(contigs_decide_kernel, few, block, 0, c->stream, flag, (const uint32_t*)rcr, (const uint32_t*)end_of,
-                       (const uint32_t*)len_of, n, sc, d_rep);
-    HIP_TRY(hipMemsetAsync(sc + n64, 0, 8, c->stream));
-    exclusive_scan_u64(c, sc, n64 + 1);
-    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hx, sc + n64, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    inf.paths = h->paths; inf.taken_paths = h->taken; inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
-    const uint64_t npaths = hx[0] >> 32, nslots = hx[0] & 0xFFFFFFFFULL;
-    uint64_t nsegs = 0, total = 0;
-    SegRec* segs = nullptr;
-    uint8_t* text = nullptr;
-    if (npaths)
-    {
-        SegRec* recs = (SegRec*)c->arena.temp(npaths * sizeof(SegRec));
-        uint64_t* pass = (uint64_t*)c->arena.temp((npaths + 1) * 8);
-        uint64_t* bytes = (uint64_t*)c->arena.temp((npaths + 1) * 8);
-        hipLaunchKernelGGL(contigs_paths_kernel, grid, block, 0, c->stream, (const uint8_t*)flag, (const uint64_t*)sc,
-                           (const uint32_t*)end_of, (const uint32_t*)len_of, n, recs);
-        hipLaunchKernelGGL(contigs_order_kernel, grid, block, 0, c->stream, (const uint2*)cur, (const uint8_t*)flag, (const uint8_t*)st,
-                           (const uint64_t*)sc, n, ord);
-        hipLaunchKernelGGL(contigs_figures_kernel, dim3(grid_for(nslots, kTB * kContigsFigSteps)), block, 0, c->stream,
-                           (const uint32_t*)ord, (uint32_t)nslots, counts, (const uint2*)cur, (const uint64_t*)sc, recs);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_select_kernel<K>), dim3(grid_for(npaths, kTB)), block, 0, c->stream, keys,
-                           (const uint32_t*)rcr, (const uint8_t*)info, recs, npaths, Kn, min_length, min_coverage, line, pass, bytes);
-        HIP_TRY(hipMemsetAsync(pass + npaths, 0, 8, c->stream));
-        HIP_TRY(hipMemsetAsync(bytes + npaths, 0, 8, c->stream));
-        exclusive_scan_u64(c, pass, npaths + 1);
-        exclusive_scan_u64(c, bytes, npaths + 1);
-        HIP_TRY(hipMemcpyAsync(hx, pass + npaths, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(hx + 1, bytes + npaths, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        nsegs = hx[0]; total = hx[1];
-        if (nsegs)
-        {
-            segs = (SegRec*)c->arena.perm(nsegs * sizeof(SegRec));
-            text = (uint8_t*)c->arena.perm(((total + 15) & ~15ULL) + 16);
-            uint32_t* base = (uint32_t*)c->arena.temp(nsegs * 4);
-            hipLaunchKernelGGL(contigs_compact_kernel, dim3(grid_for(npaths, kTB)), block, 0, c->stream, (const SegRec*)recs, npaths,
-                               (const uint64_t*)pass, (const uint64_t*)bytes, segs, base);
-            if (total)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_text_kernel<K>), dim3(grid_for(total, kTB * kContigsTextRun)), block, 0,
-                                   c->stream, keys, (const uint32_t*)ord, (const SegRec*)segs, (const uint32_t*)base, nsegs, total, Kn,
-                                   line, text);
-        }
-    }
-    else HIP_TRY(hipEventRecord(ev.e[3], c->stream));
-    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_figures, &inf.ms_text};
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
-    inf.segments = nsegs; inf.text_bytes = total;
-    c->seg_recs = segs; c->seg_text = text; c->seg_count = nsegs; c->seg_text_bytes = total;
-    *out = inf;
-}
-}  // extern "C++"
 
 int goss_gpu_segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
 {
     if (!c || !out || (flags & ~(uint32_t)GOSS_SEGMENTS_NO_LINE_BREAKS)) return GOSS_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
-    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "segments are read from a graph"; return GOSS_ERR_STATE; }
-    if (!c->finished || c->emitted) { c->last_error = "segments belong between finish and emit"; return GOSS_ERR_STATE; }
-    if (!c->res_big.empty())
-    {
-        c->last_error = "segments: the graph has multiplicities of 2^32 - 1 or more";
-        return GOSS_ERR_INVALID_ARG;
-    }
-    bool began = false;
-    int rc = guarded(c, [&]() {                          // (gives back what an earlier build holds)
-        c->seg_lo = c->arena.lo;
-        began = true;
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
-        if (c->words == 1) segments_build<Key1>(c, min_length, min_coverage, flags, out);
-        else segments_build<Key2>(c, min_length, min_coverage, flags, out);
-        t.stop();
-        c->seg_live = true;
-    });
-    if (rc != GOSS_OK)
-    {
-        // nothing is held after a failure; the result was only read
-        if (began) c->arena.lo = c->seg_lo;
-        c->seg_live = false; c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
-        std::memset(out, 0, sizeof *out);
-    }
-    return rc;
+    if (const int st = graph_pass_state(c, "segments", "segments are read from a graph", "segments belong between finish and emit")) return st;
+    return build_held(c, Held::Segments, out, [&]() { segments_build(c, min_length, min_coverage, flags, out); });
 }
 
 int goss_gpu_segments_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, goss_gpu_segment* out)
 {
     if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
-    if (!c->seg_live) { c->last_error = "segments_table needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
+    if (c->held.kind != Held::Segments) { c->last_error = "segments_table needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
     if (first > c->seg_count || count > c->seg_count - first) { c->last_error = "segments_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->seg_hold = true;
+    c->keep_held = true;
     return guarded(c, [&]() {
         if (count) HIP_TRY(hipMemcpyAsync(out, (const SegRec*)c->seg_recs + first, count * sizeof(SegRec), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -5188,9 +4871,9 @@ int goss_gpu_segments_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, gos
 int goss_gpu_segments_text(goss_gpu_ctx* c, uint64_t text_offset, uint64_t bytes, char* dst)
 {
     if (!c || (bytes && !dst)) return GOSS_ERR_INVALID_ARG;
-    if (!c->seg_live) { c->last_error = "segments_text needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
+    if (c->held.kind != Held::Segments) { c->last_error = "segments_text needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
     if (text_offset > c->seg_text_bytes || bytes > c->seg_text_bytes - text_offset) { c->last_error = "segments_text: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->seg_hold = true;
+    c->keep_held = true;
     return guarded(c, [&]() {
         if (bytes) HIP_TRY(hipMemcpyAsync(dst, c->seg_text + text_offset, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -5200,206 +4883,22 @@ int goss_gpu_segments_text(goss_gpu_ctx* c, uint64_t text_offset, uint64_t bytes
 int goss_gpu_segments_release(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (c->seg_live) { c->arena.lo = c->seg_lo; c->seg_live = false; }
-    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+    if (c->held.kind == Held::Segments) release_held(c);
     return GOSS_OK;
 }
-
-extern "C++" {
-// The EntryEdgeSet of the result (EntryEdgeSet::build, EntryEdgeSet.cc:154-287).  Working arrays under an ArenaScope;
-// the compacted columns and the file images are permanent room on top of everything else (c->ent_lo marks where it
-// began), and the images are the context's file list under names that begin with "-entries".
-template <class K>
-static void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
-{
-    static_assert(sizeof(ContigsReport) <= 128, "pinned scratch");
-    goss_gpu_entries_info inf{};
-    const uint64_t n64 = c->M;
-    if (n64 >= 0xFFFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "entries: the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t bits = n ? tips_bucket_bits(n, c->len) : 0;
-    const uint32_t steps = contigs_walk_steps();
-    inf.walk_steps = steps;
-    {
-        // rcr, nxt, pred (4 + 4 + 4), two arrays of pairs and two of weights (4 x 8), the scan (8), info, flag, st: 55
-        // bytes per edge and the table; then per entry the key, two columns, the images and what the emit kernels sort
-        const uint64_t need = n64 * 55 + (bits ? ((1ULL << bits) + 1) * 4 : 0) + (16u << 20);
-        if (c->arena.avail() < need) grow_arena(c, need);
-        c->ent_lo = c->arena.lo;
-    }
-    ArenaScope scope(c->arena);
-    EventPair ev;
-    const K* keys = (const K*)c->res_keys;
-    const uint32_t* counts = c->res_counts;
-    ContigsReport* h = (ContigsReport*)c->h_pinned;
-    uint64_t* hx = (uint64_t*)((uint8_t*)c->h_pinned + 128);
-    uint64_t nent = 0;
-    K* ekeys = nullptr;
-    uint32_t *elen = nullptr, *ecnt = nullptr, *lwr = nullptr;
-    uint8_t* upr = nullptr;
-    auto columns = [&]() {
-        ekeys = (K*)c->arena.perm(std::max<uint64_t>(nent * sizeof(K), 16));
-        elen = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
-        ecnt = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
-        upr = (uint8_t*)c->arena.perm(std::max<uint64_t>(nent, 16));
-        lwr = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
-    };
-    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    if (n == 0)
-    {
-        columns();
-        for (int i = 1; i < 4; ++i) HIP_TRY(hipEventRecord(ev.e[i], c->stream));
-    }
-    else
-    {
-        uint32_t* rcr = (uint32_t*)c->arena.temp(n64 * 4);
-        uint32_t* nxt = (uint32_t*)c->arena.temp(n64 * 4);
-        uint8_t* info = (uint8_t*)c->arena.temp(n64);
-        uint8_t* flag = (uint8_t*)c->arena.temp(n64);
-        uint8_t* st = (uint8_t*)c->arena.temp(n64);
-        uint32_t* pred = (uint32_t*)c->arena.temp(n64 * 4);
-        uint2* cur = (uint2*)c->arena.temp(n64 * 8);
-        uint2* oth = (uint2*)c->arena.temp(n64 * 8);
-        uint64_t* wcur = (uint64_t*)c->arena.temp(n64 * 8);
-        uint64_t* woth = (uint64_t*)c->arena.temp(n64 * 8);
-        uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
-        uint32_t* table = bits ? (uint32_t*)c->arena.temp(((1ULL << bits) + 1) * 4) : nullptr;
-        ContigsReport* d_rep = (ContigsReport*)c->arena.temp(sizeof(ContigsReport));
-        TipsReport* d_tips = (TipsReport*)c->arena.temp(sizeof(TipsReport));
-
-        // ---- the link pass of prune-tips, as it is
-        HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(ContigsReport), c->stream));
-        HIP_TRY(hipMemsetAsync(d_tips, 0, sizeof(TipsReport), c->stream));
-        HIP_TRY(hipMemsetAsync(&d_tips->missing_rc, 0xFF, 8, c->stream));
-        HIP_TRY(hipMemsetAsync(pred, 0, n64 * 4, c->stream));
-        const dim3 grid(grid_for(n64, kTB)), block(kTB);
-        const dim3 few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kContigsGridBlocks));
-        if (bits)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits, table);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), grid, block, 0, c->stream, keys, n, c->len, bits,
-                           (const uint32_t*)table, rcr, nxt, info, d_tips);
-        HIP_TRY(hipMemcpyAsync(hx, &d_tips->missing_rc, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        if (hx[0] != ~0ULL)
-            throw StatusError{GOSS_ERR_INVALID_ARG, "entries: edge " + std::to_string(hx[0]) +
-                                                        " has no reverse complement in the graph (lint-graph reports such edges)"};
-
-        // ---- starts, predecessors, list ranking with the weights; the numbering of the starts
-        hipLaunchKernelGGL(contigs_mark_kernel, grid, block, 0, c->stream, (const uint32_t*)rcr, (const uint32_t*)nxt,
-                           (const uint8_t*)info, n, flag, pred);
-        hipLaunchKernelGGL(entries_flags_kernel, grid, block, 0, c->stream, (const uint8_t*)flag, n, sc);
-        HIP_TRY(hipMemsetAsync(sc + n64, 0, 8, c->stream));
-        exclusive_scan_u64(c, sc, n64 + 1);
-        HIP_TRY(hipMemcpyAsync(hx, sc + n64, 8, hipMemcpyDeviceToHost, c->stream));
-        hipLaunchKernelGGL(entries_walk_kernel, few, block, 0, c->stream, (const uint32_t*)pred, (const uint8_t*)flag, counts, n, steps,
-                           cur, oth, wcur, woth, st, d_rep);
-        uint32_t rounds = 1;
-        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        nent = hx[0];
-        uint64_t open = h->open, resolved = 0;
-        while (open && rounds < 64)
-        {
-            hipLaunchKernelGGL(entries_double_kernel, few, block, 0, c->stream, (const uint2*)cur, oth, (const uint64_t*)wcur, woth,
-                               (const uint8_t*)flag, st, n, d_rep);
-            std::swap(cur, oth);
-            std::swap(wcur, woth);
-            ++rounds;
-            HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            check_launch("a kernel launch was refused");
-            const uint64_t fresh = h->resolved - resolved;
-            resolved = h->resolved;
-            if (fresh == 0) break;                          // what is open now lies on cycles without a start
-            open -= fresh;
-        }
-        inf.rounds = rounds;
-        HIP_TRY(hipEventRecord(ev.e[2], c->stream));
-
-        // ---- the records, compacted: every path's last edge writes where the path's start goes
-        columns();
-        if (nent)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(entries_keys_kernel<K>), grid, block, 0, c->stream, keys, (const uint8_t*)flag,
-                               (const uint64_t*)sc, n, ekeys);
-        hipLaunchKernelGGL(entries_paths_kernel, few, block, 0, c->stream, (const uint2*)cur, (const uint64_t*)wcur, (const uint8_t*)flag,
-                           (const uint8_t*)st, (const uint32_t*)rcr, counts, (const uint64_t*)sc, n, elen, ecnt, upr, lwr, d_rep);
-        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        check_launch("a kernel launch was refused");
-        inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
-    }
-    inf.entries = nent;
-
-    // ---- the images (EntryEdgeSet.cc:203-286): SparseArray::Builder(.edges, z, n) ... end(z) with z = 4^(K+1), two
-    // VariableByteArrays of n items, the histogram of the counts, the 40-bit IntegerArray, the header
-    const std::string base = "-entries";
-    const uint32_t ubits = 2 * c->k + 2;
-    const uint64_t zlo = ubits < 64 ? (1ULL << ubits) : 0, zhi = ubits >= 64 ? (1ULL << (ubits - 64)) : 0;
-    emit_sparse_array<K>(c, ekeys, nent, zlo, zhi, nent, zlo, zhi, base + ".edges");
-    uint64_t lines = 0;
-    emit_counts(c, ecnt, nent, nent, base + ".counts", base + ".counts-hist.txt", &lines);
-    emit_counts(c, elen, nent, nent, base + ".lengths", std::string());
-    inf.hist_size = lines;
-    {
-        std::vector<IaCol> cols;                          // RankBits = 40 (EntryEdgeSet.hh:41): ".upr" u8, ".lwr" u32
-        ia_layout(40, base + ".ends", 0, cols);
-        const uint8_t* img[2] = {upr, (const uint8_t*)lwr};
-        for (size_t i = 0; i < cols.size() && i < 2; ++i)
-        {
-            OutFile f; f.suffix = cols[i].suffix; f.size = nent * cols[i].bytes; f.dev = img[i];
-            c->files.push_back(std::move(f));
-        }
-    }
-    const uint64_t hdr[2] = {2011041901ULL, c->k};
-    add_host_file(c, base + ".header", hdr, sizeof hdr);
-    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    check_launch("a kernel launch was refused");
-    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_paths, &inf.ms_emit};
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
-    *out = inf;
-}
-}  // extern "C++"
 
 int goss_gpu_entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
 {
     if (!c || !out) return GOSS_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
-    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "an entry edge set is built from a graph"; return GOSS_ERR_STATE; }
-    if (!c->finished || c->emitted) { c->last_error = "entries belong between finish and emit"; return GOSS_ERR_STATE; }
-    if (!c->res_big.empty())
-    {
-        c->last_error = "entries: the graph has multiplicities of 2^32 - 1 or more";
-        return GOSS_ERR_INVALID_ARG;
-    }
-    bool began = false;
-    int rc = guarded(c, [&]() {                          // (gives back what an earlier build holds)
-        c->files.clear();
-        c->ent_lo = c->arena.lo;
-        began = true;
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
-        if (c->words == 1) entries_build<Key1>(c, out); else entries_build<Key2>(c, out);
-        t.stop();
-        c->ent_live = true;
-    });
-    if (rc != GOSS_OK)
-    {
-        // nothing is held after a failure; the result was only read
-        if (began) { c->arena.lo = c->ent_lo; c->files.clear(); }
-        c->ent_live = false;
-        std::memset(out, 0, sizeof *out);
-    }
-    return rc;
+    if (const int st = graph_pass_state(c, "entries", "an entry edge set is built from a graph", "entries belong between finish and emit")) return st;
+    return build_held(c, Held::Entries, out, [&]() { entries_build(c, out); });
 }
 
 int goss_gpu_entries_release(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (c->ent_live) { c->arena.lo = c->ent_lo; c->ent_live = false; c->files.clear(); }
+    if (c->held.kind == Held::Entries) release_held(c);
     return GOSS_OK;
 }
 
@@ -5785,7 +5284,7 @@ int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* c)
     else if (fs.count("-entries.header")) { kind = GOSS_OBJECT_ENTRY_EDGE_SET; base = "-entries"; }
     if (kind < 0) { t_open_error = "the context holds no emitted KmerSet, Graph, SparseArray or EntryEdgeSet"; return GOSS_ERR_STATE; }
     // what the context's stream still writes into its files (the call only reads: what is held stays)
-    c->seg_hold = true;
+    c->keep_held = true;
     int rc = guarded(c, [&]() { HIP_TRY(hipStreamSynchronize(c->stream)); });
     if (rc != GOSS_OK) { t_open_error = c->last_error; return rc; }
     return object_open(out, c->device, nullptr, kind, base, fs);

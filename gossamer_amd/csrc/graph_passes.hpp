@@ -1,0 +1,532 @@
+// graph_passes.hpp -- the passes over the decoded, sorted edge list of a finished graph: prune-tips, the linear segments
+// of print-contigs, the EntryEdgeSet of build-entry-edge-set.
+// Part of goss_gpu.hip (included there, inside its unnamed namespace, once guarded() and the emit helpers it calls are
+// defined).  Two steps are shared and live here once each:
+//
+//   link_graph   rcr / nxt / info of every edge (kernels_tips.hpp); refuses a graph that lacks a reverse complement
+//   rank_lists   starts and predecessors (contigs_mark_kernel), then the position of every edge on its path by a
+//                bounded walk and pointer doubling (kernels_contigs.hpp), with or without the multiplicities
+//
+// prune_tips_once is link_graph and the tip walk; segments_build and entries_build are link_graph, rank_lists and
+// their own records.  What a build leaves behind for later calls is the context's one held result (build_held).
+#pragma once
+
+// Temporaries of one call, given back on every way out (an exception included).
+struct ArenaScope {
+    Arena& a;
+    uint64_t mark;
+    explicit ArenaScope(Arena& arena) : a(arena), mark(arena.mark()) {}
+    ~ArenaScope() { a.release(mark); }
+    ArenaScope(const ArenaScope&) = delete;
+    ArenaScope& operator=(const ArenaScope&) = delete;
+};
+
+struct EventPair {
+    hipEvent_t e[5] = {};
+    EventPair() { for (auto& x : e) HIP_TRY(hipEventCreate(&x)); }
+    ~EventPair() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// The pinned scratch of the context as the passes use it: a report at its start, two words behind it.
+static_assert(sizeof(TipsReport) <= 128 && sizeof(ContigsReport) <= 128, "pinned scratch");
+template <class R> R* pinned_report(goss_gpu_ctx* c) { return (R*)c->h_pinned; }
+inline uint64_t* pinned_words(goss_gpu_ctx* c) { return (uint64_t*)((uint8_t*)c->h_pinned + 128); }
+
+inline void sync_checked(goss_gpu_ctx* c)
+{
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_launch("a kernel launch was refused");
+}
+
+// a[0, n) becomes its exclusive prefix sums and a[n] their total, which is on its way to *total (pinned) when this
+// returns: the caller's next sync_checked delivers it.
+inline void scan_with_total(goss_gpu_ctx* c, uint64_t* a, uint64_t n, uint64_t* total)
+{
+    HIP_TRY(hipMemsetAsync(a + n, 0, 8, c->stream));
+    exclusive_scan_u64(c, a, n + 1);
+    HIP_TRY(hipMemcpyAsync(total, a + n, 8, hipMemcpyDeviceToHost, c->stream));
+}
+
+struct NothingQueued { template <class... A> void operator()(A&&...) const {} };
+
+// ---- the state the passes ask for, and the one held result ---------------------------------------------------------
+
+// A graph, between finish and emit, every multiplicity below 2^32 - 1: GOSS_OK, or the status to refuse with
+// (last_error is set; the first two texts are the caller's own, `who` heads the third).
+int graph_pass_state(goss_gpu_ctx* c, const char* who, const char* not_a_graph, const char* out_of_place)
+{
+    if (c->mode != GOSS_MODE_GRAPH) { c->last_error = not_a_graph; return GOSS_ERR_STATE; }
+    if (!c->finished || c->emitted) { c->last_error = out_of_place; return GOSS_ERR_STATE; }
+    if (!c->res_big.empty())
+    {
+        c->last_error = std::string(who) + ": the graph has multiplicities of 2^32 - 1 or more";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    return GOSS_OK;
+}
+
+// The skeleton of goss_gpu_segments_build and goss_gpu_entries_build: guarded() gives back what an earlier build
+// holds, `body` builds on top of the permanent room as it is then, and the context holds the outcome as `kind`.
+// After a failure nothing is held and *out is zero; the result was only read.
+template <class Info, class F>
+int build_held(goss_gpu_ctx* c, Held kind, Info* out, F&& body)
+{
+    bool began = false;
+    const int rc = guarded(c, [&]() {
+        c->held = {kind, c->arena.lo};
+        began = true;
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        body();
+        t.stop();
+    });
+    if (rc != GOSS_OK)
+    {
+        if (began) release_held(c);
+        std::memset(out, 0, sizeof *out);
+    }
+    return rc;
+}
+
+// ---- the link pass --------------------------------------------------------------------------------------------------
+
+// Bits of the link pass's bucket table for n edges of len bases: about one edge per bucket, at most 2^26 entries
+// (256 MB).  GOSS_GPU_TIPS_BUCKET_BITS overrides it (0 = plain binary search; the probe's A/B).
+uint32_t tips_bucket_bits(uint64_t n, uint32_t len)
+{
+    uint32_t bits = 0;
+    while (bits < 26u && (2ULL << bits) <= n) ++bits;
+    if (const char* e = std::getenv("GOSS_GPU_TIPS_BUCKET_BITS")) bits = (uint32_t)std::min<long>(26, std::max<long>(0, std::atol(e)));
+    return std::min(bits, 2u * len);
+}
+
+// The edges of the result as the 32-bit number the link arrays rank them by, or the refusal.
+uint32_t link_edges(const goss_gpu_ctx* c, const char* who)
+{
+    if (c->M >= 0xFFFFFFFFULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, std::string(who) + ": the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
+    return (uint32_t)c->M;
+}
+
+inline uint64_t link_table_bytes(uint32_t bits) { return bits ? ((1ULL << bits) + 1) * 4 : 0; }
+
+// What link_graph takes from the arena: rcr, nxt (4 + 4), info (1) and the bucket table.
+uint64_t link_bytes(const goss_gpu_ctx* c, const char* who)
+{
+    const uint64_t n = link_edges(c, who);
+    return n * (4 + 4 + 1) + link_table_bytes(n ? tips_bucket_bits(n, c->len) : 0);
+}
+
+template <class K>
+struct GraphLinks {
+    const K* keys;
+    const uint32_t* counts;
+    uint32_t *rcr, *nxt;              // rank of the reverse complement; of the first edge that leaves to(E[i])
+    uint8_t* info;                    // out-degree of to(E[i]) and the size of the group E[i] lies in (kernels_tips.hpp)
+    uint32_t n, bits;
+    dim3 grid, block;                 // one thread per edge
+};
+
+// The link pass over the result's n >= 1 edges, complete when this returns: an edge whose reverse complement is
+// missing refuses the call.  `who` heads the messages.  `report` is the caller's device report where the kernels
+// that follow add to it (it is cleared here), or null for a private one; `before_wait(links)` queues what the caller
+// wants on the stream ahead of the wait.
+template <class K, class F = NothingQueued>
+GraphLinks<K> link_graph(goss_gpu_ctx* c, const char* who, TipsReport* report = nullptr, F&& before_wait = F())
+{
+    GraphLinks<K> l{};
+    l.keys = (const K*)c->res_keys;
+    l.counts = c->res_counts;
+    l.n = link_edges(c, who);
+    l.bits = tips_bucket_bits(l.n, c->len);
+    const uint64_t n64 = l.n;
+    l.rcr = (uint32_t*)c->arena.temp(n64 * 4);
+    l.nxt = (uint32_t*)c->arena.temp(n64 * 4);
+    l.info = (uint8_t*)c->arena.temp(n64);
+    uint32_t* table = l.bits ? (uint32_t*)c->arena.temp(link_table_bytes(l.bits)) : nullptr;
+    if (!report) report = (TipsReport*)c->arena.temp(sizeof(TipsReport));
+    l.grid = dim3(grid_for(n64, kTB));
+    l.block = dim3(kTB);
+
+    HIP_TRY(hipMemsetAsync(report, 0, sizeof(TipsReport), c->stream));
+    HIP_TRY(hipMemsetAsync(&report->missing_rc, 0xFF, 8, c->stream));
+    if (l.bits)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), l.grid, l.block, 0, c->stream, l.keys, l.n, c->len, l.bits, table);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_link_kernel<K>), l.grid, l.block, 0, c->stream, l.keys, l.n, c->len, l.bits,
+                       (const uint32_t*)table, l.rcr, l.nxt, l.info, report);
+    uint64_t* missing = pinned_words(c);
+    HIP_TRY(hipMemcpyAsync(missing, &report->missing_rc, 8, hipMemcpyDeviceToHost, c->stream));
+    before_wait(l);
+    sync_checked(c);
+    if (*missing != ~0ULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, std::string(who) + ": edge " + std::to_string(*missing) +
+                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
+    return l;
+}
+
+// ---- list ranking ---------------------------------------------------------------------------------------------------
+
+// Pointers the first ranking launch follows per lane before doubling takes over: kContigsWalkSteps, or
+// GOSS_GPU_CONTIGS_WALK=<steps> (1 = doubling alone; the probe's A/B).
+uint32_t contigs_walk_steps()
+{
+    long v = kContigsWalkSteps;
+    if (const char* e = std::getenv("GOSS_GPU_CONTIGS_WALK")) v = std::atol(e);
+    return (uint32_t)std::min<long>(4096, std::max<long>(1, v));
+}
+
+// What rank_lists takes from the arena per edge: flag, st (1 + 1), pred (4), two arrays of pairs (8 + 8) and, with the
+// multiplicities, two of weights (8 + 8).
+constexpr uint64_t rank_bytes_per_edge(bool weighted) { return 1 + 1 + 4 + 8 + 8 + (weighted ? 8 + 8 : 0); }
+
+struct ListRanks {
+    uint8_t *flag, *st;               // kCtgStart / kCtgSucc per edge; what is resolved (kCtgOpen = on a cycle without a start)
+    uint32_t* pred;
+    uint2 *cur, *oth;                 // (start, distance) of every resolved edge; the pairs of the round before the last
+    uint64_t *wcur, *woth;            // the weights beside them, or null
+    ContigsReport* report;            // on the device: open and resolved so far; the callers' kernels add their figures
+    uint32_t steps, rounds;
+    dim3 few;                         // the grid of the kernels that stride over the edges
+};
+
+// Starts, predecessors and list ranking over the links.  `counts` makes the ranking carry the multiplicities
+// (kernels_contigs.hpp, WEIGHTED); null ranks positions alone.  `after_mark(flag)` queues what the caller wants
+// between the start flags and the first ranking launch.  Complete when this returns.
+template <class K, class F = NothingQueued>
+ListRanks rank_lists(goss_gpu_ctx* c, const GraphLinks<K>& l, const uint32_t* counts, F&& after_mark = F())
+{
+    const uint64_t n64 = l.n;
+    const uint32_t n = l.n;
+    ListRanks r{};
+    r.flag = (uint8_t*)c->arena.temp(n64);
+    r.st = (uint8_t*)c->arena.temp(n64);
+    r.pred = (uint32_t*)c->arena.temp(n64 * 4);
+    r.cur = (uint2*)c->arena.temp(n64 * 8);
+    r.oth = (uint2*)c->arena.temp(n64 * 8);
+    if (counts)
+    {
+        r.wcur = (uint64_t*)c->arena.temp(n64 * 8);
+        r.woth = (uint64_t*)c->arena.temp(n64 * 8);
+    }
+    r.report = (ContigsReport*)c->arena.temp(sizeof(ContigsReport));
+    r.steps = contigs_walk_steps();
+    r.few = dim3((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kContigsGridBlocks));
+    const auto walk = counts ? contigs_walk_kernel<true> : contigs_walk_kernel<false>;
+    const auto twice = counts ? contigs_double_kernel<true> : contigs_double_kernel<false>;
+    ContigsReport* h = pinned_report<ContigsReport>(c);
+    auto fetch_report = [&]() {
+        HIP_TRY(hipMemcpyAsync(h, r.report, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+        sync_checked(c);
+    };
+
+    HIP_TRY(hipMemsetAsync(r.report, 0, sizeof(ContigsReport), c->stream));
+    HIP_TRY(hipMemsetAsync(r.pred, 0, n64 * 4, c->stream));
+    hipLaunchKernelGGL(contigs_mark_kernel, l.grid, l.block, 0, c->stream, (const uint32_t*)l.rcr, (const uint32_t*)l.nxt,
+                       (const uint8_t*)l.info, n, r.flag, r.pred);
+    after_mark((const uint8_t*)r.flag);
+    hipLaunchKernelGGL(walk, r.few, l.block, 0, c->stream, (const uint32_t*)r.pred, (const uint8_t*)r.flag, counts, n, r.steps,
+                       r.cur, r.oth, r.wcur, r.woth, r.st, r.report);
+    r.rounds = 1;
+    fetch_report();
+    uint64_t open = h->open, resolved = 0;
+    while (open && r.rounds < 64)
+    {
+        hipLaunchKernelGGL(twice, r.few, l.block, 0, c->stream, (const uint2*)r.cur, r.oth, (const uint8_t*)r.flag, r.st, n, r.report,
+                           (const uint64_t*)r.wcur, r.woth);
+        std::swap(r.cur, r.oth);
+        std::swap(r.wcur, r.woth);
+        ++r.rounds;
+        fetch_report();
+        const uint64_t fresh = h->resolved - resolved;
+        resolved = h->resolved;
+        if (fresh == 0) break;                          // what is open now lies on cycles without a start
+        open -= fresh;
+    }
+    return r;
+}
+
+// ---- prune-tips -----------------------------------------------------------------------------------------------------
+
+// One iteration of prune-tips over the result (GossCmdPruneTips.cc:279-319).  Nothing of the context changes
+// before the survivors are complete: a failure leaves the result as it was.
+template <class K>
+void prune_tips_once(goss_gpu_ctx* c, goss_gpu_tips_report* out)
+{
+    static_assert(sizeof(goss_gpu_tips_report) == 11 * 8 && sizeof(TipsReport) == 13 * 8, "tips report layout");
+    goss_gpu_tips_report rep{};
+    const uint64_t n64 = c->M;
+    rep.edges_before = rep.edges_after = n64;
+    if (out) *out = rep;
+    if (n64 == 0) return;
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    const uint64_t zap_words = ntiles * (kRedTile / 32), cand_words = (n64 + 63) / 64;
+    {
+        // the links + the two bitmaps, and the survivors once more while they are compacted
+        const uint64_t need = link_bytes(c, "prune_tips") + zap_words * 4 + cand_words * 8 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);       // (no temporary is live between two entry points)
+    }
+    ArenaScope scope(c->arena);
+    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
+    uint64_t* cand = (uint64_t*)c->arena.temp(cand_words * 8);
+    TipsReport* d_rep = (TipsReport*)c->arena.temp(sizeof(TipsReport));
+    TipsReport* h = pinned_report<TipsReport>(c);
+
+    HIP_TRY(hipMemsetAsync(zap, 0, zap_words * 4, c->stream));
+    const GraphLinks<K> l = link_graph<K>(c, "prune_tips", d_rep, [&](const GraphLinks<K>& q) {
+        const dim3 few((uint32_t)std::min<uint64_t>(q.grid.x, kTipsGridBlocks));
+        hipLaunchKernelGGL(tips_flag_kernel, few, q.block, 0, c->stream, (const uint32_t*)q.rcr, (const uint8_t*)q.info, q.n, cand, d_rep);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
+    });
+    const uint32_t n = l.n;
+    const dim3 block = l.block;
+    const uint64_t ncand = h->candidates;
+    rep.candidates = ncand;
+    if (ncand == 0) { if (out) *out = rep; return; }
+
+    uint32_t* list = (uint32_t*)c->arena.temp(ncand * 4);
+    HIP_TRY(hipMemsetAsync(list, 0xFF, ncand * 4, c->stream));
+    const uint64_t words_per_block = (cand_words + kTipsGridBlocks - 1) / kTipsGridBlocks;
+    hipLaunchKernelGGL(tips_gather_kernel, dim3(grid_for(cand_words, (uint32_t)std::max<uint64_t>(words_per_block, 1))), block, 0, c->stream,
+                       (const uint64_t*)cand, cand_words, words_per_block, list, ncand, d_rep);
+    hipLaunchKernelGGL(tips_walk_kernel, dim3(grid_for(ncand, kTB)), block, 0, c->stream, (const uint32_t*)list, ncand, n, c->k,
+                       (const uint32_t*)l.rcr, (const uint32_t*)l.nxt, (const uint8_t*)l.info, l.counts, zap, d_rep);
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), block, 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
+    uint64_t* hm = pinned_words(c);
+    scan_with_total(c, tile_counts, ntiles, hm);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(TipsReport), hipMemcpyDeviceToHost, c->stream));
+    sync_checked(c);
+    rep.tips = h->tips; rep.zapped = h->zapped;
+    rep.too_long = h->too_long; rep.both_joined = h->both_joined; rep.isolated = h->isolated; rep.outweighed = h->outweighed;
+    rep.joined_at_begin = h->joined_at_begin; rep.joined_at_end = h->joined_at_end;
+    const uint64_t m = hm[0];
+    rep.edges_after = m;
+    if (m != n64)
+    {
+        const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
+        const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
+        // a result this entry point allocated is compacted beside itself and copied back (five iterations take the
+        // permanent room of one); anybody else's arrays (a run, select_counts) are left alone
+        K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
+        uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), block, 0, c->stream, l.keys, l.counts, n64,
+                           (const uint32_t*)zap, (const uint64_t*)tile_counts, okeys, ocounts);
+        if (own)
+        {
+            if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+            if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        sync_checked(c);
+        if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
+        c->M = m;
+    }
+    if (out) *out = rep;
+}
+
+void prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_report* reports)
+{
+    for (uint32_t it = 0; it < iterations; ++it)
+    {
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        goss_gpu_tips_report* r = reports ? reports + it : nullptr;
+        if (c->words == 1) prune_tips_once<Key1>(c, r); else prune_tips_once<Key2>(c, r);
+        t.stop();
+    }
+}
+
+// ---- print-contigs --------------------------------------------------------------------------------------------------
+
+// Linear segments of the result (GossCmdPrintContigs.cc:49-193).  Temporaries under an ArenaScope; the table and the
+// text are permanent room on top of everything else: the held result.
+template <class K>
+void segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
+{
+    static_assert(sizeof(goss_gpu_segment) == sizeof(SegRec) && sizeof(SegRec) == 64, "segment layout");
+    goss_gpu_segments_info inf{};
+    const uint64_t n64 = c->M;
+    if (n64 == 0) { *out = inf; return; }
+    const uint32_t Kn = c->k;
+    const uint32_t line = (flags & GOSS_SEGMENTS_NO_LINE_BREAKS) ? 0u : 60u;
+    {
+        // the links, the ranking, the scan (8); then a record per taken path and about half a byte of text per edge
+        const uint64_t need = link_bytes(c, "segments") + n64 * (rank_bytes_per_edge(false) + 8) + n64 + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    ContigsReport* h = pinned_report<ContigsReport>(c);
+    uint64_t* hx = pinned_words(c);
+
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    const GraphLinks<K> l = link_graph<K>(c, "segments", nullptr, [&](const GraphLinks<K>&) { HIP_TRY(hipEventRecord(ev.e[1], c->stream)); });
+    const ListRanks r = rank_lists(c, l, nullptr);
+    inf.walk_steps = r.steps;
+    inf.rounds = r.rounds;
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    const uint32_t n = l.n;
+    const dim3 grid = l.grid, block = l.block, few = r.few;
+
+    // ---- ends, the rule per path, the layout of the taken paths
+    uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+    uint32_t* end_of = r.pred;                          // (the predecessors are no longer needed)
+    uint32_t* len_of = (uint32_t*)r.oth;                // (nor the pairs of the round before the last)
+    uint32_t* ord = len_of + n64;
+    hipLaunchKernelGGL(contigs_ends_kernel, few, block, 0, c->stream, (const uint2*)r.cur, (const uint8_t*)r.flag, (const uint8_t*)r.st, n,
+                       end_of, len_of, r.report);
+    hipLaunchKernelGGL(contigs_decide_kernel, few, block, 0, c->stream, r.flag, (const uint32_t*)l.rcr, (const uint32_t*)end_of,
+                       (const uint32_t*)len_of, n, sc, r.report);
+    scan_with_total(c, sc, n64, hx);
+    HIP_TRY(hipMemcpyAsync(h, r.report, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+    sync_checked(c);
+    inf.paths = h->paths; inf.taken_paths = h->taken; inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
+    const uint64_t npaths = hx[0] >> 32, nslots = hx[0] & 0xFFFFFFFFULL;
+    uint64_t nsegs = 0, total = 0;
+    SegRec* segs = nullptr;
+    uint8_t* text = nullptr;
+    if (npaths)
+    {
+        SegRec* recs = (SegRec*)c->arena.temp(npaths * sizeof(SegRec));
+        uint64_t* pass = (uint64_t*)c->arena.temp((npaths + 1) * 8);
+        uint64_t* bytes = (uint64_t*)c->arena.temp((npaths + 1) * 8);
+        hipLaunchKernelGGL(contigs_paths_kernel, grid, block, 0, c->stream, (const uint8_t*)r.flag, (const uint64_t*)sc,
+                           (const uint32_t*)end_of, (const uint32_t*)len_of, n, recs);
+        hipLaunchKernelGGL(contigs_order_kernel, grid, block, 0, c->stream, (const uint2*)r.cur, (const uint8_t*)r.flag, (const uint8_t*)r.st,
+                           (const uint64_t*)sc, n, ord);
+        hipLaunchKernelGGL(contigs_figures_kernel, dim3(grid_for(nslots, kTB * kContigsFigSteps)), block, 0, c->stream,
+                           (const uint32_t*)ord, (uint32_t)nslots, l.counts, (const uint2*)r.cur, (const uint64_t*)sc, recs);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_select_kernel<K>), dim3(grid_for(npaths, kTB)), block, 0, c->stream, l.keys,
+                           (const uint32_t*)l.rcr, (const uint8_t*)l.info, recs, npaths, Kn, min_length, min_coverage, line, pass, bytes);
+        scan_with_total(c, pass, npaths, hx);
+        scan_with_total(c, bytes, npaths, hx + 1);
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        sync_checked(c);
+        nsegs = hx[0]; total = hx[1];
+        if (nsegs)
+        {
+            segs = (SegRec*)c->arena.perm(nsegs * sizeof(SegRec));
+            text = (uint8_t*)c->arena.perm(((total + 15) & ~15ULL) + 16);
+            uint32_t* base = (uint32_t*)c->arena.temp(nsegs * 4);
+            hipLaunchKernelGGL(contigs_compact_kernel, dim3(grid_for(npaths, kTB)), block, 0, c->stream, (const SegRec*)recs, npaths,
+                               (const uint64_t*)pass, (const uint64_t*)bytes, segs, base);
+            if (total)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(contigs_text_kernel<K>), dim3(grid_for(total, kTB * kContigsTextRun)), block, 0,
+                                   c->stream, l.keys, (const uint32_t*)ord, (const SegRec*)segs, (const uint32_t*)base, nsegs, total, Kn,
+                                   line, text);
+        }
+    }
+    else HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
+    sync_checked(c);
+    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_figures, &inf.ms_text};
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    inf.segments = nsegs; inf.text_bytes = total;
+    c->seg_recs = segs; c->seg_text = text; c->seg_count = nsegs; c->seg_text_bytes = total;
+    *out = inf;
+}
+
+void segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
+{
+    if (c->words == 1) segments_build<Key1>(c, min_length, min_coverage, flags, out);
+    else segments_build<Key2>(c, min_length, min_coverage, flags, out);
+}
+
+// ---- build-entry-edge-set -------------------------------------------------------------------------------------------
+
+// The EntryEdgeSet of the result (EntryEdgeSet::build, EntryEdgeSet.cc:154-287).  Working arrays under an ArenaScope;
+// the compacted columns and the file images are permanent room on top of everything else (the held result), and the
+// images are the context's file list under names that begin with "-entries".
+template <class K>
+void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
+{
+    goss_gpu_entries_info inf{};
+    const uint64_t n64 = c->M;
+    inf.walk_steps = contigs_walk_steps();
+    {
+        // the links, the ranking with its weights, the scan (8): 55 bytes per edge and the table; then per entry the
+        // key, two columns, the images and what the emit kernels sort
+        const uint64_t need = link_bytes(c, "entries") + n64 * (rank_bytes_per_edge(true) + 8) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    uint64_t nent = 0;
+    K* ekeys = nullptr;
+    uint32_t *elen = nullptr, *ecnt = nullptr, *lwr = nullptr;
+    uint8_t* upr = nullptr;
+    auto columns = [&]() {
+        ekeys = (K*)c->arena.perm(std::max<uint64_t>(nent * sizeof(K), 16));
+        elen = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+        ecnt = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+        upr = (uint8_t*)c->arena.perm(std::max<uint64_t>(nent, 16));
+        lwr = (uint32_t*)c->arena.perm(std::max<uint64_t>(nent * 4, 16));
+    };
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (n64 == 0)
+    {
+        columns();
+        for (int i = 1; i < 4; ++i) HIP_TRY(hipEventRecord(ev.e[i], c->stream));
+    }
+    else
+    {
+        ContigsReport* h = pinned_report<ContigsReport>(c);
+        uint64_t* hx = pinned_words(c);
+        const GraphLinks<K> l = link_graph<K>(c, "entries", nullptr, [&](const GraphLinks<K>&) { HIP_TRY(hipEventRecord(ev.e[1], c->stream)); });
+        const uint32_t n = l.n;
+        // ---- list ranking with the weights; on its way, the numbering of the starts
+        uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+        const ListRanks r = rank_lists(c, l, l.counts, [&](const uint8_t* flag) {
+            hipLaunchKernelGGL(entries_flags_kernel, l.grid, l.block, 0, c->stream, flag, n, sc);
+            scan_with_total(c, sc, n64, hx);
+        });
+        nent = hx[0];
+        inf.rounds = r.rounds;
+        HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+
+        // ---- the records, compacted: every path's last edge writes where the path's start goes
+        columns();
+        if (nent)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(entries_keys_kernel<K>), l.grid, l.block, 0, c->stream, l.keys, (const uint8_t*)r.flag,
+                               (const uint64_t*)sc, n, ekeys);
+        hipLaunchKernelGGL(entries_paths_kernel, r.few, l.block, 0, c->stream, (const uint2*)r.cur, (const uint64_t*)r.wcur,
+                           (const uint8_t*)r.flag, (const uint8_t*)r.st, (const uint32_t*)l.rcr, l.counts, (const uint64_t*)sc, n, elen, ecnt,
+                           upr, lwr, r.report);
+        HIP_TRY(hipMemcpyAsync(h, r.report, sizeof(ContigsReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        sync_checked(c);
+        inf.cycle_edges = h->cycle_edges; inf.longest_path = h->longest;
+    }
+    inf.entries = nent;
+
+    // ---- the images (EntryEdgeSet.cc:203-286): SparseArray::Builder(.edges, z, n) ... end(z) with z = 4^(K+1), two
+    // VariableByteArrays of n items, the histogram of the counts, the 40-bit IntegerArray, the header
+    const std::string base = "-entries";
+    const uint32_t ubits = 2 * c->k + 2;
+    const uint64_t zlo = ubits < 64 ? (1ULL << ubits) : 0, zhi = ubits >= 64 ? (1ULL << (ubits - 64)) : 0;
+    emit_sparse_array<K>(c, ekeys, nent, zlo, zhi, nent, zlo, zhi, base + ".edges");
+    uint64_t lines = 0;
+    emit_counts(c, ecnt, nent, nent, base + ".counts", base + ".counts-hist.txt", &lines);
+    emit_counts(c, elen, nent, nent, base + ".lengths", std::string());
+    inf.hist_size = lines;
+    {
+        std::vector<IaCol> cols;                          // RankBits = 40 (EntryEdgeSet.hh:41): ".upr" u8, ".lwr" u32
+        ia_layout(40, base + ".ends", 0, cols);
+        const uint8_t* img[2] = {upr, (const uint8_t*)lwr};
+        for (size_t i = 0; i < cols.size() && i < 2; ++i)
+        {
+            OutFile f; f.suffix = cols[i].suffix; f.size = nent * cols[i].bytes; f.dev = img[i];
+            c->files.push_back(std::move(f));
+        }
+    }
+    const uint64_t hdr[2] = {2011041901ULL, c->k};
+    add_host_file(c, base + ".header", hdr, sizeof hdr);
+    HIP_TRY(hipEventRecord(ev.e[4], c->stream));
+    sync_checked(c);
+    float* ms[4] = {&inf.ms_link, &inf.ms_rank, &inf.ms_paths, &inf.ms_emit};
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    *out = inf;
+}
+
+void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
+{
+    c->files.clear();
+    if (c->words == 1) entries_build<Key1>(c, out); else entries_build<Key2>(c, out);
+}

@@ -81,26 +81,33 @@ __global__ __launch_bounds__(kTB) void contigs_mark_kernel(const uint32_t* __res
 
 // First ranking launch: every edge follows at most `steps` predecessor pointers.  pair = (ancestor, distance); an
 // edge whose ancestor is a start is resolved.  `cur` gets every pair, `oth` the resolved ones (they are final).
+// WEIGHTED (build-entry-edge-set) carries a u64 beside every pair: the multiplicities of the edge and of the d - 1
+// edges between it and its ancestor, the ancestor itself left out.  Unweighted, counts / wcur / woth are null.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kTB) void contigs_walk_kernel(const uint32_t* __restrict__ pred, const uint8_t* __restrict__ flag,
-                                                           uint32_t n, uint32_t steps, uint2* __restrict__ cur,
-                                                           uint2* __restrict__ oth, uint8_t* __restrict__ st,
-                                                           ContigsReport* __restrict__ rep)
+                                                           const uint32_t* __restrict__ counts, uint32_t n, uint32_t steps,
+                                                           uint2* __restrict__ cur, uint2* __restrict__ oth,
+                                                           uint64_t* __restrict__ wcur, uint64_t* __restrict__ woth,
+                                                           uint8_t* __restrict__ st, ContigsReport* __restrict__ rep)
 {
     uint32_t open = 0;
     for (uint64_t i64 = (uint64_t)blockIdx.x * kTB + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * kTB)
     {
         const uint32_t j = (uint32_t)i64;
         uint32_t p = j, d = 0;
+        uint64_t w = 0;
         bool done = flag[j] & kCtgStart;
         while (!done && d < steps)
         {
+            if constexpr (WEIGHTED) w += counts[p];
             p = pred[p];
             ++d;
             done = flag[p] & kCtgStart;
         }
         const uint2 v = make_uint2(p, d);
         cur[j] = v;
-        if (done) oth[j] = v; else ++open;
+        if constexpr (WEIGHTED) wcur[j] = w;
+        if (done) { oth[j] = v; if constexpr (WEIGHTED) woth[j] = w; } else ++open;
         st[j] = done ? kCtgDone : kCtgOpen;
     }
     const unsigned long long tot = ctg_wave_sum(open);
@@ -108,10 +115,13 @@ __global__ __launch_bounds__(kTB) void contigs_walk_kernel(const uint32_t* __res
 }
 
 // One doubling round: (a, d) of an open edge becomes (ancestor of a, d + distance of a), read from the pairs of
-// the round before.  An edge resolved in the round before is copied once more, so that both arrays hold it.
+// the round before (WEIGHTED: and w[j] += w[a]).  An edge resolved in the round before is copied once more, so that
+// both arrays hold it.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kTB) void contigs_double_kernel(const uint2* __restrict__ in, uint2* __restrict__ out,
                                                              const uint8_t* __restrict__ flag, uint8_t* __restrict__ st,
-                                                             uint32_t n, ContigsReport* __restrict__ rep)
+                                                             uint32_t n, ContigsReport* __restrict__ rep,
+                                                             const uint64_t* __restrict__ win, uint64_t* __restrict__ wout)
 {
     uint32_t fresh = 0;
     for (uint64_t i64 = (uint64_t)blockIdx.x * kTB + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * kTB)
@@ -120,9 +130,12 @@ __global__ __launch_bounds__(kTB) void contigs_double_kernel(const uint2* __rest
         const uint8_t s = st[j];
         if (s == kCtgDone) continue;
         const uint2 v = in[j];
-        if (s == kCtgNew) { out[j] = v; st[j] = kCtgDone; continue; }
+        uint64_t w;
+        if constexpr (WEIGHTED) w = win[j];
+        if (s == kCtgNew) { out[j] = v; if constexpr (WEIGHTED) wout[j] = w; st[j] = kCtgDone; continue; }
         const uint2 a = in[v.x];
         out[j] = make_uint2(a.x, v.y + a.y);
+        if constexpr (WEIGHTED) wout[j] = w + win[v.x];
         if (flag[a.x] & kCtgStart) { st[j] = kCtgNew; ++fresh; }
     }
     const unsigned long long tot = ctg_wave_sum(fresh);

@@ -4,17 +4,13 @@
 //
 // What it replaces: EntryEdgeSet::build (EntryEdgeSet.cc:154-287) -- per entry edge a Graph::linearPath walk
 // (Graph.tcc:19-46) that asks the Elias-Fano index for every step, then a second pass of rank(rc(end)) per entry.
-// Here the link pass of kernels_tips.hpp (rcr, nxt, info) and contigs_mark_kernel (flag, pred) give the lists; the
-// ranking is the one of kernels_contigs.hpp with a u64 weight carried next to the distance:
-//
-//   pair[j] = (a, d)   a is d predecessor pointers behind j
-//   w[j]               the multiplicities of j and of the d - 1 edges between j and a (a itself left out)
-//
-// so a doubling round is pair[j] = (pair[a].a, d + pair[a].d), w[j] += w[a], and the last edge e of a path knows the
-// whole path once it is resolved: start = a, len = d + 1, sum = w[e] + counts[a].  No edge is ordered by (path,
-// position) and no address takes one atomic per edge of a long path.  A prefix sum over the start flags numbers the
-// entries; the last edge of every path then writes the path's record where its start goes, and
-// ends = prefix[rcr[e]]: rc(e) leaves a node that is not one-in-one-out exactly when e has no successor.
+// Here the link pass of kernels_tips.hpp (rcr, nxt, info) and contigs_mark_kernel (flag, pred) give the lists, and the
+// ranking is the WEIGHTED instantiation of contigs_walk_kernel / contigs_double_kernel (kernels_contigs.hpp): the last
+// edge e of a path, once resolved, holds pair[e] = (a, d) and w[e], and knows the whole path: start = a, len = d + 1,
+// sum = w[e] + counts[a].  No edge is ordered by (path, position) and no address takes one atomic per edge of a long
+// path.  A prefix sum over the start flags numbers the entries; the last edge of every path then writes the path's
+// record where its start goes, and ends = prefix[rcr[e]]: rc(e) leaves a node that is not one-in-one-out exactly when
+// e has no successor.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,61 +21,6 @@
 #include "kernels_contigs.hpp"
 
 namespace goss {
-
-// First ranking launch (contigs_walk_kernel with the weight): at most `steps` predecessor pointers per edge.
-__global__ __launch_bounds__(kTB) void entries_walk_kernel(const uint32_t* __restrict__ pred, const uint8_t* __restrict__ flag,
-                                                           const uint32_t* __restrict__ counts, uint32_t n, uint32_t steps,
-                                                           uint2* __restrict__ cur, uint2* __restrict__ oth,
-                                                           uint64_t* __restrict__ wcur, uint64_t* __restrict__ woth,
-                                                           uint8_t* __restrict__ st, ContigsReport* __restrict__ rep)
-{
-    uint32_t open = 0;
-    for (uint64_t i64 = (uint64_t)blockIdx.x * kTB + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * kTB)
-    {
-        const uint32_t j = (uint32_t)i64;
-        uint32_t p = j, d = 0;
-        uint64_t w = 0;
-        bool done = flag[j] & kCtgStart;
-        while (!done && d < steps)
-        {
-            w += counts[p];
-            p = pred[p];
-            ++d;
-            done = flag[p] & kCtgStart;
-        }
-        const uint2 v = make_uint2(p, d);
-        cur[j] = v;
-        wcur[j] = w;
-        if (done) { oth[j] = v; woth[j] = w; } else ++open;
-        st[j] = done ? kCtgDone : kCtgOpen;
-    }
-    const unsigned long long tot = ctg_wave_sum(open);
-    if (lane_id() == 0 && tot) atomicAdd(&rep->open, tot);
-}
-
-// One doubling round (contigs_double_kernel with the weight).
-__global__ __launch_bounds__(kTB) void entries_double_kernel(const uint2* __restrict__ in, uint2* __restrict__ out,
-                                                             const uint64_t* __restrict__ win, uint64_t* __restrict__ wout,
-                                                             const uint8_t* __restrict__ flag, uint8_t* __restrict__ st,
-                                                             uint32_t n, ContigsReport* __restrict__ rep)
-{
-    uint32_t fresh = 0;
-    for (uint64_t i64 = (uint64_t)blockIdx.x * kTB + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * kTB)
-    {
-        const uint32_t j = (uint32_t)i64;
-        const uint8_t s = st[j];
-        if (s == kCtgDone) continue;
-        const uint2 v = in[j];
-        const uint64_t w = win[j];
-        if (s == kCtgNew) { out[j] = v; wout[j] = w; st[j] = kCtgDone; continue; }
-        const uint2 a = in[v.x];
-        out[j] = make_uint2(a.x, v.y + a.y);
-        wout[j] = w + win[v.x];
-        if (flag[a.x] & kCtgStart) { st[j] = kCtgNew; ++fresh; }
-    }
-    const unsigned long long tot = ctg_wave_sum(fresh);
-    if (lane_id() == 0 && tot) atomicAdd(&rep->resolved, tot);
-}
 
 // sc[i] = 1 for an entry edge: one scan numbers the entries (sc[n] becomes their number).
 __global__ __launch_bounds__(kTB) void entries_flags_kernel(const uint8_t* __restrict__ flag, uint32_t n, uint64_t* __restrict__ sc)

@@ -11,10 +11,12 @@ from bisect import bisect_left
 import numpy as np
 import pytest
 
+import contigs_model as cm
 import entries_model as em
 import gossamer_amd as g
 import tips_cases
 import tips_model as tm
+from gossamer_amd import binding
 
 pytestmark = pytest.mark.gpu
 
@@ -374,6 +376,76 @@ def test_refusals(oracle):
         assert ctx.files() == {}
         assert current(ctx) == (be, bc)
         assert ctx.lint()["missing_rc"] == 1
+
+
+def _held_segments_match(ctx, info, edges, counts, K):
+    """the segments the context holds equal the model's, by table and by text"""
+    segs, minfo = cm.linear_segments(edges, counts, K)
+    table = ctx.segments_table(0, info["segments"])
+    text = ctx.segments_text(0, info["text_bytes"])
+    assert info["segments"] == len(table) == len(segs) and len(segs) > 0
+    at = 0
+    for row, s in zip(table, segs):
+        want = cm.body(s.bases, True).encode()
+        flags = (binding.SEGMENT_INCLUDE_FIRST if s.include_fst else 0) | (binding.SEGMENT_INCLUDE_LAST if s.include_lst else 0)
+        got = tuple(int(row[f]) for f in ("first_rank", "edges", "min", "max", "s", "s2", "len", "end_rank", "text_offset", "text_bytes"))
+        assert got == (s.first_rank, s.edges, s.min, s.max, s.s, s.s2, s.len, s.end_rank, at, len(want)), s.first_rank
+        assert int(row["flags"]) & 3 == flags
+        at += len(want)
+    assert at == len(text) == info["text_bytes"] and text == cm.text_of(segs, True)
+    assert info["paths"] == minfo["starts"] and info["taken_paths"] == minfo["taken"]
+    assert info["longest_path"] == minfo["longest"]
+    assert info["cycle_edges"] == sum(1 for r in range(len(edges)) if not minfo["seen"][r])
+
+
+def _two_word_graph(K):
+    """a path with a weak spur that ends in its middle (a tip), and a ring: starts, a successor chain, cycle edges"""
+    rng = random.Random(11)
+    rnd = lambda m: "".join(rng.choice("ACGT") for _ in range(m))
+    main, ring = rnd(K + 60), rnd(50)
+    spur = rnd(5) + "ACGT"[("ACGT".index(main[19]) + 1) % 4] + main[20:20 + K]       # (leaves the path's own edge alone)
+    return graph_with_counts([(main, 9, 9), (spur, 2, 2), (ring + ring[:K], 4, 4)], K)
+
+
+@pytest.mark.parametrize("K", [15, 33])
+def test_one_held_result(oracle, K):
+    """Every transition of the context's one held result, for one-word and two-word keys: entries held -> segments take
+    their place -> an entry edge set built and given back -> prune-tips -> segments -> an entry edge set.  Every result
+    against its model on the graph as it is then; the file list is empty exactly when no entry edge set is held."""
+    edges, counts = tips_cases.combined_graph(K)[:2] if K == 15 else _two_word_graph(K)
+    pe, pc, prep = tm.prune(edges, counts, K, 1)[0]
+    assert 0 < len(pe) < len(edges)
+    with loaded(oracle, edges, counts, K) as ctx:
+        # 1: entries_build holds the images
+        model, want = em.expected(oracle, edges, counts, K)
+        info = ctx.entries_build()
+        assert info["entries"] == len(model["starts"]) > 0 and info["cycle_edges"] == model["cycle_edges"]
+        same_files(ctx.files(), want)
+        assert _status(lambda: ctx.segments_table(0, 0))[0] == -5
+        # 2: segments_build takes their place
+        sinfo = ctx.segments_build()
+        assert ctx.files() == {}
+        _held_segments_match(ctx, sinfo, edges, counts, K)
+        assert ctx.files() == {}
+        # 3: entry_edge_set builds over the held segments and gives its own images back
+        check_against_model(oracle, ctx, edges, counts, K, model, want)
+        assert ctx.files() == {}
+        assert _status(lambda: ctx.segments_table(0, 0))[0] == -5
+        assert current(ctx) == (edges, counts)
+        # 4: prune_tips changes the result
+        reps = ctx.prune_tips(1)
+        assert ctx.files() == {}
+        assert current(ctx) == (pe, pc)
+        assert reps[0]["tips"] == prep["tips"] > 0 and reps[0]["edges_after"] == len(pe)
+        # 5: segments of the pruned graph, held
+        sinfo = ctx.segments_build()
+        _held_segments_match(ctx, sinfo, pe, pc, K)
+        assert ctx.files() == {}
+        # 6: ... and its entry edge set
+        check_against_model(oracle, ctx, pe, pc, K)
+        assert ctx.files() == {}
+        assert _status(lambda: ctx.segments_table(0, 0))[0] == -5
+        assert current(ctx) == (pe, pc)
 
 
 def test_out_of_memory(oracle):

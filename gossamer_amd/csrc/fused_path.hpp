@@ -687,6 +687,12 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
     const uint32_t r32_regions = form.r32_regions(), r32_bits = form.r32_bits, r32_split = form.r32_split, rbits32 = form.rbits32;
     const uint32_t sqbit32 = c->len - 1;
     const bool narrow = form.narrow, squeeze = form.squeeze;
+    // The sub-regions hold the remainders' images (goss_words.hpp: the counting kernel's mix, done here where the issue slots
+    // are idle) unless a third level follows, which splits on the remainder's top bits and must keep key order.
+    const bool image = r32_split == 0;
+    // (both levels' kernels take the squeeze form's field and digit from goss_words.hpp, which is made for this one shape)
+    if (squeeze && (rbits32 != kNarrowSqRbits || r32_bits != kNarrowSqDigitBits))
+        throw StatusError{GOSS_ERR_HIP, "fused path: the squeeze form with other than 33-bit remainders under nine second-level bits"};
     SubTable32* dsub = (SubTable32*)c->arena.temp(sizeof(SubTable32));
     unsigned long long* cur2 = (unsigned long long*)c->arena.temp((uint64_t)r32_regions * 4);     // pairs of 32-bit cursors
     uint64_t* seg_beg = (uint64_t*)c->arena.temp((uint64_t)r32_regions * 8);
@@ -708,15 +714,17 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
     {
         PhaseTimer t(c, GOSS_T_SCATTER, n);
         const dim3 g2((uint32_t)((tiles + 7) / 8 * 8));
-#define GOSS_LAUNCH_S32N(SQ, B2, NRW)                                                                                    \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(subpart32_kernel<SQ, B2, NRW>), g2, dim3(kTB), 0, c->stream, (const Key1*)ka, (uint32_t*)kb, rbits32, \
+#define GOSS_LAUNCH_S32I(SQ, B2, NRW, IMG)                                                                               \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(subpart32_kernel<SQ, B2, NRW, IMG>), g2, dim3(kTB), 0, c->stream, (const Key1*)ka, (uint32_t*)kb, rbits32, \
                        sqbit32, cur2, (const Tile32*)tdesc, (uint32_t)tiles, (const SubTable32*)dsub, lb.ctl)
+#define GOSS_LAUNCH_S32N(SQ, B2, NRW) do { if (image) GOSS_LAUNCH_S32I(SQ, B2, NRW, true); else GOSS_LAUNCH_S32I(SQ, B2, NRW, false); } while (0)
 #define GOSS_LAUNCH_S32(SQ, B2) do { if (narrow) GOSS_LAUNCH_S32N(SQ, B2, true); else GOSS_LAUNCH_S32N(SQ, B2, false); } while (0)
         if (squeeze) GOSS_LAUNCH_S32(true, 9);          // (only the 9-bit form of an odd k-mer set needs the squeeze)
         else if (r32_bits == 9) GOSS_LAUNCH_S32(false, 9);
         else GOSS_LAUNCH_S32(false, 10);
 #undef GOSS_LAUNCH_S32
 #undef GOSS_LAUNCH_S32N
+#undef GOSS_LAUNCH_S32I
         t.stop();
     }
     hipLaunchKernelGGL(sub_bounds32_kernel, dim3(r32_regions / 256), dim3(256), 0, c->stream, (const SubTable32*)dsub,
@@ -750,7 +758,7 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
     int rc;
     for (;;)
     {
-        rc = segment_reduce32(c, rems, spare32, n, r, seg_beg, seg_end, form.r32_slots, squeeze, rbits32, sqbit32, nseg32, r32_split);
+        rc = segment_reduce32(c, rems, spare32, n, r, seg_beg, seg_end, form.r32_slots, squeeze, image, rbits32, sqbit32, nseg32, r32_split);
         if (rc != 1 || form.r32_slots >= 16384 || c->rem32_slots) break;
         // the remainders are still in their sub-regions: only the counting is redone, in the next larger table
         c->segment_retries++;

@@ -1190,10 +1190,11 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
 }
 
 // The same for the 32-bit-remainder form (subpart32_kernel's output): nseg = 2^17 .. 2^20 segments of u32 remainders, counted by
-// seg_hash_reduce32b_kernel in tables of `slots` slots; `spare` (n one-word keys) is the staging area.
+// seg_hash_reduce32b_kernel in tables of `slots` slots; `spare` (n one-word keys) is the staging area.  `image`: the
+// sub-regions hold the images of the remainders (goss_words.hpp), as the second level writes them when no third level follows.
 // Returns 0, 1 (a table overflowed) or 2 (staging area too small) like segment_reduce.
 int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_t n, Run* out, const uint64_t* seg_beg,
-                     const uint64_t* seg_end, int slots, bool squeeze, uint32_t rbits, uint32_t sqbit, uint32_t nseg, uint32_t split_bits)
+                     const uint64_t* seg_end, int slots, bool squeeze, bool image, uint32_t rbits, uint32_t sqbit, uint32_t nseg, uint32_t split_bits)
 {
     uint64_t mark = c->arena.mark();
     PhaseTimer t(c, GOSS_T_REDUCE, n);
@@ -1207,15 +1208,17 @@ int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_
     SegOut hso{};
     hso.stage_cap = cap;
     HIP_TRY(hipMemcpyAsync(so, &hso, sizeof(SegOut), hipMemcpyHostToDevice, c->stream));
-#define GOSS_LAUNCH_R32(SLOTS, SQ)                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_hash_reduce32b_kernel<SLOTS, SQ>), unit_grid(nseg), dim3(SLOTS <= 4096 ? kTB : SLOTS / 4096 * kTB), 0, c->stream, rems, seg_beg, \
+#define GOSS_LAUNCH_R32I(SLOTS, SQ, IMG)                                                                                 \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_hash_reduce32b_kernel<SLOTS, SQ, IMG>), unit_grid(nseg), dim3(SLOTS <= 4096 ? kTB : SLOTS / 4096 * kTB), 0, c->stream, rems, seg_beg, \
                        seg_end, so, seg_pos, seg_cnt, stage_keys, stage_counts, rbits, sqbit, split_bits)
+#define GOSS_LAUNCH_R32(SLOTS, SQ) do { if (image) GOSS_LAUNCH_R32I(SLOTS, SQ, true); else GOSS_LAUNCH_R32I(SLOTS, SQ, false); } while (0)
     // (buckets of four remainders, home bucket only in the fast path)
     if (slots == 2048) { if (squeeze) GOSS_LAUNCH_R32(2048, true); else GOSS_LAUNCH_R32(2048, false); }
     else if (slots == 8192) { if (squeeze) GOSS_LAUNCH_R32(8192, true); else GOSS_LAUNCH_R32(8192, false); }
     else if (slots == 16384) { if (squeeze) GOSS_LAUNCH_R32(16384, true); else GOSS_LAUNCH_R32(16384, false); }
     else { if (squeeze) GOSS_LAUNCH_R32(4096, true); else GOSS_LAUNCH_R32(4096, false); }
 #undef GOSS_LAUNCH_R32
+#undef GOSS_LAUNCH_R32I
     check_launch("32-bit segment counting kernel");
     SegOut* h = (SegOut*)c->h_pinned;
     HIP_TRY(hipMemcpyAsync(h, so, sizeof(SegOut), hipMemcpyDeviceToHost, c->stream));
@@ -1232,13 +1235,15 @@ int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_
         const int rc = count_overflowed_units<Key1>(c, nseg, seg_beg, seg_end, seg_pos, seg_cnt, &hs, stage_keys, stage_counts,
             [&](uint32_t u, uint64_t first, uint64_t cnt_u, Key1* dst) {
                 const uint64_t prefix = (uint64_t)(u >> split_bits) << rbits;          // (as the counting kernel's write-out)
-                if (squeeze)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(expand_rem32_kernel<true>), dim3(grid_for(cnt_u, kTB)), dim3(kTB), 0, c->stream, rems + first, cnt_u, prefix, sqbit, dst);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(expand_rem32_kernel<false>), dim3(grid_for(cnt_u, kTB)), dim3(kTB), 0, c->stream, rems + first, cnt_u, prefix, sqbit, dst);
+#define GOSS_LAUNCH_X32(SQ, IMG)                                                                                         \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(expand_rem32_kernel<SQ, IMG>), dim3(grid_for(cnt_u, kTB)), dim3(kTB), 0, c->stream, rems + first, cnt_u, prefix, sqbit, dst)
+                if (squeeze) { if (image) GOSS_LAUNCH_X32(true, true); else GOSS_LAUNCH_X32(true, false); }
+                else { if (image) GOSS_LAUNCH_X32(false, true); else GOSS_LAUNCH_X32(false, false); }
+#undef GOSS_LAUNCH_X32
             },
             [&](uint32_t u) -> Key1 {
                 // the unit's smallest key: its segment's prefix, and the unit's number in the top split_bits of the remainder
+                // (a plain remainder put together here, nothing read from a sub-region: images come with split_bits = 0)
                 const uint32_t rem_bits = rbits - (squeeze ? 1u : 0u);
                 const uint32_t sub = split_bits ? (u & ((1u << split_bits) - 1u)) << (rem_bits - split_bits) : 0u;
                 const uint64_t low = squeeze ? rem32_unpack<true>(sub, sqbit) : rem32_unpack<false>(sub, sqbit);

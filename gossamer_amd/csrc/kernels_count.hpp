@@ -63,12 +63,12 @@ struct SegOut {
 constexpr unsigned long long kSegOverflowed = ~0ULL;
 
 // the keys of an overflowed unit as full keys: 32-bit remainders (subpart32_kernel's output) / 12-byte records
-template <bool SQ>
+template <bool SQ, bool IMG = false>
 __global__ __launch_bounds__(kTB) void expand_rem32_kernel(const uint32_t* __restrict__ rems, uint64_t n, uint64_t prefix, uint32_t sqbit,
                                                            Key1* __restrict__ out)
 {
     const uint64_t i = (uint64_t)blockIdx.x * kTB + threadIdx.x;
-    if (i < n) out[i].lo = prefix | rem32_unpack<SQ>(rems[i], sqbit);
+    if (i < n) out[i].lo = prefix | rem32_unpack<SQ>(IMG ? r32_unimage(rems[i]) : rems[i], sqbit);
 }
 __global__ __launch_bounds__(kTB) void expand_rem96_kernel(const Rem96* __restrict__ recs, uint64_t n, uint64_t seg, uint32_t rem_bits,
                                                            Key2* __restrict__ out)
@@ -603,17 +603,26 @@ __global__ __launch_bounds__(kSegBigThreads) void seg_hash_reduce_shared_kernel(
 // that follow it.  A slot is claimed by a 32-bit CAS on its key word (marker -> key); counts are only ever added to
 // (32-bit LDS atomic).
 //
-// Every 32-bit pattern is a remainder, so "empty" cannot be a key value -- but it can be a value that never MATCHES:
-// the empty slots of bucket b hold the key E_b whose home is b ^ 1 and whose second bucket is b ^ 2.  The fast path
-// compares a key only with the slots of its home bucket, and a key that is not at home only with those of its second,
-// so neither can take an empty slot for its key and neither needs a look at the counts; the slow path's chain can reach
-// b with that very key, and skips the bucket.
+// What a sub-region holds (IMG) is not the remainder but its IMAGE (goss_words.hpp: r32_image, a bijection of the 32-bit
+// words -- the mix, turned so that the home bucket's bits lie at bits 4 and up): subpart32_kernel, which waits for
+// memory, mixes; this kernel, which is bound by what it issues, takes the byte offset of the home bucket with ONE `and`
+// and stores and compares the images as they come.  Home and second come from two 12-bit fields of the word that share
+// no bit, of which a table takes as many bits as it has buckets: the word does not depend on the table's size, and a
+// segment that overflows is recounted from the same sub-region in the next larger table.  Only the ordering at the end
+// turns the occupied slots' images back into remainders (r32_unimage, once per slot).  Without IMG -- the forms with a
+// third level, which splits on the remainder's top bits -- the words are plain remainders and the mix is computed here.
+//
+// Every 32-bit pattern is a remainder, and so every 32-bit pattern is a stored word, image or not: "empty" cannot be a
+// word's value -- but it can be a value that never MATCHES: the empty slots of bucket b hold the word E_b whose home is
+// b ^ 1 and whose second bucket is b ^ 2 (of images: those two fields put together, r32_image_marker; of plain
+// remainders: the un-mixed value with those fields).  The fast path compares a word only with the slots of its home
+// bucket, and a word that is not at home only with those of its second, so neither can take an empty slot for its
+// word and neither needs a look at the counts: a word that equals E_b is never looked for in b, because b is neither its
+// home (b ^ 1) nor its second (b ^ 2).  The slow path's chain can reach b with that very word, and skips the bucket.
 // The remainders are loaded four per lane (16 bytes); a sub-region starts on a 16-byte boundary and its capacity is a
 // multiple of four, so the last vector may be read whole.  The table is a quarter (SLOTS = 2048: 16 KB) or half (4096)
 // of the 8-byte form's, the keys half the bytes.
-constexpr uint32_t kR32Mul = 0x9E3779B1u, kR32MulInv = 0x0E8B2F51u;          // kR32Mul * kR32MulInv = 1 mod 2^32
-__host__ __device__ __forceinline__ uint32_t r32_mix(uint32_t k) { return (k ^ (k >> 15)) * kR32Mul; }
-__host__ __device__ __forceinline__ uint32_t r32_unmix(uint32_t f) { const uint32_t y = f * kR32MulInv; return y ^ (y >> 15) ^ (y >> 30); }
+// (r32_mix / r32_unmix, the image and its home, second and marker: goss_words.hpp)
 
 // Which of a bucket's four slots holds the key: the byte offset of the slot (0, 4, 8, 12), or 16 for none.  Four compares
 // into four scalar masks, then four selects: written out because the compiler runs every compare and its select through
@@ -653,8 +662,8 @@ __device__ __forceinline__ void r32b_pick4(uint32_t (&t)[4], const uint32_t (&of
 }
 
 // The counting kernel.  These kernels are bound by what they issue, not by what they read (profiles/r04), and their LDS
-// pipe is 70-85 % busy (profiles/r05/SUMMARY.md), so the fast path is as short as it gets: mix, ONE 16-byte read of the
-// home bucket, four compare-selects for the offset of the count word (or of a word of the lane's own behind the table,
+// pipe is 70-85 % busy (profiles/r05/SUMMARY.md), so the fast path is as short as it gets: the bucket's offset (one `and`
+// of an image; mix, shift, shift of a plain remainder), ONE 16-byte read of the home bucket, four compare-selects for the offset of the count word (or of a word of the lane's own behind the table,
 // for a miss), one unconditional add.  A bucket shows a key four candidates, so few keys live outside their home bucket
 // (load 0.19: 0.13 % of them; the pair layout of rounds 3-4, two candidates a bucket and two buckets read per key,
 // had 1.8 % and 51 vector instructions and three LDS operations per key).  A key that is not at home (that per-mille,
@@ -668,7 +677,7 @@ __device__ __forceinline__ void r32b_pick4(uint32_t (&t)[4], const uint32_t (&of
 // the same 16 waves per CU and the same 16 slots per thread in the ordering as the 4 096-slot table's.
 template <int SLOTS> struct R32bCfg { static constexpr int kThreads = SLOTS <= 4096 ? kTB : SLOTS == 8192 ? 2 * kTB : 4 * kTB;
                                       static constexpr int kOcc = SLOTS == 2048 ? 5 : SLOTS == 4096 ? 4 : SLOTS == 8192 ? 2 : 1; };
-template <int SLOTS, bool SQ>
+template <int SLOTS, bool SQ, bool IMG = false>
 __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) void seg_hash_reduce32b_kernel(const uint32_t* __restrict__ rems, const uint64_t* __restrict__ seg_off,
                                                                 const uint64_t* __restrict__ seg_end, SegOut* __restrict__ so,
                                                                 uint64_t* __restrict__ seg_pos, uint64_t* __restrict__ seg_cnt,
@@ -711,8 +720,8 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
     const lds_bytes tb = (lds_bytes)tab;
     uint32_t* const tkey = reinterpret_cast<uint32_t*>(tab);
     uint32_t* const tcnt = tkey + SLOTS;
-    // (f of the marker: home b ^ 1, odd field 3 -> second bucket b ^ 2)
-    auto marker = [](uint32_t bkt) -> uint32_t { return r32_unmix(((bkt ^ 1u) << (32 - BB)) | (3u << (32 - 2 * BB))); };
+    // (the marker: home b ^ 1, odd field 3 -> second bucket b ^ 2.  Of images it is two fields put together)
+    auto marker = [](uint32_t bkt) -> uint32_t { return IMG ? r32_image_marker(bkt) : r32_plain_marker(bkt, BB); };
     for (uint32_t i = tid; i < NB; i += NT)
     {
         const uint32_t m = marker(i);
@@ -726,8 +735,10 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
 
     lds_vu32 vovf = (lds_vu32)&ovf;
     const uint32_t dummy = 8u * (uint32_t)SLOTS + 4u * (tid & 63u);          // the lane's own word behind the table
-    auto home_of = [](uint32_t f) -> uint32_t { return f >> (32 - BB); };
-    auto second_of = [](uint32_t f, uint32_t h) -> uint32_t { return h ^ (((f >> (32 - 2 * BB)) & (NB - 1u)) | 1u); };
+    // f: what home and second are taken from -- the word itself when the sub-regions hold images, else its mix
+    auto f_of = [](uint32_t word) -> uint32_t { return IMG ? word : r32_mix(word); };
+    auto home16_of = [](uint32_t f) -> uint32_t { return IMG ? r32_image_home_bytes(f, NB) : r32_plain_home(f, BB) << 4; };          // byte offset of the home bucket
+    auto second_of = [](uint32_t f, uint32_t h) -> uint32_t { return IMG ? r32_image_second(f, h, NB) : r32_plain_second(f, h, BB); };
 
     constexpr int kVec = GOSS_R32B_VEC;                      // 16-byte loads in flight per lane
     const uint32_t head = (uint32_t)(b & 3ULL);
@@ -766,8 +777,8 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
 #pragma unroll
             for (int j = 0; j < 4; ++j)
             {
-                f[j] = r32_mix(kk[j]);
-                a1[j] = home_of(f[j]) << 4;
+                f[j] = f_of(kk[j]);
+                a1[j] = home16_of(f[j]);
                 q[j] = *(lds_bucket_plain)(tb + a1[j]);
             }
 #pragma unroll
@@ -822,8 +833,8 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
                     const uint32_t j = __ffs(pd) - 1;
                     pd &= pd - 1;
                     key = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-                    f = r32_mix(key);
-                    bk = home_of(f);
+                    f = f_of(key);
+                    bk = home16_of(f) >> 4;
                     st = 0;
                     busy = true;
                 }
@@ -902,7 +913,12 @@ __global__ __launch_bounds__(R32bCfg<SLOTS>::kThreads, R32bCfg<SLOTS>::kOcc) voi
     __shared__ uint32_t big;
     unsigned long long ck[kPer];              // count << 32 | remainder
 #pragma unroll
-    for (int j = 0; j < kPer; ++j) ck[j] = ((unsigned long long)tcnt[tid * kPer + j] << 32) | tkey[tid * kPer + j];
+    for (int j = 0; j < kPer; ++j)
+    {
+        // (the one place where an image is turned back: every slot once, ~1 % of a segment's work)
+        const uint32_t word = tkey[tid * kPer + j];
+        ck[j] = ((unsigned long long)tcnt[tid * kPer + j] << 32) | (IMG ? r32_unimage(word) : word);
+    }
     for (uint32_t i = tid; i < kBins; i += NT) bins[i] = 0;
     if (tid == 0) big = 0;
     __syncthreads();

@@ -8,6 +8,7 @@
 
 #include "goss_key.hpp"
 #include "kernels_common.hpp"
+#include "goss_words.hpp"
 
 namespace goss {
 
@@ -624,7 +625,7 @@ __device__ __forceinline__ uint32_t bit_select(uint32_t mask, uint32_t ones, uin
 // FAST: the 32-bit forms of the window arithmetic and of the digit -- keys of 32 bits or more whose digit lies at bit 34
 // or above (the headline's: len >= 21, digit = the key's top eight bits); the host picks the instantiation.
 // NARROW (round 5): what leaves is not the 8-byte key but what the second level of the 32-bit-remainder form needs of
-// it -- the 32-bit remainder (rem32_pack, kernels_partition.hpp) and the second-level digit (<= 10 bits) -- TWELVE keys
+// it -- the 32-bit remainder (rem32_pack, goss_words.hpp) and the second-level digit (<= 10 bits) -- TWELVE keys
 // to a 64-byte granule instead of eight: a granule is four 16-byte chunks {rem, rem, rem, D}, D = the three digits
 // at bits 0, 10, 20 and, at bits 30-31, how many of the chunk's three keys are keys (pads: an all-zero chunk holds
 // none); slot s = 4 m + c of a granule is field m of chunk c.  5.33 bytes per key written here and read by
@@ -634,6 +635,9 @@ __device__ __forceinline__ uint32_t bit_select(uint32_t mask, uint32_t ones, uin
 // the bucket's thread holds in registers AS A GRANULE (48 + 24 bytes) between tiles and copies to the head of the
 // next piece with six wide LDS writes -- no key is moved one by one and the new keys simply follow (rank + carried).
 // Cursors, blocks and regions keep counting 8-byte slots: a granule is eight of them whatever it holds.
+// The squeeze form (k = 25: 33-bit remainders, nine digit bits) leaves the squeeze to the second level, which has issue
+// slots to spare: the remainder field is the key's low word as it is and the 10-bit digit field the low ten bits of
+// the high word -- key bit 32 with the digit above it (one instruction per key where squeeze and digit took four).
 template <int MODE, int NH, int REPK, bool REC = false, bool FAST = false, bool NARROW = false, bool PACKED = false>
 __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const uint8_t* __restrict__ bases_aligned, uint32_t mis,
                                                             uint64_t nstarts, uint64_t navail, uint32_t len,
@@ -1077,7 +1081,17 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
             {
                 // 32-bit halves, constant shifts: the forward form rolled (the bases it takes in, pre-shifted once:
                 // base i + len - 1 at bits 2 i of nx), the reverse complement by funnel shifts of the complemented words
-                const uint32_t kmhi = (uint32_t)(kmask >> 32);
+                // kLoose: nothing looks at the high word above the key's bits, so they are not cleared -- two instructions
+                // per window.  The readers of the high word in this form (one strand representative by the central base's
+                // bit, narrow output, no histograms) and the bits they take:
+                //   rank_key    the first-level digit, `& 0x3FC` behind its shift: the key's top eight bits;
+                //   put         the second-level digit, a bit field below the first-level digit (ubfe / `& nr_dmask`), or in
+                //               the squeeze form the low ten bits; the remainder takes bit 0 at most (see there);
+                //   the roll    `fhi` is shifted UP into the next window's: what is above the key leaves the register.
+                // The strand is picked from `mid`, not from the key.  REPK 0 / 2 compare or hash whole keys, the forms with
+                // histograms count whole digits of them, the 8-byte form stores them: all those clear the bits.
+                constexpr bool kLoose = MODE == 0 && REPK == 1 && NARROW && NH == 0;
+                [[maybe_unused]] const uint32_t kmhi = (uint32_t)(kmask >> 32);
                 const uint32_t cw0 = ~(uint32_t)blo, cw1 = ~(uint32_t)(blo >> 32), cw2 = ~(uint32_t)bhi;
                 const uint32_t pn = bits - 2;                                  // 30 .. 60
                 const uint32_t nx = (uint32_t)((blo >> pn) | (bhi << (64 - pn)));
@@ -1090,11 +1104,13 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
                     if (i)
                     {
                         const uint32_t nb = (nx >> (2 * i)) & 3u;
-                        fhi = __builtin_amdgcn_alignbit(fhi, flo, 30) & kmhi;
+                        fhi = __builtin_amdgcn_alignbit(fhi, flo, 30);
+                        if constexpr (!kLoose) fhi &= kmhi;
                         flo = (flo << 2) | nb;
                     }
                     const uint32_t rlo = i ? __builtin_amdgcn_alignbit(cw1, cw0, 2 * i) : cw0;
-                    const uint32_t rhi = (i ? __builtin_amdgcn_alignbit(cw2, cw1, 2 * i) : cw1) & kmhi;
+                    uint32_t rhi = i ? __builtin_amdgcn_alignbit(cw2, cw1, 2 * i) : cw1;
+                    if constexpr (!kLoose) rhi &= kmhi;
                     if (MODE == 0 && REPK == 1)
                     {
                         const uint32_t sel = (uint32_t)__builtin_amdgcn_sbfe((int32_t)mid, 2 * i, 1);        // all ones: the reverse complement
@@ -1305,11 +1321,22 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
                     for (int i = 0; i < NK; ++i)
                     {
                         const uint32_t klo = (uint32_t)kreg[i].lo, khi = (uint32_t)(kreg[i].lo >> 32);
-                        uint32_t rem = klo & lomask;
-                        // (the bits above the squeezed one, moved down by one; what leaves the word at the top is the digit's)
-                        if (kSq) rem |= __builtin_amdgcn_alignbit(khi, klo, nr_sqbit + 1u) << nr_sqbit;
-                        const uint32_t dg = kHi ? __builtin_amdgcn_ubfe(khi, nr_rbits - 32u, dbits)
-                                                : (__builtin_amdgcn_alignbit(khi, klo, nr_rbits) & nr_dmask);
+                        uint32_t rem, dg;
+                        if constexpr (kSq && kHi)
+                        {
+                            // the squeeze form (33-bit remainders, nine digit bits: goss_words.hpp): the low word as it is and
+                            // the ten bits above it -- the remainder's top bit under the digit.  The second level squeezes.
+                            rem = klo;
+                            dg = narrow_sq_field(khi);
+                        }
+                        else
+                        {
+                            rem = klo & lomask;
+                            // (the bits above the squeezed one, moved down by one; what leaves the word at the top is the digit's)
+                            if (kSq) rem |= __builtin_amdgcn_alignbit(khi, klo, nr_sqbit + 1u) << nr_sqbit;
+                            dg = kHi ? __builtin_amdgcn_ubfe(khi, nr_rbits - 32u, dbits)
+                                     : (__builtin_amdgcn_alignbit(khi, klo, nr_rbits) & nr_dmask);
+                        }
                         const uint32_t la = tb[i] + (rk[i] << 2);
                         *reinterpret_cast<uint32_t*>(lds_all + la) = rem;
                         *reinterpret_cast<uint16_t*>(lds_all + kDigBase + (la >> 1)) = (uint16_t)dg;

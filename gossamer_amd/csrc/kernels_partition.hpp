@@ -7,6 +7,7 @@
 
 #include "goss_key.hpp"
 #include "kernels_common.hpp"
+#include "goss_words.hpp"
 
 namespace goss {
 
@@ -563,7 +564,10 @@ __global__ __launch_bounds__(kTB) void radix_onesweep_kernel(const K* __restrict
 // 33 bits left, and the strand representative of an odd-length k-mer has one bit that is always clear (bit len - 1,
 // the low bit of its middle base: extract1_part_kernel picks the strand by it), which is squeezed out: 32 bits.
 // This kernel reads 8-byte keys and writes 4-byte remainders; seg_hash_reduce32b_kernel counts those: 12 + 4 bytes per
-// key behind the first level instead of 16 + 8.  Applies while 2 len - 17 - (odd k-mer set ? 1 : 0) <= 32.
+// key behind the first level instead of 16 + 8.  IMG: what is written is the remainder's image (goss_words.hpp: a
+// bijection, the counting kernel's mix turned by 16 bits) -- four instructions per key in a kernel that waits for HBM and
+// leaves most of its issue slots unused, taken from the counting kernel, which has none to spare.  The host asks for
+// images unless a third level follows (subsplit32_kernel splits on the remainder's top bits).  Applies while 2 len - 17 - (odd k-mer set ? 1 : 0) <= 32.
 // Ten bits at the second level (2^18 sub-regions) where nine leave 33 bits and there is no bit to squeeze out (graphs of
 // k = 24, k-mer sets of k = 26 would need twelve: not served).  More distinct keys than the tables of 2^17 / 2^18 segments
 // hold (reads with sequencing errors: every error makes up to k new k-mers) do NOT get more second-level bits -- runs of
@@ -577,20 +581,7 @@ struct SubTable32 {
     uint32_t cap[kSub32RegionsMax];
 };
 
-// low `rbits` bits of a key, bit `sqbit` (always clear) taken out when SQ
-template <bool SQ>
-__host__ __device__ __forceinline__ uint32_t rem32_pack(uint64_t key, uint32_t rbits, uint32_t sqbit)
-{
-    const uint64_t x = key & ((1ULL << rbits) - 1ULL);
-    if (!SQ) return (uint32_t)x;
-    return (uint32_t)(((x >> (sqbit + 1)) << sqbit) | (x & ((1ULL << sqbit) - 1ULL)));
-}
-template <bool SQ>
-__host__ __device__ __forceinline__ uint64_t rem32_unpack(uint32_t r, uint32_t sqbit)
-{
-    if (!SQ) return r;
-    return (((uint64_t)r >> sqbit) << (sqbit + 1)) | ((uint64_t)r & ((1ULL << sqbit) - 1ULL));
-}
+// (rem32_pack / rem32_unpack, the squeeze form's field and the image of a remainder: goss_words.hpp)
 
 // Where the second level's tiles lie: tile t is the (t - tile_first[b])-th run of kTile slots of region b.  Worked out once
 // per tile by this kernel (a binary search) so that a tile's workgroup learns its place with ONE scalar load
@@ -629,7 +620,9 @@ __global__ void tiles32_kernel(const GapTable* __restrict__ gt, Tile32* __restri
 // NARROW (round 5): the regions hold what extract1_part_kernel<.., NARROW> wrote -- 16-byte chunks {remainder, remainder,
 // remainder, D} with the three second-level digits at bits 0, 10, 20 of D and the number of keys the chunk holds at
 // bits 30-31: a lane takes a chunk with one 16-byte load, three keys, and has nothing to pack (5.33 bytes read per
-// key instead of 8).
+// key instead of 8).  In the squeeze form (SQ) the first level has not squeezed: the chunk holds the keys' low words
+// and, as 10-bit fields, the remainder's top bit (key bit 32) under the nine digit bits -- the digit is field >> 1, and
+// the remainder is squeezed here (narrow_sq_rem, goss_words.hpp).
 // Chunks per thread of the narrow form: 10 at nine digit bits (30 keys a thread, 7 680 a tile, 50 KB of LDS: three
 // workgroups per CU), 9 at ten bits (whose 1 024 counters and bases take 4 KB more).  Measured on C2 (round 5, tiles of
 // 5 / 6 / 7 / 8 / 9 / 10 chunks on 5 / 5 / 4 / 3 / 3 / 3 workgroups per CU): 30.9 / 28.8 / 25.8 / 25.1 / 24.1 / 23.6 ms --
@@ -639,12 +632,14 @@ __global__ void tiles32_kernel(const GapTable* __restrict__ gt, Tile32* __restri
 #define GOSS_S32_OCCN 3
 #endif
 template <int B2> struct Sub32N { static constexpr int kChunks = B2 == 9 ? GOSS_S32_CH : GOSS_S32_CH - 1; static constexpr int kTileSlots = kTB * kChunks * 2; };
-template <bool SQ, int B2, bool NARROW = false>
+template <bool SQ, int B2, bool NARROW = false, bool IMG = false>
 __global__ __launch_bounds__(kTB, NARROW ? GOSS_S32_OCCN : GOSS_S32_OCC) void subpart32_kernel(const Key1* __restrict__ keys_in, uint32_t* __restrict__ out,
                                                            uint32_t rbits, uint32_t sqbit, unsigned long long* __restrict__ cursors,
                                                            const Tile32* __restrict__ desc, uint32_t total_tiles,
                                                            const SubTable32* __restrict__ sub, LookbackCtl* __restrict__ ctl)
 {
+    // (the squeeze form is that of 33-bit remainders under nine digit bits: goss_words.hpp's field and digit are made for it)
+    static_assert(!SQ || B2 == (int)kNarrowSqDigitBits, "the squeeze form has nine second-level bits");
     constexpr int kSub32ChunksN = Sub32N<B2>::kChunks;
     constexpr int kItems = NARROW ? 3 * kSub32ChunksN : kSub32Items;
     static_assert(NARROW || kItems <= 32, "one bit of `have` per key");
@@ -672,6 +667,8 @@ __global__ __launch_bounds__(kTB, NARROW ? GOSS_S32_OCCN : GOSS_S32_OCC) void su
 
     // (a workgroup that has just started issues its key loads ahead of the others' ranking and staging: 30.85 -> 30.05 ms)
     __builtin_amdgcn_s_setprio(3);
+    // (the squeeze form's 10-bit field: the digit above the remainder's top bit)
+    [[maybe_unused]] auto field_digit = [](uint32_t field) -> uint32_t { return SQ ? narrow_sq_digit(field) : field & (ND - 1u); };
     Key1 key[NARROW ? 1 : kItems];
     [[maybe_unused]] uint32_t rem[NARROW ? kItems : 1], dw[NARROW ? kSub32ChunksN : 1];
     uint16_t rank[kItems];
@@ -700,7 +697,7 @@ __global__ __launch_bounds__(kTB, NARROW ? GOSS_S32_OCCN : GOSS_S32_OCC) void su
         // (key r of the thread = field r % 3 of its chunk r / 3: a key iff the chunk holds more than r % 3 of them)
 #pragma unroll
         for (int r = 0; r < kItems; ++r)
-            if ((dw[r / 3] >> 30) > (uint32_t)(r % 3)) rank[r] = (uint16_t)atomicAdd(&hist[(dw[r / 3] >> (10 * (r % 3))) & (ND - 1u)], 1u);
+            if ((dw[r / 3] >> 30) > (uint32_t)(r % 3)) rank[r] = (uint16_t)atomicAdd(&hist[field_digit(dw[r / 3] >> (10 * (r % 3)))], 1u);
     }
     else
     {
@@ -782,16 +779,19 @@ __global__ __launch_bounds__(kTB, NARROW ? GOSS_S32_OCCN : GOSS_S32_OCC) void su
         {
             if constexpr (NARROW)
             {
-                const uint32_t d = (dw[r / 3] >> (10 * (r % 3))) & (ND - 1u);
+                const uint32_t field = dw[r / 3] >> (10 * (r % 3));
+                const uint32_t d = field_digit(field);
                 const uint32_t at = hist[d] + rank[r];
-                stage[at] = rem[r];
+                const uint32_t word = SQ ? narrow_sq_rem(rem[r], field, sqbit) : rem[r];
+                stage[at] = IMG ? r32_image(word) : word;
                 sdig[at] = (uint16_t)d;
             }
             else
             {
             const uint32_t d = (uint32_t)(key[r].lo >> rbits) & (ND - 1u);
             const uint32_t at = hist[d] + rank[r];
-            stage[at] = rem32_pack<SQ>(key[r].lo, rbits, sqbit);
+            const uint32_t word = rem32_pack<SQ>(key[r].lo, rbits, sqbit);
+            stage[at] = IMG ? r32_image(word) : word;
             sdig[at] = (uint16_t)d;
             }
         }

@@ -217,6 +217,7 @@ struct goss_gpu_ctx {
     std::vector<Run> runs;
     std::vector<BigMap> big_maps;       // per run that has them: the counts >= 2^32 - 1 (graph mode; marker 0xFFFFFFFF in the run)
     BigMap res_big;                     // ... of the result (its u32 counts hold the value modulo 2^32, as the reference stores it)
+    bool pushed_counts = false;         // a run came in with its counts (goss_gpu_push_run_*): an entry 0xFFFFFFFF of it is that number
     uint64_t windows = 0, keys_total = 0;
     bool finished = false, emitted = false;
     // a group's route-and-exchange round failed half way: what this context had staged may be in records that were
@@ -522,6 +523,31 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
 // the step read (`keys`/`vals` in `nruns` sorted pieces; vals == nullptr: raw keys, each worth 1) plus
 // what the input runs' own big maps hold for the key.  A k-mer set stores no counts: nothing to do.
 constexpr uint32_t kMaxBig = 256;
+// The entries of a run that carry 0xFFFFFFFF: how many there are, and the place and the key (hi, lo) of the first kMaxBig.
+struct Saturated { uint64_t n = 0; std::vector<uint64_t> at; std::vector<std::pair<uint64_t, uint64_t>> key; };
+static Saturated find_saturated(goss_gpu_ctx* c, const void* keys, const uint32_t* counts, uint64_t m)
+{
+    Saturated s;
+    uint64_t mark = c->arena.mark();
+    unsigned long long* found = (unsigned long long*)c->arena.temp((kMaxBig + 1) * 8);
+    HIP_TRY(hipMemsetAsync(found, 0, 8, c->stream));
+    hipLaunchKernelGGL(find_saturated_kernel, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, counts, m, found, kMaxBig);
+    std::vector<unsigned long long> hfound(kMaxBig + 1);
+    HIP_TRY(hipMemcpyAsync(hfound.data(), found, (kMaxBig + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->arena.release(mark);
+    s.n = hfound[0];
+    const uint32_t nq = (uint32_t)std::min<unsigned long long>(hfound[0], kMaxBig);
+    for (uint32_t q = 0; q < nq; ++q)
+    {
+        uint64_t kw[2] = {0, 0};
+        HIP_TRY(hipMemcpy(kw, (const uint8_t*)keys + hfound[1 + q] * c->words * 8, c->words * 8, hipMemcpyDeviceToHost));
+        s.at.push_back(hfound[1 + q]);
+        s.key.emplace_back(c->words == 2 ? kw[1] : 0ULL, kw[0]);
+    }
+    return s;
+}
+
 template <class K>
 void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t* vals, const std::vector<uint64_t>& run_off,
                         const std::vector<int>& in_bigs)
@@ -532,36 +558,33 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!hf[0]) return;
     uint64_t mark = c->arena.mark();
-    unsigned long long* found = (unsigned long long*)c->arena.temp((kMaxBig + 1) * 8);
-    HIP_TRY(hipMemsetAsync(found, 0, 8, c->stream));
-    hipLaunchKernelGGL(find_saturated_kernel, dim3(grid_for(out.m, 256)), dim3(256), 0, c->stream, (const uint32_t*)out.counts, out.m, found, kMaxBig);
-    std::vector<unsigned long long> hfound(kMaxBig + 1);
-    HIP_TRY(hipMemcpyAsync(hfound.data(), found, (kMaxBig + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint32_t nq = (uint32_t)hfound[0];
-    if (nq > kMaxBig) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "more than 256 keys occurred 2^32 times or more"};
+    const Saturated sat = find_saturated(c, out.keys, out.counts, out.m);
+    if (sat.n > kMaxBig) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "more than 256 keys occurred 2^32 times or more"};
     const uint32_t nruns = (uint32_t)run_off.size() - 1;
     if (nruns > 1024) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "a key occurred 2^32 times or more in a merge of more than 1024 runs"};
+    const uint32_t nq = (uint32_t)sat.n;
     if (nq)
     {
+        std::vector<K> hq(nq);
+        for (uint32_t q = 0; q < nq; ++q)
+        {
+            if constexpr (sizeof(K) == 8) hq[q] = K{sat.key[q].second}; else hq[q] = K{sat.key[q].second, sat.key[q].first};
+        }
         K* dq = (K*)c->arena.temp(nq * sizeof(K));
         uint64_t* doff = (uint64_t*)c->arena.temp((nruns + 1) * 8);
         unsigned long long* dsum = (unsigned long long*)c->arena.temp(2 * nq * 8);
-        for (uint32_t q = 0; q < nq; ++q)
-            HIP_TRY(hipMemcpyAsync(dq + q, (const K*)out.keys + hfound[1 + q], sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dq, hq.data(), nq * sizeof(K), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(doff, run_off.data(), (nruns + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemsetAsync(dsum, 0, 2 * nq * 8, c->stream));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(sum_equal_kernel<K>), dim3(nq), dim3(std::max<uint32_t>(64, (nruns + 63) / 64 * 64)), 0, c->stream,
                            keys, vals, (const uint64_t*)doff, nruns, (const K*)dq, nq, dsum, dsum + nq);
-        std::vector<K> hq(nq);
         std::vector<unsigned long long> hs(2 * nq);
-        HIP_TRY(hipMemcpyAsync(hq.data(), dq, nq * sizeof(K), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(hs.data(), dsum, 2 * nq * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         BigMap bm;
         for (uint32_t q = 0; q < nq; ++q)
         {
-            const std::pair<uint64_t, uint64_t> kk(key_hi_word(hq[q]), key_lo_word(hq[q]));
+            const std::pair<uint64_t, uint64_t>& kk = sat.key[q];
             uint64_t exact = hs[q], markers = 0;
             for (int b : in_bigs)
                 if (b >= 0)
@@ -569,7 +592,12 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
                     auto it = c->big_maps[b].find(kk);
                     if (it != c->big_maps[b].end()) { exact += it->second; ++markers; }
                 }
-            if (markers != hs[nq + q]) throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated entry without its exact count"};
+            // an entry 0xFFFFFFFF that no input map accounts for came in with a pushed run (goss_gpu_push_run_*: a graph
+            // read from disk, a caller's own run), and there it is no marker but the multiplicity 2^32 - 1 itself; where no
+            // run was pushed every marker has its map, and one without is a bookkeeping error as before
+            if (markers > hs[nq + q] || (!c->pushed_counts && markers != hs[nq + q]))
+                throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated entry without its exact count"};
+            exact += (hs[nq + q] - markers) * 0xFFFFFFFFULL;
             bm[kk] = exact;
         }
         c->big_maps.push_back(std::move(bm));
@@ -577,6 +605,21 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
     }
     HIP_TRY(hipMemsetAsync(c->d_flags, 0, 4, c->stream));
     c->arena.release(mark);
+}
+
+// A pushed run that reaches the result through no merge (it was the only one): its entries 0xFFFFFFFF are the
+// multiplicity 2^32 - 1 itself, and a graph's result lists every count that large beside the run (goss_gpu_big_counts).
+template <class K>
+void adopt_literal_counts(goss_gpu_ctx* c, Run& r)
+{
+    if (c->mode != GOSS_MODE_GRAPH || r.m == 0 || r.big >= 0) return;
+    const Saturated sat = find_saturated(c, r.keys, r.counts, r.m);
+    if (sat.n > kMaxBig) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "more than 256 keys occurred 2^32 times or more"};
+    if (!sat.n) return;
+    BigMap bm;
+    for (const auto& kk : sat.key) bm[kk] = 0xFFFFFFFFULL;
+    c->big_maps.push_back(std::move(bm));
+    r.big = (int)c->big_maps.size() - 1;
 }
 
 // ---- run compaction ---------------------------------------------------------------------
@@ -3316,7 +3359,12 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
         ensure_arena(c);
         flush_staging(c);
         release_pending(c, true);          // (every asynchronous push has been copied by now: the buffers go back)
+        const bool unmerged = c->runs.size() == 1;          // (a merge resolves its own counts: resolve_big_counts)
         if (c->words == 1) merge_runs<Key1>(c); else merge_runs<Key2>(c);
+        if (unmerged && c->pushed_counts)
+        {
+            if (c->words == 1) adopt_literal_counts<Key1>(c, c->runs[0]); else adopt_literal_counts<Key2>(c, c->runs[0]);
+        }
         if (!c->runs.empty() && c->runs[0].rep)
         {
             if (c->mode == GOSS_MODE_GRAPH)
@@ -3348,28 +3396,23 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
             {
                 c->res_big = c->big_maps[c->runs[0].big];
                 uint64_t mark = c->arena.mark();
-                unsigned long long* found = (unsigned long long*)c->arena.temp((kMaxBig + 1) * 8);
-                HIP_TRY(hipMemsetAsync(found, 0, 8, c->stream));
-                hipLaunchKernelGGL(find_saturated_kernel, dim3(grid_for(c->M, 256)), dim3(256), 0, c->stream, (const uint32_t*)c->res_counts, c->M, found, kMaxBig);
-                std::vector<unsigned long long> hfound(kMaxBig + 1);
-                HIP_TRY(hipMemcpyAsync(hfound.data(), found, (kMaxBig + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                const uint32_t nq = (uint32_t)std::min<unsigned long long>(hfound[0], kMaxBig);
+                const Saturated sat = find_saturated(c, c->res_keys, c->res_counts, c->M);
+                const uint32_t nq = (uint32_t)sat.at.size();
                 std::vector<uint32_t> vals(nq);
                 for (uint32_t q = 0; q < nq; ++q)
                 {
-                    uint64_t kw[2] = {0, 0};
-                    HIP_TRY(hipMemcpy(kw, (const uint8_t*)c->res_keys + hfound[1 + q] * c->words * 8, c->words * 8, hipMemcpyDeviceToHost));
-                    auto it = c->res_big.find(std::make_pair(c->words == 2 ? kw[1] : 0ULL, kw[0]));
+                    auto it = c->res_big.find(sat.key[q]);
                     if (it == c->res_big.end()) throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated result entry without its exact count"};
                     vals[q] = (uint32_t)(it->second & 0xFFFFFFFFULL);
                 }
                 if (nq)
                 {
                     uint32_t* dv = (uint32_t*)c->arena.temp(nq * 4);
+                    unsigned long long* dat = (unsigned long long*)c->arena.temp(nq * 8);
                     HIP_TRY(hipMemcpyAsync(dv, vals.data(), nq * 4, hipMemcpyHostToDevice, c->stream));
+                    HIP_TRY(hipMemcpyAsync(dat, sat.at.data(), nq * 8, hipMemcpyHostToDevice, c->stream));
                     hipLaunchKernelGGL(patch_counts_kernel, dim3(grid_for(nq, 64)), dim3(64), 0, c->stream, c->res_counts,
-                                       (const unsigned long long*)(found + 1), (const uint32_t*)dv, nq);
+                                       (const unsigned long long*)dat, (const uint32_t*)dv, nq);
                     HIP_TRY(hipStreamSynchronize(c->stream));
                 }
                 c->arena.release(mark);
@@ -4219,6 +4262,7 @@ int goss_gpu_reset(goss_gpu_ctx* c)
         c->runs.clear();
         c->big_maps.clear();
         c->res_big.clear();
+        c->pushed_counts = false;
         c->files.clear();
         c->windows = c->keys_total = 0;
         c->space_choice = -1;
@@ -4254,6 +4298,7 @@ int goss_gpu_push_run_device(goss_gpu_ctx* c, const void* d_keys, const uint32_t
         HIP_TRY(hipMemcpyAsync(r.counts, d_counts, m * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->runs.push_back(r);
+        c->pushed_counts = true;
         // keys_total keeps meaning "keys inserted": a run stands for the sum of its counts,
         // which the caller accounts for; windows are not known here.
     });
@@ -4277,6 +4322,7 @@ int goss_gpu_push_run_host(goss_gpu_ctx* c, const uint64_t* keys, const uint32_t
         HIP_TRY(hipMemcpyAsync(r.counts, counts, m * 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->runs.push_back(r);
+        c->pushed_counts = true;
     });
 }
 
@@ -4504,6 +4550,7 @@ int goss_gpu_push_run_sparse(goss_gpu_ctx* c, const goss_gpu_sparse_run* s)
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
         c->runs.push_back(r);
+        c->pushed_counts = true;
     });
 }
 
@@ -4557,6 +4604,7 @@ int goss_gpu_push_run_graph(goss_gpu_ctx* c, const goss_gpu_sparse_run* edges, c
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
         c->runs.push_back(r);
+        c->pushed_counts = true;
     });
 }
 

@@ -35,6 +35,8 @@ SYMBOLS = [
     "goss_gpu_prune_tips",
     "goss_gpu_segments_build", "goss_gpu_segments_table", "goss_gpu_segments_text", "goss_gpu_segments_release",
     "goss_gpu_entries_build", "goss_gpu_entries_release", "goss_gpu_entries_length", "goss_gpu_entries_end_rank",
+    "goss_gpu_components_mark_host", "goss_gpu_components_mark_device", "goss_gpu_components_build", "goss_gpu_components_table",
+    "goss_gpu_components_labels", "goss_gpu_components_keep", "goss_gpu_components_release",
 ]
 
 # every symbol include/goss_gpu_match.h declares (reads against an object)
@@ -79,6 +81,23 @@ ENTRIES_INFO_FIELDS = (("entries", C.c_uint64), ("cycle_edges", C.c_uint64), ("l
 
 class EntriesInfo(C.Structure):
     _fields_ = list(ENTRIES_INFO_FIELDS)
+
+
+# goss_gpu_mark_info, goss_gpu_components_info and goss_gpu_component, in the order of their fields
+MARK_INFO_FIELDS = (("windows", C.c_uint64), ("hits", C.c_uint64), ("marked_total", C.c_uint64), ("ms", C.c_float))
+COMPONENTS_INFO_FIELDS = (("components", C.c_uint64), ("marked_edges", C.c_uint64), ("largest", C.c_uint64), ("launches", C.c_uint32),
+                          ("ms_link", C.c_float), ("ms_label", C.c_float), ("ms_figures", C.c_float))
+COMPONENT_DTYPE = [("s", "<u8"), ("s2", "<u8"), ("edges", "<u8"), ("start", "<u4"), ("min", "<u4"), ("max", "<u4"), ("mirror", "<u4")]
+COMPONENTS_MARKED = 1
+COMPONENT_NONE = 0xFFFFFFFF
+
+
+class MarkInfo(C.Structure):
+    _fields_ = list(MARK_INFO_FIELDS)
+
+
+class ComponentsInfo(C.Structure):
+    _fields_ = list(COMPONENTS_INFO_FIELDS)
 
 
 def format_double(x):
@@ -710,6 +729,52 @@ class Context:
         finally:
             self.entries_release()
         return files, info
+
+    def mark_reads(self, bases):
+        """Between finish and emit, graph mode: mark the edges that the forward (K+1)-windows of the reads in `bases`
+        (bytes, '\\n' between reads) touch (goss_gpu_components_mark_host); the marks add up over the calls and are
+        held until components_release or any call that gives back a held result.  Returns the info dict."""
+        inf = MarkInfo()
+        self._L.goss_gpu_components_mark_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(MarkInfo)]
+        self._check(self._L.goss_gpu_components_mark_host(self._h, bases, len(bases), C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in MARK_INFO_FIELDS}
+
+    def components(self, marked=False):
+        """The connected components of the graph -- of the marked edges with marked=True -- as `goss count-components`
+        numbers them: (info dict, numpy structured array of the table, COMPONENT_DTYPE) with the true figures (the
+        reference's rows count the start edge twice).  The labels and the table stay held for component_labels."""
+        import numpy as np
+        inf = ComponentsInfo()
+        self._L.goss_gpu_components_build.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ComponentsInfo)]
+        self._check(self._L.goss_gpu_components_build(self._h, COMPONENTS_MARKED if marked else 0, C.byref(inf)))
+        table = np.zeros(inf.components, dtype=COMPONENT_DTYPE)
+        self._L.goss_gpu_components_table.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_components_table(self._h, 0, inf.components, table.ctypes.data_as(C.c_void_p)))
+        return {name: getattr(inf, name) for name, _ in COMPONENTS_INFO_FIELDS}, table
+
+    def component_labels(self, first=0, count=None):
+        """The component index of every edge after components(): np.uint32[M], COMPONENT_NONE where unmarked."""
+        import numpy as np
+        if count is None:
+            count = self.result_ptrs()[2] - first
+        out = np.zeros(count, dtype=np.uint32)
+        self._L.goss_gpu_components_labels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_components_labels(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def keep_component(self, edge_rank):
+        """The result becomes the whole-graph component of the edge of that rank and that of its reverse complement
+        (goss_gpu_components_keep); returns the number of edges kept."""
+        kept = C.c_uint64()
+        self._L.goss_gpu_components_keep.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        self._check(self._L.goss_gpu_components_keep(self._h, edge_rank, C.byref(kept)))
+        if getattr(self, "counts", None) is not None:
+            self.counts.distinct = int(kept.value)       # what result() copies
+        return int(kept.value)
+
+    def components_release(self):
+        self._L.goss_gpu_components_release.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_components_release(self._h))
 
     def check_index(self, files, base=""):
         """goss_gpu_check_index on a SparseArray given as {suffix: bytes} (files[base + ".header"]

@@ -82,8 +82,9 @@ struct Run { void* keys; uint32_t* counts; uint64_t m; int big = -1; bool rep = 
 struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
 
 // What a build entry point left on top of the permanent room for later calls to read (graph_passes.hpp): the segment
-// table and text of goss_gpu_segments_build, or the images of goss_gpu_entries_build.  One record: at most one is held.
-enum class Held : uint8_t { None, Segments, Entries };
+// table and text of goss_gpu_segments_build, the images of goss_gpu_entries_build, or the marks, labels and table of the
+// components entry points.  One record: at most one is held.
+enum class Held : uint8_t { None, Segments, Entries, Components };
 struct HeldResult { Held kind = Held::None; uint64_t lo = 0; };          // lo: the permanent top before the build
 
 // Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
@@ -237,6 +238,14 @@ struct goss_gpu_ctx {
     void* seg_recs = nullptr;
     uint8_t* seg_text = nullptr;
     uint64_t seg_count = 0, seg_text_bytes = 0;
+    // Held::Components, bottom to top: the marks (goss_gpu_components_mark_*; null = none), then from cmp_built_lo on
+    // what goss_gpu_components_build left: a component index per edge and the table
+    uint32_t* cmp_marks = nullptr;
+    uint64_t cmp_mark_words = 0, cmp_built_lo = 0, cmp_marked = 0;      // cmp_marked: bits set in the marks
+    uint32_t* cmp_labels = nullptr;
+    void* cmp_recs = nullptr;
+    uint64_t cmp_count = 0;
+    bool cmp_built = false;
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -364,6 +373,7 @@ bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
     rebase(c->res_keys); rebase(c->res_counts);
     rebase(c->tips_keys); rebase(c->tips_counts);
     rebase(c->seg_recs); rebase(c->seg_text);
+    rebase(c->cmp_marks); rebase(c->cmp_labels); rebase(c->cmp_recs);
     for (auto& f : c->files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
     (void)hipFree(a.base);
     a.base = nb; a.hi = target - top; a.size = target;
@@ -2727,13 +2737,16 @@ void emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_bytes, ui
 
 void wait_background_thread(goss_gpu_ctx* c);
 
-// Give back what the context holds (segments or an entry edge set), if anything: the permanent room from held.lo on.
+// Give back what the context holds (segments, an entry edge set or components), if anything: the permanent room from held.lo on.
 void release_held(goss_gpu_ctx* c)
 {
     if (c->held.kind != Held::None) c->arena.lo = c->held.lo;
     if (c->held.kind == Held::Entries) c->files.clear();
     c->held = HeldResult();
     c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
+    c->cmp_marks = nullptr; c->cmp_labels = nullptr; c->cmp_recs = nullptr;
+    c->cmp_mark_words = c->cmp_built_lo = c->cmp_count = c->cmp_marked = 0;
+    c->cmp_built = false;
 }
 
 // wait_bg: the call works on the arena or the runs -- the thread that counts a full staging buffer must have ended
@@ -4952,6 +4965,82 @@ int goss_gpu_entries_release(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind == Held::Entries) release_held(c);
+    return GOSS_OK;
+}
+
+static int components_mark_entry(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, bool on_host, goss_gpu_mark_info* out)
+{
+    if (!c || !out || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (const int st = graph_pass_state(c, "components", "edges are marked in a graph", "marking belongs between finish and emit")) return st;
+    return build_held(c, Held::Components, out, [&]() { components_mark(c, bases, nbytes, on_host, out); },
+                      c->held.kind == Held::Components && c->cmp_marks);
+}
+
+int goss_gpu_components_mark_host(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, goss_gpu_mark_info* out)
+{
+    return components_mark_entry(c, bases, nbytes, true, out);
+}
+
+int goss_gpu_components_mark_device(goss_gpu_ctx* c, const void* d_bases, uint64_t nbytes, goss_gpu_mark_info* out)
+{
+    return components_mark_entry(c, d_bases, nbytes, false, out);
+}
+
+int goss_gpu_components_build(goss_gpu_ctx* c, uint32_t flags, goss_gpu_components_info* out)
+{
+    if (!c || !out || (flags & ~(uint32_t)GOSS_COMPONENTS_MARKED)) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (const int st = graph_pass_state(c, "components", "components are found in a graph", "components belong between finish and emit")) return st;
+    const bool marks = c->held.kind == Held::Components && c->cmp_marks;
+    if ((flags & GOSS_COMPONENTS_MARKED) && !marks)
+    {
+        c->last_error = "components_build: GOSS_COMPONENTS_MARKED needs goss_gpu_components_mark_host / _device before it";
+        return GOSS_ERR_STATE;
+    }
+    return build_held(c, Held::Components, out, [&]() {
+        if (marks) components_drop_built(c); else c->cmp_built_lo = c->arena.lo;
+        components_build(c, flags, out);
+    }, marks);
+}
+
+int goss_gpu_components_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, goss_gpu_component* out)
+{
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind != Held::Components || !c->cmp_built) { c->last_error = "components_table needs goss_gpu_components_build before it"; return GOSS_ERR_STATE; }
+    if (first > c->cmp_count || count > c->cmp_count - first) { c->last_error = "components_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    c->keep_held = true;
+    return guarded(c, [&]() {
+        if (count) HIP_TRY(hipMemcpyAsync(out, (const CompRec*)c->cmp_recs + first, count * sizeof(CompRec), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+int goss_gpu_components_labels(goss_gpu_ctx* c, uint64_t first, uint64_t count, uint32_t* out)
+{
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind != Held::Components || !c->cmp_built) { c->last_error = "components_labels needs goss_gpu_components_build before it"; return GOSS_ERR_STATE; }
+    if (first > c->M || count > c->M - first) { c->last_error = "components_labels: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    c->keep_held = true;
+    return guarded(c, [&]() {
+        if (count) HIP_TRY(hipMemcpyAsync(out, c->cmp_labels + first, count * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+int goss_gpu_components_keep(goss_gpu_ctx* c, uint64_t edge_rank, uint64_t* kept)
+{
+    if (!c || !kept) return GOSS_ERR_INVALID_ARG;
+    *kept = 0;
+    if (const int st = graph_pass_state(c, "components", "a component is kept of a graph", "keeping a component belongs between finish and emit")) return st;
+    if (edge_rank >= c->M) { c->last_error = "components_keep: the graph has no edge of that rank"; return GOSS_ERR_INVALID_ARG; }
+    return guarded(c, [&]() { *kept = components_keep(c, (uint32_t)edge_rank); });
+}
+
+int goss_gpu_components_release(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind == Held::Components) release_held(c);
     return GOSS_OK;
 }
 

@@ -24,3 +24,4 @@
 #include "kernels_contigs.hpp"
 #include "kernels_entries.hpp"
 #include "kernels_match.hpp"
+#include "kernels_components.hpp"

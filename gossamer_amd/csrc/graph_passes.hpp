@@ -8,7 +8,8 @@
 //                bounded walk and pointer doubling (kernels_contigs.hpp), with or without the multiplicities
 //
 // prune_tips_once is link_graph and the tip walk; segments_build and entries_build are link_graph, rank_lists and
-// their own records.  What a build leaves behind for later calls is the context's one held result (build_held).
+// their own records; components_build and components_keep are link_graph and a union-find over the links.  What a
+// build leaves behind for later calls is the context's one held result (build_held).
 #pragma once
 
 // Temporaries of one call, given back on every way out (an exception included).
@@ -28,7 +29,7 @@ struct EventPair {
 };
 
 // The pinned scratch of the context as the passes use it: a report at its start, two words behind it.
-static_assert(sizeof(TipsReport) <= 128 && sizeof(ContigsReport) <= 128, "pinned scratch");
+static_assert(sizeof(TipsReport) <= 128 && sizeof(ContigsReport) <= 128 && sizeof(CompReport) <= 128, "pinned scratch");
 template <class R> R* pinned_report(goss_gpu_ctx* c) { return (R*)c->h_pinned; }
 inline uint64_t* pinned_words(goss_gpu_ctx* c) { return (uint64_t*)((uint8_t*)c->h_pinned + 128); }
 
@@ -65,15 +66,18 @@ int graph_pass_state(goss_gpu_ctx* c, const char* who, const char* not_a_graph, 
     return GOSS_OK;
 }
 
-// The skeleton of goss_gpu_segments_build and goss_gpu_entries_build: guarded() gives back what an earlier build
-// holds, `body` builds on top of the permanent room as it is then, and the context holds the outcome as `kind`.
+// The skeleton of goss_gpu_segments_build, goss_gpu_entries_build and the components entry points: guarded() gives
+// back what an earlier build holds, `body` builds on top of the permanent room as it is then, and the context holds
+// the outcome as `kind`.
 // After a failure nothing is held and *out is zero; the result was only read.
+// `extend`: what is held is of this kind already and stays (the marks of count-components): body goes on from it.
 template <class Info, class F>
-int build_held(goss_gpu_ctx* c, Held kind, Info* out, F&& body)
+int build_held(goss_gpu_ctx* c, Held kind, Info* out, F&& body, bool extend = false)
 {
     bool began = false;
+    c->keep_held = extend;
     const int rc = guarded(c, [&]() {
-        c->held = {kind, c->arena.lo};
+        if (!extend) c->held = {kind, c->arena.lo};
         began = true;
         PhaseTimer t(c, GOSS_T_REDUCE, c->M);
         body();
@@ -246,6 +250,30 @@ ListRanks rank_lists(goss_gpu_ctx* c, const GraphLinks<K>& l, const uint32_t* co
 
 // ---- prune-tips -----------------------------------------------------------------------------------------------------
 
+// The result becomes its m edges whose bit in the removal bitmap `zap` is clear (tile_offsets: the scanned counts of
+// tips_keep_count_kernel).  A result that prune-tips or keep-component allocated is compacted beside itself and
+// copied back (five iterations take the permanent room of one); anybody else's arrays (a run, select_counts) are
+// left alone and the survivors take new permanent room.  Complete when this returns.
+template <class K>
+void replace_result(goss_gpu_ctx* c, const K* keys, const uint32_t* counts, uint64_t n64, const uint32_t* zap, const uint64_t* tile_offsets,
+                    uint64_t ntiles, uint64_t m)
+{
+    const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
+    const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
+    K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
+    uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), dim3(kTB), 0, c->stream, keys, counts, n64, zap,
+                       tile_offsets, okeys, ocounts);
+    if (own)
+    {
+        if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+        if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    sync_checked(c);
+    if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
+    c->M = m;
+}
+
 // One iteration of prune-tips over the result (GossCmdPruneTips.cc:279-319).  Nothing of the context changes
 // before the survivors are complete: a failure leaves the result as it was.
 template <class K>
@@ -300,25 +328,7 @@ void prune_tips_once(goss_gpu_ctx* c, goss_gpu_tips_report* out)
     rep.joined_at_begin = h->joined_at_begin; rep.joined_at_end = h->joined_at_end;
     const uint64_t m = hm[0];
     rep.edges_after = m;
-    if (m != n64)
-    {
-        const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
-        const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
-        // a result this entry point allocated is compacted beside itself and copied back (five iterations take the
-        // permanent room of one); anybody else's arrays (a run, select_counts) are left alone
-        K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
-        uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), block, 0, c->stream, l.keys, l.counts, n64,
-                           (const uint32_t*)zap, (const uint64_t*)tile_counts, okeys, ocounts);
-        if (own)
-        {
-            if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
-            if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
-        }
-        sync_checked(c);
-        if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
-        c->M = m;
-    }
+    if (m != n64) replace_result<K>(c, l.keys, l.counts, n64, zap, tile_counts, ntiles, m);
     if (out) *out = rep;
 }
 
@@ -529,4 +539,195 @@ void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
 {
     c->files.clear();
     if (c->words == 1) entries_build<Key1>(c, out); else entries_build<Key2>(c, out);
+}
+
+// ---- count-components ---------------------------------------------------------------------------------------------
+
+// The held result of count-components, bottom to top: the marks (a bit per edge, goss_gpu_components_mark_*), then
+// what goss_gpu_components_build left -- a label per edge and the table.  The marks outlive the builds that use
+// them; a new mark call or build drops the labels and the table above them.
+inline void components_drop_built(goss_gpu_ctx* c)
+{
+    c->arena.lo = c->cmp_built_lo;
+    c->cmp_labels = nullptr; c->cmp_recs = nullptr; c->cmp_count = 0; c->cmp_built = false;
+}
+
+// Every forward (K+1)-window of the byte-form reads is looked up among the edges and the bits of those found are
+// OR-ed into the marks (GossCmdCountComponents.cc:229-241).  The first call takes the zeroed bitmap.
+template <class K>
+void components_mark(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, bool on_host, goss_gpu_mark_info* out)
+{
+    goss_gpu_mark_info inf{};
+    const uint32_t n = link_edges(c, "components");
+    const uint32_t bits = n ? tips_bucket_bits(n, c->len) : 0;
+    const uint64_t words = ((uint64_t)n + 63) / 64 * 2;
+    {
+        // the marks; the reads' copy, the bucket table
+        const uint64_t need = (c->cmp_marks ? 0 : words * 4) + (on_host ? nbytes : 0) + link_table_bytes(bits) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    if (c->cmp_marks) components_drop_built(c);
+    else
+    {
+        c->cmp_marks = (uint32_t*)c->arena.perm(std::max<uint64_t>(words * 4, 16));
+        c->cmp_mark_words = words;
+        c->cmp_built_lo = c->arena.lo;
+        HIP_TRY(hipMemsetAsync(c->cmp_marks, 0, std::max<uint64_t>(words * 4, 16), c->stream));
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    const uint8_t* d_bases = (const uint8_t*)bases;
+    if (on_host && nbytes)
+    {
+        uint8_t* d = (uint8_t*)c->arena.temp(nbytes);
+        HIP_TRY(hipMemcpyAsync(d, bases, nbytes, hipMemcpyHostToDevice, c->stream));
+        d_bases = d;
+    }
+    uint32_t* table = bits ? (uint32_t*)c->arena.temp(link_table_bytes(bits)) : nullptr;
+    CompReport* d_rep = (CompReport*)c->arena.temp(sizeof(CompReport));
+    CompReport* h = pinned_report<CompReport>(c);
+    const K* keys = (const K*)c->res_keys;
+    const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(CompReport), c->stream));
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (n && ntiles)
+    {
+        if (bits)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), dim3(grid_for(n, kTB)), dim3(kTB), 0, c->stream, keys, n, c->len, bits, table);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(components_mark_kernel<K>), unit_grid(ntiles), dim3(kTB), 0, c->stream, keys, n, c->len, bits,
+                           (const uint32_t*)table, d_bases, nbytes, ntiles, (uint32_t)(((uintptr_t)d_bases & 7u) == 0), c->cmp_marks, d_rep);
+    }
+    if (words)
+        hipLaunchKernelGGL(components_popcount_kernel, dim3((uint32_t)std::min<uint64_t>(grid_for(words, kTB), kTipsGridBlocks)), dim3(kTB), 0,
+                           c->stream, (const uint32_t*)c->cmp_marks, words, d_rep);
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(CompReport), hipMemcpyDeviceToHost, c->stream));
+    sync_checked(c);
+    inf.windows = h->windows; inf.hits = h->hits; inf.marked_total = h->marked;
+    c->cmp_marked = h->marked;
+    HIP_TRY(hipEventElapsedTime(&inf.ms, ev.e[0], ev.e[1]));
+    *out = inf;
+}
+
+void components_mark(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, bool on_host, goss_gpu_mark_info* out)
+{
+    if (c->words == 1) components_mark<Key1>(c, bases, nbytes, on_host, out); else components_mark<Key2>(c, bases, nbytes, on_host, out);
+}
+
+// parent[i] = the smallest rank of the component of edge i among the marked edges (every edge when marks is null),
+// kCompNone where unmarked: three launches over the edges (kernels_components.hpp).  sc as components_flatten_kernel
+// takes it.  Queued, not waited for.
+template <class K>
+uint32_t* components_label(goss_gpu_ctx* c, const GraphLinks<K>& l, const uint32_t* marks, uint64_t* sc, uint32_t* launches)
+{
+    uint32_t* parent = (uint32_t*)c->arena.temp((uint64_t)l.n * 4);
+    hipLaunchKernelGGL(components_init_kernel, l.grid, l.block, 0, c->stream, marks, l.n, parent);
+    hipLaunchKernelGGL(components_hook_kernel, l.grid, l.block, 0, c->stream, (const uint32_t*)l.rcr, (const uint32_t*)l.nxt,
+                       (const uint8_t*)l.info, marks, l.n, parent);
+    hipLaunchKernelGGL(components_flatten_kernel, l.grid, l.block, 0, c->stream, parent, l.n, sc);
+    if (launches) *launches = 3;
+    return parent;
+}
+
+// The components of the marked edges (GossCmdCountComponents.cc:244-258), numbered by ascending smallest rank, with
+// their true figures.  Working arrays under an ArenaScope; the labels and the table are permanent room above the marks.
+template <class K>
+void components_build(goss_gpu_ctx* c, uint32_t flags, goss_gpu_components_info* out)
+{
+    static_assert(sizeof(goss_gpu_component) == sizeof(CompRec), "component layout");
+    goss_gpu_components_info inf{};
+    const uint64_t n64 = c->M;
+    const uint32_t* marks = (flags & GOSS_COMPONENTS_MARKED) ? c->cmp_marks : nullptr;
+    c->cmp_built = true;
+    if (n64 == 0) { *out = inf; return; }
+    {
+        // the links, parent (4), the scan (8); the labels (4) and 40 bytes per component stay.  The table is taken
+        // once the components are counted, when the arena can no longer grow: its room is asked for here by the
+        // only bound there is before the labelling, a component per marked edge
+        const uint64_t most = marks ? std::min<uint64_t>(n64, c->cmp_marked) : n64;
+        const uint64_t need = link_bytes(c, "components") + n64 * (4 + 8 + 4) + most * sizeof(CompRec) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    uint32_t* labels = (uint32_t*)c->arena.perm(n64 * 4);
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    CompReport* h = pinned_report<CompReport>(c);
+    uint64_t* hx = pinned_words(c);
+
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    const GraphLinks<K> l = link_graph<K>(c, "components", nullptr, [&](const GraphLinks<K>&) { HIP_TRY(hipEventRecord(ev.e[1], c->stream)); });
+    const uint32_t n = l.n;
+    uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+    CompReport* d_rep = (CompReport*)c->arena.temp(sizeof(CompReport));
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(CompReport), c->stream));
+    const uint32_t* parent = components_label<K>(c, l, marks, sc, &inf.launches);
+    scan_with_total(c, sc, n64, hx);
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    sync_checked(c);
+    const uint64_t ncomp = hx[0];
+
+    CompRec* recs = (CompRec*)c->arena.perm(std::max<uint64_t>(ncomp * sizeof(CompRec), 16));
+    const dim3 few((uint32_t)std::min<uint64_t>(l.grid.x, kTipsGridBlocks));
+    hipLaunchKernelGGL(components_number_kernel, l.grid, l.block, 0, c->stream, parent, (const uint64_t*)sc, (const uint32_t*)l.rcr, n, labels, recs);
+    hipLaunchKernelGGL(components_figures_kernel, few, l.block, 0, c->stream, (const uint32_t*)labels, l.counts, n, recs);
+    if (ncomp)
+        hipLaunchKernelGGL(components_largest_kernel, dim3((uint32_t)std::min<uint64_t>(grid_for(ncomp, kTB), kTipsGridBlocks)), l.block, 0, c->stream,
+                           (const CompRec*)recs, ncomp, d_rep);
+    if (marks)
+        hipLaunchKernelGGL(components_popcount_kernel, dim3((uint32_t)std::min<uint64_t>(grid_for(c->cmp_mark_words, kTB), kTipsGridBlocks)), l.block, 0,
+                           c->stream, marks, c->cmp_mark_words, d_rep);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(CompReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    sync_checked(c);
+    inf.components = ncomp;
+    inf.marked_edges = marks ? h->marked : n64;
+    inf.largest = h->largest;
+    float* ms[3] = {&inf.ms_link, &inf.ms_label, &inf.ms_figures};
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    c->cmp_labels = labels; c->cmp_recs = recs; c->cmp_count = ncomp;
+    *out = inf;
+}
+
+void components_build(goss_gpu_ctx* c, uint32_t flags, goss_gpu_components_info* out)
+{
+    if (c->words == 1) components_build<Key1>(c, flags, out); else components_build<Key2>(c, flags, out);
+}
+
+// The result becomes the whole-graph component of edge e and that of rc(e) (what -O writes,
+// GossCmdCountComponents.cc:270-309): the labels of every edge, a removal bitmap, the compaction of prune-tips.
+// Nothing of the context changes before the survivors are complete.
+template <class K>
+uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
+{
+    const uint64_t n64 = c->M;
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    const uint64_t zap_words = ntiles * (kRedTile / 32);
+    static_assert(kRedTile % 64 == 0, "a wave writes 64 bits of the bitmap");
+    {
+        // the links, parent (4), the bitmap, and the survivors once more while they are compacted
+        const uint64_t need = link_bytes(c, "components") + n64 * 4 + zap_words * 4 + (ntiles + 1) * 8 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
+    HIP_TRY(hipMemsetAsync(zap, 0, zap_words * 4, c->stream));
+    const GraphLinks<K> l = link_graph<K>(c, "components");
+    const uint32_t* parent = components_label<K>(c, l, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(components_zap_kernel, l.grid, l.block, 0, c->stream, parent, (const uint32_t*)l.rcr, l.n, e, (uint64_t*)zap);
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), l.block, 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
+    uint64_t* hm = pinned_words(c);
+    scan_with_total(c, tile_counts, ntiles, hm);
+    sync_checked(c);
+    const uint64_t m = hm[0];
+    if (m != n64) replace_result<K>(c, l.keys, l.counts, n64, zap, tile_counts, ntiles, m);
+    return m;
+}
+
+uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
+{
+    PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+    const uint64_t m = c->words == 1 ? components_keep<Key1>(c, e) : components_keep<Key2>(c, e);
+    t.stop();
+    return m;
 }

@@ -296,6 +296,19 @@ private:
     const std::string mIn;
 };
 
+// GossCmdCountComponents (GossCmdCountComponents.{hh,cc}): the connected components of a graph, or of the edges that
+// the forward (K + 1)-windows of the given reads touch, as a table on standard output; with pOut, the component of the
+// first row's start edge and its mirror image written as a graph.  Two defects of the reference are kept because they
+// decide its output: every row counts its start edge twice, and the component written is the first listed, not the largest.
+class GossCmdCountComponents {
+public:
+    GossCmdCountComponents(const std::string& pIn, const std::string& pOut, const strings& pFastas, const strings& pFastqs, const strings& pLines)
+        : mIn(pIn), mOut(pOut), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const strings mFastas, mFastqs, mLines;
+};
+
 // GossCmdExtractReads (GossCmdExtractReads.{hh,cc}): the reads with at least one (K + 1)-mer that is an edge of the graph, as
 // parsed, one per line, in input order (line files, then FASTA, then FASTQ).
 class GossCmdExtractReads {
@@ -325,6 +338,10 @@ public:
 private:
     const std::string mIn, mMatch, mNonMatch; const strings mFastas, mFastqs, mLines; const bool mPairs, mCount; const uint64_t mNumThreads;
 };
+
+// Bytes of reads in byte form ('\n' after each) handed to the device per batch by the commands that look reads up in a
+// graph or k-mer set: GossCmdContext::batchBytes, or GOSS_MATCH_BATCH=<bytes> (tests).
+size_t matchBatchBytes(const GossCmdContext& cxt);
 
 // pairFiles (GossCmdFilterReads.cc:164-172): "a.b.fq" -> "a.b_1.fq", "a.b_2.fq"
 void pairFiles(const std::string& pBaseName, std::string& pName1, std::string& pName2);

@@ -91,17 +91,6 @@ struct Object {
     }
 };
 
-size_t matchBatchBytes(const GossCmdContext& cxt)
-{
-    if (const char* e = std::getenv("GOSS_MATCH_BATCH"))
-    {
-        char* end = nullptr;
-        unsigned long long v = strtoull(e, &end, 10);
-        if (end != e && *end == 0 && v > 0) return (size_t)v;
-    }
-    return cxt.batchBytes;
-}
-
 // Reads in, one verdict per read out, in order: batches end at read boundaries and hold `cap` bytes (one read more than
 // that is a batch of its own).
 class Matcher {
@@ -196,6 +185,17 @@ uint64_t parseItem(const Item& it, const ReadSink& sink)
 }
 
 }  // namespace
+
+size_t matchBatchBytes(const GossCmdContext& cxt)
+{
+    if (const char* e = std::getenv("GOSS_MATCH_BATCH"))
+    {
+        char* end = nullptr;
+        unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && *end == 0 && v > 0) return (size_t)v;
+    }
+    return cxt.batchBytes;
+}
 
 void pairFiles(const std::string& pBaseName, std::string& pName1, std::string& pName2)
 {

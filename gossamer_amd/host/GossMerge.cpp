@@ -1051,6 +1051,99 @@ void GossCmdBuildEntryEdgeSet::operator()(const GossCmdContext& pCxt)
     log(info, elapsed(t0));
 }
 
+// GossCmdCountComponents::operator() (GossCmdCountComponents.cc:171-311).  The reads are parsed in the reference's
+// item order (line files, FASTA, FASTQ) and handed over in byte form, '\n' after each, in batches as extract-reads
+// cuts them; the device marks, labels and sums (goss_gpu_components_*).  The table is read 64 K rows at a time.  The
+// reference adds the start edge of every component twice (:252-255): the device reports the true figures and the
+// start edge's multiplicity is added once more here, so that the rows are the reference's.
+void GossCmdCountComponents::operator()(const GossCmdContext& pCxt)
+{
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    uint64_t z = 0;
+    g.check(goss_gpu_result(g.h, nullptr, nullptr, &z), "counting");
+
+    log(info, "marking used edges");
+    const bool marked = !(mLines.empty() && mFastas.empty() && mFastqs.empty());
+    if (marked)
+    {
+        const size_t cap = matchBatchBytes(pCxt);
+        std::vector<char> buf;
+        goss_gpu_mark_info mi{};
+        uint64_t windows = 0, hits = 0;
+        auto flush = [&]() {
+            g.check(goss_gpu_components_mark_host(g.h, buf.data(), buf.size(), &mi), "marking a batch of reads");
+            windows += mi.windows; hits += mi.hits;
+            buf.clear();
+        };
+        ReadSink sink = [&](const char* seq, size_t len) {
+            if (!buf.empty() && buf.size() + len + 1 > cap) flush();
+            buf.insert(buf.end(), seq, seq + len);
+            buf.push_back('\n');
+        };
+        for (auto& f : mLines) parseLines(f, sink);
+        for (auto& f : mFastas) parseFasta(f, sink);
+        for (auto& f : mFastqs) parseFastq(f, sink);
+        flush();                                          // (also takes the bitmap when no read came)
+        log(info, "windows: " + num(windows) + ", of them edges: " + num(hits) + ", edges marked: " + num(mi.marked_total));
+    }
+
+    log(info, "finding components");
+    goss_gpu_components_info inf;
+    g.check(goss_gpu_components_build(g.h, marked ? GOSS_COMPONENTS_MARKED : 0u, &inf), "finding the components");
+    log(info, "components: " + num(inf.components) + ", marked edges: " + num(inf.marked_edges) + ", largest: " + num(inf.largest) + " edges");
+
+    std::ostringstream line;
+    auto put = [&]() {
+        const std::string text = line.str();
+        if (!text.empty() && fwrite(text.data(), 1, text.size(), stdout) != text.size()) throw Error::Write("-");
+        line.str(std::string());
+    };
+    line << "Comp\tSize\tMin\tMax\tMean\tStd Dev\n";
+    put();
+    const uint64_t rows = 1u << 16, window = 4u << 20;
+    std::vector<goss_gpu_component> table;
+    std::vector<uint32_t> mult;                          // the multiplicities of the edges [multAt, multAt + mult.size())
+    uint64_t multAt = 0, firstStart = 0;
+    for (uint64_t first = 0; first < inf.components; first += rows)
+    {
+        const uint64_t cnt = std::min(rows, inf.components - first);
+        table.resize((size_t)cnt);
+        g.check(goss_gpu_components_table(g.h, first, cnt, table.data()), "reading the component table");
+        if (first == 0) firstStart = table[0].start;
+        for (uint64_t j = 0; j < cnt; ++j)
+        {
+            const goss_gpu_component& c = table[(size_t)j];
+            if (c.start < multAt || c.start >= multAt + mult.size())
+            {
+                multAt = c.start;
+                mult.resize((size_t)std::min(window, z - multAt));
+                g.check(goss_gpu_result_copy(g.h, multAt, mult.size(), nullptr, mult.data()), "reading the multiplicities");
+            }
+            const uint64_t m = mult[(size_t)(c.start - multAt)];
+            const uint64_t mNumEdges = c.edges + 1, mCountSum = c.s + m, mCountSum2 = c.s2 + m * m;
+            const double mean = mCountSum / double(mNumEdges);
+            const double stdDev = sqrt(double(mNumEdges) * mCountSum2 - (double(mCountSum) * mCountSum)) / mNumEdges;
+            line << (first + j) << '\t' << mNumEdges << '\t' << c.min << '\t' << c.max << '\t' << mean << '\t' << stdDev << '\n';
+        }
+        put();
+    }
+    fflush(stdout);
+
+    if (!mOut.empty() && inf.components)
+    {
+        log(info, "Writing largest component");
+        uint64_t kept = 0;
+        g.check(goss_gpu_components_keep(g.h, firstStart, &kept), "keeping the component");
+        g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+        writeOut(g, mOut);
+    }
+    else g.check(goss_gpu_components_release(g.h), "releasing the components");
+}
+
 void GossCmdMergeKmerSets::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, false, mIns, mMaxMerge, mOut); }
 void GossCmdMergeGraphs::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, true, mIns, mMaxMerge, mOut); }
 

@@ -659,6 +659,75 @@ int goss_gpu_entries_build(goss_gpu_ctx* ctx, goss_gpu_entries_info* info);
 int goss_gpu_entries_release(goss_gpu_ctx* ctx);
 
 /*
+ * Between finish and emit, graph mode: the connected components of the graph the context holds, or of
+ * the edges that reads touch, as `goss count-components` finds them (GossCmdCountComponents.cc:37-127,
+ * 171-311, a serial flood fill there).
+ *
+ * Marked edges: all of them, or -- after goss_gpu_components_mark_host / _device and with
+ * GOSS_COMPONENTS_MARKED -- the edges found by looking up every forward (K+1)-window of every read
+ * (GossRead::Iterator(read, K + 1): ACGTacgt only, any other byte restarts the window; the bytes are
+ * reads with '\n' after or between them, as goss_gpu_object_match_reads takes them).  The reverse
+ * complement of a window is not looked up: the marks are in general not symmetric.
+ * Components: two marked edges belong together when they share a node in any role (the same from-node,
+ * the same to-node, the to-node of one the from-node of the other); a component is a class of the
+ * transitive closure over marked edges.  Components are numbered from 0 by their smallest rank, `start`.
+ *
+ * The link pass of goss_gpu_prune_tips names the at most twelve edges that share a node with an edge;
+ * the labelling is a lock-free union-find over them, `launches` launches over the edges whatever the
+ * graph's diameter, and its outcome does not depend on scheduling.  The figures are integer atomics.
+ * The reference counts the start edge of every component twice (GossCmdCountComponents.cc:252-255: add,
+ * then follow() meets it still marked); the table here holds the true figures, and a caller that wants
+ * the reference's rows adds the start edge's multiplicity once more.
+ *
+ * mark: the first call takes a zeroed bitmap of one bit per edge, later calls OR into it; marked_total
+ * is the number of bits set after the call.  The marks are part of the held result: they outlive the
+ * builds that use them and are given back by goss_gpu_components_release or by any entry point that
+ * gives back segments or entries (the rule of goss_gpu_segments_build).
+ * build: any number of times; the result is only read.  A label per edge and the table are held above
+ * the marks (about 25 bytes per edge of working room while building, 4 per edge and 40 per component
+ * afterwards); the next mark call or build replaces them.
+ * table / labels: any sub-range.  labels: the component's index per edge, 0xFFFFFFFF where unmarked.
+ * mirror: the index of the component that holds the reverse complement of the start edge (the
+ * component's own index when it is its own mirror image), 0xFFFFFFFF when that edge is unmarked.
+ * keep: labels the whole graph, whatever is marked, and reduces the result to the component of
+ * edge_rank and that of its reverse complement -- what the reference's -O writes for the start of its
+ * first component (it logs "largest" and never sorts, GossCmdCountComponents.cc:270-309).  Whatever is
+ * held is given back; a following goss_gpu_emit writes Graph::Builder(K, out, fac, *kept).
+ *
+ * GOSS_ERR_STATE: a k-mer-set context, before finish, after emit; table / labels without a build;
+ * GOSS_COMPONENTS_MARKED without marks.
+ * GOSS_ERR_INVALID_ARG: an edge without its reverse complement (last_error names its index); 2^32 - 1
+ * edges or more; multiplicities of 2^32 - 1 or more; a range past the end; an unknown flag;
+ * edge_rank >= the number of edges.
+ * GOSS_ERR_OOM: it does not fit the arena; nothing is held afterwards and the result is intact.
+ */
+#define GOSS_COMPONENTS_MARKED 1u
+typedef struct {
+    uint64_t windows, hits;                        /* of this call: valid windows, windows that are edges */
+    uint64_t marked_total;                         /* bits set in the marks after this call */
+    float ms;                                      /* HIP-event time of the call's kernels */
+} goss_gpu_mark_info;
+typedef struct {
+    uint64_t components;
+    uint64_t marked_edges;
+    uint64_t largest;                              /* edges of the component that has the most */
+    uint32_t launches;                             /* over the edges, for the labelling */
+    float ms_link, ms_label, ms_figures;           /* HIP-event time of the three parts */
+} goss_gpu_components_info;
+typedef struct {
+    uint64_t s, s2;                                /* sum and sum of squares of the multiplicities (mod 2^64) */
+    uint64_t edges;
+    uint32_t start, min, max, mirror;
+} goss_gpu_component;
+int goss_gpu_components_mark_host(goss_gpu_ctx* ctx, const void* bases, uint64_t nbytes, goss_gpu_mark_info* info);
+int goss_gpu_components_mark_device(goss_gpu_ctx* ctx, const void* d_bases, uint64_t nbytes, goss_gpu_mark_info* info);
+int goss_gpu_components_build(goss_gpu_ctx* ctx, uint32_t flags, goss_gpu_components_info* info);
+int goss_gpu_components_table(goss_gpu_ctx* ctx, uint64_t first, uint64_t count, goss_gpu_component* out);
+int goss_gpu_components_labels(goss_gpu_ctx* ctx, uint64_t first, uint64_t count, uint32_t* out);
+int goss_gpu_components_keep(goss_gpu_ctx* ctx, uint64_t edge_rank, uint64_t* kept);
+int goss_gpu_components_release(goss_gpu_ctx* ctx);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */

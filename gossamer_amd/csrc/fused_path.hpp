@@ -593,7 +593,7 @@ void launch_first_level(const FusedChunk<K>& ch, const FusedForm& form, bool can
         const bool fastk = a.nh == 0 && 2 * c->len >= 32 && a.part_shift >= 34 && !c->no_fast32;
         const bool narrow = form.msd && form.rem32() && form.narrow;
         const uint32_t nr_rbits = form.rbits32, nr_sqbit = form.squeeze ? c->len - 1 : 0u, nr_dmask = (1u << form.r32_bits) - 1u;
-        const uint32_t nr_capg = std::min(656u, std::max(576u, c->narrow_capg));          // (granules of the kernel's LDS layout: kernels_extract.hpp, kSlots)
+        const uint32_t nr_capg = std::max(576u, c->narrow_capg);          // (the kernel takes its LDS layout's own number of granules where that is less: kernels_extract.hpp, kSlots)
         if (ch.graph_mode) launch_extract1_part<1, 0>(c, a, fastk, narrow, nr_rbits, nr_sqbit, nr_dmask, nr_capg);
         // gossamer's canonical form computed per window (many distinct keys: choose_key_space)
         else if (canon_l1) launch_extract1_part<0, 2>(c, a, fastk, narrow, nr_rbits, nr_sqbit, nr_dmask, nr_capg);

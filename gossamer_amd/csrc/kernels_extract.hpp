@@ -596,7 +596,10 @@ __host__ __device__ inline uint32_t rec_windows(uint32_t w2) { return (w2 >> 27)
 #define GOSS_E1_OCC 3
 #endif
 #ifndef GOSS_E1_NCH
-#define GOSS_E1_NCH 4          // (NARROW) chunks of three keys per lane and round of the store loop
+// (NARROW) chunks of three keys per lane and round of the store loop, which walks the tile's whole granules alone (the
+// store list): C2's mean tile has ~285 of them, 1 140 chunks -- one round of 5 x 256.  First level on C2: 5: 25.64-25.69 ms,
+// 3 (two rounds): 26.07-26.14; the loop over every granule of the layout, 4 (three rounds): 28.01-28.16
+#define GOSS_E1_NCH 5
 #endif
 // Wave priorities by phase (s_setprio; the SIMD's issue arbiter takes priority before age).  The three workgroups of a
 // CU are in different phases; a wave in the store phase issues few instructions, each of which starts a long-latency
@@ -650,7 +653,8 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
     // tile's vectors are fetched as they are and nothing is encoded
     static_assert(!(PACKED && REC), "records are not bases");
     // (nr_capg: granules of the LDS layout a tile may take before its carried granules are sent off short -- the layout's
-    // 664, or down to the 576 a tile without carried keys needs at most: tests make the rare path common with it)
+    // own number at most (kSlots / 12), or down to the 576 a tile without carried keys needs at most: tests make the rare
+    // path common with it)
     static_assert(!NARROW || NH == 0, "the narrow form is the two-level form's");
     // MODE 0: one key per window, 16 windows per thread.  MODE 1 (graph): forward key and
     // reverse complement of every window, 8 windows per thread -- 16 keys per thread either way.
@@ -666,31 +670,52 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
     constexpr uint32_t kGran = NARROW ? 12 : 8;                      // keys per 64-byte granule
     // the NEW keys of the 256 buckets, each bucket's rounded up to whole granules: at most T * S keys and 7 (11) slots per bucket
     // NARROW: a bucket's piece holds its carried keys as well -- at most T * S + 2 * 256 * 11 slots, but 27 per bucket on
-    // average (16 new, 5.5 carried, 5.5 of rounding) with a deviation of ~80 for the whole tile: 656 granules are what
+    // average (16 new, 5.5 carried, 5.5 of rounding) with a deviation of ~80 for the whole tile: 653 granules (below) are what
     // three workgroups per CU leave room for and 12 deviations above the mean; a tile that needs more (keys dealt out
     // on purpose) first sends every carried granule to its bucket as it is, short, and then holds T * S + 256 * 11 at most
-    constexpr uint32_t kSlots = NARROW ? 656 * 12 : T * S + 256 * kCarry;
+    // NARROW, the store list: one entry per WHOLE granule of the tile -- where it goes in `out` (`gal`, 4 bytes) and where it
+    // lies in the layout (`lgl`, 2 bytes: its digits' byte offset, 24 x granule; its remainders lie at twice that).  A
+    // tile's keys and carried keys are at most T * S + 256 * 11 = 576 granules.  The store loop reads the entries of whole
+    // rounds (64 kCh entries): `lgl` has a round's multiple of entries, every one of them always the offset of a granule
+    // of the layout (zero at the start, stale later), so that what is read through them lies in the layout; the
+    // reads past `gal`'s 576 entries land in dh and tab behind it and are never used.  The layout gets the granules
+    // (72 bytes each, and 128 spare slots of 6 bytes) that the list and the tables leave of the 53 760 bytes a
+    // workgroup may have with three on a CU: 653 with five chunks per round (656 before there was a list)
+    constexpr uint32_t kListMax = (T * S + 256 * 11) / 12;           // whole granules of a tile at most
+    constexpr uint32_t kListN = (kListMax + 64 * GOSS_E1_NCH - 1) / (64 * GOSS_E1_NCH) * (64 * GOSS_E1_NCH);
+    constexpr uint32_t kLdsBudget = 53760;                           // bytes of LDS per workgroup at three per CU
+    constexpr uint32_t kTabBytes = (288 + 288 + 8) * 4;              // dh, tab, sh_scan
+    constexpr uint32_t kListBytes = NARROW ? kListN * 2 + kListMax * 4 : 0;
+    static_assert(kLdsBudget > kListBytes + kTabBytes + 128 * 6, "the list and the tables leave room for a layout");
+    constexpr uint32_t kLayG = ((kLdsBudget - kListBytes - kTabBytes) / 6 - 128) / 12;
+    constexpr uint32_t kSlots = NARROW ? kLayG * 12 : T * S + 256 * kCarry;
     static_assert(kSlots % kGran == 0 && kSlots >= T * S + 256 * kCarry, "whole granules, and room for a tile without carried keys");
+    // (the scan of phase C carries the layout's granules in the low half of a word and the whole ones in the high half)
+    static_assert(kSlots / kGran + 256 < 65536 && (T * S + 256 * kCarry) / kGran + 256 < 65536, "both sums of the packed scan stay below 2^16");
+    static_assert(!NARROW || (kSlots / 12 - 1) * 24 < 65536, "a granule's digit offset is a 16-bit list entry");
+    static_assert((kListN - kListMax) * 4 <= 2 * 288 * 4, "the reads past the list's addresses stay inside dh and tab");
     // + 128 slots nobody reads: the keys of windows that are not valid go there (they rank themselves in one of 32
     // spare counters, 8 threads each: at most 128 per counter and tile) instead of under a branch, whose exec-mask
     // bookkeeping costs scalar issue slots; reads past the live part land there too
     constexpr uint32_t kGarb = kSlots;
     constexpr int kPairs = GOSS_E1_NK >= 16 ? 5 : 3;                 // pairs of keys per lane and round of the store loop
     constexpr uint32_t kStep = 2 * kPairs * kTB;                     // slots per round: two rounds cover the 4 096 + 3.5 x 256 slots an average tile takes
-    // granules of the layout; entry kSlots / kGran is always kSkip.  (NARROW: the store loop reads its table entries, remainders
-    // and digits at fixed strides from the lane's first chunk, past the layout's end in its last round -- up to chunk
-    // 3 071 = granule 767, slot 9 220: all inside this allocation, and nothing of it is stored)
-    constexpr uint32_t kNG = NARROW ? 772 : kSlots / kGran + 4;
-    constexpr uint32_t kSkip = 0xFFFFFFFFu;
+    // granules of the layout; entry kSlots / kGran is always kSkip.  (NARROW has the store list in front of dh instead)
+    constexpr uint32_t kNG = NARROW ? 0 : kSlots / kGran + 4;
+    [[maybe_unused]] constexpr uint32_t kSkip = 0xFFFFFFFFu;
     // NARROW: remainders (4 bytes a slot), then digits (2 bytes a slot)
     constexpr uint32_t kSortedBytes = NARROW ? (kSlots + 128) * 6 : (kSlots + 128) * 8;
     constexpr uint32_t kDigBase = (kSlots + 128) * 4;
     static_assert(kDigBase % 16 == 0, "the digit array starts on a 16-byte boundary");
-    __shared__ __attribute__((aligned(64))) unsigned char lds_all[kSortedBytes + (288 + 288 + kNG + 8 + (NH ? 256 * NH : 0)) * 4];
+    static_assert(kSortedBytes % 4 == 0 && kListBytes % 4 == 0, "the list and the tables behind it are arrays of words");
+    __shared__ __attribute__((aligned(64))) unsigned char lds_all[kSortedBytes + kListBytes + kTabBytes + (kNG + (NH ? 256 * NH : 0)) * 4];
+    static_assert(!NARROW || sizeof(lds_all) <= kLdsBudget, "three workgroups per CU");
     Key1* const sorted = reinterpret_cast<Key1*>(lds_all);
-    uint32_t* const dh = reinterpret_cast<uint32_t*>(lds_all + kSortedBytes);       // new keys of this tile per digit (rank counter); 32 spare ones for windows that are not valid
+    [[maybe_unused]] uint16_t* const lgl = reinterpret_cast<uint16_t*>(lds_all + kSortedBytes);                  // [kListN] NARROW, per whole granule of the tile: 24 x its granule of the layout
+    [[maybe_unused]] uint32_t* const gal = reinterpret_cast<uint32_t*>(lds_all + kSortedBytes + (NARROW ? kListN * 2 : 0));   // [kListMax] ... and slot / 8 in `out` it is stored to
+    uint32_t* const dh = reinterpret_cast<uint32_t*>(lds_all + kSortedBytes + kListBytes);       // new keys of this tile per digit (rank counter); 32 spare ones for windows that are not valid
     uint32_t* const tab = dh + 288;              // per bucket: the byte offset in `sorted` of its first NEW key (stream start + keys carried in); spare ones: kGarb
-    uint32_t* const gaddr = tab + 288;           // [kNG] per granule of `sorted`: slot / 8 in `out` it is stored to, or kSkip
+    [[maybe_unused]] uint32_t* const gaddr = tab + 288;           // [kNG] (8-byte form) per granule of `sorted`: slot / 8 in `out` it is stored to, or kSkip
     uint32_t* const sh_scan = gaddr + kNG;       // [kWaves + 1]
     uint32_t& sh_ovf = sh_scan[6];
     uint32_t* const lh = sh_scan + 8;            // [256 NH] histograms of the next NH digits
@@ -702,7 +727,13 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
     if (NH > 1) lh[tid + 256] = 0;
     dh[tid] = 0;
     if (tid < 32) { dh[256 + tid] = 0; tab[256 + tid] = kGarb << (NARROW ? 2 : 3); }
-    if (tid == 0) { sh_ovf = 0; gaddr[kSlots / kGran] = kSkip; }
+    if (tid == 0) sh_ovf = 0;
+    if constexpr (NARROW)
+    {
+        // (every entry of the store list names a granule of the layout from the start: see kListN)
+        for (uint32_t j = tid; j < kListN / 2; j += kTB) reinterpret_cast<uint32_t*>(lgl)[j] = 0;
+    }
+    else if (tid == 0) gaddr[kSlots / kGran] = kSkip;
     const uint64_t my_start = gt->reg_start[tid], my_cap = gt->reg_cap[tid];
     const uint32_t B = 1u << blk_log2;
     const uint32_t bits = 2 * len;
@@ -1159,6 +1190,7 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
         // with carried keys when there are enough of them (b + carried >= 8: the rest stay in the registers where
         // they are); otherwise it is not stored and its b keys join the carried ones after the scatter.
         uint32_t total_slots = 0, part_at = 0, absorb = 0;
+        [[maybe_unused]] uint32_t whole = 0;         // (NARROW) whole granules of the tile: the length of the store list
         if constexpr (NARROW)
         {
             // carried + new keys of the bucket: whole granules leave, the rest is the granule carried on
@@ -1166,7 +1198,11 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
             uint32_t tot = ccnt + cnt;
             uint32_t fg = (tot * 0xAAABu) >> 19;                       // tot / 12 (tot < 2^13)
             uint32_t rest = tot - 12u * fg;
-            uint32_t g_at = block_excl_scan_open_u32(fg + (rest ? 1u : 0u), sh_scan, &total_slots);      // (granules; the barrier behind phase C closes it)
+            // one scan for two prefixes: the granules of the layout in front of the bucket's piece (low half) and the whole
+            // ones among them, the bucket's place in the store list (high half)
+            uint32_t both = 0;
+            uint32_t at2 = block_excl_scan_open_u32(((fg + (rest ? 1u : 0u)) | (fg << 16)), sh_scan, &both);      // (granules; the barrier behind phase C closes it)
+            total_slots = both & 0xFFFFu;
             GOSS_STAMP(6);
             dh[tid] = 0;                               // ready for the next tile (its ranking starts behind two barriers)
             if (tid < 32) dh[256 + tid] = 0;
@@ -1196,7 +1232,7 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
                 }
                 else wpos += fl;
             };
-            if (total_slots > nr_capg)
+            if (total_slots > min(nr_capg, kSlots / 12u))
             {
                 // (more granules than the layout holds -- never with keys that spread: see kSlots.  Every carried granule
                 // goes to its bucket short, its chunks saying how many keys they hold, and the tile is laid out without)
@@ -1210,8 +1246,11 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
                 tot = cnt;
                 fg = (tot * 0xAAABu) >> 19;
                 rest = tot - 12u * fg;
-                g_at = block_excl_scan_open_u32(fg + (rest ? 1u : 0u), sh_scan, &total_slots);
+                at2 = block_excl_scan_open_u32(((fg + (rest ? 1u : 0u)) | (fg << 16)), sh_scan, &both);
+                total_slots = both & 0xFFFFu;
             }
+            whole = both >> 16;
+            const uint32_t g_at = at2 & 0xFFFFu, w_at = at2 >> 16;
             const uint32_t fl = fg << 3;               // 8-byte slots stored now
             part_at = 12u * (g_at + fg);               // the granule carried on, if any
             take_room(fl);
@@ -1219,12 +1258,12 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
             {
                 const uint32_t t8 = thr >> 3;
                 const uint32_t yb = tby - t8;
+                // the bucket's entries of the store list: its whole granules, the first fg of its piece
 #pragma unroll
                 for (uint32_t g = 0; g < 3; ++g)
-                    if (g < fg) gaddr[g_at + g] = (g < t8 ? tbx : yb) + g;
+                    if (g < fg) { gal[w_at + g] = (g < t8 ? tbx : yb) + g; lgl[w_at + g] = (uint16_t)(24u * (g_at + g)); }
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (uint32_t g = 3; g < fg; ++g) gaddr[g_at + g] = (g < t8 ? tbx : yb) + g;
-                if (rest) gaddr[g_at + fg] = kSkip;
+                for (uint32_t g = 3; g < fg; ++g) { gal[w_at + g] = (g < t8 ? tbx : yb) + g; lgl[w_at + g] = (uint16_t)(24u * (g_at + g)); }
             }
             // the carried granule to the head of the piece (phase A's arrays in `sorted` are dead: every thread is past
             // phase B); whole, the new keys follow behind the `ccnt` that count.  (Not without carried keys: a bucket that
@@ -1396,30 +1435,45 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
             }
             if (sh_ovf == 0)
             {
-                // a lane stores chunk c = tid & 3 of a granule: slots c, c + 4, c + 8 -- three remainders and their digits.
-                // Chunk i = tid + 256 u of a round lies 3 072 u bytes (remainders) / 1 536 u bytes (digits) / 256 u bytes
-                // (granule table) behind chunk tid: every LDS read of a round is one address register + a constant
+                // chunk i of the tile is chunk i & 3 of the granule that entry i >> 2 of the store list names: slots c, c + 4,
+                // c + 8 of it -- three remainders and their digits.  Only whole granules are listed, so every chunk that is
+                // read is stored, but for the last round's tail.  A lane's chunks of a round are tid + 256 u: its list
+                // entries lie 256 u bytes (addresses) / 128 u bytes (offsets) behind entry tid / 4, one address register + a
+                // constant each.  All entries of a round are read first, then the data they point to, then the stores.
                 constexpr int kCh = GOSS_E1_NCH;                             // chunks per lane and round
-                static_assert(kSlots / 12u * 4u <= 2624u + 64u && kCh == 4, "the reads past the layout stay inside the allocation (kNG)");
-                const uint32_t nchunk = total_slots << 2;                    // (total_slots: granules of the layout)
-                const uint32_t c = tid & 3u;
-                Key1* const lane_out = out + 2u * c;
-                const unsigned char* lp = lds_all + (12u * tid - 8u * c);                  // remainder of slot c of granule tid / 4
-                const unsigned char* dp = lds_all + kDigBase + (6u * tid - 4u * c);
-                const unsigned char* gp = reinterpret_cast<const unsigned char*>(gaddr) + (tid & ~3u);
-                for (uint32_t base = 0; base < nchunk; base += kCh * kTB, lp += 12u * kCh * kTB, dp += 6u * kCh * kTB, gp += kCh * kTB)
+                static_assert(kListN % (64 * kCh) == 0 && kListN >= kListMax, "whole rounds of entries: no read past lgl");
+                const uint32_t nchunk = whole << 2;
+                // (what the loop derives from the thread's number is worked out here, tile by tile: held from tile to tile
+                // it takes registers that the ranking phase has not got -- the forms at 168 VGPRs spill for each)
+                uint32_t t = tid;
+                asm volatile("" : "+v"(t));
+                const uint32_t c2 = (t & 3u) << 1;                            // 2 c: the digit of slot c, in bytes
+                Key1* const lane_out = out + c2;
+                const unsigned char* ep = reinterpret_cast<const unsigned char*>(lgl) + ((t >> 2) << 1);
+                const unsigned char* gp = reinterpret_cast<const unsigned char*>(gal) + (t & ~3u);
+                for (uint32_t base = 0; base < nchunk; base += kCh * kTB, gp += kCh * kTB, ep += kCh * kTB / 2)
                 {
-                    uint32_t r0[kCh], r1[kCh], r2[kCh], d0[kCh], d1[kCh], d2[kCh], ga[kCh];
+                    uint32_t r0[kCh], r1[kCh], r2[kCh], d0[kCh], d1[kCh], d2[kCh], ga[kCh], lo[kCh];
 #pragma unroll
                     for (int u = 0; u < kCh; ++u)
                     {
-                        r0[u] = *reinterpret_cast<const uint32_t*>(lp + 3072 * u);
-                        r1[u] = *reinterpret_cast<const uint32_t*>(lp + 3072 * u + 16);
-                        r2[u] = *reinterpret_cast<const uint32_t*>(lp + 3072 * u + 32);
-                        d0[u] = *reinterpret_cast<const uint16_t*>(dp + 1536 * u);
-                        d1[u] = *reinterpret_cast<const uint16_t*>(dp + 1536 * u + 8);
-                        d2[u] = *reinterpret_cast<const uint16_t*>(dp + 1536 * u + 16);
+                        lo[u] = *reinterpret_cast<const uint16_t*>(ep + 128 * u);
                         ga[u] = *reinterpret_cast<const uint32_t*>(gp + 256 * u);
+                    }
+#pragma unroll
+                    for (int u = 0; u < kCh; ++u) asm volatile("" : "+v"(lo[u]));
+#pragma unroll
+                    for (int u = 0; u < kCh; ++u)
+                    {
+                        const uint32_t x = lo[u] + c2;                        // digit of slot c of the granule; its remainder lies at twice that
+                        const unsigned char* const dp = lds_all + kDigBase + x;
+                        const unsigned char* const lp = lds_all + 2u * x;
+                        r0[u] = *reinterpret_cast<const uint32_t*>(lp);
+                        r1[u] = *reinterpret_cast<const uint32_t*>(lp + 16);
+                        r2[u] = *reinterpret_cast<const uint32_t*>(lp + 32);
+                        d0[u] = *reinterpret_cast<const uint16_t*>(dp);
+                        d1[u] = *reinterpret_cast<const uint16_t*>(dp + 8);
+                        d2[u] = *reinterpret_cast<const uint16_t*>(dp + 16);
                     }
 #pragma unroll
                     for (int u = 0; u < kCh; ++u) asm volatile("" : "+v"(r0[u]), "+v"(r1[u]), "+v"(r2[u]), "+v"(d0[u]), "+v"(d1[u]), "+v"(d2[u]), "+v"(ga[u]));
@@ -1428,7 +1482,7 @@ __global__ __launch_bounds__(kTB, GOSS_E1_OCC) void extract1_part_kernel(const u
                     for (int u = 0; u < kCh; ++u)
                     {
                         const uint4 ch = make_uint4(r0[u], r1[u], r2[u], d0[u] | (d1[u] << 10) | (d2[u] << 20) | (3u << 30));
-                        if (ga[u] != kSkip && tid + u * kTB < left) *reinterpret_cast<uint4*>(lane_out + ((uint64_t)ga[u] << 3)) = ch;
+                        if (tid + u * kTB < left) *reinterpret_cast<uint4*>(lane_out + ((uint64_t)ga[u] << 3)) = ch;
                     }
                 }
             }

@@ -37,6 +37,7 @@ SYMBOLS = [
     "goss_gpu_entries_build", "goss_gpu_entries_release", "goss_gpu_entries_length", "goss_gpu_entries_end_rank",
     "goss_gpu_components_mark_host", "goss_gpu_components_mark_device", "goss_gpu_components_build", "goss_gpu_components_table",
     "goss_gpu_components_labels", "goss_gpu_components_keep", "goss_gpu_components_release",
+    "goss_gpu_components_grow", "goss_gpu_components_marks", "goss_gpu_components_keep_marked",
 ]
 
 # every symbol include/goss_gpu_match.h declares (reads against an object)
@@ -92,8 +93,18 @@ COMPONENTS_MARKED = 1
 COMPONENT_NONE = 0xFFFFFFFF
 
 
+# goss_gpu_grow_info, in the order of its fields
+GROW_INFO_FIELDS = (("marked_before", C.c_uint64), ("mirrored", C.c_uint64), ("marked_total", C.c_uint64), ("passes_run", C.c_uint32),
+                    ("launches", C.c_uint32), ("ms_link", C.c_float), ("ms_label", C.c_float), ("ms_grow", C.c_float))
+GROW_LINEAR_PATHS = 1
+
+
 class MarkInfo(C.Structure):
     _fields_ = list(MARK_INFO_FIELDS)
+
+
+class GrowInfo(C.Structure):
+    _fields_ = list(GROW_INFO_FIELDS)
 
 
 class ComponentsInfo(C.Structure):
@@ -768,6 +779,37 @@ class Context:
         kept = C.c_uint64()
         self._L.goss_gpu_components_keep.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         self._check(self._L.goss_gpu_components_keep(self._h, edge_rank, C.byref(kept)))
+        if getattr(self, "counts", None) is not None:
+            self.counts.distinct = int(kept.value)       # what result() copies
+        return int(kept.value)
+
+    def grow_marks(self, radius=1, linear_paths=False):
+        """After mark_reads: the marks take in their mirror image and grow by `radius` passes as `goss build-subgraph`
+        grows them -- by nodes, or with linear_paths by linear paths (goss_gpu_components_grow).  Returns (info dict,
+        added): added[i] = the edges pass i brought, 0 for the passes that were not run because nothing could follow.
+        The marks stay held; components(marked=True), marks() and keep_marked() work on them."""
+        inf = GrowInfo()
+        added = (C.c_uint64 * max(radius, 1))()
+        self._L.goss_gpu_components_grow.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(GrowInfo)]
+        self._check(self._L.goss_gpu_components_grow(self._h, radius, GROW_LINEAR_PATHS if linear_paths else 0, added, C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in GROW_INFO_FIELDS}, [int(a) for a in added[:radius]]
+
+    def marks(self, first=0, count=None):
+        """The marks as they are now: np.bool_[M], one per edge in rank order (goss_gpu_components_marks)."""
+        import numpy as np
+        if count is None:
+            count = self.result_ptrs()[2] - first
+        out = np.zeros(count, dtype=np.uint8)
+        self._L.goss_gpu_components_marks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_components_marks(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out.astype(np.bool_)
+
+    def keep_marked(self):
+        """The result becomes its marked edges (goss_gpu_components_keep_marked); what was held is given back.
+        Returns the number of edges kept; a following emit() writes the subgraph."""
+        kept = C.c_uint64()
+        self._L.goss_gpu_components_keep_marked.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self._check(self._L.goss_gpu_components_keep_marked(self._h, C.byref(kept)))
         if getattr(self, "counts", None) is not None:
             self.counts.distinct = int(kept.value)       # what result() copies
         return int(kept.value)

@@ -5044,6 +5044,59 @@ int goss_gpu_components_release(goss_gpu_ctx* c)
     return GOSS_OK;
 }
 
+int goss_gpu_components_grow(goss_gpu_ctx* c, uint32_t radius, uint32_t flags, uint64_t* added, goss_gpu_grow_info* out)
+{
+    if (!c || !out || (flags & ~(uint32_t)GOSS_GROW_LINEAR_PATHS)) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (added) std::fill(added, added + radius, (uint64_t)0);
+    if (const int st = graph_pass_state(c, "components_grow", "marks are grown in a graph", "growing the marks belongs between finish and emit")) return st;
+    if (c->held.kind != Held::Components || !c->cmp_marks)
+    {
+        c->last_error = "components_grow needs goss_gpu_components_mark_host / _device before it";
+        return GOSS_ERR_STATE;
+    }
+    return build_held(c, Held::Components, out, [&]() {
+        components_drop_built(c);
+        components_grow(c, radius, flags, added, out);
+    }, true);
+}
+
+int goss_gpu_components_marks(goss_gpu_ctx* c, uint64_t first, uint64_t count, uint8_t* out)
+{
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind != Held::Components || !c->cmp_marks) { c->last_error = "components_marks needs goss_gpu_components_mark_host / _device before it"; return GOSS_ERR_STATE; }
+    if (first > c->M || count > c->M - first) { c->last_error = "components_marks: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    c->keep_held = true;
+    return guarded(c, [&]() {
+        if (!count) return;
+        const uint64_t w0 = first / 32, w1 = (first + count + 31) / 32;
+        std::vector<uint32_t> words((size_t)(w1 - w0));
+        HIP_TRY(hipMemcpyAsync(words.data(), c->cmp_marks + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (uint64_t i = 0; i < count; ++i)
+        {
+            const uint64_t b = first + i;
+            out[i] = (uint8_t)((words[(size_t)(b / 32 - w0)] >> (b & 31u)) & 1u);
+        }
+    });
+}
+
+int goss_gpu_components_keep_marked(goss_gpu_ctx* c, uint64_t* kept)
+{
+    if (!c || !kept) return GOSS_ERR_INVALID_ARG;
+    *kept = 0;
+    if (const int st = graph_pass_state(c, "components", "the marked edges are kept of a graph", "keeping the marked edges belongs between finish and emit")) return st;
+    if (c->held.kind != Held::Components || !c->cmp_marks)
+    {
+        c->last_error = "components_keep_marked needs goss_gpu_components_mark_host / _device before it";
+        return GOSS_ERR_STATE;
+    }
+    c->keep_held = true;                                 // (the marks are read first; components_keep_marked gives them back)
+    const int rc = guarded(c, [&]() { *kept = components_keep_marked(c); });
+    if (c->held.kind != Held::None) release_held(c);
+    return rc;
+}
+
 int goss_gpu_emit_count_bits(goss_gpu_ctx* c, uint32_t mask, const char* suffix)
 {
     if (!c || !suffix || !mask) return GOSS_ERR_INVALID_ARG;

@@ -25,3 +25,4 @@
 #include "kernels_entries.hpp"
 #include "kernels_match.hpp"
 #include "kernels_components.hpp"
+#include "kernels_subgraph.hpp"

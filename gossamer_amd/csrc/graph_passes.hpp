@@ -1,5 +1,5 @@
 // graph_passes.hpp -- the passes over the decoded, sorted edge list of a finished graph: prune-tips, the linear segments
-// of print-contigs, the EntryEdgeSet of build-entry-edge-set.
+// of print-contigs, the EntryEdgeSet of build-entry-edge-set, count-components, build-subgraph.
 // Part of goss_gpu.hip (included there, inside its unnamed namespace, once guarded() and the emit helpers it calls are
 // defined).  Two steps are shared and live here once each:
 //
@@ -8,8 +8,9 @@
 //                bounded walk and pointer doubling (kernels_contigs.hpp), with or without the multiplicities
 //
 // prune_tips_once is link_graph and the tip walk; segments_build and entries_build are link_graph, rank_lists and
-// their own records; components_build and components_keep are link_graph and a union-find over the links.  What a
-// build leaves behind for later calls is the context's one held result (build_held).
+// their own records; components_build and components_keep are link_graph and a union-find over the links;
+// components_grow is link_graph and the passes of build-subgraph over the marks.  What a build leaves behind for
+// later calls is the context's one held result (build_held).
 #pragma once
 
 // Temporaries of one call, given back on every way out (an exception included).
@@ -728,6 +729,162 @@ uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
 {
     PhaseTimer t(c, GOSS_T_REDUCE, c->M);
     const uint64_t m = c->words == 1 ? components_keep<Key1>(c, e) : components_keep<Key2>(c, e);
+    t.stop();
+    return m;
+}
+
+// ---- build-subgraph -------------------------------------------------------------------------------------------------
+
+constexpr uint32_t kGrowReadBack = 16;                 // passes queued between two looks at what they added
+
+// The marks become their mirror image's union and grow by `radius` passes (GossCmdBuildSubgraph.cc:95-128, 178-199;
+// kernels_subgraph.hpp states what a pass is in either mode).  The passes are queued kGrowReadBack at a time without
+// a wait between them; the host then reads what each added and stops once a pass added nothing -- nothing can follow
+// an empty frontier -- and the entries of `added` it did not run stay 0.  The frontier, the fringe and, with
+// GOSS_GROW_LINEAR_PATHS, the segment labels and their hit flags are working arrays under an ArenaScope; the marks
+// stay held, now grown.
+template <class K>
+void components_grow(goss_gpu_ctx* c, uint32_t radius, uint32_t flags, uint64_t* added, goss_gpu_grow_info* out)
+{
+    goss_gpu_grow_info inf{};
+    const bool linear = (flags & GOSS_GROW_LINEAR_PATHS) != 0;
+    const uint64_t n64 = c->M, words = c->cmp_mark_words;
+    inf.marked_before = inf.mirrored = inf.marked_total = c->cmp_marked;
+    if (n64 == 0) { *out = inf; return; }
+    {
+        // the links, the frontier and the fringe; the segment labels (4) and their hit flags (1)
+        const uint64_t need = link_bytes(c, "components_grow") + words * 8 + (linear ? n64 * 5 : 0) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    uint32_t* I = c->cmp_marks;
+    uint32_t* P = (uint32_t*)c->arena.temp(words * 4);
+    uint32_t* fringe = (uint32_t*)c->arena.temp(words * 4);
+    unsigned long long* d_added = (unsigned long long*)c->arena.temp(kGrowReadBack * 8);
+    CompReport* d_rep = (CompReport*)c->arena.temp(sizeof(CompReport));
+    CompReport* h = pinned_report<CompReport>(c);
+    uint64_t* hx = pinned_words(c);
+    static_assert(kGrowReadBack * 8 <= 128, "pinned scratch");
+
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    const GraphLinks<K> l = link_graph<K>(c, "components_grow", nullptr, [&](const GraphLinks<K>&) { HIP_TRY(hipEventRecord(ev.e[1], c->stream)); });
+    const uint32_t n = l.n;
+    const dim3 block = l.block;
+    const dim3 few((uint32_t)std::min<uint64_t>(grid_for(words, kTB), kTipsGridBlocks));
+
+    uint32_t* label = nullptr;
+    uint8_t* hit = nullptr;
+    if (linear)
+    {
+        label = (uint32_t*)c->arena.temp(n64 * 4);
+        hit = (uint8_t*)c->arena.temp(n64);
+        HIP_TRY(hipMemsetAsync(hit, 0, n64, c->stream));
+        hipLaunchKernelGGL(components_init_kernel, l.grid, block, 0, c->stream, (const uint32_t*)nullptr, n, label);
+        hipLaunchKernelGGL(subgraph_hook_kernel, l.grid, block, 0, c->stream, (const uint32_t*)l.rcr, (const uint32_t*)l.nxt,
+                           (const uint8_t*)l.info, n, label);
+        hipLaunchKernelGGL(components_flatten_kernel, l.grid, block, 0, c->stream, label, n, (uint64_t*)nullptr);
+        inf.launches += 3;
+    }
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(CompReport), c->stream));
+    HIP_TRY(hipMemsetAsync(fringe, 0, words * 4, c->stream));
+    hipLaunchKernelGGL(subgraph_mirror_kernel, l.grid, block, 0, c->stream, (const uint32_t*)l.rcr, n, I);
+    hipLaunchKernelGGL(components_popcount_kernel, few, block, 0, c->stream, (const uint32_t*)I, words, d_rep);
+    inf.launches += 2;
+    HIP_TRY(hipMemcpyAsync(P, I, words * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(CompReport), hipMemcpyDeviceToHost, c->stream));
+    sync_checked(c);
+    // from here on the marks are the mirrored ones whatever happens: the count follows them
+    inf.mirrored = inf.marked_total = c->cmp_marked = h->marked;
+
+    uint64_t total = inf.mirrored;                         // (once every edge is marked no pass can add)
+    for (uint32_t first = 0; first < radius && total < n64; first += kGrowReadBack)
+    {
+        const uint32_t cnt = std::min(kGrowReadBack, radius - first);
+        HIP_TRY(hipMemsetAsync(d_added, 0, kGrowReadBack * 8, c->stream));
+        for (uint32_t p = 0; p < cnt; ++p)
+        {
+            if (linear)
+            {
+                hipLaunchKernelGGL(subgraph_hit_kernel, few, block, 0, c->stream, (const uint32_t*)P, words, (const uint32_t*)l.rcr,
+                                   (const uint32_t*)label, hit);
+                hipLaunchKernelGGL(subgraph_cover_kernel, l.grid, block, 0, c->stream, (const uint32_t*)l.rcr, (const uint32_t*)l.nxt,
+                                   (const uint8_t*)l.info, (const uint32_t*)label, (const uint8_t*)hit, n, I, fringe);
+                hipLaunchKernelGGL(subgraph_settle_kernel<true>, few, block, 0, c->stream, I, P, fringe, words, d_added + p);
+                inf.launches += 3;
+            }
+            else
+            {
+                hipLaunchKernelGGL(subgraph_push_kernel, few, block, 0, c->stream, (const uint32_t*)P, words, (const uint32_t*)l.rcr,
+                                   (const uint32_t*)l.nxt, (const uint8_t*)l.info, (const uint32_t*)I, fringe);
+                hipLaunchKernelGGL(subgraph_settle_kernel<false>, few, block, 0, c->stream, I, P, fringe, words, d_added + p);
+                inf.launches += 2;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(hx, d_added, kGrowReadBack * 8, hipMemcpyDeviceToHost, c->stream));
+        sync_checked(c);
+        inf.passes_run += cnt;
+        bool dry = false;
+        for (uint32_t p = 0; p < cnt; ++p)
+        {
+            const uint64_t a = linear ? hx[p] - total : hx[p];     // (linear-path mode counts I itself)
+            total += a;
+            if (added) added[first + p] = a;
+            dry = dry || a == 0;
+        }
+        c->cmp_marked = inf.marked_total = total;
+        if (dry) break;
+    }
+    HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    sync_checked(c);
+    float* ms[3] = {&inf.ms_link, &inf.ms_label, &inf.ms_grow};
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    if (!linear) inf.ms_label = 0;                       // (two events with nothing between them)
+    *out = inf;
+}
+
+void components_grow(goss_gpu_ctx* c, uint32_t radius, uint32_t flags, uint64_t* added, goss_gpu_grow_info* out)
+{
+    if (c->words == 1) components_grow<Key1>(c, radius, flags, added, out); else components_grow<Key2>(c, radius, flags, added, out);
+}
+
+// The result becomes its marked edges (what build-subgraph writes, GossCmdBuildSubgraph.cc:201-209): ~marks as the
+// removal bitmap, the compaction of prune-tips.  The bitmap is a temporary; once it is queued the marks -- the held
+// result -- are given back, so that the survivors may take the permanent room.  Nothing of the result changes before
+// the survivors are complete.
+template <class K>
+uint64_t components_keep_marked(goss_gpu_ctx* c)
+{
+    const uint64_t n64 = c->M;
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    const uint64_t zap_words = ntiles * (kRedTile / 32);
+    {
+        // the bitmap, the tile counts, and the survivors once more while they are compacted
+        const uint64_t need = zap_words * 4 + (ntiles + 1) * 8 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    if (n64 == 0) { release_held(c); return 0; }
+    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
+    hipLaunchKernelGGL(subgraph_zap_kernel, dim3(grid_for(zap_words, kTB)), dim3(kTB), 0, c->stream, (const uint32_t*)c->cmp_marks,
+                       c->cmp_mark_words, n64, zap, zap_words);
+    release_held(c);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), dim3(kTB), 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
+    uint64_t* hm = pinned_words(c);
+    scan_with_total(c, tile_counts, ntiles, hm);
+    sync_checked(c);
+    const uint64_t m = hm[0];
+    if (m != n64) replace_result<K>(c, (const K*)c->res_keys, c->res_counts, n64, zap, tile_counts, ntiles, m);
+    return m;
+}
+
+uint64_t components_keep_marked(goss_gpu_ctx* c)
+{
+    PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+    const uint64_t m = c->words == 1 ? components_keep_marked<Key1>(c) : components_keep_marked<Key2>(c);
     t.stop();
     return m;
 }

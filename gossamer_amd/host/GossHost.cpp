@@ -1928,6 +1928,7 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  print-contigs    print all the non-branching paths in the given assembly graph\n"
               << "  build-entry-edge-set  build an entry edge set for a graph\n"
               << "  count-components  count connected components in the graph represented by the given reads\n"
+              << "  build-subgraph   generate a subgraph of an existing graph\n"
               << "  extract-reads    extract reads which map on to a graph\n"
               << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n";
     if (t)
@@ -2221,6 +2222,67 @@ int gossMain(int argc, char* argv[])
             try
             {
                 GossCmdCountComponents cmd(in, outName, fastas, fastqs, lines);
+                cmd(cxt);
+            }
+            catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "build-subgraph")
+        {
+            // GossCmdFactoryBuildSubgraph::create (GossCmdBuildSubgraph.cc:215-268)
+            static const OptDef kSubgraph[] = {
+                {"graph-in", "G", kStrings, "name of the input graph object"},
+                {"graph-out", "O", kString, "name of the output graph object"},
+                {"fasta-in", "I", kStrings, "input file in FASTA format"},
+                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
+                {"line-in", "", kStrings, "input file with one sequence per line"},
+                {"buffer-size", "B", kU64, "maximum size (in GB) for in-memory buffers (default: 2)"},
+                {"radius", "", kU64, "distance of the furthest node to include from any source"},
+                {"linear-paths", "", kFlag, "interpret radius in terms of linear paths, not nodes"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            for (auto& d : kSubgraph) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            std::string in, outName;
+            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+            else if (opts.strs("graph-in").size() != 1)
+            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+            else in = opts.str("graph-in");
+            chk.mandatoryOut("graph-out", outName);
+            strings fastas, fastqs, lines;
+            chk.repeatingIn("fasta-in", fastas);
+            chk.repeatingIn("fastq-in", fastqs);
+            chk.repeatingIn("line-in", lines);
+            uint64_t radius = 1, B = 2;
+            chk.optionalU64("radius", radius);
+            chk.optionalU64("buffer-size", B);
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0, budgetGb = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
+            try
+            {
+                GossCmdBuildSubgraph cmd(in, outName, fastas, fastqs, lines, radius, opts.count("linear-paths") != 0, B << 30);
                 cmd(cxt);
             }
             catch (Error& e) { e.cmd = cmdName; throw; }

@@ -309,6 +309,20 @@ private:
     const std::string mIn, mOut; const strings mFastas, mFastqs, mLines;
 };
 
+// GossCmdBuildSubgraph (GossCmdBuildSubgraph.{hh,cc}): the part of a graph within pRadius steps -- nodes, or with
+// pLinearPaths linear paths -- of the edges that the (K + 1)-windows of the given reads and their reverse complements
+// touch, written as a graph.  pBufferSize is accepted and unused, as in the reference.
+class GossCmdBuildSubgraph {
+public:
+    GossCmdBuildSubgraph(const std::string& pIn, const std::string& pOut, const strings& pFastas, const strings& pFastqs, const strings& pLines,
+                         uint64_t pRadius, bool pLinearPaths, uint64_t pBufferSize)
+        : mIn(pIn), mOut(pOut), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines), mRadius(pRadius), mLinearPaths(pLinearPaths),
+          mBufferSize(pBufferSize) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const strings mFastas, mFastqs, mLines; const uint64_t mRadius; const bool mLinearPaths; const uint64_t mBufferSize;
+};
+
 // GossCmdExtractReads (GossCmdExtractReads.{hh,cc}): the reads with at least one (K + 1)-mer that is an edge of the graph, as
 // parsed, one per line, in input order (line files, then FASTA, then FASTQ).
 class GossCmdExtractReads {

@@ -1144,6 +1144,68 @@ void GossCmdCountComponents::operator()(const GossCmdContext& pCxt)
     else g.check(goss_gpu_components_release(g.h), "releasing the components");
 }
 
+// GossCmdBuildSubgraph::operator() (GossCmdBuildSubgraph.cc:132-212).  The reads are parsed and handed over as
+// count-components hands them over; the device marks the forward windows, adds the mirror image (the reference looks
+// up every window's reverse complement too, ReverseComplementAdapter), grows the marks and compacts the graph to them
+// (goss_gpu_components_grow / _keep_marked).  The per-pass lines are the reference's; a pass the device did not run,
+// because nothing can follow a pass that added nothing, identified 0 edges.
+void GossCmdBuildSubgraph::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    (void)mBufferSize;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+
+    const size_t cap = matchBatchBytes(pCxt);
+    std::vector<char> buf;
+    goss_gpu_mark_info mi{};
+    uint64_t reads = 0, windows = 0, hits = 0;
+    auto flush = [&]() {
+        g.check(goss_gpu_components_mark_host(g.h, buf.data(), buf.size(), &mi), "marking a batch of reads");
+        windows += mi.windows; hits += mi.hits;
+        buf.clear();
+    };
+    ReadSink sink = [&](const char* seq, size_t len) {
+        if (!buf.empty() && buf.size() + len + 1 > cap) flush();
+        buf.insert(buf.end(), seq, seq + len);
+        buf.push_back('\n');
+        ++reads;
+    };
+    for (auto& f : mLines) parseLines(f, sink);
+    for (auto& f : mFastas) parseFasta(f, sink);
+    for (auto& f : mFastqs) parseFastq(f, sink);
+    if (reads == 0) throw Error::General("No valid reads.");                  // ReverseComplementAdapter.hh:77-86
+    flush();
+    log(info, "windows: " + num(windows) + ", of them edges: " + num(hits) + ", edges marked: " + num(mi.marked_total));
+
+    // Growing by a and then by b is growing by a + b (the frontier of a call is all that is marked, whose inner edges
+    // have nothing left to add), so the passes are asked for 4096 at a time and no further once one added nothing.
+    const uint32_t flags = mLinearPaths ? GOSS_GROW_LINEAR_PATHS : 0u;
+    std::vector<uint64_t> added;
+    goss_gpu_grow_info inf{};
+    uint64_t pass = 0, mirrored = mi.marked_total, total = mi.marked_total;
+    do
+    {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(mRadius - pass, 4096);
+        added.assign(cnt, 0);
+        g.check(goss_gpu_components_grow(g.h, cnt, flags, added.data(), &inf), "growing the marks");
+        if (pass == 0) mirrored = inf.mirrored;
+        total = inf.marked_total;
+        for (uint32_t i = 0; i < cnt; ++i) log(info, "pass " + num(pass + i) + " identified " + num(added[i]) + " additional edges.");
+        pass += cnt;
+    } while (pass < mRadius && added.back() != 0);
+    log(info, "edges with their mirror images: " + num(mirrored) + ", in the subgraph: " + num(total));
+
+    uint64_t kept = 0;
+    g.check(goss_gpu_components_keep_marked(g.h, &kept), "keeping the marked edges");
+    g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, elapsed(t0));
+}
+
 void GossCmdMergeKmerSets::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, false, mIns, mMaxMerge, mOut); }
 void GossCmdMergeGraphs::operator()(const GossCmdContext& pCxt) { runMerge(pCxt, true, mIns, mMaxMerge, mOut); }
 

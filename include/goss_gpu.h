@@ -728,6 +728,51 @@ int goss_gpu_components_keep(goss_gpu_ctx* ctx, uint64_t edge_rank, uint64_t* ke
 int goss_gpu_components_release(goss_gpu_ctx* ctx);
 
 /*
+ * Between finish and emit, graph mode, after goss_gpu_components_mark_host / _device: the marks grown by a
+ * radius, as `goss build-subgraph` grows them (GossCmdBuildSubgraph.cc:95-212, `radius` serial scans over a
+ * bitset of all edges there), and the result reduced to the marked edges.
+ *
+ * Marks: the reference looks up every (K+1)-window of every read and its reverse complement
+ * (ReverseComplementAdapter, :178-191; the window rules are those of goss_gpu_components_mark_*), and its
+ * graph is symmetric (:141-146).  grow therefore begins with the mirror image: I[rc(i)] |= I[i].
+ * Node mode (SingleFollower, :56-72): P = I; `radius` times, F = the edges not in I that leave to(e) or
+ * enter from(e) for some e in P (the other edges out of from(e) and into to(e) do not count), I |= F, P = F;
+ * added[pass] = |F|, what the reference logs as "pass <i> identified <n> additional edges.".
+ * Linear-path mode (GOSS_GROW_LINEAR_PATHS; SegmentFollower, :74-92): a segment is a maximal set of edges
+ * joined through nodes with exactly one edge in and one out (Graph::linearPath from e and from rc(e),
+ * Graph.tcc:19-46); a cycle of such nodes is one segment.  Per pass every segment that holds an edge of P,
+ * and its mirror segment, joins I whole; F = the edges still outside I with a predecessor or a successor in
+ * such a segment; I |= F, P = F; added[pass] = the growth of I, the covered segments included.  The edges of
+ * the last pass stay single edges.  The reference's next frontier depends on its scan order (it assigns
+ * fringe[k] = !interesting[k] while `interesting` changes, :65, :85-88); I after every pass does not.
+ * Radius 0 gives the mirrored marks only.
+ *
+ * grow: the labels and the table of an earlier build are dropped, as a mark call drops them; the marks stay
+ * held, now grown, and goss_gpu_components_build(GOSS_COMPONENTS_MARKED) works on them.  The passes are
+ * queued 16 at a time; once a pass added nothing no further pass is launched, and the entries of `added`
+ * that were not run are 0 (passes_run: the passes launched).  Working room: the link arrays (9 bytes per
+ * edge and the bucket table), a quarter of a byte per edge, and 5 bytes per edge in linear-path mode.
+ * marks: a byte per edge, 0 or 1, any sub-range.
+ * keep_marked: the result becomes its marked edges in rank order with their multiplicities (:201-209), by
+ * the compaction of goss_gpu_prune_tips; whatever is held is given back; a following goss_gpu_emit writes
+ * Graph::Builder(K, out, fac, *kept) -- the empty graph when nothing is marked.
+ *
+ * GOSS_ERR_STATE: no marks; a k-mer-set context; before finish; after emit.
+ * GOSS_ERR_INVALID_ARG: an unknown flag; a range past the end; an edge without its reverse complement;
+ * multiplicities of 2^32 - 1 or more.
+ * GOSS_ERR_OOM: it does not fit the arena; nothing is held afterwards and the result is intact.
+ */
+#define GOSS_GROW_LINEAR_PATHS 1u
+typedef struct {
+    uint64_t marked_before, mirrored, marked_total; /* bits set: on entry, after the mirror images, after the last pass */
+    uint32_t passes_run, launches;
+    float ms_link, ms_label, ms_grow;              /* HIP-event time; ms_label is 0 in node mode */
+} goss_gpu_grow_info;
+int goss_gpu_components_grow(goss_gpu_ctx* ctx, uint32_t radius, uint32_t flags, uint64_t* added /* radius entries, or NULL */, goss_gpu_grow_info* info);
+int goss_gpu_components_marks(goss_gpu_ctx* ctx, uint64_t first, uint64_t count, uint8_t* out /* a byte per edge */);
+int goss_gpu_components_keep_marked(goss_gpu_ctx* ctx, uint64_t* kept);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */

@@ -150,7 +150,7 @@ template <class K>
 struct FusedChunk {
     static constexpr bool kOne = std::is_same<K, Key1>::value;          // one-word keys
     goss_gpu_ctx* c;
-    const uint8_t* d_bases;
+    ReadSrc src;
     uint64_t nstarts, navail;
     K* ka; uint64_t ka_slots;
     K* kb; uint64_t kb_slots;
@@ -232,6 +232,18 @@ int plan_sample(const FusedChunk<K>& ch, FusedSample* sm)
     return kFusedGoOn;
 }
 
+// The slices of one-word keys from bytes or a packed string, with the plain kernel told where they lie.
+template <int MODE, int P, bool REP>
+void launch_sample1(goss_gpu_ctx* c, const ReadSrc::Launch& in, uint64_t nstarts, uint64_t navail, Key1* ka, uint64_t nsuper, uint64_t slice_tiles,
+                    uint64_t slice_stride)
+{
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper, 2048);
+    with_bool(in.kind == ReadSrc::Packed, [&](auto pk) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, 8, 8, REP, decltype(pk)::value>), dim3(grid), dim3(kTB), 0, c->stream, in.base, in.mis,
+                           nstarts, navail, c->len, ka, c->d_ctr, 0xFFFFFFFFu, nsuper, slice_tiles, slice_stride, in.bad);
+    });
+}
+
 // The sample's keys into ch.ka; returns how many.  rep: one-word k-mer sets in strand-representative space (what the
 // fused kernel counts in, unless the first level computes canonical forms).
 template <class K>
@@ -239,58 +251,42 @@ uint64_t extract_sample(const FusedChunk<K>& ch, const FusedSample& sm, bool rep
 {
     constexpr bool kOne = FusedChunk<K>::kOne;
     goss_gpu_ctx* c = ch.c;
+    const ReadSrc& src = ch.src;
     const uint64_t nstarts = ch.nstarts, navail = ch.navail, nslices = sm.nslices, slice_starts = sm.slice_starts, slice_stride = sm.slice_stride;
     K* ka = ch.ka;
     c->mute_timing = true;
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(ExtractCounters), c->stream));
     {
-        const uintptr_t addr0 = (uintptr_t)ch.d_bases;
-        const uint32_t mis0 = c->rec_mode ? 0u : (uint32_t)(addr0 & 15u);          // (records are taken where they lie)
         // (a packed string whose sample is the whole chunk: the slice kernels below, told to take every tile in turn --
         // they have a packed form, the plain kernels behind extract_dispatch read bytes)
-        const bool whole_pk = nslices == 1 && c->pk.on && !c->rec_mode;
+        const bool whole_pk = nslices == 1 && src.packed();
         const uint64_t slice_tiles = whole_pk ? 0 : slice_starts / sm.super, nsuper = whole_pk ? (nstarts + sm.super - 1) / sm.super : slice_tiles * nslices;
-        if (nslices == 1 && !whole_pk)
-        {
-            c->extract_rep = ch.use_rep && rep;
-            extract_dispatch<K>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka);
-            c->extract_rep = false;
-        }
-        else if (!kOne && c->rec_mode)
+        if (nslices == 1 && !whole_pk) extract_dispatch<K>(c, src, nstarts, navail, ka, ch.use_rep && rep);
+        else if (!kOne && src.records())
         {
             // slices of a super-tile's window slots of two-word records
             const uint64_t P = rec_slots(c);
             const uint64_t slice_groups = std::max<uint64_t>(1, slice_starts / P / kRecGroup);
-            launch_extract_records2(c, (const SkRec2*)ch.d_bases, nstarts / P, (Key2*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
+            launch_extract_records2(c, (const SkRec2*)src.bytes, nstarts / P, (Key2*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
                                     ch.rep_graph && rep);
         }
         else if constexpr (!kOne)
         {
-            if (ch.graph_mode) launch_extract2<1, 4, 8>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka, slice_tiles, slice_stride, nsuper);
-            else launch_extract2<0, 8, 8>(c, (const uint8_t*)(addr0 - mis0), mis0, nstarts, navail, ka, slice_tiles, slice_stride, nsuper, ch.rep_graph && rep);
+            if (ch.graph_mode) launch_extract2<1, 4, 8>(c, src, nstarts, navail, ka, slice_tiles, slice_stride, nsuper);
+            else launch_extract2<0, 8, 8>(c, src, nstarts, navail, ka, slice_tiles, slice_stride, nsuper, ch.rep_graph && rep);
         }
-        else if (c->rec_mode)
+        else if (src.records())
         {
             // slices of a super-tile's window slots = 2048 records each, in strand-representative space for k-mer sets
             const uint64_t P = rec_slots(c);
             const uint64_t slice_groups = slice_starts / P / kRecGroup;
-            launch_extract_records(c, (const SkRec*)ch.d_bases, nstarts / P, (Key1*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
+            launch_extract_records(c, (const SkRec*)src.bytes, nstarts / P, (Key1*)ka, slice_groups * nslices, slice_groups, slice_stride / P,
                                    ch.use_rep && rep);
         }
-        else
-        {
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper, 2048);
-            const uint8_t* src = (const uint8_t*)(addr0 - mis0); const uint16_t* pbad = nullptr;
-            if (c->pk.on) pk_ptrs(c, src, &src, &pbad);
-#define GOSS_LAUNCH_SAMPLE1(MODE, P, REP, PK)                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, 8, 8, REP, PK>), dim3(grid), dim3(kTB), 0, c->stream, src, mis0, nstarts, navail, \
-                       c->len, ka, c->d_ctr, 0xFFFFFFFFu, nsuper, slice_tiles, slice_stride, pbad)
-            if (ch.graph_mode) { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(1, 8, false, true); else GOSS_LAUNCH_SAMPLE1(1, 8, false, false); }
-            else if (rep)      // strand representatives: the key space the fused kernel counts in
-            { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(0, 16, true, true); else GOSS_LAUNCH_SAMPLE1(0, 16, true, false); }
-            else { if (c->pk.on) GOSS_LAUNCH_SAMPLE1(0, 16, false, true); else GOSS_LAUNCH_SAMPLE1(0, 16, false, false); }
-#undef GOSS_LAUNCH_SAMPLE1
-        }
+        else if (ch.graph_mode) launch_sample1<1, 8, false>(c, src.launch(), nstarts, navail, ka, nsuper, slice_tiles, slice_stride);
+        // strand representatives: the key space the fused kernel counts in
+        else if (rep) launch_sample1<0, 16, true>(c, src.launch(), nstarts, navail, ka, nsuper, slice_tiles, slice_stride);
+        else launch_sample1<0, 16, false>(c, src.launch(), nstarts, navail, ka, nsuper, slice_tiles, slice_stride);
     }
     c->extract_hist_shift = 0xFFFFFFFFu;
     ExtractCounters* hcs = (ExtractCounters*)c->h_pinned;
@@ -502,9 +498,8 @@ void size_bucket_regions(const std::vector<unsigned long long>& hh, const FusedS
 }
 
 // ---- 3. extraction that partitions -------------------------------------------------------------
-// Run-time choices -> template arguments of the first-level kernels: f is called with a std::bool_constant /
-// std::integral_constant of the value.
-template <class F> void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// Run-time choices -> template arguments of the first-level kernels (with_bool, and for the digit histograms): f is
+// called with a std::integral_constant of the value.
 template <class F> void with_digit_hists(int nh, F&& f)
 {
     if (nh == 0) f(std::integral_constant<int, 0>{});
@@ -513,8 +508,8 @@ template <class F> void with_digit_hists(int nh, F&& f)
 }
 
 struct FirstLevelLaunch {
-    const uint8_t* d_bases; const uint8_t* aligned; const uint8_t* pk_src; const uint16_t* pk_bad;
-    uint32_t mis; uint64_t nstarts, navail;
+    ReadSrc::Launch in;
+    uint64_t nstarts, navail;
     void* ka; PartCounters* pc; const GapTable* dgt;
     uint32_t part_shift; uint64_t nsuper; uint32_t blk_log2, grid;
     int nh;          // digit histograms the kernel takes for the look-back passes behind it (0: two-level form)
@@ -530,18 +525,16 @@ void launch_extract1_part(goss_gpu_ctx* c, const FirstLevelLaunch& a, bool fastk
     with_digit_hists(a.nh, [&](auto nh_c) { with_bool(fastk, [&](auto fast_c) { with_bool(narrow, [&](auto narrow_c) {
         constexpr int NH = decltype(nh_c)::value;
         constexpr bool FAST = NH == 0 && decltype(fast_c)::value, NRW = NH == 0 && decltype(narrow_c)::value;
-        if (c->rec_mode)
+        if (a.in.kind == ReadSrc::Records)          // (navail: the records)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, REPK, true, FAST, NRW>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                               a.d_bases, 0u, a.nstarts, a.nstarts / rec_slots(c), c->len, (Key1*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
+                               a.in.base, a.in.mis, a.nstarts, a.nstarts / rec_slots(c), c->len, (Key1*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
                                nr_rbits, nr_sqbit, nr_dmask, nr_capg);
-        else if (c->pk.on)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, REPK, false, FAST, NRW, true>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                               a.pk_src, a.mis, a.nstarts, a.navail, c->len, (Key1*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
-                               nr_rbits, nr_sqbit, nr_dmask, nr_capg, a.pk_bad);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, REPK, false, FAST, NRW>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                               a.aligned, a.mis, a.nstarts, a.navail, c->len, (Key1*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
-                               nr_rbits, nr_sqbit, nr_dmask, nr_capg, (const uint16_t*)nullptr);
+            with_bool(a.in.kind == ReadSrc::Packed, [&](auto pk) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_part_kernel<MODE, NH, REPK, false, FAST, NRW, decltype(pk)::value>), dim3(a.grid), dim3(kTB), 0,
+                                   c->stream, a.in.base, a.in.mis, a.nstarts, a.navail, c->len, (Key1*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
+                                   nr_rbits, nr_sqbit, nr_dmask, nr_capg, a.in.bad);
+            });
     }); }); });
 }
 
@@ -552,19 +545,16 @@ void launch_extract2_part(goss_gpu_ctx* c, const FirstLevelLaunch& a)
     with_digit_hists(a.nh, [&](auto nh_c) {
         constexpr int NH = decltype(nh_c)::value;
         if constexpr (MODE == 0)
-            if (c->rec_mode)
+            if (a.in.kind == ReadSrc::Records)
             {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<0, NH, GOSS_FUSED_NKEYS2, NBH, true>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                                   a.d_bases, 0u, a.nstarts, a.nstarts / rec_slots(c), c->len, (Key2*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2);
+                                   a.in.base, a.in.mis, a.nstarts, a.nstarts / rec_slots(c), c->len, (Key2*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2);
                 return;
             }
-        if (c->pk.on)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<MODE, NH, GOSS_FUSED_NKEYS2, NBH, false, true>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                               a.pk_src, a.mis, a.nstarts, a.navail, c->len, (Key2*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2, a.pk_bad);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<MODE, NH, GOSS_FUSED_NKEYS2, NBH>), dim3(a.grid), dim3(kTB), 0, c->stream,
-                               a.aligned, a.mis, a.nstarts, a.navail, c->len, (Key2*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2,
-                               (const uint16_t*)nullptr);
+        with_bool(a.in.kind == ReadSrc::Packed, [&](auto pk) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_part_kernel<MODE, NH, GOSS_FUSED_NKEYS2, NBH, false, decltype(pk)::value>), dim3(a.grid), dim3(kTB), 0,
+                               c->stream, a.in.base, a.in.mis, a.nstarts, a.navail, c->len, (Key2*)a.ka, a.pc, a.dgt, a.part_shift, a.nsuper, a.blk_log2, a.in.bad);
+        });
     });
 }
 
@@ -574,11 +564,8 @@ void launch_first_level(const FusedChunk<K>& ch, const FusedForm& form, bool can
     goss_gpu_ctx* c = ch.c;
     const uint32_t shift = ch.keybits - form.segbits, npass = (form.segbits + 7) / 8;
     FirstLevelLaunch a{};
-    const uintptr_t addr = (uintptr_t)ch.d_bases;
-    a.d_bases = ch.d_bases;
-    a.mis = (uint32_t)(addr & 15u);
-    a.aligned = (const uint8_t*)(addr - a.mis);
-    if (c->pk.on && !c->rec_mode) { pk_ptrs(c, a.aligned, &a.pk_src, &a.pk_bad); c->pk_fused_chunks++; }          // (a packed string: the group `aligned` stands for)
+    a.in = ch.src.launch();
+    if (ch.src.packed()) c->pk_fused_chunks++;
     a.nstarts = ch.nstarts; a.navail = ch.navail;
     a.ka = ch.ka; a.pc = pc; a.dgt = dgt;
     a.part_shift = form.msd ? ch.keybits - 8 : shift;           // the fused kernel's digit
@@ -900,12 +887,12 @@ int count_dense(const FusedChunk<K>& ch, const FusedForm& form, const FirstLevel
 
 // ---- the driver --------------------------------------------------------------------------------
 template <class K>
-int fused_chunk_once(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, uint64_t navail, K* ka, uint64_t ka_slots, K* kb, uint64_t kb_slots)
+int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, K* ka, uint64_t ka_slots, K* kb, uint64_t kb_slots)
 {
     constexpr bool kOne = FusedChunk<K>::kOne;
     const uint32_t keybits = 2 * c->len;
-    if (c->rec_mode && !kOne && c->mode == GOSS_MODE_GRAPH && !c->graph_rep) return kFusedDeclined;          // (the record form extracts one key per window)
-    FusedChunk<K> ch{c, d_bases, nstarts, navail, ka, ka_slots, kb, kb_slots, keybits};
+    if (src.records() && !kOne && c->mode == GOSS_MODE_GRAPH && !c->graph_rep) return kFusedDeclined;          // (the record form extracts one key per window)
+    FusedChunk<K> ch{c, src, nstarts, navail, ka, ka_slots, kb, kb_slots, keybits};
     ch.rep_graph = c->mode == GOSS_MODE_GRAPH && c->graph_rep;
     ch.rep_kmer = c->mode != GOSS_MODE_GRAPH && kOne;
     ch.use_rep = ch.rep_graph || ch.rep_kmer;
@@ -1025,18 +1012,18 @@ int fused_chunk_once(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, 
     c->windows += fl.windows;
     c->keys_total += ch.rep_graph ? 2 * fl.n : fl.n;          // (the adapter's key stream: two keys per window of a graph)
     c->fused_chunks++;
-    if (c->rec_mode) c->rec_chunks++;
+    if (src.records()) c->rec_chunks++;
     return kFusedDone;
 }
 
 // A 32-bit-remainder form that overflowed has adjusted the context (more sub-segments, or never that form): the chunk again.
 template <class K>
-int process_chunk_fused(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, uint64_t navail, K* ka, uint64_t ka_slots,
+int process_chunk_fused(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, K* ka, uint64_t ka_slots,
                         K* kb, uint64_t kb_slots)
 {
     for (;;)
     {
-        const int rc = fused_chunk_once<K>(c, d_bases, nstarts, navail, ka, ka_slots, kb, kb_slots);
+        const int rc = fused_chunk_once<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots);
         if (rc != kFusedAgain) return rc;
     }
 }

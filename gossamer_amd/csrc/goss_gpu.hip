@@ -22,6 +22,7 @@
 
 #include "goss_kernels.hpp"
 #include "goss_reader.hpp"
+#include "goss_read_src.hpp"
 
 using namespace goss;
 
@@ -119,10 +120,8 @@ struct goss_gpu_ctx {
     // A packed staging buffer (round 5): what goss_gpu_push_packed_host* hands over stays 2-bit codes + flags in HBM --
     // u32 of codes per sixteen positions from the buffer's start, u16 of flags per sixteen positions behind them -- and the
     // kernels that read bases take it as it is (load_group16, kernels_common.hpp).  A buffer holds bytes OR packed
-    // groups (stage_pk[i]); `pk` describes the packed string a count is running on: the plumbing between the entry
-    // points and the kernels goes on passing byte addresses -- made-up ones (pk.fake + position) that only the launch
-    // sites turn into the two real pointers (pk_ptrs).
-    struct PackedSrc { bool on = false; const uint32_t* codes = nullptr; const uint16_t* bad = nullptr; } pk;
+    // groups (stage_pk[i]); staged_src makes the ReadSrc (goss_read_src.hpp) of what one holds, and that value -- the
+    // two arrays and a position for a packed string -- is what travels from the entry points to the launch sites.
     bool stage_pk[2] = {false, false};
     uint8_t* stage_buf[2] = {nullptr, nullptr};
     int stage_cur = 0;
@@ -136,7 +135,6 @@ struct goss_gpu_ctx {
     bool mute_timing = false;           // set around auxiliary launches (the distinct-count estimate)
     uint32_t segment_retries = 0;       // segment path attempts that overflowed an LDS table
     uint32_t extract_hist_shift = 0xFFFFFFFFu;   // digits histogrammed by the last extraction (or none)
-    bool extract_rep = false;           // the next one-word k-mer extraction stores strand representatives (fused path's sample)
     uint32_t rep_chunks = 0;            // chunks counted in strand-representative space and mapped to canonical order afterwards
     bool graph_rep = true;              // GOSS_GPU_NO_GRAPH_REP=1: the fused path of a graph build counts both strands of every window (round 3's form)
     int canon_l1 = 1;                   // GOSS_GPU_CANON_L1=0|1|2: the fused first level computes gossamer's canonical form itself never / from kCanonL1At distinct keys per window on / always
@@ -198,8 +196,6 @@ struct goss_gpu_ctx {
     int big_rounds_min = 0;             // GOSS_GPU_BIG_ROUNDS_MIN=<r>: at least 2^r (tests)
     uint32_t big_table_chunks = 0;      // chunks counted that way
     uint32_t wide_table_chunks = 0;     // ... of them, two-word keys in the 6144-slot table
-    bool rec_mode = false;              // the current push is a string of super-k-mer records (goss_gpu_push_records_device): "bases" point at
-                                        // SkRec records, a "window start" is one of a record's 16 window slots
     uint32_t rec_chunks = 0;            // chunks counted from records by the fused path
     bool deferred = false;              // goss_gpu_set_deferred: host pushes only stage; a full staging buffer is reported, not counted
                                         // (the caller then runs goss_gpu_group_route_exchange: the exchange before counting)
@@ -673,42 +669,43 @@ Run reduce_runs(goss_gpu_ctx* c, const K* keys, const uint32_t* vals, uint64_t n
     return r;
 }
 
-// ---- packed strings (ctx.pk) ---------------------------------------------------------------------------------------
-constexpr uintptr_t kPkFake = (uintptr_t)1 << 44;          // "address" of position 0 of the packed string being counted (a multiple of 16)
+// ---- packed strings ------------------------------------------------------------------------------------------------
 // groups of a packed staging buffer of `cap` positions, and its two arrays
 static inline uint64_t pk_groups(uint64_t cap) { return cap / 16 + 4; }
 static inline uint32_t* pk_codes_of(uint8_t* buf) { return (uint32_t*)buf; }
 static inline uint16_t* pk_bad_of(uint8_t* buf, uint64_t cap) { return (uint16_t*)(buf + pk_groups(cap) * 4); }
-// a 16-byte aligned made-up address -> the codes and flags of its group
-static inline void pk_ptrs(const goss_gpu_ctx* c, const uint8_t* aligned, const uint8_t** src, const uint16_t** bad)
+// Run-time choices -> template arguments of a kernel: f is called with a std::bool_constant of the value (with int_c<N>
+// for the choices the caller makes itself).
+template <class F> void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int N> using int_c = std::integral_constant<int, N>;
+// Bytes of `n` positions of the packed string `p`, for the kernels that have no packed form (the plain extraction of
+// small inputs and of the fallback sequence -- never the fused path's): unpacked into a temporary of the arena (the
+// caller releases its mark).  Returns the byte string over the temporary.
+static ReadSrc pk_unpack_temp(goss_gpu_ctx* c, const ReadSrc& p, uint64_t n)
 {
-    const uint64_t g = ((uintptr_t)aligned - kPkFake) >> 4;
-    *src = (const uint8_t*)(c->pk.codes + g);
-    *bad = c->pk.bad + g;
-}
-// Bytes of `n` positions of the packed string from made-up address `p` on, for the kernels that have no packed form (the
-// plain extraction of small inputs and of the fallback sequence -- never the fused path's): unpacked into a temporary
-// of the arena (the caller releases its mark).  Returns the aligned byte address; *mis as for a byte string.
-static const uint8_t* pk_unpack_temp(goss_gpu_ctx* c, const uint8_t* p, uint64_t n, uint32_t* mis)
-{
-    const uintptr_t addr = (uintptr_t)p;
-    *mis = (uint32_t)(addr & 15u);
-    const uint8_t* src; const uint16_t* bad;
-    pk_ptrs(c, (const uint8_t*)(addr - *mis), &src, &bad);
-    const uint64_t groups = (n + *mis + 15) / 16;
+    const ReadSrc::Launch in = p.launch();
+    const uint64_t groups = (n + in.mis + 15) / 16;
     c->pk_unpacked_chunks++;
     uint8_t* out = (uint8_t*)c->arena.temp((groups + 1) * 16 + 64);
-    hipLaunchKernelGGL(unpack_bases_kernel, dim3(grid_for(groups + 1, kTB)), dim3(kTB), 0, c->stream, (const uint32_t*)src, bad, groups,
-                       n + *mis, out);
-    return out;
+    hipLaunchKernelGGL(unpack_bases_kernel, dim3(grid_for(groups + 1, kTB)), dim3(kTB), 0, c->stream, (const uint32_t*)in.base, in.bad, groups,
+                       n + in.mis, out);
+    return ReadSrc::of_bytes(out + in.mis);
 }
 
+// The plain kernels: extract_dispatch takes bytes or records (a packed string is unpacked first, process_chunk), and
+// `rep` says that the keys are strand representatives -- the key space of the fused path, whose sample this then is.
 template <class K>
-void extract_dispatch(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, K* out);
+void extract_dispatch(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, K* out, bool rep);
+inline void refuse_packed(const ReadSrc& src)
+{
+    if (src.packed()) throw StatusError{GOSS_ERR_STATE, "a packed string handed to a kernel that reads bytes"};
+}
 template <class K> bool use_segment_path(const goss_gpu_ctx* c);
 template <int MODE, int P, int G>
-void launch_extract1(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, Key1* out)
+void launch_extract1(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, Key1* out, bool rep)
 {
+    refuse_packed(src);
+    const ReadSrc::Launch in = src.launch();
     constexpr int T = kTB * P * G;
     const uint64_t nsuper = (nstarts + T - 1) / T;
     // persistent grid: 4 workgroups per CU (LDS-limited), 256 CUs
@@ -716,12 +713,12 @@ void launch_extract1(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint
     // fused digit histograms for the 16-bit partition that follows on the segment path
     c->extract_hist_shift = use_segment_path<Key1>(c) ? 2 * c->len - kSegBits : 0xFFFFFFFFu;
 #define GOSS_LAUNCH_E1(NB)                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, G, NB>), dim3(grid), dim3(kTB), 0, c->stream, aligned, mis, \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, G, NB>), dim3(grid), dim3(kTB), 0, c->stream, in.base, in.mis, \
                        nstarts, navail, c->len, out, c->d_ctr, c->extract_hist_shift, nsuper)
     if (MODE == 1) { GOSS_LAUNCH_E1(8); return; }          // graph mode does not hash
-    if (MODE == 0 && c->extract_rep)
+    if (MODE == 0 && rep)
     {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, G, 8, true>), dim3(grid), dim3(kTB), 0, c->stream, aligned, mis,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(extract1_kernel<MODE, P, G, 8, true>), dim3(grid), dim3(kTB), 0, c->stream, in.base, in.mis,
                            nstarts, navail, c->len, out, c->d_ctr, c->extract_hist_shift, nsuper);
         return;
     }
@@ -739,9 +736,10 @@ void launch_extract1(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint
 #undef GOSS_LAUNCH_E1
 }
 // window slots of a record (the most windows one holds): a string of n records counts as 16 n window starts
-inline uint32_t rec_slots(const goss_gpu_ctx*) { return 16u; }
+inline uint32_t rec_slots(const goss_gpu_ctx*) { return (uint32_t)ReadSrc::kRecSlots; }
 // bytes of a record: 12 for one-word keys (SkRec), 20 for two-word keys (SkRec2)
 inline uint64_t rec_bytes(const goss_gpu_ctx* c) { return c->words == 1 ? sizeof(SkRec) : sizeof(SkRec2); }
+inline ReadSrc records_src(const goss_gpu_ctx* c, const void* first) { return ReadSrc::of_records(first, (uint32_t)rec_bytes(c)); }
 
 // records -> keys with the plain kernel: all records (slice_groups = 0) or slices of them (the fused path's sample)
 void launch_extract_records(goss_gpu_ctx* c, const SkRec* recs, uint64_t nrecs, Key1* out, uint64_t ngroups, uint64_t slice_groups,
@@ -776,64 +774,60 @@ void launch_extract_records2(goss_gpu_ctx* c, const SkRec2* recs, uint64_t nrecs
 }
 
 template <>
-void extract_dispatch<Key1>(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, Key1* out)
+void extract_dispatch<Key1>(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, Key1* out, bool rep)
 {
     c->extract_hist_shift = 0xFFFFFFFFu;
-    if (c->rec_mode)
+    if (src.records())
     {
         const uint64_t nrecs = nstarts / rec_slots(c);
-        launch_extract_records(c, (const SkRec*)aligned, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, c->extract_rep);
+        launch_extract_records(c, (const SkRec*)src.bytes, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, rep);
         return;
     }
-    // (extract_rep in graph mode: one strand representative per window -- the fused path's key space for graphs)
-    if (c->mode == GOSS_MODE_KMER_SET || c->extract_rep) launch_extract1<0, 16, 8>(c, aligned, mis, nstarts, navail, out);
-    else launch_extract1<1, 8, 8>(c, aligned, mis, nstarts, navail, out);
+    // (rep in graph mode: one strand representative per window -- the fused path's key space for graphs)
+    if (c->mode == GOSS_MODE_KMER_SET || rep) launch_extract1<0, 16, 8>(c, src, nstarts, navail, out, rep);
+    else launch_extract1<1, 8, 8>(c, src, nstarts, navail, out, false);
 }
 // significant bytes of a two-word key's high word, rounded up to the instantiated classes 2/4/6/8
 inline int key2_nbh(const goss_gpu_ctx* c) { const int nb = (int)(2 * c->len + 7) / 8 - 8; return nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 6 ? 6 : 8; }
 
+// (bytes or a packed string -- only the fused path's sample comes here with one: the plain extraction of a whole chunk unpacks first)
 template <int MODE, int P, int G>
-void launch_extract2(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, Key2* out,
+void launch_extract2(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, Key2* out,
                      uint64_t slice_tiles = 0, uint64_t slice_stride = 0, uint64_t nsuper_override = 0, bool rep = false)
 {
     constexpr int T = kTB * P * G;
     const uint64_t nsuper = nsuper_override ? nsuper_override : (nstarts + T - 1) / T;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nsuper ? nsuper : 1, 1024 * 2);
-    // (a packed string -- only the fused path's sample comes here with one: the plain extraction of a whole chunk unpacks first)
-    const uint8_t* pk_src = nullptr; const uint16_t* pk_bad = nullptr;
-    if (c->pk.on) pk_ptrs(c, aligned, &pk_src, &pk_bad);
-#define GOSS_LAUNCH_E2(NBH)                                                                                           \
-    do {                                                                                                              \
-        if (c->pk.on)                                                                                                 \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_kernel<MODE, P, G, NBH, true>), dim3(grid), dim3(kTB), 0, c->stream, pk_src, mis, nstarts,  \
-                               navail, c->len, out, c->d_ctr, nsuper, slice_tiles, slice_stride, pk_bad);             \
-        else                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_kernel<MODE, P, G, NBH>), dim3(grid), dim3(kTB), 0, c->stream, aligned, mis, nstarts,  \
-                               navail, c->len, out, c->d_ctr, nsuper, slice_tiles, slice_stride, (const uint16_t*)nullptr); \
-    } while (0)
-    if (MODE == 1) { GOSS_LAUNCH_E2(8); return; }             // graph mode does not hash
-    if (rep) { GOSS_LAUNCH_E2(0); return; }                   // strand representatives (NBH 0): no hash either
+    const ReadSrc::Launch in = src.launch();
+    auto launch = [&](auto nbh) {
+        with_bool(in.kind == ReadSrc::Packed, [&](auto pk) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(extract2_kernel<MODE, P, G, decltype(nbh)::value, decltype(pk)::value>), dim3(grid), dim3(kTB), 0,
+                               c->stream, in.base, in.mis, nstarts, navail, c->len, out, c->d_ctr, nsuper, slice_tiles, slice_stride, in.bad);
+        });
+    };
+    if (MODE == 1) { launch(int_c<8>{}); return; }             // graph mode does not hash
+    if (rep) { launch(int_c<0>{}); return; }                   // strand representatives (NBH 0): no hash either
     switch (key2_nbh(c))
     {
-        case 2: GOSS_LAUNCH_E2(2); break;
-        case 4: GOSS_LAUNCH_E2(4); break;
-        case 6: GOSS_LAUNCH_E2(6); break;
-        default: GOSS_LAUNCH_E2(8); break;
+        case 2: launch(int_c<2>{}); break;
+        case 4: launch(int_c<4>{}); break;
+        case 6: launch(int_c<6>{}); break;
+        default: launch(int_c<8>{}); break;
     }
-#undef GOSS_LAUNCH_E2
 }
 template <>
-void extract_dispatch<Key2>(goss_gpu_ctx* c, const uint8_t* aligned, uint32_t mis, uint64_t nstarts, uint64_t navail, Key2* out)
+void extract_dispatch<Key2>(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail, Key2* out, bool rep)
 {
-    if (c->rec_mode)
+    if (src.records())
     {
         // two-word records -> keys with the plain kernel (their counting goes through the unfused sequence)
         const uint64_t nrecs = nstarts / rec_slots(c);
-        launch_extract_records2(c, (const SkRec2*)aligned, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, c->extract_rep);
+        launch_extract_records2(c, (const SkRec2*)src.bytes, nrecs, out, (nrecs + kRecGroup - 1) / kRecGroup, 0, 0, rep);
         return;
     }
-    if (c->mode == GOSS_MODE_KMER_SET || c->extract_rep) launch_extract2<0, 8, 8>(c, aligned, mis, nstarts, navail, out, 0, 0, 0, c->extract_rep);
-    else launch_extract2<1, 4, 8>(c, aligned, mis, nstarts, navail, out);
+    refuse_packed(src);
+    if (c->mode == GOSS_MODE_KMER_SET || rep) launch_extract2<0, 8, 8>(c, src, nstarts, navail, out, 0, 0, 0, rep);
+    else launch_extract2<1, 4, 8>(c, src, nstarts, navail, out);
 }
 
 inline uint32_t key_digits(const goss_gpu_ctx* c) { return (2 * c->len + 7) / 8; }
@@ -1515,10 +1509,10 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
 // ---- fused extraction + first partition pass, and the counting behind it -----------------------
 #include "fused_path.hpp"
 
-// Process window starts [0, nstarts) of a device-resident byte string (navail readable bytes,
-// navail >= nstarts): extract -> sort -> reduce -> append a run.
+// Process window starts [0, nstarts) of a device-resident source (bytes or packed: navail readable positions,
+// navail >= nstarts; records: navail 0): extract -> sort -> reduce -> append a run.
 template <class K>
-void process_chunk(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, uint64_t navail)
+void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64_t navail)
 {
     const uint32_t S = c->mode == GOSS_MODE_GRAPH ? 2 : 1;
     const uint64_t cap = nstarts * S;              // upper bound on keys
@@ -1554,7 +1548,7 @@ void process_chunk(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, ui
     }
     K* ka = (K*)c->arena.temp(ka_slots * sizeof(K));
     K* kb = (K*)c->arena.temp(kb_slots * sizeof(K));
-    int frc = process_chunk_fused<K>(c, d_bases, nstarts, navail, ka, ka_slots, kb, kb_slots);
+    int frc = process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots);
     if (frc == kFusedDone) { if (reduced) c->valid_sized_chunks++; c->arena.release(mark); return; }
     if (reduced)
     {
@@ -1565,28 +1559,18 @@ void process_chunk(goss_gpu_ctx* c, const uint8_t* d_bases, uint64_t nstarts, ui
         full_slots(cap);
         ka = (K*)c->arena.temp(ka_slots * sizeof(K));
         kb = (K*)c->arena.temp(kb_slots * sizeof(K));
-        if (frc == kFusedNeedFull && process_chunk_fused<K>(c, d_bases, nstarts, navail, ka, ka_slots, kb, kb_slots) == kFusedDone)
+        if (frc == kFusedNeedFull && process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots) == kFusedDone)
         {
             c->arena.release(mark);
             return;
         }
     }
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(ExtractCounters), c->stream));
-    uintptr_t addr = (uintptr_t)d_bases;
-    uint32_t mis = c->rec_mode ? 0u : (uint32_t)(addr & 15u);
-    const uint8_t* aligned = (const uint8_t*)(addr - mis);
     {
         PhaseTimer t(c, GOSS_T_EXTRACT, nstarts);
-        if (c->pk.on && !c->rec_mode)
-        {
-            // (a packed string outside the fused path -- a small input, or the sequence a chunk falls back to: the plain
-            // kernels read bytes, and this chunk's are made here; released with the chunk's other temporaries)
-            aligned = pk_unpack_temp(c, d_bases, navail, &mis);
-            const auto keep = c->pk; c->pk.on = false;
-            extract_dispatch<K>(c, aligned, mis, nstarts, navail, ka);
-            c->pk = keep;
-        }
-        else extract_dispatch<K>(c, aligned, mis, nstarts, navail, ka);
+        // (a packed string outside the fused path -- a small input, or the sequence a chunk falls back to: the plain
+        // kernels read bytes, and this chunk's are made here; released with the chunk's other temporaries)
+        extract_dispatch<K>(c, src.packed() ? pk_unpack_temp(c, src, navail) : src, nstarts, navail, ka, false);
         t.stop();
     }
     ExtractCounters* h = (ExtractCounters*)c->h_pinned;
@@ -1784,7 +1768,7 @@ void merge_runs(goss_gpu_ctx* c)
 // Largest number of window starts one chunk may cover with the memory currently free.
 // optimistic: size the chunk for the segment-hash path (two key buffers + look-back status;
 // its output is bounded by kSegCount * kSegLimit entries).  If a chunk then needs the full
-// sort with a large output and runs out of memory, push_device halves it and retries.
+// sort with a large output and runs out of memory, push_source halves it and retries.
 uint64_t chunk_capacity(goss_gpu_ctx* c, bool optimistic)
 {
     const uint64_t ksz = c->words * 8;
@@ -1818,26 +1802,20 @@ uint64_t chunk_capacity(goss_gpu_ctx* c, bool optimistic)
 // Share of the window starts of a pushed string that begin a valid window, estimated from 64 MB of
 // evenly spread slices: a non-base removes at most `len` windows.  One point of margin; the
 // fused path checks the figure against its own sample and asks for full buffers when it was low.
-double estimate_valid_fraction(goss_gpu_ctx* c, const uint8_t* d, uint64_t nbytes)
+double estimate_valid_fraction(goss_gpu_ctx* c, const ReadSrc& d, uint64_t nbytes)
 {
     constexpr uint32_t kSlice = 16384;
     constexpr uint64_t kSlices = 4096;
-    const uint8_t* al = (const uint8_t*)(((uintptr_t)d + 15) & ~(uintptr_t)15);
-    const uint64_t skip = (uint64_t)(al - d);
+    const uint64_t skip = d.to_next16();
     if (nbytes < skip + 2 * kSlices * kSlice) return 1.0;
     const uint64_t stride = ((nbytes - skip - kSlice) / (kSlices - 1)) & ~15ULL;
+    const ReadSrc::Launch al = d.advance(skip).launch();          // (the first whole sixteen: mis 0)
     c->mute_timing = true;
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, 16, c->stream));
-    if (c->pk.on)
-    {
-        const uint8_t* src; const uint16_t* bad;
-        pk_ptrs(c, al, &src, &bad);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(nonbase_sample_kernel<true>), dim3(1024), dim3(kTB), 0, c->stream, (const uint8_t*)bad, kSlices, stride,
-                           kSlice, (unsigned long long*)c->d_ctr);
-    }
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(nonbase_sample_kernel<false>), dim3(1024), dim3(kTB), 0, c->stream, al, kSlices, stride, kSlice,
-                           (unsigned long long*)c->d_ctr);
+    with_bool(d.packed(), [&](auto pk) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(nonbase_sample_kernel<decltype(pk)::value>), dim3(1024), dim3(kTB), 0, c->stream,
+                           decltype(pk)::value ? (const uint8_t*)al.bad : al.base, kSlices, stride, kSlice, (unsigned long long*)c->d_ctr);
+    });
     c->mute_timing = false;
     unsigned long long* h = (unsigned long long*)c->h_pinned;
     HIP_TRY(hipMemcpyAsync(h, c->d_ctr, 16, hipMemcpyDeviceToHost, c->stream));
@@ -1847,17 +1825,26 @@ double estimate_valid_fraction(goss_gpu_ctx* c, const uint8_t* d, uint64_t nbyte
     return std::min(1.0, std::max(0.05, f));
 }
 
+// One push, counted in chunks: `n` bytes / positions of a base string, or `n` super-k-mer records (kernels_route.hpp),
+// which count like a string of bases -- a "window start" being one of a record's 16 window slots.  nwindows (records;
+// 0 = unknown) sizes the key buffers where a base string is sampled for its share of valid windows.
 template <class K>
-void push_device(goss_gpu_ctx* c, const uint8_t* d, uint64_t nbytes)
+void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwindows = 0)
 {
-    if (nbytes < c->len) return;
+    const bool recs = src.records();
+    if (recs ? n == 0 : n < c->len) return;
     ensure_arena(c);
-    const uint64_t nstarts_total = nbytes - c->len + 1;
+    const uint64_t nstarts_total = recs ? n * rec_slots(c) : n - c->len + 1;
+    struct FracOff { goss_gpu_ctx* c; ~FracOff() { c->valid_frac = 1.0; } } fracOff{c};
     c->valid_frac = 1.0;
     if (c->size_by_valid && c->fused && c->path == 0 && nstarts_total > kValidSizingMin)
     {
-        c->valid_frac = estimate_valid_fraction(c, d, nbytes);
-        if (c->debug) std::fprintf(stderr, "libgossgpu: valid windows per window start, estimated: %.3f\n", c->valid_frac);
+        if (recs) { if (nwindows) c->valid_frac = std::min(1.0, std::max(0.05, (double)nwindows / (double)nstarts_total + 0.01)); }
+        else
+        {
+            c->valid_frac = estimate_valid_fraction(c, src, n);
+            if (c->debug) std::fprintf(stderr, "libgossgpu: valid windows per window start, estimated: %.3f\n", c->valid_frac);
+        }
     }
     uint64_t done = 0;
     uint64_t limit = 0;                 // chunk size cap after an out-of-memory retry
@@ -1885,16 +1872,17 @@ void push_device(goss_gpu_ctx* c, const uint8_t* d, uint64_t nbytes)
                 capn = std::min<uint64_t>(capn, ((left + parts - 1) / parts + 4095) & ~4095ULL);
             }
         }
-        uint64_t ns = std::min(capn, nstarts_total - done);
-        uint64_t navail = std::min(nbytes - done, ns + c->len - 1);
+        const uint64_t ns = std::min(capn, nstarts_total - done);          // (a multiple of 4096 slots = whole records, but for the last)
+        const uint64_t navail = recs ? 0 : std::min(n - done, ns + c->len - 1);
         const uint64_t lo0 = c->arena.lo, hi0 = c->arena.hi;
         const size_t runs0 = c->runs.size();
-        // (behind this chunk: the rest of this push and what the push's own caller has said lies behind IT)
+        // (behind this chunk of a base string: the rest of this push and what the push's own caller has said lies behind
+        // IT; a push of records leaves the figure as it is)
         struct MoreOff { goss_gpu_ctx* c; uint64_t was; ~MoreOff() { c->more_starts = was; } } moreOff{c, c->more_starts};
-        c->more_starts = moreOff.was + (nstarts_total - done - ns);
+        if (!recs) c->more_starts = moreOff.was + (nstarts_total - done - ns);
         try
         {
-            process_chunk<K>(c, d + done, ns, navail);
+            process_chunk<K>(c, src.advance(done), ns, navail);
         }
         catch (const StatusError& e)
         {
@@ -1920,66 +1908,10 @@ void push_device(goss_gpu_ctx* c, const uint8_t* d, uint64_t nbytes)
         }
     }
 }
-
-// A string of super-k-mer records (kernels_route.hpp) counted like a string of bases: the same chunk loop, a
-// "window start" being one of a record's P window slots.  nwindows (0 = unknown) sizes the key buffers.
-template <class K>
-void push_records(goss_gpu_ctx* c, const uint8_t* d, uint64_t nrecs, uint64_t nwindows)
+// (the key width is the context's)
+void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwindows = 0)
 {
-    if (nrecs == 0) return;
-    ensure_arena(c);
-    const uint64_t P = rec_slots(c);
-    struct Mode { goss_gpu_ctx* c; ~Mode() { c->rec_mode = false; c->valid_frac = 1.0; } } mode{c};
-    c->rec_mode = true;
-    const uint64_t nstarts_total = nrecs * P;
-    c->valid_frac = 1.0;
-    if (nwindows && c->size_by_valid && c->fused && c->path == 0 && nstarts_total > kValidSizingMin)
-        c->valid_frac = std::min(1.0, std::max(0.05, (double)nwindows / (double)nstarts_total + 0.01));
-    uint64_t done = 0, limit = 0;
-    while (done < nstarts_total)
-    {
-        const bool optimistic = use_segment_path<K>(c);
-        uint64_t capn = chunk_capacity(c, optimistic);
-        if (capn < 4096) capn = chunk_capacity(c, false);
-        if (capn < 4096)
-        {
-            if (c->runs.size() > 1) { merge_runs<K>(c); capn = chunk_capacity(c, false); }
-            if (capn < 4096 && grow_arena(c, 0)) capn = chunk_capacity(c, false);
-            if (capn < 4096) throw StatusError{GOSS_ERR_OOM, "HBM budget too small for one chunk"};
-        }
-        if (limit && capn > limit) capn = limit;
-        {
-            const uint64_t left = nstarts_total - done;
-            if (left > capn)
-            {
-                const uint64_t parts = (left + capn - 1) / capn;
-                capn = std::min<uint64_t>(capn, ((left + parts - 1) / parts + 4095) & ~4095ULL);
-            }
-        }
-        const uint64_t ns = std::min(capn, nstarts_total - done);          // (a multiple of 4096 slots = whole records, but for the last)
-        const uint64_t lo0 = c->arena.lo, hi0 = c->arena.hi;
-        const size_t runs0 = c->runs.size();
-        try
-        {
-            process_chunk<K>(c, d + (done / P) * rec_bytes(c), ns, 0);
-        }
-        catch (const StatusError& e)
-        {
-            if (e.status != GOSS_ERR_OOM || ns <= 8192) throw;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->arena.lo = lo0; c->arena.hi = hi0;
-            c->runs.resize(runs0);
-            c->mute_timing = false;             // (a phase that gave up part-way may have left it set)
-            if (grow_arena(c, 0)) continue;
-            limit = (ns / 2) & ~4095ULL;
-            continue;
-        }
-        done += ns;
-        uint64_t run_bytes = 0;
-        for (auto& r : c->runs) run_bytes += r.m * (c->words * 8 + 4);
-        if (c->runs.size() > 1 && run_bytes > c->arena.size / 4 &&
-            (c->arena.avail() >= 2 * run_bytes + (512ULL << 20) || grow_arena(c, 2 * run_bytes + (512ULL << 20)))) merge_runs<K>(c);
-    }
+    if (c->words == 1) push_source<Key1>(c, src, n, nwindows); else push_source<Key2>(c, src, n, nwindows);
 }
 
 // ---- on-disk arrays ---------------------------------------------------------------------
@@ -2955,17 +2887,15 @@ static void wait_background(goss_gpu_ctx* c)
     }
 }
 
+// what a staging buffer holds, as a source: bytes, or -- packed -- its two arrays from position 0
+static ReadSrc staged_src(const goss_gpu_ctx* c, const uint8_t* buf, bool packed)
+{
+    return packed ? ReadSrc::of_packed(pk_codes_of((uint8_t*)buf), pk_bad_of((uint8_t*)buf, c->stage_cap)) : ReadSrc::of_bytes(buf);
+}
 static void count_staged(goss_gpu_ctx* c, const uint8_t* buf, uint64_t n, bool packed = false)
 {
     const auto t1 = std::chrono::steady_clock::now();
-    struct PkOff { goss_gpu_ctx* c; ~PkOff() { c->pk.on = false; } } pkOff{c};
-    if (packed)
-    {
-        // (a packed buffer: counted as the string at the made-up address kPkFake, which the launch sites resolve)
-        c->pk.on = true; c->pk.codes = pk_codes_of((uint8_t*)buf); c->pk.bad = pk_bad_of((uint8_t*)buf, c->stage_cap);
-        buf = (const uint8_t*)kPkFake;
-    }
-    if (c->words == 1) push_device<Key1>(c, buf, n); else push_device<Key2>(c, buf, n);
+    push_source(c, staged_src(c, buf, packed), n);
     c->flush_count_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
     c->flushes++;
 }
@@ -3041,8 +2971,7 @@ int goss_gpu_push_bases_device(goss_gpu_ctx* c, const void* d_bases, uint64_t nb
     if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         flush_staging(c);
-        if (c->words == 1) push_device<Key1>(c, (const uint8_t*)d_bases, nbytes);
-        else push_device<Key2>(c, (const uint8_t*)d_bases, nbytes);
+        push_source(c, ReadSrc::of_bytes(d_bases), nbytes);
     });
 }
 
@@ -3055,8 +2984,7 @@ int goss_gpu_expect_bases(goss_gpu_ctx* c, uint64_t total_bases)
     return GOSS_OK;
 }
 
-// Packed bases that are already resident in HBM: counted where they lie, like goss_gpu_push_bases_device's bytes -- the
-// context's packed string (ctx.pk) is the caller's two arrays for the length of the call.
+// Packed bases that are already resident in HBM: counted where they lie, like goss_gpu_push_bases_device's bytes.
 int goss_gpu_push_packed_device(goss_gpu_ctx* c, const uint32_t* d_codes, const uint16_t* d_nonbase, uint64_t nbases)
 {
     if (!c || (nbases && (!d_codes || !d_nonbase))) return GOSS_ERR_INVALID_ARG;
@@ -3066,10 +2994,7 @@ int goss_gpu_push_packed_device(goss_gpu_ctx* c, const uint32_t* d_codes, const 
     if (c->deferred) { c->last_error = "a deferred context takes host pushes only (its staging buffer is what the group routes)"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         flush_staging(c);
-        struct PkOff { goss_gpu_ctx* c; ~PkOff() { c->pk.on = false; } } pkOff{c};
-        c->pk.on = true; c->pk.codes = d_codes; c->pk.bad = d_nonbase;
-        if (c->words == 1) push_device<Key1>(c, (const uint8_t*)kPkFake, nbases);
-        else push_device<Key2>(c, (const uint8_t*)kPkFake, nbases);
+        push_source(c, ReadSrc::of_packed(d_codes, d_nonbase), nbases);
     });
 }
 
@@ -3845,6 +3770,75 @@ int goss_gpu_group_emit(goss_gpu_ctx* const* ctxs, uint32_t n, uint64_t estimate
 extern "C++" {
 namespace {
 
+// Bases -> super-k-mer records in nparts parts (goss_gpu_route_records_device; the group's exchange round routes its
+// staging buffers through here).  part_records comes back with what every part holds -- or, when a part's room was too
+// small (GOSS_ERR_BUFFER), needs.
+void route_records(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nbytes, uint32_t nparts, void* d_records, const uint64_t* part_first,
+                   const uint64_t* part_cap, uint64_t* part_records, uint64_t* part_windows)
+{
+    if (c->len > 63) throw StatusError{GOSS_ERR_INVALID_ARG, "records carry windows of at most 63 bases"};
+    for (uint32_t p = 0; p < nparts; ++p) { part_records[p] = 0; if (part_windows) part_windows[p] = 0; }
+    if (nbytes < c->len) return;
+    // counters and the parts' places: a small device block of its own (the arena may not be mapped yet, and need not
+    // be), kept for the context's life -- hipFree waits for the whole device, also for a collective of the caller
+    // that is still moving the records of the piece before
+    const size_t tab = (size_t)kRouteMaxParts * 8;
+    if (!c->d_route) HIP_TRY(hipMalloc(&c->d_route, sizeof(RouteCounters) + 2 * tab));
+    RouteCounters* rc = (RouteCounters*)c->d_route;
+    unsigned long long* dfirst = (unsigned long long*)((uint8_t*)c->d_route + sizeof(RouteCounters));
+    unsigned long long* dcap = dfirst + kRouteMaxParts;
+    HIP_TRY(hipMemsetAsync(rc, 0, sizeof(RouteCounters), c->stream));
+    HIP_TRY(hipMemcpyAsync(dfirst, part_first, nparts * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dcap, part_cap, nparts * 8, hipMemcpyHostToDevice, c->stream));
+    const uint64_t nstarts = nbytes - c->len + 1;
+    const uint64_t ntiles = (nstarts + kTB * 16 - 1) / (kTB * 16);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, 256 * GOSS_ROUTE_OCC);
+    const ReadSrc::Launch in = src.launch();          // (bytes, or a packed staging buffer routed as it is)
+    const uint32_t maxwin = 16;          // (the counting side takes records of any length in both modes)
+    // slots a workgroup takes ahead per part: ~8 tiles' worth (a tile cuts ~550 records); what it does not use ends as pads
+    const uint32_t block = std::max<uint32_t>(32, std::min<uint32_t>(GOSS_ROUTE_BLOCK, 8 * GOSS_ROUTE_BLOCK / nparts));
+    {
+        PhaseTimer t(c, GOSS_T_EXTRACT, nstarts);
+        with_bool(in.kind == ReadSrc::Packed, [&](auto pk) {
+            constexpr bool PK = decltype(pk)::value;
+            auto route1 = [&](auto w) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records_kernel<decltype(w)::value, PK>), dim3(grid), dim3(kTB), 0, c->stream, in.base, in.mis, nstarts,
+                                   nbytes, c->len, maxwin, nparts, block, (SkRec*)d_records, (const unsigned long long*)dfirst,
+                                   (const unsigned long long*)dcap, rc, ntiles, in.bad);
+            };
+            if (c->words == 2)
+                // two-word keys: 20-byte records, the minimizer taken over the central 31 / 30 bases of a window (17 positions)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records2_kernel<17, PK>), dim3((uint32_t)std::min<uint64_t>(ntiles, 256 * 4)), dim3(kTB), 0,
+                                   c->stream, in.base, in.mis, nstarts, nbytes, c->len, nparts, block, (SkRec2*)d_records,
+                                   (const unsigned long long*)dfirst, (const unsigned long long*)dcap, rc, ntiles, in.bad);
+            else
+                switch (route_positions(c->len))
+                {
+                    case 17: route1(int_c<17>{}); break;
+                    case 13: route1(int_c<13>{}); break;
+                    case 9: route1(int_c<9>{}); break;
+                    case 5: route1(int_c<5>{}); break;
+                    default: route1(int_c<1>{}); break;
+                }
+        });
+        t.stop();
+    }
+    std::vector<unsigned long long> h(sizeof(RouteCounters) / 8);
+    HIP_TRY(hipMemcpyAsync(h.data(), rc, sizeof(RouteCounters), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const RouteCounters* hr = (const RouteCounters*)h.data();
+    for (uint32_t p = 0; p < nparts; ++p) { part_records[p] = hr->records[p]; if (part_windows) part_windows[p] = hr->windows[p]; }
+#if defined(GOSS_STAMPS)
+    if (nparts <= 128 && hr->records[128 + 7])
+    {
+        const double n = (double)hr->records[128 + 7];
+        std::fprintf(stderr, "libgossgpu: routing stamps per tile (ticks of wave 0): A %.0f  B %.0f  barrier %.0f  runs+scan %.0f  C %.0f  room %.0f  D %.0f   (%.0f tiles)\n",
+                     hr->records[128] / n, hr->records[129] / n, hr->records[130] / n, hr->records[131] / n, hr->records[132] / n, hr->records[133] / n, hr->records[134] / n, n);
+    }
+#endif
+    if (hr->overflow) throw StatusError{GOSS_ERR_BUFFER, "a part's record buffer is too small (part_records holds what every part needs)"};
+}
+
 // RCCL, loaded at run time (the library links against nothing but HIP): point-to-point sends and receives inside one
 // group call are an all-to-all at full xGMI bandwidth.  Absent library, communicators that cannot be made (the same
 // device twice) or GOSS_GROUP_TRANSPORT=peer -> hipMemcpyPeerAsync.
@@ -3972,14 +3966,23 @@ void group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int transport, 
                             { (void)hipGetLastError(); throw StatusError{GOSS_ERR_OOM, "no device memory for the routed records"}; }
                             c->grp_send_cap = tot;
                         }
-                        // (a packed staging buffer is routed as it is: ctx.pk for the call's duration)
-                        const bool pk = c->stage_pk[c->stage_cur];
-                        if (pk) { c->pk.on = true; c->pk.codes = pk_codes_of(c->stage); c->pk.bad = pk_bad_of(c->stage, c->stage_cap); }
-                        const int rc = goss_gpu_route_records_device(c, pk ? (const void*)kPkFake : (const void*)c->stage, nb, n, c->grp_send, first[i].data(), cap.data(),
-                                                                     recs[i].data(), wins[i].data());
-                        c->pk.on = false;
-                        if (rc == GOSS_OK) break;
-                        if (rc != GOSS_ERR_BUFFER || attempt) throw StatusError{rc, "routing the staged reads: " + c->last_error};
+                        // (a packed staging buffer is routed as it is)
+                        try
+                        {
+                            route_records(c, staged_src(c, c->stage, c->stage_pk[c->stage_cur]), nb, n, c->grp_send, first[i].data(), cap.data(),
+                                          recs[i].data(), wins[i].data());
+                            check_launch("a kernel launch was refused");
+                            break;
+                        }
+                        catch (const StatusError& e)
+                        {
+                            if (e.status != GOSS_ERR_BUFFER || attempt) throw StatusError{e.status, "routing the staged reads: " + e.msg};
+                        }
+                        catch (const HipError& e)
+                        {
+                            throw StatusError{GOSS_ERR_HIP, std::string("routing the staged reads: ") + e.what + ": " + hipGetErrorString(e.e)};
+                        }
+                        catch (const std::bad_alloc&) { throw StatusError{GOSS_ERR_OOM, "routing the staged reads: host allocation failed"}; }
                         for (uint32_t p = 0; p < n; ++p) cap[p] = recs[i][p] + 1;
                     }
                     c->stage_fill = 0;          // (the windows of these bases now live in the records)
@@ -4084,7 +4087,7 @@ void group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int transport, 
             {
                 HIP_TRY(hipSetDevice(c->device));
                 (void)hipGetLastError();
-                if (c->words == 1) push_records<Key1>(c, c->grp_inbox, nrec, w); else push_records<Key2>(c, c->grp_inbox, nrec, w);
+                push_source(c, records_src(c, c->grp_inbox), nrec, w);
                 check_launch("a kernel launch was refused");
             }
             catch (const HipError& e) { c->bg_status = GOSS_ERR_HIP; c->bg_error = std::string(e.what) + ": " + hipGetErrorString(e.e); }
@@ -4411,83 +4414,7 @@ int goss_gpu_route_records_device(goss_gpu_ctx* c, const void* d_bases, uint64_t
     if (!c || (!d_bases && nbytes) || nparts == 0 || nparts > (uint32_t)kRouteMaxParts || !part_first || !part_cap || !part_records)
         return GOSS_ERR_INVALID_ARG;
     if (c->len > 63) { c->last_error = "records carry windows of at most 63 bases"; return GOSS_ERR_INVALID_ARG; }
-    return guarded(c, [&]() {
-        for (uint32_t p = 0; p < nparts; ++p) { part_records[p] = 0; if (part_windows) part_windows[p] = 0; }
-        if (nbytes < c->len) return;
-        // counters and the parts' places: a small device block of its own (the arena may not be mapped yet, and need not
-        // be), kept for the context's life -- hipFree waits for the whole device, also for a collective of the caller
-        // that is still moving the records of the piece before
-        const size_t tab = (size_t)kRouteMaxParts * 8;
-        if (!c->d_route) HIP_TRY(hipMalloc(&c->d_route, sizeof(RouteCounters) + 2 * tab));
-        RouteCounters* rc = (RouteCounters*)c->d_route;
-        unsigned long long* dfirst = (unsigned long long*)((uint8_t*)c->d_route + sizeof(RouteCounters));
-        unsigned long long* dcap = dfirst + kRouteMaxParts;
-        HIP_TRY(hipMemsetAsync(rc, 0, sizeof(RouteCounters), c->stream));
-        HIP_TRY(hipMemcpyAsync(dfirst, part_first, nparts * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dcap, part_cap, nparts * 8, hipMemcpyHostToDevice, c->stream));
-        const uint64_t nstarts = nbytes - c->len + 1;
-        const uint64_t ntiles = (nstarts + kTB * 16 - 1) / (kTB * 16);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, 256 * GOSS_ROUTE_OCC);
-        const uintptr_t addr = (uintptr_t)d_bases;
-        const uint32_t mis = (uint32_t)(addr & 15u);
-        const uint8_t* aligned = (const uint8_t*)(addr - mis);
-        const uint32_t maxwin = 16;          // (the counting side takes records of any length in both modes)
-        // slots a workgroup takes ahead per part: ~8 tiles' worth (a tile cuts ~550 records); what it does not use ends as pads
-        const uint32_t block = std::max<uint32_t>(32, std::min<uint32_t>(GOSS_ROUTE_BLOCK, 8 * GOSS_ROUTE_BLOCK / nparts));
-        {
-            PhaseTimer t(c, GOSS_T_EXTRACT, nstarts);
-            // (a packed staging buffer -- the group's exchange round sets ctx.pk -- is routed as it is)
-            const uint8_t* src = aligned; const uint16_t* pbad = nullptr;
-            if (c->pk.on) pk_ptrs(c, aligned, &src, &pbad);
-#define GOSS_LAUNCH_ROUTE(W)                                                                                                \
-    do {                                                                                                                    \
-        if (c->pk.on)                                                                                                       \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records_kernel<W, true>), dim3(grid), dim3(kTB), 0, c->stream, src, mis, nstarts, nbytes, \
-                               c->len, maxwin, nparts, block, (SkRec*)d_records, (const unsigned long long*)dfirst, (const unsigned long long*)dcap, rc, ntiles, pbad); \
-        else                                                                                                                \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records_kernel<W, false>), dim3(grid), dim3(kTB), 0, c->stream, src, mis, nstarts, nbytes, \
-                               c->len, maxwin, nparts, block, (SkRec*)d_records, (const unsigned long long*)dfirst, (const unsigned long long*)dcap, rc, ntiles, pbad); \
-    } while (0)
-            if (c->words == 2)
-            {
-                // two-word keys: 20-byte records, the minimizer taken over the central 31 / 30 bases of a window (17 positions)
-                const dim3 g2((uint32_t)std::min<uint64_t>(ntiles, 256 * 4));
-                if (c->pk.on)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records2_kernel<17, true>), g2, dim3(kTB), 0, c->stream, src, mis,
-                                       nstarts, nbytes, c->len, nparts, block, (SkRec2*)d_records, (const unsigned long long*)dfirst,
-                                       (const unsigned long long*)dcap, rc, ntiles, pbad);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(route_records2_kernel<17, false>), g2, dim3(kTB), 0, c->stream, src, mis,
-                                       nstarts, nbytes, c->len, nparts, block, (SkRec2*)d_records, (const unsigned long long*)dfirst,
-                                       (const unsigned long long*)dcap, rc, ntiles, pbad);
-            }
-            else
-            switch (route_positions(c->len))
-            {
-                case 17: GOSS_LAUNCH_ROUTE(17); break;
-                case 13: GOSS_LAUNCH_ROUTE(13); break;
-                case 9: GOSS_LAUNCH_ROUTE(9); break;
-                case 5: GOSS_LAUNCH_ROUTE(5); break;
-                default: GOSS_LAUNCH_ROUTE(1); break;
-            }
-#undef GOSS_LAUNCH_ROUTE
-            t.stop();
-        }
-        std::vector<unsigned long long> h(sizeof(RouteCounters) / 8);
-        HIP_TRY(hipMemcpyAsync(h.data(), rc, sizeof(RouteCounters), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const RouteCounters* hr = (const RouteCounters*)h.data();
-        for (uint32_t p = 0; p < nparts; ++p) { part_records[p] = hr->records[p]; if (part_windows) part_windows[p] = hr->windows[p]; }
-#if defined(GOSS_STAMPS)
-        if (nparts <= 128 && hr->records[128 + 7])
-        {
-            const double n = (double)hr->records[128 + 7];
-            std::fprintf(stderr, "libgossgpu: routing stamps per tile (ticks of wave 0): A %.0f  B %.0f  barrier %.0f  runs+scan %.0f  C %.0f  room %.0f  D %.0f   (%.0f tiles)\n",
-                         hr->records[128] / n, hr->records[129] / n, hr->records[130] / n, hr->records[131] / n, hr->records[132] / n, hr->records[133] / n, hr->records[134] / n, n);
-        }
-#endif
-        if (hr->overflow) throw StatusError{GOSS_ERR_BUFFER, "a part's record buffer is too small (part_records holds what every part needs)"};
-    });
+    return guarded(c, [&]() { route_records(c, ReadSrc::of_bytes(d_bases), nbytes, nparts, d_records, part_first, part_cap, part_records, part_windows); });
 }
 
 int goss_gpu_push_records_device(goss_gpu_ctx* c, const void* d_records, uint64_t nrecords, uint64_t nwindows)
@@ -4498,8 +4425,7 @@ int goss_gpu_push_records_device(goss_gpu_ctx* c, const void* d_records, uint64_
     if (c->len > 63) { c->last_error = "records carry windows of at most 63 bases"; return GOSS_ERR_INVALID_ARG; }
     return guarded(c, [&]() {
         flush_staging(c);
-        if (c->words == 1) push_records<Key1>(c, (const uint8_t*)d_records, nrecords, nwindows);
-        else push_records<Key2>(c, (const uint8_t*)d_records, nrecords, nwindows);
+        push_source(c, records_src(c, d_records), nrecords, nwindows);
     });
 }
 

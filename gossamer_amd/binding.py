@@ -43,6 +43,9 @@ SYMBOLS = [
 # every symbol include/goss_gpu_match.h declares (reads against an object)
 MATCH_SYMBOLS = ["goss_gpu_object_match_reads", "goss_gpu_object_match_reads_host"]
 
+# every symbol include/goss_gpu_near.h declares (compute-near-kmers on an object)
+NEAR_SYMBOLS = ["goss_gpu_object_near_kmers", "goss_gpu_object_near_kmers_host"]
+
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
 
@@ -896,6 +899,7 @@ class Context:
 OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY, OBJECT_ENTRY_EDGE_SET = 0, 1, 2, 3
 QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
 MATCH_NORMALIZE, MATCH_ANY = 1, 4
+NEAR_WHOLE_BASES, NEAR_NORMALIZE = 1, 2          # Object.near_kmers: the two departures from the reference's loop
 ERR_BUFFER = -9
 
 
@@ -961,6 +965,8 @@ def _declare_object(L):
     L.goss_gpu_object_match_reads.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(MatchInfo)]
     L.goss_gpu_entries_length.argtypes = [P, P, U64, P]
     L.goss_gpu_entries_end_rank.argtypes = [P, P, U64, P]
+    L.goss_gpu_object_near_kmers.argtypes = [P, P, P, C.c_uint32, P, P, C.POINTER(U64)]
+    L.goss_gpu_object_near_kmers_host.argtypes = [P, P, P, C.c_uint32, P, P, C.POINTER(U64)]
     L._object_declared = True
 
 
@@ -1129,6 +1135,35 @@ class Object:
         e = self._out(t, n, torch.int64)
         self._check(self._L.goss_gpu_entries_end_rank(self._h, t.data_ptr(), n, e.data_ptr()))
         return self._back(e, staged, np.uint64)
+
+    def near_kmers(self, lhs, rhs, whole_bases=False, normalize=False):
+        """(lhs_new, rhs_new, gray): compute-near-kmers over a KmerSet's two membership bitmaps
+        (goss_gpu_object_near_kmers).  A k-mer of one side only that has a neighbour of the other side only in the set
+        loses both bits; gray is how many did.  lhs, rhs: (count + 63) // 64 words in WordyBitVector layout, as numpy
+        uint64 arrays (numpy comes back), as bytes read from the .lhs-bits / .rhs-bits files (bytes come back) or as
+        device int64 tensors (tensors come back).  With both flags off the result is the reference's; whole_bases
+        flips whole bases instead of the reference's bit-shifted masks, normalize looks every neighbour up in its
+        canonical form."""
+        import numpy as np
+        import torch
+        as_bytes = isinstance(lhs, (bytes, bytearray, memoryview))
+        if as_bytes:
+            lhs, rhs = np.frombuffer(bytes(lhs), dtype=np.uint64).copy(), np.frombuffer(bytes(rhs), dtype=np.uint64).copy()
+        tl, nl, staged = self._input(lhs, 1)
+        tr, nr, _ = self._input(rhs, 1)
+        nwords = (self.count + 63) // 64
+        if nl != nr or nl < nwords or (nwords and nl != nwords):
+            raise ValueError("the bitmaps must hold %d words each" % nwords)
+        ol, orr = torch.zeros_like(tl), torch.zeros_like(tr)
+        _torch_ready()
+        flags =(NEAR_WHOLE_BASES if whole_bases else 0) | (NEAR_NORMALIZE if normalize else 0)
+        gray = C.c_uint64(0)
+        self._check(self._L.goss_gpu_object_near_kmers(self._h, tl.data_ptr() if nwords else None, tr.data_ptr() if nwords else None, flags,
+                                                       ol.data_ptr() if nwords else None, orr.data_ptr() if nwords else None, C.byref(gray)))
+        a, b = self._back(ol, staged, np.uint64), self._back(orr, staged, np.uint64)
+        if as_bytes:
+            a, b = a.tobytes(), b.tobytes()
+        return a, b, gray.value
 
     def match_reads(self, bases, normalize=False, any=False, starts=False, flags=0, max_reads=None):
         """(windows, hits[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_match_reads.

@@ -5090,8 +5090,8 @@ struct goss_gpu_object {
     bool asymmetric = false;
     uint8_t* mem = nullptr;                 // every image, then the query's failure word
     uint64_t bytes = 0;
-    unsigned long long* d_bad = nullptr;
-    unsigned long long* h_bad = nullptr;    // (page-locked)
+    unsigned long long* d_bad = nullptr;    // [0] the failure word, [1] near_kmers' gray total
+    unsigned long long* h_bad = nullptr;    // (page-locked, two words)
     QueryObj q{};
     QueryEntries qe{};                      // an EntryEdgeSet's lengths and ends
     std::string last_error;
@@ -5337,7 +5337,7 @@ int object_open(goss_gpu_object** out, int device, void* stream, int kind, const
     int rc = obj_guarded(device, t_open_error, [&]() {
         if (stream) o->stream = (hipStream_t)stream;
         else { HIP_TRY(hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking)); o->own_stream = true; }
-        HIP_TRY(hipHostMalloc((void**)&o->h_bad, 8, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void**)&o->h_bad, 16, hipHostMallocDefault));    // (the failure word; near_kmers: the gray total)
         open_object(o, kind, base, files);
     });
     if (rc != GOSS_OK) { object_free(o); return rc; }
@@ -5499,6 +5499,68 @@ int goss_gpu_entries_end_rank(goss_gpu_object* o, const uint64_t* d_ranks, uint6
     return object_query(o, n, [&](dim3 grid) {
         hipLaunchKernelGGL(query_end_rank_kernel, grid, dim3(256), 0, o->stream, o->qe, d_ranks, n, d_ends, o->d_bad);
     });
+}
+
+// compute-near-kmers (GossCmdComputeNearKmers.cc:58-121): kernels_near.hpp
+int goss_gpu_object_near_kmers(goss_gpu_object* o, const uint64_t* d_lhs, const uint64_t* d_rhs, uint32_t flags,
+                               uint64_t* d_lhs_out, uint64_t* d_rhs_out, uint64_t* gray)
+{
+    if (!o || !gray || (flags & ~(uint32_t)(GOSS_NEAR_WHOLE_BASES | GOSS_NEAR_NORMALIZE))) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "near_kmers needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    *gray = 0;
+    const uint64_t nwords = (o->q.s.count + 63) / 64, bytes = nwords * 8;
+    if (nwords == 0) return GOSS_OK;
+    if (!d_lhs || !d_rhs || !d_lhs_out || !d_rhs_out) { o->last_error = "near_kmers: a bitmap pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
+    auto overlap = [&](const void* a, const void* b) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return x < y + bytes && y < x + bytes;
+    };
+    if (overlap(d_lhs_out, d_lhs) || overlap(d_lhs_out, d_rhs) || overlap(d_rhs_out, d_lhs) || overlap(d_rhs_out, d_rhs) ||
+        overlap(d_lhs_out, d_rhs_out))
+    {
+        o->last_error = "near_kmers: an output bitmap overlaps an input or the other output (the kernel reads old bits only)";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    return obj_guarded(o->device, o->last_error, [&]() {
+        HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
+        HIP_TRY(hipMemsetAsync(o->d_bad + 1, 0, 8, o->stream));
+        const dim3 grid((uint32_t)std::min<uint64_t>(((nwords + 63) / 64 + 3) / 4, 65536));       // (a wave per 64 words)
+        if (o->key_words == 1)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(near_kmers_kernel<Key1>), grid, dim3(256), 0, o->stream, o->q, d_lhs, d_rhs, flags, d_lhs_out, d_rhs_out, o->d_bad + 1, o->d_bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(near_kmers_kernel<Key2>), grid, dim3(256), 0, o->stream, o->q, d_lhs, d_rhs, flags, d_lhs_out, d_rhs_out, o->d_bad + 1, o->d_bad);
+        HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 16, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        const unsigned long long bad = o->h_bad[0];
+        if (bad != ~0ULL)
+            throw StatusError{GOSS_ERR_INVALID_ARG, "rank " + std::to_string(bad >> 2) + ": the index walk cannot answer (damaged object)"};
+        *gray = o->h_bad[1];
+    });
+}
+
+int goss_gpu_object_near_kmers_host(goss_gpu_object* o, const uint64_t* lhs, const uint64_t* rhs, uint32_t flags,
+                                    uint64_t* lhs_out, uint64_t* rhs_out, uint64_t* gray)
+{
+    if (!o || !gray) return GOSS_ERR_INVALID_ARG;
+    const uint64_t nwords = o->kind == GOSS_OBJECT_KMER_SET ? (o->q.s.count + 63) / 64 : 0, bytes = nwords * 8;
+    if (nwords == 0) return goss_gpu_object_near_kmers(o, nullptr, nullptr, flags, nullptr, nullptr, gray);
+    if (!lhs || !rhs || !lhs_out || !rhs_out) { o->last_error = "near_kmers: a bitmap pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
+    uint64_t* d = nullptr;
+    int rc = obj_guarded(o->device, o->last_error, [&]() {
+        HIP_TRY(hipMalloc((void**)&d, 4 * bytes));
+        HIP_TRY(hipMemcpyAsync(d, lhs, bytes, hipMemcpyHostToDevice, o->stream));
+        HIP_TRY(hipMemcpyAsync(d + nwords, rhs, bytes, hipMemcpyHostToDevice, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    });
+    if (rc == GOSS_OK) rc = goss_gpu_object_near_kmers(o, d, d + nwords, flags, d + 2 * nwords, d + 3 * nwords, gray);
+    if (rc == GOSS_OK)
+        rc = obj_guarded(o->device, o->last_error, [&]() {
+            HIP_TRY(hipMemcpyAsync(lhs_out, d + 2 * nwords, bytes, hipMemcpyDeviceToHost, o->stream));
+            HIP_TRY(hipMemcpyAsync(rhs_out, d + 3 * nwords, bytes, hipMemcpyDeviceToHost, o->stream));
+            HIP_TRY(hipStreamSynchronize(o->stream));
+        });
+    if (d) (void)hipFree(d);
+    return rc;
 }
 
 }  // extern "C"

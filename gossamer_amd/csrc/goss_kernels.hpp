@@ -26,3 +26,4 @@
 #include "kernels_match.hpp"
 #include "kernels_components.hpp"
 #include "kernels_subgraph.hpp"
+#include "kernels_near.hpp"

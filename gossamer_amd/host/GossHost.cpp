@@ -1919,6 +1919,7 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  restore-graph    read in a graph from a robust text representation.\n"
               << "  intersect-kmer-sets  generate the intersection of the given k-mer sets\n"
               << "  merge-and-annotate-kmer-sets  Decorate a graph with an assignment of kmers to graphs.\n"
+              << "  compute-near-kmers  Decorate a graph with an assignment of kmers to graphs.\n"
               << "  merge-graphs     create a new graph by merging zero or more existing graphs\n"
               << "  merge-kmer-sets  create a new graph by merging zero or more existing graphs\n"
               << "  subtract-kmer-set  subtract the second k-mer set from the first\n"
@@ -1961,7 +1962,8 @@ int gossMain(int argc, char* argv[])
         const bool isRestore = cmdName == "restore-graph", isLint = cmdName == "lint-graph";
         const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
         const bool isContigs = cmdName == "print-contigs", isEntries = cmdName == "build-entry-edge-set";
-        if (isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
+        const bool isNear = cmdName == "compute-near-kmers";
+        if (isNear || isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
         {
             // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
             // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
@@ -1971,7 +1973,8 @@ int gossMain(int argc, char* argv[])
             // GossCmdFactoryMergeAndAnnotateKmerSets::create (GossCmdMergeAndAnnotateKmerSets.cc:209-224),
             // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378),
             // GossCmdFactoryTrimGraph::create (GossCmdTrimGraph.cc:130-172), GossCmdFactoryPruneTips::create
-            // (GossCmdPruneTips.cc:347-373), GossCmdFactoryBuildEntryEdgeSet::create (GossCmdBuildEntryEdgeSet.cc:68-84)
+            // (GossCmdPruneTips.cc:347-373), GossCmdFactoryBuildEntryEdgeSet::create (GossCmdBuildEntryEdgeSet.cc:68-84),
+            // GossCmdFactoryComputeNearKmers::create (GossCmdComputeNearKmers.cc:230-243)
             static const OptDef kTrimPrune[] = {
                 {"cutoff", "C", kU64, "coverage cutoff"},
                 {"estimate-only", "", kFlag, "only estimate the coverage cutoff (trim-graph)"},
@@ -2031,7 +2034,8 @@ int gossMain(int argc, char* argv[])
             uint64_t cutoff = 0, iterations = 1;
             std::string notOffered;                 // a part of trim-graph / prune-tips that this build refuses
             uint64_t minLength = 0, minCoverage = 0;
-            if (isDump || isLint || isContigs || isEntries)
+            uint64_t nearThreads = 4;                       // (compute-near-kmers: the loop is the device's)
+            if (isDump || isLint || isContigs || isEntries || isNear)
             {
                 // getRepeatingOnce("graph-in") (GossOptionChecker.hh:235-254)
                 if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
@@ -2043,6 +2047,7 @@ int gossMain(int argc, char* argv[])
                     uint64_t ignoredThreads = 4;            // (the walk is the device's)
                     chk.optionalU64("num-threads", ignoredThreads);
                 }
+                if (isNear) chk.optionalU64("num-threads", nearThreads);
                 if (isContigs)
                 {
                     uint64_t ignoredThreads = 1;
@@ -2161,6 +2166,7 @@ int gossMain(int argc, char* argv[])
                 else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
                 else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
                 else if (isEntries) { GossCmdBuildEntryEdgeSet cmd(ins[0]); cmd(cxt); }
+                else if (isNear) { GossCmdComputeNearKmers cmd(ins[0], nearThreads); cmd(cxt); }
                 else if (isContigs)
                 {
                     GossCmdPrintContigs cmd(ins[0], minCoverage, minLength, opts.count("no-sequence") != 0, opts.count("verbose-headers") != 0,

@@ -220,6 +220,18 @@ private:
     const std::string mLhs, mRhs, mOut;
 };
 
+// GossCmdComputeNearKmers (GossCmdComputeNearKmers.{hh,cc}): rewrites <in>.lhs-bits / <in>.rhs-bits, clearing both bits of
+// every k-mer of one side that has a neighbour of the other side in the set -- with the reference's masks (b << j, a shift
+// by bits) and its lookup of the neighbour as it is, not normalised, because those decide the files `xenome classify` reads.
+// pNumThreads is accepted and unused.
+class GossCmdComputeNearKmers {
+public:
+    GossCmdComputeNearKmers(const std::string& pIn, uint64_t pNumThreads) : mIn(pIn), mNumThreads(pNumThreads) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn; const uint64_t mNumThreads;
+};
+
 // Text form and self-check of existing objects: GossCmdDumpKmerSet.hh, GossCmdDumpGraph.hh,
 // GossCmdRestoreGraph.hh (in = text file, out = graph), GossCmdLintGraph.hh.  "-" = stdin/stdout.
 class GossCmdDumpKmerSet {

@@ -6,6 +6,7 @@
 // (goss_gpu_push_run_sparse); the merge itself is the library's merge of sorted runs; the output
 // files are the device-built images, as for the build commands.
 #include <fcntl.h>
+#include <glob.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -518,6 +519,96 @@ void GossCmdMergeAndAnnotateKmerSets::operator()(const GossCmdContext& pCxt)
     printf("%llu\t%llu\t%llu\n", (unsigned long long)infos[0].count, (unsigned long long)infos[1].count,
            (unsigned long long)common);
     fflush(stdout);
+    log(info, elapsed(t0));
+}
+
+namespace {
+
+// the whole of `data` under `name`
+void writeWhole(const std::string& name, const void* data, size_t bytes)
+{
+    FILE* fp = fopen(name.c_str(), "wb");
+    if (!fp) throw Error::Errno(name, errno);
+    const bool ok = fwrite(data, 1, bytes, fp) == bytes;
+    if (fclose(fp) != 0 || !ok) { ::unlink(name.c_str()); throw Error::Write(name); }
+}
+
+}  // namespace
+
+// GossCmdComputeNearKmers::operator() (GossCmdComputeNearKmers.cc:150-227): the k-mer set is opened on the device as it
+// lies on disk, the two bitmaps go through goss_gpu_object_near_kmers_host with flags 0 -- the reference's loop as it
+// stands -- and come back under their names.  The reference overwrites them in place; here each is written beside its
+// file and renamed over it once both are complete, so a failure leaves the old pair.
+void GossCmdComputeNearKmers::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    (void)mNumThreads;
+    const ObjectInfo si = objectInfo(mIn, false);
+    // KmerSet(name, fac): <in>.header and every file of <in>.kmers
+    std::vector<std::string> names{mIn + ".header"};
+    {
+        glob_t g{};
+        std::string pat;
+        for (char c : mIn) { if (c == '*' || c == '?' || c == '[' || c == '\\') pat += '\\'; pat += c; }
+        pat += ".kmers[.-]*";
+        if (::glob(pat.c_str(), 0, nullptr, &g) == 0)
+            for (size_t i = 0; i < g.gl_pathc; ++i) names.push_back(g.gl_pathv[i]);
+        globfree(&g);
+    }
+    std::vector<Mapped> maps(names.size());
+    std::vector<goss_gpu_named_file> nf(names.size());
+    for (size_t i = 0; i < names.size(); ++i)
+    {
+        maps[i].open(names[i]);
+        nf[i] = goss_gpu_named_file{names[i].c_str(), maps[i].p, maps[i].n};
+    }
+    const std::string lname = mIn + ".lhs-bits", rname = mIn + ".rhs-bits";
+    Mapped lhs, rhs;
+    lhs.open(lname);
+    rhs.open(rname);
+    // WordyBitVector::Builder after count push_backX calls: (count - 1) / 64 + 1 words, one word for none
+    const uint64_t nwords = si.count ? (si.count - 1) / 64 + 1 : 1;
+    for (const auto& f : {std::make_pair(&lname, &lhs), std::make_pair(&rname, &rhs)})
+        if (f.second->n != nwords * 8)
+            throw Error::General("\tfile '" + *f.first + "' holds " + num(f.second->n) + " bytes; the " + num(si.count) + " k-mers of '" + mIn
+                                 + "' need " + num(nwords * 8) + "\n");
+    struct Obj {
+        goss_gpu_object* h = nullptr;
+        ~Obj() { if (h) goss_gpu_object_close(h); }
+    } obj;
+    int rc = goss_gpu_object_open(&obj.h, pCxt.device, nullptr, GOSS_OBJECT_KMER_SET, mIn.c_str(), nf.data(), (uint32_t)nf.size());
+    if (rc != GOSS_OK)
+    {
+        std::string msg = "\tunable to open graph '" + mIn + "'\n\t" + goss_gpu_strerror(rc);
+        const char* d = goss_gpu_object_last_error(nullptr);
+        if (d && *d) msg += std::string(" (") + d + ")";
+        throw Error::General(msg + "\n");
+    }
+    log(info, "initialising bitsets");
+    std::vector<uint64_t> lb(nwords, 0), rb(nwords, 0);
+    log(info, "calculating grey set");
+    uint64_t gray = 0;
+    rc = goss_gpu_object_near_kmers_host(obj.h, (const uint64_t*)lhs.p, (const uint64_t*)rhs.p, 0, lb.data(), rb.data(), &gray);
+    if (rc != GOSS_OK)
+    {
+        std::string msg = std::string("calculating the gray set: ") + goss_gpu_strerror(rc);
+        const char* d = goss_gpu_object_last_error(obj.h);
+        if (d && *d) msg += std::string(" (") + d + ")";
+        throw Error::General(msg + "\n");
+    }
+    log(info, "found " + num(gray) + " gray bits (out of " + num(si.count) + ").");
+    const std::string tag = ".tmp" + num((uint64_t)::getpid());
+    writeWhole(lname + tag, lb.data(), nwords * 8);
+    try { writeWhole(rname + tag, rb.data(), nwords * 8); }
+    catch (...) { ::unlink((lname + tag).c_str()); throw; }
+    if (::rename((lname + tag).c_str(), lname.c_str()) != 0 || ::rename((rname + tag).c_str(), rname.c_str()) != 0)
+    {
+        const int e = errno;
+        ::unlink((lname + tag).c_str());
+        ::unlink((rname + tag).c_str());
+        throw Error::Errno(lname, e);
+    }
     log(info, elapsed(t0));
 }
 

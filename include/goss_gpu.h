@@ -966,6 +966,12 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * in a header of its own. */
 #include "goss_gpu_match.h"
 
+/* compute-near-kmers on an object (goss_gpu_object_near_kmers, goss_gpu_object_near_kmers_host): the loop of
+ * GossCmdComputeNearKmers.cc:58-121 over a KmerSet's .lhs-bits / .rhs-bits, with flags 0 as the reference runs it (masks
+ * shifted by bits, the neighbour looked up un-normalised) and GOSS_NEAR_WHOLE_BASES / GOSS_NEAR_NORMALIZE as the two
+ * departures from it; likewise a part of this ABI kept in a header of its own. */
+#include "goss_gpu_near.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -745,7 +745,8 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
     int rc;
     for (;;)
     {
-        rc = segment_reduce32(c, rems, spare32, n, r, seg_beg, seg_end, form.r32_slots, squeeze, image, rbits32, sqbit32, nseg32, r32_split);
+        const Rem32Layout lay{seg_beg, seg_end, nseg32, form.r32_slots, squeeze, image, rbits32, sqbit32, r32_split};
+        rc = segment_reduce32(c, rems, spare32, n, r, lay);
         if (rc != 1 || form.r32_slots >= 16384 || c->rem32_slots) break;
         // the remainders are still in their sub-regions: only the counting is redone, in the next larger table
         c->segment_retries++;

@@ -580,6 +580,33 @@ class Context:
         self.emit_device()
         return self.files()
 
+    def emit_estimate(self, m):
+        """emit with the SparseArray size estimate M = m instead of the exact count (goss_gpu_emit_estimate: what the
+        merges and graph-to-kmer-set build with)."""
+        self._L.goss_gpu_emit_estimate.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(self._L.goss_gpu_emit_estimate(self._h, m))
+        return self.files()
+
+    def emit_count_bits(self, mask, suffix):
+        """After emit: append the file `suffix`, one bit per result item, set where count & mask != 0
+        (goss_gpu_emit_count_bits: the .lhs-bits / .rhs-bits of merge-and-annotate-kmer-sets)."""
+        self._L.goss_gpu_emit_count_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p]
+        self._check(self._L.goss_gpu_emit_count_bits(self._h, mask, suffix.encode()))
+        return self.files()
+
+    def emit_dump(self, flags=0):
+        """After finish: the text form of the object as the one file ".dump" (goss_gpu_emit_dump)."""
+        self._L.goss_gpu_emit_dump.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(self._L.goss_gpu_emit_dump(self._h, flags))
+        return self.files()
+
+    def emit_dump_range(self, flags, first, count):
+        """The text of elements [first, first + count) only, the header lines in front of the piece that starts at 0
+        (goss_gpu_emit_dump_range)."""
+        self._L.goss_gpu_emit_dump_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
+        self._check(self._L.goss_gpu_emit_dump_range(self._h, flags, first, count))
+        return self.files()
+
     def emit_part(self, first_index, total, estimate=0, prev_last_high=None):
         """Distributed emission, this range's part (goss_gpu_emit_part; with prev_last_high -- the high part of the last
         key of the ranges below, emit_last_high of their owners -- goss_gpu_emit_part_ranges: "-d0" blocks too)."""
@@ -640,8 +667,9 @@ class Context:
                                                        N_end & mask, N_end >> 64))
         return self.files()
 
-    def lint(self, asymmetric=False):
-        """goss_gpu_lint on the finished graph: dict of the problem counts of lint-graph's pass 1."""
+    def lint(self, asymmetric=False, examples=False):
+        """goss_gpu_lint on the finished graph: dict of the problem counts of lint-graph's pass 1; with `examples` also
+        "nexamples" and "examples", the (index, kind, other) of the offending edges the report holds (32 at the most)."""
         class LintReport(C.Structure):
             _fields_ = [("missing_rc", C.c_uint64), ("count_mismatch", C.c_uint64), ("zero_count", C.c_uint64),
                         ("order_violation", C.c_uint64), ("nexamples", C.c_uint32), ("pad", C.c_uint32),
@@ -649,8 +677,12 @@ class Context:
         rep = LintReport()
         self._L.goss_gpu_lint.argtypes = [C.c_void_p, C.c_int, C.POINTER(LintReport)]
         self._check(self._L.goss_gpu_lint(self._h, 1 if asymmetric else 0, C.byref(rep)))
-        return {"missing_rc": rep.missing_rc, "count_mismatch": rep.count_mismatch, "zero_count": rep.zero_count,
-                "order_violation": rep.order_violation}
+        out = {"missing_rc": rep.missing_rc, "count_mismatch": rep.count_mismatch, "zero_count": rep.zero_count,
+               "order_violation": rep.order_violation}
+        if examples:
+            out["nexamples"] = rep.nexamples
+            out["examples"] = [(int(rep.ex_index[i]), int(rep.ex_kind[i]), int(rep.ex_other[i])) for i in range(min(rep.nexamples, 32))]
+        return out
 
     def prune_tips(self, iterations=1):
         """Between finish and emit, graph mode: `iterations` rounds of prune-tips on the device (goss_gpu_prune_tips).

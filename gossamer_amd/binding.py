@@ -45,6 +45,7 @@ MATCH_SYMBOLS = ["goss_gpu_object_match_reads", "goss_gpu_object_match_reads_hos
 
 # every symbol include/goss_gpu_near.h declares (compute-near-kmers on an object)
 NEAR_SYMBOLS = ["goss_gpu_object_near_kmers", "goss_gpu_object_near_kmers_host"]
+CLASSIFY_SYMBOLS = ["goss_gpu_object_classify_reads", "goss_gpu_object_classify_bits_host", "goss_gpu_object_classify_reads_host"]
 
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
@@ -932,6 +933,7 @@ OBJECT_KMER_SET, OBJECT_GRAPH, OBJECT_SPARSE_ARRAY, OBJECT_ENTRY_EDGE_SET = 0, 1
 QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
 MATCH_NORMALIZE, MATCH_ANY = 1, 4
 NEAR_WHOLE_BASES, NEAR_NORMALIZE = 1, 2          # Object.near_kmers: the two departures from the reference's loop
+CLASSIFY_NORMALIZE = 1                           # Object.classify_reads: look up each window's canonical form
 ERR_BUFFER = -9
 
 
@@ -978,6 +980,13 @@ class MatchInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ClassifyInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("windows", C.c_uint64), ("counts", C.c_uint64 * 16), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {"reads": self.reads, "windows": self.windows, "counts": list(self.counts), "ms": self.ms}
+
+
 def _declare_object(L):
     if getattr(L, "_object_declared", False):
         return
@@ -999,6 +1008,9 @@ def _declare_object(L):
     L.goss_gpu_entries_end_rank.argtypes = [P, P, U64, P]
     L.goss_gpu_object_near_kmers.argtypes = [P, P, P, C.c_uint32, P, P, C.POINTER(U64)]
     L.goss_gpu_object_near_kmers_host.argtypes = [P, P, P, C.c_uint32, P, P, C.POINTER(U64)]
+    L.goss_gpu_object_classify_reads.argtypes = [P, P, U64, P, P, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
+    L.goss_gpu_object_classify_bits_host.argtypes = [P, P, P]
+    L.goss_gpu_object_classify_reads_host.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
     L._object_declared = True
 
 
@@ -1197,6 +1209,24 @@ class Object:
             a, b = a.tobytes(), b.tobytes()
         return a, b, gray.value
 
+    # the bases of a batch of reads on the device: (uint8 tensor, staged?)
+    def _bases(self, bases):
+        import numpy as np
+        import torch
+        if isinstance(bases, torch.Tensor):
+            if not bases.is_cuda or bases.element_size() != 1:
+                raise ValueError("torch inputs must be device tensors of bytes")
+            _torch_ready()
+            return bases.contiguous().reshape(-1), False
+        arr = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1)
+        return torch.from_numpy(arr.copy()).to("cuda:%d" % self.device), True
+
+    @staticmethod
+    def _count_reads(t):
+        n = t.numel()
+        return int((t == 10).sum()) + (1 if n and int(t[-1]) != 10 else 0)
+
     def match_reads(self, bases, normalize=False, any=False, starts=False, flags=0, max_reads=None):
         """(windows, hits[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_match_reads.
         windows[r]: valid L-windows of read r; hits[r]: how many are in the object, or with any=True 1 / 0.
@@ -1204,22 +1234,14 @@ class Object:
         come back).  The outputs are sized by counting the newlines; max_reads overrides that."""
         import numpy as np
         import torch
-        if isinstance(bases, torch.Tensor):
-            if not bases.is_cuda or bases.element_size() != 1:
-                raise ValueError("torch inputs must be device tensors of bytes")
-            t, staged = bases.contiguous().reshape(-1), False
-            _torch_ready()
-        else:
-            arr = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1)
-            t, staged = torch.from_numpy(arr.copy()).to("cuda:%d" % self.device), True
+        t, staged = self._bases(bases)
         n = t.numel()
         flags |= (MATCH_NORMALIZE if normalize else 0) | (MATCH_ANY if any else 0)
         info = MatchInfo()
         call = self._L.goss_gpu_object_match_reads
         ptr = t.data_ptr() if n else None
         if max_reads is None:
-            max_reads = int((t == 10).sum()) + (1 if n and int(t[-1]) != 10 else 0)
+            max_reads = self._count_reads(t)
         w = self._out(t, max_reads, torch.int32)
         h = self._out(t, max_reads, torch.int32)
         s = self._out(t, max_reads + 1, torch.int64) if starts else None
@@ -1229,6 +1251,64 @@ class Object:
         self._check(rc)
         r = info.reads
         out = [self._back(w[:r], staged, np.uint32), self._back(h[:r], staged, np.uint32)]
+        if starts:
+            out.append(self._back(s[:r + 1], staged, np.uint64))
+        return tuple(out) + (info.as_dict(),)
+
+    def classify_bits(self, lhs, rhs):
+        """Keeps a KmerSet's two membership bitmaps on the device for later classify_reads calls
+        (goss_gpu_object_classify_bits_host); a second call replaces the pair.  lhs, rhs: (count + 63) // 64 words each,
+        as numpy uint64 arrays or as the bytes of the .lhs-bits / .rhs-bits files."""
+        import numpy as np
+        nwords = (self.count + 63) // 64
+        arrs = []
+        for b in (lhs, rhs):
+            a = np.frombuffer(bytes(b), dtype=np.uint64) if isinstance(b, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+            if a.size < nwords or (nwords and a.size != nwords):
+                raise ValueError("the bitmaps must hold %d words each" % nwords)
+            arrs.append(np.ascontiguousarray(a))
+        self._check(self._L.goss_gpu_object_classify_bits_host(self._h, arrs[0].ctypes.data if nwords else None,
+                                                               arrs[1].ctypes.data if nwords else None))
+
+    def classify_reads(self, bases, lhs=None, rhs=None, normalize=True, starts=False, flags=0, max_reads=None):
+        """(classes, windows[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_classify_reads.
+        classes[r]: the OR of 1 << (2 * lhs[rank] + rhs[rank]) over the windows of read r that are in the set (bit 0: neither
+        side, 1: right only, 2: left only, 3: both); windows[r]: its valid K-windows.  lhs, rhs: the bitmaps as near_kmers
+        takes them (numpy, bytes, device int64 tensors), or both None for the pair kept by classify_bits.  bases and
+        what comes back: as match_reads.  info: reads, windows, counts (reads per mask, a list of 16) and ms."""
+        import numpy as np
+        import torch
+        t, staged = self._bases(bases)
+        n = t.numel()
+        nwords = (self.count + 63) // 64
+        keep, ptrs = [], []
+        for b in (lhs, rhs):                     # (one of the two None: the call itself refuses)
+            if b is None:
+                ptrs.append(None)
+                continue
+            if isinstance(b, (bytes, bytearray, memoryview)):
+                b = np.frombuffer(bytes(b), dtype=np.uint64).copy()
+            tb, nb, _ = self._input(b, 1)
+            if nb < nwords or (nwords and nb != nwords):
+                raise ValueError("the bitmaps must hold %d words each" % nwords)
+            keep.append(tb)
+            ptrs.append(tb.data_ptr() if nwords else None)
+        pl, pr = ptrs
+        flags |= CLASSIFY_NORMALIZE if normalize else 0
+        info = ClassifyInfo()
+        if max_reads is None:
+            max_reads = self._count_reads(t)
+        c = self._out(t, max_reads, torch.int32)
+        w = self._out(t, max_reads, torch.int32)
+        s = self._out(t, max_reads + 1, torch.int64) if starts else None
+        rc = self._L.goss_gpu_object_classify_reads(self._h, t.data_ptr() if n else None, n, pl, pr, flags, max_reads, c.data_ptr(), w.data_ptr(),
+                                                    s.data_ptr() if starts else None, C.byref(info))
+        if rc == ERR_BUFFER:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), "needs max_reads = %d" % info.reads)
+        self._check(rc)
+        r = info.reads
+        out = [self._back(c[:r], staged, np.uint32), self._back(w[:r], staged, np.uint32)]
         if starts:
             out.append(self._back(s[:r + 1], staged, np.uint64))
         return tuple(out) + (info.as_dict(),)

@@ -3575,6 +3575,9 @@ struct goss_gpu_object {
     uint64_t match_stage_bytes = 0;
     unsigned long long* h_match = nullptr;
     hipEvent_t match_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // goss_gpu_object_classify_bits_host: the kept pair, lhs then rhs, (count + 63) / 64 words each
+    uint64_t* classify_bits = nullptr;
+    bool classify_kept = false;
 };
 
 namespace {
@@ -3794,6 +3797,7 @@ void object_free(goss_gpu_object* o)
     if (o->match_tmp) (void)hipFree(o->match_tmp);
     if (o->match_stage) (void)hipFree(o->match_stage);
     if (o->h_match) (void)hipHostFree(o->h_match);
+    if (o->classify_bits) (void)hipFree(o->classify_bits);
     for (hipEvent_t e : o->match_ev) if (e) (void)hipEventDestroy(e);
     if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
@@ -4068,27 +4072,27 @@ void match_scan(hipStream_t st, uint64_t* a, uint64_t n, uint64_t* partial)
     hipLaunchKernelGGL(scan_apply_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, st, a, n, (const uint64_t*)partial);
 }
 
-template <class K>
-void match_launch(goss_gpu_object* o, bool any, uint64_t ntiles, const uint8_t* bases, uint64_t nbytes, const uint64_t* tile_read,
-                  uint32_t flags, uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad)
+template <class K, int MODE>
+void match_launch(goss_gpu_object* o, uint64_t ntiles, const uint8_t* bases, uint64_t nbytes, const uint64_t* tile_read, uint32_t flags,
+                  uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad, const uint64_t* lhs, const uint64_t* rhs)
 {
-    if (any)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, true>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
-                           tile_read, flags, aligned, w, h, starts, bad);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, false>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
-                           tile_read, flags, aligned, w, h, starts, bad);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, MODE>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
+                       tile_read, flags, aligned, w, h, starts, bad, lhs, rhs);
 }
 
-}  // namespace
+// what one pass over the reads leaves on the host
+struct ReadsPass {
+    uint64_t reads = 0;
+    unsigned long long sums[3] = {0, 0, 0};     // windows, hits, reads with a hit
+    unsigned long long counts[16] = {};         // kModeClassify: reads per mask
+    float ms = 0;
+};
 
-extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                           uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, goss_gpu_match_info* info)
+// goss_gpu_object_match_reads and goss_gpu_object_classify_reads past their own argument checks: `what` names the call in
+// messages, `mode` is the kernel's (kModeCount / kModeAny / kModeClassify; d_hits then receives the masks, read at lhs / rhs)
+int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+               uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, const uint64_t* lhs, const uint64_t* rhs, ReadsPass* res)
 {
-    if (info) std::memset(info, 0, sizeof *info);
-    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (flags & ~(uint32_t)(GOSS_MATCH_NORMALIZE | GOSS_MATCH_ANY)) { o->last_error = "match_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
-    if (o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "match_reads needs a KmerSet or a Graph: a bare SparseArray has no key length"; return GOSS_ERR_INVALID_ARG; }
     if (nbytes == 0)
     {
         if (!d_read_starts) return GOSS_OK;
@@ -4100,19 +4104,21 @@ extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bas
     return obj_guarded(o->device, o->last_error, [&]() {
         const uint8_t* bases = (const uint8_t*)d_bases;
         const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
-        // working memory: [0, 64) sums[3], bad[2]; then the tiles' newline counts (+ 1: the total) and the scan's partial sums
+        // working memory: [0, 256) sums[3], bad[2] at word 4, the classes' counts[16] at word 8; then the tiles' newline
+        // counts (+ 1: the total) and the scan's partial sums
         const uint64_t npartial = 2 * ((ntiles + 1 + kScanChunk - 1) / kScanChunk) + 64;
-        uint8_t* mem = match_room(o->match_mem, o->match_bytes, 64 + (ntiles + 1 + npartial) * 8);
+        uint8_t* mem = match_room(o->match_mem, o->match_bytes, 256 + (ntiles + 1 + npartial) * 8);
         unsigned long long* sums = (unsigned long long*)mem;
         unsigned long long* bad = sums + 4;
-        uint64_t* tiles = (uint64_t*)(mem + 64);
+        unsigned long long* counts = sums + 8;
+        uint64_t* tiles = (uint64_t*)(mem + 256);
         uint64_t* partial = tiles + ntiles + 1;
-        if (!o->h_match) HIP_TRY(hipHostMalloc((void**)&o->h_match, 64, hipHostMallocDefault));
+        if (!o->h_match) HIP_TRY(hipHostMalloc((void**)&o->h_match, 256, hipHostMallocDefault));
         for (hipEvent_t& e : o->match_ev) if (!e) HIP_TRY(hipEventCreate(&e));
         const uint32_t aligned = ((uintptr_t)bases & 7u) == 0;
 
         // reads: one '\n' count per tile, scanned; the last byte decides whether a read is left open
-        HIP_TRY(hipMemsetAsync(mem, 0, 32, o->stream));
+        HIP_TRY(hipMemsetAsync(mem, 0, 256, o->stream));
         HIP_TRY(hipMemsetAsync(bad, 0xFF, 16, o->stream));
         HIP_TRY(hipMemsetAsync(tiles + ntiles, 0, 8, o->stream));
         HIP_TRY(hipEventRecord(o->match_ev[0], o->stream));
@@ -4122,12 +4128,12 @@ extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bas
         HIP_TRY(hipMemcpyAsync(&o->h_match[0], tiles + ntiles, 8, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipMemcpyAsync(&o->h_match[1], bases + nbytes - 1, 1, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
-        check_launch("match_reads: counting the reads");
+        check_launch((what + ": counting the reads").c_str());
         const bool open_end = (uint8_t)(o->h_match[1] & 0xFF) != (uint8_t)'\n';
         const uint64_t reads = o->h_match[0] + (open_end ? 1 : 0);
-        if (info) info->reads = reads;
+        res->reads = reads;
         if ((d_windows || d_hits || d_read_starts) && reads > max_reads)
-            throw StatusError{GOSS_ERR_BUFFER, "match_reads: the input holds " + std::to_string(reads) + " reads, the output arrays " + std::to_string(max_reads)};
+            throw StatusError{GOSS_ERR_BUFFER, what + ": the input holds " + std::to_string(reads) + " reads, the output arrays " + std::to_string(max_reads)};
 
         // outputs the caller left out are still the kernel's counters
         uint32_t* w = d_windows;
@@ -4145,28 +4151,83 @@ extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bas
             HIP_TRY(hipMemsetAsync(h, 0, reads * 4, o->stream));
         }
         HIP_TRY(hipEventRecord(o->match_ev[2], o->stream));
-        if (o->key_words == 1) match_launch<Key1>(o, flags & GOSS_MATCH_ANY, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad);
-        else match_launch<Key2>(o, flags & GOSS_MATCH_ANY, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad);
+        auto launch = [&](auto key) {
+            typedef decltype(key) K;
+            if (mode == kModeAny) match_launch<K, kModeAny>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
+            else if (mode == kModeClassify) match_launch<K, kModeClassify>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
+            else match_launch<K, kModeCount>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
+        };
+        if (o->key_words == 1) launch(Key1{});
+        else launch(Key2{});
+        if (mode == kModeClassify && reads)
+            hipLaunchKernelGGL(classify_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256, 2048)), dim3(kTB), 0, o->stream,
+                               (const uint32_t*)h, reads, counts);
         hipLaunchKernelGGL(match_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256 + 1, 2048)), dim3(kTB), 0, o->stream,
                            (const uint32_t*)w, (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
         HIP_TRY(hipEventRecord(o->match_ev[3], o->stream));
-        HIP_TRY(hipMemcpyAsync(o->h_match, mem, 48, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipMemcpyAsync(o->h_match, mem, 192, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
-        check_launch("match_reads: matching");
+        check_launch((what + ": matching").c_str());
         if (o->h_match[4] != ~0ULL)
-            throw StatusError{GOSS_ERR_INVALID_ARG, "match_reads: the window at byte " + std::to_string(o->h_match[4] >> 2) + ": the index walk cannot answer (damaged object)"};
+            throw StatusError{GOSS_ERR_INVALID_ARG, what + ": the window at byte " + std::to_string(o->h_match[4] >> 2) + ": the index walk cannot answer (damaged object)"};
         if (o->h_match[5] != ~0ULL)
-            throw StatusError{GOSS_ERR_INVALID_ARG, "match_reads: read " + std::to_string(o->h_match[5]) + " has 2^32 - 1 windows or more"};
-        if (info)
-        {
-            float a = 0, b = 0;
-            HIP_TRY(hipEventElapsedTime(&a, o->match_ev[0], o->match_ev[1]));
-            HIP_TRY(hipEventElapsedTime(&b, o->match_ev[2], o->match_ev[3]));
-            info->windows = o->h_match[0]; info->hits = o->h_match[1]; info->matched_reads = o->h_match[2];
-            info->ms = a + b;
-        }
+            throw StatusError{GOSS_ERR_INVALID_ARG, what + ": read " + std::to_string(o->h_match[5]) + " has 2^32 - 1 windows or more"};
+        float a = 0, b = 0;
+        HIP_TRY(hipEventElapsedTime(&a, o->match_ev[0], o->match_ev[1]));
+        HIP_TRY(hipEventElapsedTime(&b, o->match_ev[2], o->match_ev[3]));
+        for (int i = 0; i < 3; ++i) res->sums[i] = o->h_match[i];
+        for (int i = 0; i < 16; ++i) res->counts[i] = o->h_match[8 + i];
+        res->ms = a + b;
     });
 }
+
+}  // namespace
+
+extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                           uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, goss_gpu_match_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)(GOSS_MATCH_NORMALIZE | GOSS_MATCH_ANY)) { o->last_error = "match_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    if (o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "match_reads needs a KmerSet or a Graph: a bare SparseArray has no key length"; return GOSS_ERR_INVALID_ARG; }
+    ReadsPass res;
+    const int rc = reads_pass(o, "match_reads", flags & GOSS_MATCH_ANY ? kModeAny : kModeCount, d_bases, nbytes, flags, max_reads, d_windows, d_hits,
+                              d_read_starts, nullptr, nullptr, &res);
+    if (info)
+    {
+        info->reads = res.reads;
+        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->hits = res.sums[1]; info->matched_reads = res.sums[2]; info->ms = res.ms; }
+    }
+    return rc;
+}
+
+namespace {
+
+// The host forms: the batch goes to a buffer the object keeps, `call(d_bases, d_a, d_b, d_starts, &reads)` answers it there,
+// and 4 bytes per read and array come back (a: windows, b: hits / classes).
+template <class Call>
+int reads_staged(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint64_t max_reads, uint32_t* a, uint32_t* b, uint64_t* read_starts, Call call)
+{
+    uint32_t* da = nullptr; uint32_t* db = nullptr; uint64_t* ds = nullptr;
+    int rc = obj_guarded(o->device, o->last_error, [&]() {
+        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL;
+        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, b0 + 2 * each + (max_reads + 1) * 8);
+        da = (uint32_t*)(mem + b0); db = (uint32_t*)(mem + b0 + each); ds = (uint64_t*)(mem + b0 + 2 * each);
+        HIP_TRY(hipMemcpyAsync(mem, bases, nbytes, hipMemcpyHostToDevice, o->stream));
+    });
+    if (rc != GOSS_OK) return rc;
+    uint64_t reads = 0;
+    rc = call(o->match_stage, a ? da : nullptr, b ? db : nullptr, read_starts ? ds : nullptr, &reads);
+    if (rc != GOSS_OK) return rc;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        if (a && reads) HIP_TRY(hipMemcpyAsync(a, da, reads * 4, hipMemcpyDeviceToHost, o->stream));
+        if (b && reads) HIP_TRY(hipMemcpyAsync(b, db, reads * 4, hipMemcpyDeviceToHost, o->stream));
+        if (read_starts) HIP_TRY(hipMemcpyAsync(read_starts, ds, (reads + 1) * 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    });
+}
+
+}  // namespace
 
 extern "C" int goss_gpu_object_match_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
                                                 uint32_t* windows, uint32_t* hits, uint64_t* read_starts, goss_gpu_match_info* info)
@@ -4178,23 +4239,89 @@ extern "C" int goss_gpu_object_match_reads_host(goss_gpu_object* o, const void* 
         if (read_starts) read_starts[0] = 0;
         return goss_gpu_object_match_reads(o, nullptr, 0, flags, max_reads, nullptr, nullptr, nullptr, info);
     }
-    uint32_t* dw = nullptr; uint32_t* dh = nullptr; uint64_t* ds = nullptr;
-    int rc = obj_guarded(o->device, o->last_error, [&]() {
-        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL;
-        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, b0 + 2 * each + (max_reads + 1) * 8);
-        dw = (uint32_t*)(mem + b0); dh = (uint32_t*)(mem + b0 + each); ds = (uint64_t*)(mem + b0 + 2 * each);
-        HIP_TRY(hipMemcpyAsync(mem, bases, nbytes, hipMemcpyHostToDevice, o->stream));
-    });
-    if (rc != GOSS_OK) return rc;
-    goss_gpu_match_info mine;
-    rc = goss_gpu_object_match_reads(o, o->match_stage, nbytes, flags, max_reads, windows ? dw : nullptr, hits ? dh : nullptr,
-                                     read_starts ? ds : nullptr, &mine);
-    if (info) *info = mine;
-    if (rc != GOSS_OK) return rc;
+    return reads_staged(o, bases, nbytes, max_reads, windows, hits, read_starts,
+                        [&](const void* d, uint32_t* dw, uint32_t* dh, uint64_t* ds, uint64_t* reads) {
+                            goss_gpu_match_info mine;
+                            const int rc = goss_gpu_object_match_reads(o, d, nbytes, flags, max_reads, dw, dh, ds, &mine);
+                            if (info) *info = mine;
+                            *reads = mine.reads;
+                            return rc;
+                        });
+}
+
+// ============================================================================================
+// Reads classified against an annotated KmerSet (goss_gpu_object_classify_reads): the classify mode of kernels_match.hpp
+// ============================================================================================
+
+extern "C" int goss_gpu_object_classify_bits_host(goss_gpu_object* o, const uint64_t* lhs, const uint64_t* rhs)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "classify_bits needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    const uint64_t nwords = (o->q.s.count + 63) / 64, bytes = nwords * 8;
+    if (nwords && (!lhs || !rhs)) { o->last_error = "classify_bits: a bitmap pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
     return obj_guarded(o->device, o->last_error, [&]() {
-        if (windows && mine.reads) HIP_TRY(hipMemcpyAsync(windows, dw, mine.reads * 4, hipMemcpyDeviceToHost, o->stream));
-        if (hits && mine.reads) HIP_TRY(hipMemcpyAsync(hits, dh, mine.reads * 4, hipMemcpyDeviceToHost, o->stream));
-        if (read_starts) HIP_TRY(hipMemcpyAsync(read_starts, ds, (mine.reads + 1) * 8, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
+        if (nwords && !o->classify_bits) HIP_TRY(hipMalloc((void**)&o->classify_bits, 2 * bytes));      // (count never changes)
+        if (nwords)
+        {
+            HIP_TRY(hipMemcpyAsync(o->classify_bits, lhs, bytes, hipMemcpyHostToDevice, o->stream));
+            HIP_TRY(hipMemcpyAsync(o->classify_bits + nwords, rhs, bytes, hipMemcpyHostToDevice, o->stream));
+            HIP_TRY(hipStreamSynchronize(o->stream));
+        }
+        o->classify_kept = true;
     });
+}
+
+extern "C" int goss_gpu_object_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint64_t* d_lhs, const uint64_t* d_rhs,
+                                              uint32_t flags, uint64_t max_reads, uint32_t* d_classes, uint32_t* d_windows, uint64_t* d_read_starts,
+                                              goss_gpu_classify_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)GOSS_CLASSIFY_NORMALIZE) { o->last_error = "classify_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "classify_reads needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (!d_lhs != !d_rhs) { o->last_error = "classify_reads: one bitmap pointer is NULL and the other is not"; return GOSS_ERR_INVALID_ARG; }
+    const uint64_t nwords = (o->q.s.count + 63) / 64;
+    if (!d_lhs && nwords)
+    {
+        if (!o->classify_kept)
+        {
+            o->last_error = "classify_reads: no bitmaps given and none kept (goss_gpu_object_classify_bits_host)";
+            return GOSS_ERR_INVALID_ARG;
+        }
+        d_lhs = o->classify_bits;
+        d_rhs = o->classify_bits + nwords;
+    }
+    ReadsPass res;
+    const int rc = reads_pass(o, "classify_reads", kModeClassify, d_bases, nbytes, flags, max_reads, d_windows, d_classes, d_read_starts, d_lhs, d_rhs, &res);
+    if (info)
+    {
+        info->reads = res.reads;
+        if (rc == GOSS_OK)
+        {
+            info->windows = res.sums[0];
+            for (int i = 0; i < 16; ++i) info->counts[i] = res.counts[i];
+            info->ms = res.ms;
+        }
+    }
+    return rc;
+}
+
+extern "C" int goss_gpu_object_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                                   uint32_t* classes, uint32_t* windows, uint64_t* read_starts, goss_gpu_classify_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (nbytes == 0)
+    {
+        if (read_starts) read_starts[0] = 0;
+        return goss_gpu_object_classify_reads(o, nullptr, 0, nullptr, nullptr, flags, max_reads, nullptr, nullptr, nullptr, info);
+    }
+    return reads_staged(o, bases, nbytes, max_reads, windows, classes, read_starts,
+                        [&](const void* d, uint32_t* dw, uint32_t* dc, uint64_t* ds, uint64_t* reads) {
+                            goss_gpu_classify_info mine;
+                            const int rc = goss_gpu_object_classify_reads(o, d, nbytes, nullptr, nullptr, flags, max_reads, dc, dw, ds, &mine);
+                            if (info) *info = mine;
+                            *reads = mine.reads;
+                            return rc;
+                        });
 }

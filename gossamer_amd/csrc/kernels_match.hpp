@@ -24,6 +24,10 @@
 // for the tile's first read also what earlier tiles left in hits[]), and inside a run every eighth window walks
 // first -- the other seven follow only where their read is still unmatched after that ballot.
 //
+// Classify mode (goss_gpu_object_classify_reads) is the count mode's walk with the rank kept: a hit at rank r reads bit r
+// of two bitmaps, c = 2 * lhs[r] + rhs[r], and the read's word is the OR of 1 << c over its hits -- four ballots a run
+// cut by the same lane intervals, one LDS atomicOr per interval, one global atomicOr per read and tile.
+//
 // A walk that cannot answer (damaged image) leaves the lowest such byte position in bad[0]; a read whose window
 // count reaches 2^32 - 1 leaves its index in bad[1].
 #pragma once
@@ -39,6 +43,7 @@
 namespace goss {
 
 enum : uint32_t { kMatchNormalize = 1, kMatchAny = 4 };
+enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2 };      // what hits[] receives: a sum, 1 / 0, a 4-bit mask
 constexpr uint32_t kMatchTile = 2048;                    // positions per workgroup: 256 lanes x 8 bytes
 constexpr uint32_t kMatchRuns = kMatchTile / 64;         // runs of 64 positions, 8 per wave
 constexpr uint32_t kMatchGroups = kMatchTile / 8 + 8;    // 8-byte groups staged: the tile and a halo of 64 positions
@@ -121,12 +126,27 @@ __global__ __launch_bounds__(256) void match_sums_kernel(const uint32_t* __restr
     if (starts && blockIdx.x == 0 && threadIdx.x == 0) starts[reads] = end;
 }
 
-template <class K, bool ANY>
+// classes[i] & 15 counted into out[0..15]: an LDS histogram per block, one global add per non-zero bin
+__global__ __launch_bounds__(256) void classify_sums_kernel(const uint32_t* __restrict__ classes, uint64_t reads, unsigned long long* __restrict__ out)
+{
+    __shared__ uint32_t s_bin[16];
+    if (threadIdx.x < 16) s_bin[threadIdx.x] = 0;
+    __syncthreads();
+    // (32-bit bins: a block of a grid of 2,048 sees 2^32 reads only in an input of 2^43)
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < reads; i += (uint64_t)gridDim.x * blockDim.x)
+        atomicAdd(&s_bin[classes[i] & 15u], 1u);
+    __syncthreads();
+    if (threadIdx.x < 16 && s_bin[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)s_bin[threadIdx.x]);
+}
+
+template <class K, int MODE>
 __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t ntiles,
                                                           const uint64_t* __restrict__ tile_read, uint32_t flags, uint32_t aligned,
                                                           uint32_t* __restrict__ windows, uint32_t* __restrict__ hits,
-                                                          uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad)
+                                                          uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad,
+                                                          const uint64_t* __restrict__ lhs, const uint64_t* __restrict__ rhs)
 {
+    constexpr bool ANY = MODE == kModeAny, CLS = MODE == kModeClassify;
     __shared__ uint64_t s_codes[kMatchGroups / 4];       // 32 bases per word, first base lowest
     __shared__ uint64_t s_inv[kMatchGroups / 8];         // bit = not one of ACGTacgt (or beyond the input)
     __shared__ uint64_t s_nl[kMatchRuns];                // bit = '\n'
@@ -197,6 +217,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
 
         bool done = ANY && __atomic_load_n(&s_hit[local], __ATOMIC_RELAXED) != 0;
         uint64_t hb = 0;
+        uint32_t cls = 0;                                // CLS: the class of this lane's hit
 #pragma unroll
         for (uint32_t ph = 0; ph < (ANY ? 2u : 1u); ++ph)
         {
@@ -218,17 +239,31 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
                 if (flags & kMatchNormalize) x = canonical(x, rc);
                 uint64_t r;
                 if (!rd_sparse_access_rank<K>(o.s, x, &r, &hit)) { q_fail(bad, p, kQBadWalk); hit = false; }
+                if (CLS && hit)
+                {
+                    if (r >= o.s.count) { q_fail(bad, p, kQBadWalk); hit = false; }      // (the bitmaps end at count)
+                    else cls = (uint32_t)((lhs[r >> 6] >> (r & 63)) & 1) << 1 | (uint32_t)((rhs[r >> 6] >> (r & 63)) & 1);
+                }
             }
             const uint64_t b = __ballot(hit);
             hb |= b;
             if (ANY) done = done || (b & seg) != 0;
         }
 
+        uint32_t mask = 0;
+        if (CLS && hb)
+        {
+            const bool hit = (hb >> lane) & 1;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (__ballot(hit && cls == j) & seg) mask |= 1u << j;
+        }
         if (lane == first)
         {
             const uint32_t nw = (uint32_t)__popcll(vb & seg), nh = (uint32_t)__popcll(hb & seg);
             if (nw) atomicAdd(&s_win[local], nw);
-            if (nh) atomicAdd(&s_hit[local], nh);
+            if (CLS) { if (mask) atomicOr(&s_hit[local], mask); }
+            else if (nh) atomicAdd(&s_hit[local], nh);
         }
     }
     __syncthreads();
@@ -244,6 +279,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
         if (nh)
         {
             if (ANY) atomicOr(&hits[read0 + i], 1u);
+            else if (CLS) atomicOr(&hits[read0 + i], nh);
             else atomicAdd(&hits[read0 + i], nh);
         }
     }

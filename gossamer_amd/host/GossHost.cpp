@@ -1931,7 +1931,8 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  count-components  count connected components in the graph represented by the given reads\n"
               << "  build-subgraph   generate a subgraph of an existing graph\n"
               << "  extract-reads    extract reads which map on to a graph\n"
-              << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n";
+              << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n"
+              << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -2381,6 +2382,81 @@ int gossMain(int argc, char* argv[])
                     cmd(cxt);
                 }
                 else { GossCmdExtractReads cmd(in, fastas, fastqs, lines, outName); cmd(cxt); }
+            }
+            catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "group-reads")
+        {
+            // GossCmdFactoryGroupReads::create (GossCmdGroupReads.cc:1037-1084)
+            static const OptDef kGroup[] = {
+                {"graph-in", "G", kStrings, "name of the input graph object"},
+                {"fasta-in", "I", kStrings, "input file in FASTA format"},
+                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
+                {"line-in", "", kStrings, "input file with one sequence per line"},
+                {"max-memory", "M", kString, "maximum memory (in GB) to use (default: unlimited)"},
+                {"pairs", "", kFlag, "treat reads as pairs"},
+                {"lhs-name", "", kString, "name for left-hand side reads"},
+                {"rhs-name", "", kString, "name for right-hand side reads"},
+                {"output-filename-prefix", "", kString, "prefix for output files"},
+                {"dont-write-reads", "", kFlag, "do not produce any output read files"},
+                {"preserve-read-order", "", kFlag, "maintain the same relative ordering of reads in output files"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            for (auto& d : kGroup) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            std::string in;
+            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+            else if (opts.strs("graph-in").size() != 1)
+            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+            else in = opts.str("graph-in");
+            strings fastas, fastqs, lines;
+            chk.repeatingIn("fasta-in", fastas);
+            chk.repeatingIn("fastq-in", fastqs);
+            chk.repeatingIn("line-in", lines);
+            double M = 1.0e9;
+            if (opts.count("max-memory"))
+            {
+                const std::string& v = opts.str("max-memory");
+                char* end = nullptr;
+                errno = 0;
+                M = strtod(v.c_str(), &end);
+                if (v.empty() || errno || *end) throw Error::Usage("the argument ('" + v + "') for option '--max-memory' is invalid\n");
+            }
+            uint64_t T = 4;
+            chk.optionalU64("num-threads", T);
+            std::string lhsName = "lhs", rhsName = "rhs", prefix;
+            if (opts.count("lhs-name")) lhsName = opts.str("lhs-name");
+            if (opts.count("rhs-name")) rhsName = opts.str("rhs-name");
+            if (opts.count("output-filename-prefix")) prefix = opts.str("output-filename-prefix");
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            try
+            {
+                GossCmdGroupReads cmd(in, fastas, fastqs, lines, opts.count("pairs") != 0, M, T, lhsName, rhsName, prefix,
+                                      opts.count("dont-write-reads") != 0, opts.count("preserve-read-order") != 0);
+                cmd(cxt);
             }
             catch (Error& e) { e.cmd = cmdName; throw; }
             return 0;

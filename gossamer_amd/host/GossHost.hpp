@@ -365,6 +365,29 @@ private:
     const std::string mIn, mMatch, mNonMatch; const strings mFastas, mFastqs, mLines; const bool mPairs, mCount; const uint64_t mNumThreads;
 };
 
+// GossCmdGroupReads (GossCmdGroupReads.{hh,cc}, what `xenome classify` runs): every read (or, pPairs, every pair of reads
+// of files 2i and 2i + 1) gets the 4-bit mask of the classes -- neither side, right only, left only, both: the set's
+// .lhs-bits / .rhs-bits -- that its normalised K-mers fall into, and goes to one of [prefix_]{neither, both, ambiguous,
+// <lhs name>, <rhs name>}[_1|_2].{txt, fasta, fastq} by that mask; the table of the sixteen masks and the summary go to
+// standard output (pDontWriteReads: no file, one line of five percentages).  Only one group of inputs is processed -- the
+// line files, else the FASTA files, else the FASTQ files --, as in the reference, which exits after the first group.
+// Departures: the output keeps the input's order whatever pPreserveReadOrder says; pMaxMemory is accepted and exactly
+// one pass is made (the reference's passes partition the ranks and OR the masks: the same result); pNumThreads is unused;
+// pPairs is false when not given (the reference leaves it uninitialised); pair files of unequal length are an error.
+class GossCmdGroupReads {
+public:
+    GossCmdGroupReads(const std::string& pIn, const strings& pFastas, const strings& pFastqs, const strings& pLines, bool pPairs,
+                      double pMaxMemory, uint64_t pNumThreads, const std::string& pLhsName, const std::string& pRhsName,
+                      const std::string& pPrefix, bool pDontWriteReads, bool pPreserveReadOrder)
+        : mIn(pIn), mLhsName(pLhsName), mRhsName(pRhsName), mPrefix(pPrefix), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines),
+          mPairs(pPairs), mDontWriteReads(pDontWriteReads), mPreserveReadOrder(pPreserveReadOrder), mMaxMemory(pMaxMemory),
+          mNumThreads(pNumThreads) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mLhsName, mRhsName, mPrefix; const strings mFastas, mFastqs, mLines;
+    const bool mPairs, mDontWriteReads, mPreserveReadOrder; const double mMaxMemory; const uint64_t mNumThreads;
+};
+
 // Bytes of reads in byte form ('\n' after each) handed to the device per batch by the commands that look reads up in a
 // graph or k-mer set: GossCmdContext::batchBytes, or GOSS_MATCH_BATCH=<bytes> (tests).
 size_t matchBatchBytes(const GossCmdContext& cxt);

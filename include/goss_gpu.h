@@ -972,6 +972,11 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * departures from it; likewise a part of this ABI kept in a header of its own. */
 #include "goss_gpu_near.h"
 
+/* group-reads on an object (goss_gpu_object_classify_reads, goss_gpu_object_classify_bits_host,
+ * goss_gpu_object_classify_reads_host): per read, which of the four classes of an annotated KmerSet its k-mers fall
+ * into -- the loop of GossCmdGroupReads.cc:381-485 over the same .lhs-bits / .rhs-bits; likewise a header of its own. */
+#include "goss_gpu_classify.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ SYMBOLS = [
     "goss_gpu_components_mark_host", "goss_gpu_components_mark_device", "goss_gpu_components_build", "goss_gpu_components_table",
     "goss_gpu_components_labels", "goss_gpu_components_keep", "goss_gpu_components_release",
     "goss_gpu_components_grow", "goss_gpu_components_marks", "goss_gpu_components_keep_marked",
+    "goss_gpu_pool_begin", "goss_gpu_pool_add_masks", "goss_gpu_pool_sizes", "goss_gpu_pool_intersections",
+    "goss_gpu_pool_emit_index", "goss_gpu_pool_release",
 ]
 
 # every symbol include/goss_gpu_match.h declares (reads against an object)
@@ -113,6 +115,26 @@ class GrowInfo(C.Structure):
 
 class ComponentsInfo(C.Structure):
     _fields_ = list(COMPONENTS_INFO_FIELDS)
+
+
+# pool-samples (csrc/kernels_pool.hpp): rows of the pair tile, words of a row per visit of a workgroup of
+# pool_pairs_kernel, words of a row per workgroup of pool_positions_kernel
+POOL_TILE = 64
+POOL_PAIR_WORDS = 128
+POOL_POS_WORDS = 128
+
+
+def pool_similarity_text(inter, sizes):
+    """the <out>.sim text of pool-samples (GossCmdPoolSamples.cc): for every i < j one line "i\tj\tsim\n" with
+    sim = double(inter) / double(|i| + |j| - inter) as a C++ ostream prints it; inter[i][j] = common k-mers"""
+    out = []
+    n = len(sizes)
+    for i in range(n):
+        for j in range(i + 1, n):
+            x = int(inter[i][j])
+            u = int(sizes[i]) + int(sizes[j]) - x
+            out.append("%d\t%d\t%s\n" % (i, j, format_double(float(x) / float(u)) if u else "-nan"))
+    return "".join(out)
 
 
 def format_double(x):
@@ -853,6 +875,44 @@ class Context:
     def components_release(self):
         self._L.goss_gpu_components_release.argtypes = [C.c_void_p]
         self._check(self._L.goss_gpu_components_release(self._h))
+
+    def pool_begin(self, nsets, z):
+        """goss_gpu_pool_begin: zeroed bit rows of nsets samples over a union of z k-mers, held by the context"""
+        self._L.goss_gpu_pool_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+        self._check(self._L.goss_gpu_pool_begin(self._h, nsets, z))
+        self._pool_sets = nsets
+
+    def pool_add_masks(self, first_set, nbits, masks_ptr, z):
+        """goss_gpu_pool_add_masks: masks_ptr is a device pointer to z u32 (bit i: the k-mer is in sample first_set + i)"""
+        self._L.goss_gpu_pool_add_masks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]
+        _torch_ready()
+        self._check(self._L.goss_gpu_pool_add_masks(self._h, first_set, nbits, C.c_void_p(masks_ptr), z))
+
+    def pool_sizes(self):
+        """the k-mers of every sample: a list of ints"""
+        n = getattr(self, "_pool_sets", 1)          # (without a begin the library refuses before it writes)
+        out = (C.c_uint64 * n)()
+        self._L.goss_gpu_pool_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self._check(self._L.goss_gpu_pool_sizes(self._h, out))
+        return [int(x) for x in out]
+
+    def pool_intersections(self):
+        """the common k-mers of every pair of samples: nsets lists of nsets ints, symmetric, the diagonal the sizes"""
+        n = getattr(self, "_pool_sets", 1)          # (without a begin the library refuses before it writes)
+        out = (C.c_uint64 * (n * n))()
+        self._L.goss_gpu_pool_intersections.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self._check(self._L.goss_gpu_pool_intersections(self._h, out))
+        return [[int(out[i * n + j]) for j in range(n)] for i in range(n)]
+
+    def pool_emit_index(self):
+        """goss_gpu_pool_emit_index: the files of the <out>-index SparseArray as {suffix: bytes}"""
+        self._L.goss_gpu_pool_emit_index.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_pool_emit_index(self._h))
+        return self.files()
+
+    def pool_release(self):
+        self._L.goss_gpu_pool_release.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_pool_release(self._h))
 
     def check_index(self, files, base=""):
         """goss_gpu_check_index on a SparseArray given as {suffix: bytes} (files[base + ".header"]

@@ -85,7 +85,7 @@ struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
 // What a build entry point left on top of the permanent room for later calls to read (graph_passes.hpp): the segment
 // table and text of goss_gpu_segments_build, the images of goss_gpu_entries_build, or the marks, labels and table of the
 // components entry points.  One record: at most one is held.
-enum class Held : uint8_t { None, Segments, Entries, Components };
+enum class Held : uint8_t { None, Segments, Entries, Components, Pool };
 struct HeldResult { Held kind = Held::None; uint64_t lo = 0; };          // lo: the permanent top before the build
 
 // Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
@@ -242,6 +242,13 @@ struct goss_gpu_ctx {
     void* cmp_recs = nullptr;
     uint64_t cmp_count = 0;
     bool cmp_built = false;
+    // Held::Pool (pool_path.hpp), bottom to top: the bit rows, the samples' sizes, then from pool_top on the positions
+    // and file images of goss_gpu_pool_emit_index
+    unsigned long long* pool_rows = nullptr;
+    unsigned long long* pool_sizes = nullptr;
+    uint64_t pool_z = 0, pool_top = 0;
+    uint32_t pool_sets = 0;
+    std::vector<bool> pool_added;         // per sample: its row has been written
     std::vector<OutFile> files;
     ExtractCounters* d_ctr = nullptr;     // device counters
     uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
@@ -370,6 +377,7 @@ bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
     rebase(c->tips_keys); rebase(c->tips_counts);
     rebase(c->seg_recs); rebase(c->seg_text);
     rebase(c->cmp_marks); rebase(c->cmp_labels); rebase(c->cmp_recs);
+    rebase(c->pool_rows); rebase(c->pool_sizes);
     for (auto& f : c->files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
     (void)hipFree(a.base);
     a.base = nb; a.hi = target - top; a.size = target;
@@ -1143,8 +1151,9 @@ void wait_background_thread(goss_gpu_ctx* c);
 void release_held(goss_gpu_ctx* c)
 {
     if (c->held.kind != Held::None) c->arena.lo = c->held.lo;
-    if (c->held.kind == Held::Entries) c->files.clear();
+    if (c->held.kind == Held::Entries || c->held.kind == Held::Pool) c->files.clear();
     c->held = HeldResult();
+    c->pool_rows = nullptr; c->pool_sizes = nullptr; c->pool_z = c->pool_top = 0; c->pool_sets = 0; c->pool_added.clear();
     c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
     c->cmp_marks = nullptr; c->cmp_labels = nullptr; c->cmp_recs = nullptr;
     c->cmp_mark_words = c->cmp_built_lo = c->cmp_count = c->cmp_marked = 0;
@@ -1204,6 +1213,9 @@ int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
 
 // ---- prune-tips, print-contigs, build-entry-edge-set: the passes over a finished graph ---------
 #include "graph_passes.hpp"
+
+// ---- pool-samples: bit rows, pair counts, the index ---------------------------------------------
+#include "pool_path.hpp"
 
 }  // namespace
 
@@ -3491,6 +3503,76 @@ int goss_gpu_components_keep_marked(goss_gpu_ctx* c, uint64_t* kept)
     const int rc = guarded(c, [&]() { *kept = components_keep_marked(c); });
     if (c->held.kind != Held::None) release_held(c);
     return rc;
+}
+
+// ---- pool-samples ---------------------------------------------------------------------------------------------------
+
+static int pool_state(goss_gpu_ctx* c, const char* who)
+{
+    if (c->held.kind == Held::Pool) return GOSS_OK;
+    c->last_error = std::string(who) + " needs goss_gpu_pool_begin before it";
+    return GOSS_ERR_STATE;
+}
+
+int goss_gpu_pool_begin(goss_gpu_ctx* c, uint32_t nsets, uint64_t z)
+{
+    if (!c || nsets == 0 || z == 0) return GOSS_ERR_INVALID_ARG;
+    if (z > ~0ULL / nsets) { c->last_error = "pool_begin: z * nsets does not fit 64 bits"; return GOSS_ERR_INVALID_ARG; }
+    // the rows are permanent allocations: between pushes a later merge or an out-of-memory rollback would rewind the
+    // permanent end underneath them (the rule of goss_gpu_emit_sparse_array)
+    if (!c->finished && (!c->runs.empty() || c->stage_fill))
+    {
+        c->last_error = "pool_begin while a count is in progress (reset or finish first)";
+        return GOSS_ERR_STATE;
+    }
+    const int rc = guarded(c, [&]() { pool_begin(c, nsets, z); });
+    if (rc != GOSS_OK && c->held.kind != Held::None) release_held(c);
+    return rc;
+}
+
+int goss_gpu_pool_add_masks(goss_gpu_ctx* c, uint32_t first_set, uint32_t nbits, const uint32_t* d_masks, uint64_t z)
+{
+    if (!c || !d_masks || nbits == 0 || nbits > 32) return GOSS_ERR_INVALID_ARG;
+    if (const int st = pool_state(c, "pool_add_masks")) return st;
+    if (z != c->pool_z) { c->last_error = "pool_add_masks: z differs from goss_gpu_pool_begin's"; return GOSS_ERR_INVALID_ARG; }
+    if (first_set >= c->pool_sets || nbits > c->pool_sets - first_set) { c->last_error = "pool_add_masks: sets past the end"; return GOSS_ERR_INVALID_ARG; }
+    for (uint32_t i = 0; i < nbits; ++i)
+        if (c->pool_added[first_set + i]) { c->last_error = "pool_add_masks: set " + std::to_string(first_set + i) + " was added before"; return GOSS_ERR_STATE; }
+    c->keep_held = true;
+    return guarded(c, [&]() { pool_add_masks(c, first_set, nbits, d_masks); });
+}
+
+int goss_gpu_pool_sizes(goss_gpu_ctx* c, uint64_t* sizes)
+{
+    if (!c || !sizes) return GOSS_ERR_INVALID_ARG;
+    if (const int st = pool_state(c, "pool_sizes")) return st;
+    c->keep_held = true;
+    return guarded(c, [&]() { pool_sizes(c, sizes); });
+}
+
+int goss_gpu_pool_intersections(goss_gpu_ctx* c, uint64_t* inter)
+{
+    if (!c || !inter) return GOSS_ERR_INVALID_ARG;
+    if (const int st = pool_state(c, "pool_intersections")) return st;
+    c->keep_held = true;
+    return guarded(c, [&]() { pool_intersections(c, inter); });
+}
+
+int goss_gpu_pool_emit_index(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (const int st = pool_state(c, "pool_emit_index")) return st;
+    c->keep_held = true;
+    const int rc = guarded(c, [&]() { pool_emit_index(c); });
+    if (rc != GOSS_OK) { c->files.clear(); c->arena.lo = c->pool_top; }       // the rows stay; no half-built index does
+    return rc;
+}
+
+int goss_gpu_pool_release(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind == Held::Pool) release_held(c);
+    return GOSS_OK;
 }
 
 int goss_gpu_emit_count_bits(goss_gpu_ctx* c, uint32_t mask, const char* suffix)

@@ -27,3 +27,4 @@
 #include "kernels_components.hpp"
 #include "kernels_subgraph.hpp"
 #include "kernels_near.hpp"
+#include "kernels_pool.hpp"

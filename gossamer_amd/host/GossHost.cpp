@@ -1932,7 +1932,8 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  build-subgraph   generate a subgraph of an existing graph\n"
               << "  extract-reads    extract reads which map on to a graph\n"
               << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n"
-              << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n";
+              << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n"
+              << "  pool-samples     pool all the samples\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -2175,6 +2176,68 @@ int gossMain(int argc, char* argv[])
                     cmd(cxt);
                 }
                 else { GossCmdMergeAndAnnotateKmerSets cmd(ins[0], ins[1], outName); cmd(cxt); }
+            }
+            catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "pool-samples")
+        {
+            // GossCmdFactoryPoolSamples::create (GossCmdPoolSamples.cc:255-318)
+            static const OptDef kPool[] = {
+                {"kmer-set-in", "", kStrings, "input k-mer set"},
+                {"kmer-sets-in", "", kStrings, "input file containing k-mer sets"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            for (auto& d : kCommon) if (std::string(d.lng) != "line-in") t.defs.push_back(d);
+            for (auto& d : kPool) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            uint64_t K = 25;
+            if (opts.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
+            uint64_t B = 2;
+            chk.optionalU64("buffer-size", B);
+            uint64_t S = 0;
+            { uint64_t slots = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16)); S = (uint64_t)std::log2((double)slots); }
+            uint64_t N = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16));
+            uint64_t T = 4;
+            chk.optionalU64("num-threads", T);
+            std::string outName;
+            chk.mandatoryOut("graph-out", outName);          // (optional in the reference: see GossCmdPoolSamples)
+            strings kmerSets, fastas, fastqs;
+            if (opts.count("kmer-set-in")) kmerSets = opts.strs("kmer-set-in");
+            chk.expand("kmer-sets-in", kmerSets);
+            chk.repeatingIn("fasta-in", fastas);
+            chk.expand("fastas-in", fastas);
+            chk.repeatingIn("fastq-in", fastqs);
+            chk.expand("fastqs-in", fastqs);
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0, budgetGb = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
+            cxt.tmpDir = tmpDirOption(opts.vals);
+            try
+            {
+                GossCmdPoolSamples cmd(K, S, N, T, outName, fastas, fastqs, kmerSets);
+                cmd(cxt);
             }
             catch (Error& e) { e.cmd = cmdName; throw; }
             return 0;

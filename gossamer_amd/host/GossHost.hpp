@@ -220,6 +220,24 @@ private:
     const std::string mLhs, mRhs, mOut;
 };
 
+// GossCmdPoolSamples (GossCmdPoolSamples.{hh,cc}; same constructor arguments): the samples -- the given k-mer sets, then
+// a k-mer set <out>-a<i> per FASTA file, then <out>-q<i> per FASTQ file -- are merged into <out>-union, their membership in
+// the union is written as the SparseArray <out>-index (sample i's k-mer of union rank r at position i * z + r), and the
+// Jaccard similarity of every pair goes to <out>.sim.  Departures: pOutPrefix is mandatory (without it the reference
+// writes under temporary names and to a file called ".sim"); samples of different K are a usage error (the reference
+// compares their raw values); pT only reaches the builds of the per-file sets (the pairs are the device's).
+class GossCmdPoolSamples {
+public:
+    GossCmdPoolSamples(const uint64_t& pK, const uint64_t& pS, const uint64_t& pN, const uint64_t& pT, const std::string& pOutPrefix,
+                       const strings& pFastaNames, const strings& pFastqNames, const strings& pKmerSets)
+        : mK(pK), mS(pS), mN(pN), mT(pT), mOutPrefix(pOutPrefix), mFastaNames(pFastaNames), mFastqNames(pFastqNames), mKmerSets(pKmerSets) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const uint64_t mK, mS, mN, mT;
+    const std::string mOutPrefix;
+    const strings mFastaNames, mFastqNames, mKmerSets;
+};
+
 // GossCmdComputeNearKmers (GossCmdComputeNearKmers.{hh,cc}): rewrites <in>.lhs-bits / <in>.rhs-bits, clearing both bits of
 // every k-mer of one side that has a neighbour of the other side in the set -- with the reference's masks (b << j, a shift
 // by bits) and its lookup of the neighbour as it is, not normalised, because those decide the files `xenome classify` reads.

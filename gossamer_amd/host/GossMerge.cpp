@@ -522,6 +522,126 @@ void GossCmdMergeAndAnnotateKmerSets::operator()(const GossCmdContext& pCxt)
     log(info, elapsed(t0));
 }
 
+// GossCmdPoolSamples::operator() (GossCmdPoolSamples.cc:112-252).  Steps 1 and 2 are the reference's: a k-mer set per
+// input file, then GossCmdMergeKmerSets(samples, 8, <out>-union).  Where it then walks the union once per sample and runs
+// a two-pointer merge over SparseArray::select per pair, the samples are merged once more here as runs of weights 1 << i:
+// the merged count of a union k-mer is its membership mask, the masks become bit rows (goss_gpu_pool_add_masks), and
+// every pair is popcount(row_i & row_j) along the rows.  More than kPoolSlab samples go in slabs of kPoolSlab merged
+// together with the union itself at weight 1 << kPoolSlab, so that every slab's result has exactly the union's keys in
+// the union's order.  kPoolSlab = 30: the largest sum, 2^31 - 1, stays below the lock bit of the counting table's slots.
+void GossCmdPoolSamples::operator()(const GossCmdContext& pCxt)
+{
+    constexpr size_t kPoolSlab = 30;
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    strings samples;
+    for (auto& n : mKmerSets) { log(info, "including k-mer set " + n); samples.push_back(n); }
+    // TODO in the reference too: pairs of input files
+    for (size_t i = 0; i < mFastaNames.size(); ++i)
+    {
+        log(info, "building k-mer set of " + mFastaNames[i]);
+        const std::string out = mOutPrefix + "-a" + num(i);
+        samples.push_back(out);
+        GossCmdBuildKmerSet cmd(mK, mS, mN, mT, out, strings(1, mFastaNames[i]), strings(), strings());
+        cmd(pCxt);
+    }
+    for (size_t i = 0; i < mFastqNames.size(); ++i)
+    {
+        log(info, "building k-mer set of " + mFastqNames[i]);
+        const std::string out = mOutPrefix + "-q" + num(i);
+        samples.push_back(out);
+        GossCmdBuildKmerSet cmd(mK, mS, mN, mT, out, strings(), strings(1, mFastqNames[i]), strings());
+        cmd(pCxt);
+    }
+    if (samples.empty())
+    {
+        log(info, "no samples");
+        return;
+    }
+    std::vector<ObjectInfo> infos;
+    const uint64_t mergeBudget = setBudget(pCxt, samples, infos);
+    for (size_t i = 1; i < samples.size(); ++i)
+        if (infos[i].K != infos[0].K)
+            throw Error::Usage("all samples must have the same kmer-size.\n" + samples[0] + " has k=" + num(infos[0].K) + ".\n"
+                               + samples[i] + " has k=" + num(infos[i].K) + ".\n");
+    const uint64_t K = infos[0].K;
+    if (K > 63 || K == 0) throw Error::General("unable to build a graph with k=" + num(K));
+
+    log(info, "merging sets");
+    const std::string unionName = mOutPrefix + "-union";
+    { GossCmdMergeKmerSets cmd(samples, 8, unionName); cmd(pCxt); }
+
+    uint64_t m = 0;
+    for (auto& o : infos) m += o.count;
+    const uint64_t z = objectInfo(unionName, false).count;
+    const uint64_t S = samples.size();
+    log(info, num(z) + " " + num(K) + "-mers in union");
+    if (z == 0) throw Error::General("every sample is empty: there is nothing to pool\n");
+    if (S > 0xFFFFFFFFULL || z > ~0ULL / S) throw Error::General("the sample x k-mer array does not fit 64 bits\n");
+
+    // the pool's context holds the rows; the merging context is reset between slabs without disturbing them
+    const uint64_t rowBytes = S * ((z + 63) / 64) * 8;
+    log(info, "allocating " + num(rowBytes) + " bytes of sample x k-mer rows");
+    GpuCtx pool;
+    pool.check(goss_gpu_create(&pool.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET,
+                               pCxt.hbmBudget ? pCxt.hbmBudget : rowBytes + m * 40 + (1ULL << 30), nullptr), "creating the GPU context");
+    pool.check(goss_gpu_pool_begin(pool.h, (uint32_t)S, z), "allocating the sample x k-mer rows");
+    {
+        log(info, "merging the samples into membership masks");
+        GpuCtx g;
+        struct stat st;
+        uint64_t budget = mergeBudget;
+        if (!pCxt.hbmBudget)
+        {
+            if (::stat((unionName + ".kmers.high-bits").c_str(), &st) == 0) budget += (uint64_t)st.st_size * 6;
+            budget += z * 24 * 6;
+        }
+        g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+        if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
+        const bool withUnion = S > kPoolSlab;
+        for (size_t first = 0; first < S; first += kPoolSlab)
+        {
+            const size_t nbits = std::min<size_t>(kPoolSlab, S - first);
+            log(info, "constructing bit rows for samples " + num(first) + " to " + num(first + nbits - 1));
+            g.check(goss_gpu_reset(g.h), "resetting the GPU context");
+            for (size_t i = 0; i < nbits; ++i) pushObject(g, samples[first + i], false, 1u << i);
+            if (withUnion) pushObject(g, unionName, false, 1u << kPoolSlab);
+            goss_gpu_counts counts;
+            g.check(goss_gpu_finish(g.h, &counts), "merging");
+            const uint32_t* masks = nullptr; uint64_t got = 0;
+            g.check(goss_gpu_result(g.h, nullptr, &masks, &got), "reading the masks");
+            if (got != z) throw Error::General("the samples do not merge to their union (" + num(got) + " k-mers, the union has " + num(z) + ")\n");
+            pool.check(goss_gpu_pool_add_masks(pool.h, (uint32_t)first, (uint32_t)nbits, masks, z), "building the bit rows");
+        }
+    }
+
+    log(info, "constructing bit array");
+    pool.check(goss_gpu_pool_emit_index(pool.h), "building the on-disk arrays");
+    writeOut(pool, mOutPrefix + "-index");
+
+    log(info, "calculating similarity matrix");
+    std::vector<uint64_t> sizes(S), inter(S * S);
+    pool.check(goss_gpu_pool_sizes(pool.h, sizes.data()), "reading the samples' sizes");
+    pool.check(goss_gpu_pool_intersections(pool.h, inter.data()), "counting the common k-mers");
+    for (size_t i = 0; i < S; ++i)
+        if (sizes[i] != infos[i].count)
+            throw Error::General("sample " + samples[i] + " has " + num(infos[i].count) + " k-mers but " + num(sizes[i]) + " were found in the union\n");
+    std::ostringstream mat;
+    for (size_t i = 0; i < S; ++i)
+        for (size_t j = i + 1; j < S; ++j)
+        {
+            const uint64_t interSz = inter[i * S + j], unionSz = sizes[i] + sizes[j] - interSz;
+            mat << i << '\t' << j << '\t' << (double(interSz) / double(unionSz)) << '\n';
+        }
+    const std::string text = mat.str(), simName = mOutPrefix + ".sim";
+    FILE* fp = std::fopen(simName.c_str(), "wb");
+    if (!fp) throw Error::Errno(simName, errno);
+    const bool ok = text.empty() || std::fwrite(text.data(), 1, text.size(), fp) == text.size();
+    const int werr = errno;
+    if (std::fclose(fp) != 0 || !ok) throw Error::Errno(simName, ok ? errno : werr);
+    log(info, elapsed(t0));
+}
+
 namespace {
 
 // the whole of `data` under `name`

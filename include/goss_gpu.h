@@ -773,6 +773,38 @@ int goss_gpu_components_marks(goss_gpu_ctx* ctx, uint64_t first, uint64_t count,
 int goss_gpu_components_keep_marked(goss_gpu_ctx* ctx, uint64_t* kept);
 
 /*
+ * pool-samples (GossCmdPoolSamples.cc): the membership of nsets samples in a union of z k-mers, held by a context as a
+ * bit matrix of nsets rows of ceil(z / 64) u64 words (row i word w bit b: the k-mer of rank 64 w + b is in sample i), the
+ * number of common k-mers of every pair of samples, and the reference's "<out>-index" SparseArray.  Where the reference
+ * runs nsets (nsets - 1) / 2 two-pointer merges over SparseArray::select, every pair here is popcount(row_i & row_j)
+ * summed along the rows: integer adds only, exact and independent of scheduling.  The context's (k, mode) play no part.
+ *
+ * begin: zeroed rows and sizes on top of the context's permanent room -- a held result like the segments, entries
+ *   and components above: every entry point except the pool's own, goss_gpu_file_*, goss_gpu_result*, and the stat /
+ *   timing getters gives it back.  nsets * ceil(z / 64) * 8 bytes.
+ * add_masks: d_masks is a device pointer to z u32, one per k-mer of the union in rank order; bit i (i < nbits <= 32) says
+ *   whether the k-mer is in sample first_set + i, bits at or above nbits are ignored.  With the samples merged as runs of
+ *   weights 1 << i (goss_gpu_push_run_sparse) the d_counts of goss_gpu_result of ANOTHER context on the same device are
+ *   such masks; the call returns when they have been read, so that context may be reset at once.  Rows first_set ...
+ *   first_set + nbits - 1 are written whole; a sample may be added once.
+ * sizes: sizes[i] = k-mers of sample i.  intersections: inter[i * nsets + j] = common k-mers of samples i and j,
+ *   row-major, symmetric, the diagonal equal to the sizes.  Both are host arrays.  A sample not added yet is empty.
+ * emit_index: for sample i in order, the ranks r of its k-mers in increasing order as the positions i * z + r, through
+ *   the SparseArray emitter with N = z * nsets, M = the sum of the sizes, end(N) -- the files of
+ *   goss_gpu_emit_sparse_array, read with goss_gpu_file_*.  8 bytes per position and the images, above the rows.
+ *
+ * GOSS_ERR_INVALID_ARG: nsets or z zero; z * nsets >= 2^64; nbits outside 1..32; sets past nsets; a z that differs from
+ *   begin's.  GOSS_ERR_OOM: the rows do not fit the arena (nothing is held).  GOSS_ERR_STATE: begin while a count is in
+ *   progress; any other call without begin; a sample added twice.
+ */
+int goss_gpu_pool_begin(goss_gpu_ctx* ctx, uint32_t nsets, uint64_t z);
+int goss_gpu_pool_add_masks(goss_gpu_ctx* ctx, uint32_t first_set, uint32_t nbits, const uint32_t* d_masks, uint64_t z);
+int goss_gpu_pool_sizes(goss_gpu_ctx* ctx, uint64_t* sizes /* nsets */);
+int goss_gpu_pool_intersections(goss_gpu_ctx* ctx, uint64_t* inter /* nsets * nsets */);
+int goss_gpu_pool_emit_index(goss_gpu_ctx* ctx);
+int goss_gpu_pool_release(goss_gpu_ctx* ctx);
+
+/*
  * Page-locked host memory for the buffers handed to goss_gpu_push_bases_host (the copy to the
  * device then runs at PCIe speed instead of going through the driver's bounce buffers).
  */

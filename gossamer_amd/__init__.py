@@ -7,4 +7,5 @@ the C ABI for tests and bench.py.
 from .binding import (Context, GossGpuError, MODE_GRAPH, MODE_KMER_SET, SYMBOLS,  # noqa: F401
                       OBJECT_ENTRY_EDGE_SET, OBJECT_GRAPH, OBJECT_KMER_SET, OBJECT_SPARSE_ARRAY, MATCH_ANY, MATCH_NORMALIZE, MATCH_SYMBOLS, CLASSIFY_NORMALIZE, CLASSIFY_SYMBOLS, NEAR_NORMALIZE, NEAR_SYMBOLS, NEAR_WHOLE_BASES, Object, encode_kmers,
                       group_emit, group_exchange, group_route_exchange, load, synth_reads_host,
-                      POOL_PAIR_WORDS, POOL_POS_WORDS, POOL_TILE, format_double, pool_similarity_text)
+                      POOL_PAIR_WORDS, POOL_POS_WORDS, POOL_TILE, format_double, pool_similarity_text,
+                      TAXO_MANY, TAXO_NONE, TAXO_NORMALIZE, TAXO_SYMBOLS, format_phylogeny, parse_phylogeny, phylogeny_nodes)

@@ -49,6 +49,12 @@ MATCH_SYMBOLS = ["goss_gpu_object_match_reads", "goss_gpu_object_match_reads_hos
 NEAR_SYMBOLS = ["goss_gpu_object_near_kmers", "goss_gpu_object_near_kmers_host"]
 CLASSIFY_SYMBOLS = ["goss_gpu_object_classify_reads", "goss_gpu_object_classify_bits_host", "goss_gpu_object_classify_reads_host"]
 
+# every symbol include/goss_gpu_taxo.h declares (annotate-kmers and classify-reads on an object)
+TAXO_SYMBOLS = ["goss_gpu_object_taxo_tree_host", "goss_gpu_object_taxo_annotation_host", "goss_gpu_object_taxo_annotation_read",
+                "goss_gpu_object_taxo_annotate", "goss_gpu_object_taxo_annotate_host", "goss_gpu_object_taxo_classify_reads",
+                "goss_gpu_object_taxo_classify_reads_host", "goss_gpu_object_taxo_pair", "goss_gpu_object_taxo_pair_host",
+                "goss_gpu_object_taxo_tally", "goss_gpu_object_taxo_tally_host"]
+
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
 
@@ -994,6 +1000,8 @@ QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
 MATCH_NORMALIZE, MATCH_ANY = 1, 4
 NEAR_WHOLE_BASES, NEAR_NORMALIZE = 1, 2          # Object.near_kmers: the two departures from the reference's loop
 CLASSIFY_NORMALIZE = 1                           # Object.classify_reads: look up each window's canonical form
+TAXO_NORMALIZE = 1                               # Object.taxo_annotate / taxo_classify_reads: canonical windows
+TAXO_NONE, TAXO_MANY = 0xFFFFFFFF, 0xFFFFFFFE    # Object.taxo_classify_reads: no class / classes on more than one path
 ERR_BUFFER = -9
 
 
@@ -1047,6 +1055,82 @@ class ClassifyInfo(C.Structure):
         return {"reads": self.reads, "windows": self.windows, "counts": list(self.counts), "ms": self.ms}
 
 
+class TaxoInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64), ("none", C.c_uint64), ("many", C.c_uint64),
+                ("unannotated", C.c_uint64), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def parse_phylogeny(text):
+    """A phylogeny file -- a nested token list, "(" key value ... child ... ")" -- as {"anns": {key: value}, "kids": [...]}"""
+    toks = text.decode() if isinstance(text, (bytes, bytearray)) else text
+    toks = toks.split()
+    stack, root, i = [], None, 0
+    while i < len(toks):
+        tok = toks[i]
+        if tok == "(":
+            node = {"anns": {}, "kids": []}
+            if stack:
+                stack[-1]["kids"].append(node)
+            elif root is not None:
+                raise ValueError("phylogeny: tokens after the root's ')'")
+            else:
+                root = node
+            stack.append(node)
+            i += 1
+        elif tok == ")":
+            if not stack:
+                raise ValueError("phylogeny: ')' without '('")
+            stack.pop()
+            i += 1
+        else:
+            if not stack or stack[-1]["kids"] or i + 1 >= len(toks) or toks[i + 1] in ("(", ")"):
+                raise ValueError("phylogeny: stray token %r" % tok)
+            stack[-1]["anns"][tok] = toks[i + 1]
+            i += 2
+    if root is None or stack:
+        raise ValueError("phylogeny: unbalanced")
+    return root
+
+
+def format_phylogeny(root):
+    """The text AnnotTree::write makes of a parsed phylogeny: one space per depth, "(" on a line of its own, one
+    key TAB value line per annotation in key order, the children in order, ")"."""
+    out, todo = [], [(root, 0)]
+    while todo:
+        node, d = todo.pop()
+        if node is None:
+            out.append(" " * d + ")\n")
+            continue
+        out.append(" " * d + "(\n")
+        out += [" " * (d + 1) + k + "\t" + node["anns"][k] + "\n" for k in sorted(node["anns"])]
+        todo.append((None, d))
+        todo += [(c, d + 1) for c in reversed(node["kids"])]
+    return "".join(out)
+
+
+def phylogeny_nodes(root, need=("node", "name")):
+    """(nodes in file order, ids, parent_index) of a parsed phylogeny, as Object.taxo_tree takes them; a node without one
+    of `need`, or with a node id that is no uint32, raises"""
+    nodes, ids, parent, todo = [], [], [], [(root, None)]
+    while todo:
+        node, p = todo.pop()
+        i = len(nodes)
+        for k in need:
+            if k not in node["anns"]:
+                raise ValueError("phylogeny: node %d (in file order) has no '%s'" % (i, k))
+        v = node["anns"]["node"]
+        if not v.isdigit() or int(v) > 0xFFFFFFFF:
+            raise ValueError("phylogeny: node %d (in file order) has the id %r" % (i, v))
+        nodes.append(node)
+        ids.append(int(v))
+        parent.append(i if p is None else p)
+        todo += [(c, i) for c in reversed(node["kids"])]
+    return nodes, ids, parent
+
+
 def _declare_object(L):
     if getattr(L, "_object_declared", False):
         return
@@ -1071,6 +1155,18 @@ def _declare_object(L):
     L.goss_gpu_object_classify_reads.argtypes = [P, P, U64, P, P, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
     L.goss_gpu_object_classify_bits_host.argtypes = [P, P, P]
     L.goss_gpu_object_classify_reads_host.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
+    U32 = C.c_uint32
+    L.goss_gpu_object_taxo_tree_host.argtypes = [P, U32, P, P]
+    L.goss_gpu_object_taxo_annotation_host.argtypes = [P, P]
+    L.goss_gpu_object_taxo_annotation_read.argtypes = [P, P, P]
+    L.goss_gpu_object_taxo_annotate.argtypes = [P, P, U64, P, U32, U64, P, C.POINTER(TaxoInfo)]
+    L.goss_gpu_object_taxo_annotate_host.argtypes = [P, P, U64, P, U32, U64, P, C.POINTER(TaxoInfo)]
+    L.goss_gpu_object_taxo_classify_reads.argtypes = [P, P, U64, U32, U64, P, P, P, C.POINTER(TaxoInfo)]
+    L.goss_gpu_object_taxo_classify_reads_host.argtypes = [P, P, U64, U32, U64, P, P, P, C.POINTER(TaxoInfo)]
+    L.goss_gpu_object_taxo_pair.argtypes = [P, P, P, U64, P]
+    L.goss_gpu_object_taxo_pair_host.argtypes = [P, P, P, U64, P]
+    L.goss_gpu_object_taxo_tally.argtypes = [P, P, U64, P]
+    L.goss_gpu_object_taxo_tally_host.argtypes = [P, P, U64, P]
     L._object_declared = True
 
 
@@ -1372,3 +1468,125 @@ class Object:
         if starts:
             out.append(self._back(s[:r + 1], staged, np.uint64))
         return tuple(out) + (info.as_dict(),)
+
+    # -- a taxonomy over the set's k-mers (goss_gpu_object_taxo_*) --
+    def taxo_tree(self, ids, parent_index):
+        """Validates, numbers and uploads a tree: ids[i] the node's id, parent_index[i] the index of its parent, the root
+        its own (goss_gpu_object_taxo_tree_host).  A second call replaces the tree and drops the annotation.  Every
+        per-node array of the taxo_ calls is in this order."""
+        import numpy as np
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        p = np.ascontiguousarray(parent_index, dtype=np.uint32).reshape(-1)
+        if a.size != p.size:
+            raise ValueError("ids and parent_index differ in length")
+        self._check(self._L.goss_gpu_object_taxo_tree_host(self._h, a.size, a.ctypes.data if a.size else None, p.ctypes.data if a.size else None))
+        self._taxo_n = int(a.size)
+
+    def taxo_annotation(self, ann=None):
+        """Starts an all-untouched annotation (None) or loads one: `count` node ids as a numpy uint32 array or as the bytes
+        of a .annotation file, TAXO_NONE for an untouched k-mer (goss_gpu_object_taxo_annotation_host)."""
+        import numpy as np
+        if ann is None:
+            return self._check(self._L.goss_gpu_object_taxo_annotation_host(self._h, None))
+        a = np.frombuffer(bytes(ann), dtype=np.uint32) if isinstance(ann, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(ann, dtype=np.uint32).reshape(-1)
+        if a.size != self.count:
+            raise ValueError("the annotation must hold %d node ids" % self.count)
+        a = np.ascontiguousarray(a) if a.size else np.zeros(1, dtype=np.uint32)     # (a pointer that is not NULL)
+        self._check(self._L.goss_gpu_object_taxo_annotation_host(self._h, a.ctypes.data))
+
+    def _u32(self, a, like=None):
+        """a uint32 array on the device: (int32 tensor, staged?)"""
+        import numpy as np
+        import torch
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda or a.element_size() != 4:
+                raise ValueError("torch inputs must be device tensors of 32-bit values")
+            _torch_ready()
+            return a.contiguous().reshape(-1), False
+        arr = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+        return torch.from_numpy(arr.view(np.int32).copy()).to("cuda:%d" % self.device), True
+
+    def taxo_annotate(self, bases, read_nodes, normalize=True, flags=0, max_reads=None):
+        """(windows, info): every window of every read of `bases` that is in the set takes the read's node into its
+        k-mer's class by lca (goss_gpu_object_taxo_annotate).  read_nodes: one node id per read (numpy uint32 or a device
+        int32 tensor with the same bits), or one id for all.  bases and what comes back: as match_reads.  info: reads,
+        windows, hits, ms."""
+        import numpy as np
+        import torch
+        t, staged = self._bases(bases)
+        n = t.numel()
+        if max_reads is None:
+            max_reads = self._count_reads(t)
+        if isinstance(read_nodes, int):
+            read_nodes = np.full(max_reads, read_nodes, dtype=np.uint32)
+        rn, _ = self._u32(read_nodes)
+        if rn.numel() != max_reads:
+            raise ValueError("read_nodes must hold %d node ids" % max_reads)
+        w = self._out(t, max_reads, torch.int32)
+        info = TaxoInfo()
+        rc = self._L.goss_gpu_object_taxo_annotate(self._h, t.data_ptr() if n else None, n, rn.data_ptr() if max_reads else None,
+                                                   flags | (TAXO_NORMALIZE if normalize else 0), max_reads, w.data_ptr(), C.byref(info))
+        if rc == ERR_BUFFER:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), "needs max_reads = %d" % info.reads)
+        self._check(rc)
+        return self._back(w[:info.reads], staged, np.uint32), info.as_dict()
+
+    def taxo_read_annotation(self):
+        """(annotation, counts): the node id of every rank (TAXO_NONE where untouched) and, per node, the ranks whose class
+        is exactly that node (goss_gpu_object_taxo_annotation_read); numpy uint32 / uint64."""
+        import numpy as np
+        ann = np.zeros(max(1, self.count), dtype=np.uint32)
+        counts = np.zeros(max(1, getattr(self, "_taxo_n", 0)), dtype=np.uint64)
+        self._check(self._L.goss_gpu_object_taxo_annotation_read(self._h, ann.ctypes.data, counts.ctypes.data))
+        return ann[:self.count], counts[:getattr(self, "_taxo_n", 0)]
+
+    def taxo_classify_reads(self, bases, normalize=True, starts=False, flags=0, max_reads=None):
+        """(result, windows[, starts], info) per read of `bases`: goss_gpu_object_taxo_classify_reads.  result[r]: the
+        deepest class among the read's windows when those classes lie on one root-to-leaf path, TAXO_MANY when they do
+        not, TAXO_NONE without any.  bases and what comes back: as match_reads.  info: reads, windows, none, many,
+        unannotated, ms."""
+        import numpy as np
+        import torch
+        t, staged = self._bases(bases)
+        n = t.numel()
+        info = TaxoInfo()
+        if max_reads is None:
+            max_reads = self._count_reads(t)
+        c = self._out(t, max_reads, torch.int32)
+        w = self._out(t, max_reads, torch.int32)
+        s = self._out(t, max_reads + 1, torch.int64) if starts else None
+        rc = self._L.goss_gpu_object_taxo_classify_reads(self._h, t.data_ptr() if n else None, n, flags | (TAXO_NORMALIZE if normalize else 0),
+                                                         max_reads, c.data_ptr(), w.data_ptr(), s.data_ptr() if starts else None, C.byref(info))
+        if rc == ERR_BUFFER:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), "needs max_reads = %d" % info.reads)
+        self._check(rc)
+        r = info.reads
+        out = [self._back(c[:r], staged, np.uint32), self._back(w[:r], staged, np.uint32)]
+        if starts:
+            out.append(self._back(s[:r + 1], staged, np.uint64))
+        return tuple(out) + (info.as_dict(),)
+
+    def taxo_pair(self, a, b):
+        """the join of two result arrays, mate by mate (goss_gpu_object_taxo_pair): the deeper node when one is an
+        ancestor-or-equal of the other, TAXO_MANY when not, the other where one is TAXO_NONE"""
+        import numpy as np
+        import torch
+        ta, staged = self._u32(a)
+        tb, _ = self._u32(b)
+        if ta.numel() != tb.numel():
+            raise ValueError("the two arrays differ in length")
+        out = torch.empty_like(ta)
+        n = ta.numel()
+        self._check(self._L.goss_gpu_object_taxo_pair(self._h, ta.data_ptr() if n else None, tb.data_ptr() if n else None, n,
+                                                      out.data_ptr() if n else None))
+        return self._back(out, staged, np.uint32)
+
+    def taxo_tally(self, values):
+        """how often each node occurs among `values` (node ids, TAXO_NONE, TAXO_MANY), in the order of the tree, then the
+        NONEs and the MANYs: n_nodes + 2 numpy uint64 (goss_gpu_object_taxo_tally)"""
+        import numpy as np
+        tv, _ = self._u32(values)
+        counts = np.zeros(getattr(self, "_taxo_n", 0) + 2, dtype=np.uint64)
+        self._check(self._L.goss_gpu_object_taxo_tally(self._h, tv.data_ptr() if tv.numel() else None, tv.numel(), counts.ctypes.data))
+        return counts

@@ -3660,6 +3660,16 @@ struct goss_gpu_object {
     // goss_gpu_object_classify_bits_host: the kept pair, lhs then rhs, (count + 63) / 64 words each
     uint64_t* classify_bits = nullptr;
     bool classify_kept = false;
+    // goss_gpu_object_taxo_*: the tree in one allocation -- parent, last, id by pre-order number, then the sorted ids and
+    // their classes, then n + 2 bins --, the annotation (a class per rank), working memory that only grows
+    uint32_t taxo_n = 0;
+    uint32_t* taxo_tree = nullptr;
+    unsigned long long* taxo_bins = nullptr;
+    std::vector<uint32_t> taxo_pre;         // the pre-order number of the i-th node as given
+    uint32_t* taxo_ann = nullptr;
+    bool taxo_ann_kept = false;
+    uint8_t* taxo_tmp = nullptr;
+    uint64_t taxo_tmp_bytes = 0;
 };
 
 namespace {
@@ -3880,6 +3890,9 @@ void object_free(goss_gpu_object* o)
     if (o->match_stage) (void)hipFree(o->match_stage);
     if (o->h_match) (void)hipHostFree(o->h_match);
     if (o->classify_bits) (void)hipFree(o->classify_bits);
+    if (o->taxo_tree) (void)hipFree(o->taxo_tree);
+    if (o->taxo_ann) (void)hipFree(o->taxo_ann);
+    if (o->taxo_tmp) (void)hipFree(o->taxo_tmp);
     for (hipEvent_t e : o->match_ev) if (e) (void)hipEventDestroy(e);
     if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
@@ -4156,24 +4169,29 @@ void match_scan(hipStream_t st, uint64_t* a, uint64_t n, uint64_t* partial)
 
 template <class K, int MODE>
 void match_launch(goss_gpu_object* o, uint64_t ntiles, const uint8_t* bases, uint64_t nbytes, const uint64_t* tile_read, uint32_t flags,
-                  uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad, const uint64_t* lhs, const uint64_t* rhs)
+                  uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad, const uint64_t* lhs, const uint64_t* rhs,
+                  const TaxoView& tx)
 {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, MODE>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
-                       tile_read, flags, aligned, w, h, starts, bad, lhs, rhs);
+                       tile_read, flags, aligned, w, h, starts, bad, lhs, rhs, tx);
 }
 
 // what one pass over the reads leaves on the host
 struct ReadsPass {
     uint64_t reads = 0;
-    unsigned long long sums[3] = {0, 0, 0};     // windows, hits, reads with a hit
+    unsigned long long sums[4] = {0, 0, 0, 0};  // windows, hits, reads with a hit; kModeTaxon: hits at a rank without a class
     unsigned long long counts[16] = {};         // kModeClassify: reads per mask
     float ms = 0;
 };
 
 // goss_gpu_object_match_reads and goss_gpu_object_classify_reads past their own argument checks: `what` names the call in
-// messages, `mode` is the kernel's (kModeCount / kModeAny / kModeClassify; d_hits then receives the masks, read at lhs / rhs)
+// messages, `mode` is the kernel's (kModeCount / kModeAny / kModeClassify; d_hits then receives the masks, read at lhs / rhs).
+// kModeAnnotate / kModeTaxon read and write what `tx` points at (kernels_taxo.hpp; tx.read_class holds max_reads classes,
+// so the batch must fit); `post(hits, reads)` runs on the stream behind the kernel, inside the timed stretch.
+typedef std::function<void(uint32_t*, uint64_t)> ReadsPost;
 int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-               uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, const uint64_t* lhs, const uint64_t* rhs, ReadsPass* res)
+               uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, const uint64_t* lhs, const uint64_t* rhs, ReadsPass* res,
+               TaxoView tx = TaxoView{}, const ReadsPost& post = ReadsPost())
 {
     if (nbytes == 0)
     {
@@ -4186,7 +4204,7 @@ int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void
     return obj_guarded(o->device, o->last_error, [&]() {
         const uint8_t* bases = (const uint8_t*)d_bases;
         const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
-        // working memory: [0, 256) sums[3], bad[2] at word 4, the classes' counts[16] at word 8; then the tiles' newline
+        // working memory: [0, 256) sums[4], bad[2] at word 4, the classes' counts[16] at word 8; then the tiles' newline
         // counts (+ 1: the total) and the scan's partial sums
         const uint64_t npartial = 2 * ((ntiles + 1 + kScanChunk - 1) / kScanChunk) + 64;
         uint8_t* mem = match_room(o->match_mem, o->match_bytes, 256 + (ntiles + 1 + npartial) * 8);
@@ -4214,7 +4232,7 @@ int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void
         const bool open_end = (uint8_t)(o->h_match[1] & 0xFF) != (uint8_t)'\n';
         const uint64_t reads = o->h_match[0] + (open_end ? 1 : 0);
         res->reads = reads;
-        if ((d_windows || d_hits || d_read_starts) && reads > max_reads)
+        if ((d_windows || d_hits || d_read_starts || tx.read_class) && reads > max_reads)
             throw StatusError{GOSS_ERR_BUFFER, what + ": the input holds " + std::to_string(reads) + " reads, the output arrays " + std::to_string(max_reads)};
 
         // outputs the caller left out are still the kernel's counters
@@ -4235,10 +4253,13 @@ int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void
         HIP_TRY(hipEventRecord(o->match_ev[2], o->stream));
         auto launch = [&](auto key) {
             typedef decltype(key) K;
-            if (mode == kModeAny) match_launch<K, kModeAny>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
-            else if (mode == kModeClassify) match_launch<K, kModeClassify>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
-            else match_launch<K, kModeCount>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs);
+            if (mode == kModeAny) match_launch<K, kModeAny>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
+            else if (mode == kModeClassify) match_launch<K, kModeClassify>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
+            else if (mode == kModeAnnotate) match_launch<K, kModeAnnotate>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
+            else if (mode == kModeTaxon) match_launch<K, kModeTaxon>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
+            else match_launch<K, kModeCount>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
         };
+        tx.unann = sums + 3;
         if (o->key_words == 1) launch(Key1{});
         else launch(Key2{});
         if (mode == kModeClassify && reads)
@@ -4246,6 +4267,7 @@ int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void
                                (const uint32_t*)h, reads, counts);
         hipLaunchKernelGGL(match_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256 + 1, 2048)), dim3(kTB), 0, o->stream,
                            (const uint32_t*)w, (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
+        if (post && reads) post(h, reads);
         HIP_TRY(hipEventRecord(o->match_ev[3], o->stream));
         HIP_TRY(hipMemcpyAsync(o->h_match, mem, 192, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
@@ -4257,7 +4279,7 @@ int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void
         float a = 0, b = 0;
         HIP_TRY(hipEventElapsedTime(&a, o->match_ev[0], o->match_ev[1]));
         HIP_TRY(hipEventElapsedTime(&b, o->match_ev[2], o->match_ev[3]));
-        for (int i = 0; i < 3; ++i) res->sums[i] = o->h_match[i];
+        for (int i = 0; i < 4; ++i) res->sums[i] = o->h_match[i];
         for (int i = 0; i < 16; ++i) res->counts[i] = o->h_match[8 + i];
         res->ms = a + b;
     });
@@ -4406,4 +4428,405 @@ extern "C" int goss_gpu_object_classify_reads_host(goss_gpu_object* o, const voi
                             *reads = mine.reads;
                             return rc;
                         });
+}
+
+// ============================================================================================
+// A taxonomy over a KmerSet's k-mers (goss_gpu_object_taxo_*): kernels_taxo.hpp and the annotate / taxon modes of
+// kernels_match.hpp
+// ============================================================================================
+
+namespace {
+
+inline dim3 taxo_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 2048)); }
+
+struct TaxoTables {
+    const uint32_t *parent, *last, *id, *sorted_id, *sorted_class;
+};
+TaxoTables taxo_tables(const goss_gpu_object* o)
+{
+    const uint32_t* t = o->taxo_tree;
+    const uint64_t n = o->taxo_n;
+    return TaxoTables{t, t + n, t + 2 * n, t + 3 * n, t + 4 * n};
+}
+
+// the checks every taxo call but the tree's begins with; *empty: the set has no k-mers, and the call has nothing to do
+int taxo_ready(goss_gpu_object* o, const char* what, bool need_ann, bool* empty)
+{
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = std::string(what) + " needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    *empty = o->q.s.count == 0;
+    if (*empty) return GOSS_OK;
+    if (!o->taxo_n) { o->last_error = std::string(what) + ": no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
+    if (need_ann && !o->taxo_ann_kept) { o->last_error = std::string(what) + ": no annotation (goss_gpu_object_taxo_annotation_host)"; return GOSS_ERR_STATE; }
+    return GOSS_OK;
+}
+
+// out[0..z) = the classes of the node ids in[0..z) (device arrays); an id the tree lacks throws, `item` naming what i counts
+void taxo_dense(goss_gpu_object* o, const char* what, const char* item, const uint32_t* in, uint64_t z, uint32_t allow, uint32_t* out)
+{
+    if (!z) return;
+    const TaxoTables t = taxo_tables(o);
+    HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
+    hipLaunchKernelGGL(taxo_dense_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, in, z, t.sorted_id, t.sorted_class, o->taxo_n, allow, out, o->d_bad);
+    HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    check_launch(what);
+    const unsigned long long bad = *o->h_bad;
+    if (bad == ~0ULL) return;
+    uint32_t id = 0;
+    HIP_TRY(hipMemcpy(&id, in + bad, 4, hipMemcpyDeviceToHost));
+    throw StatusError{GOSS_ERR_INVALID_ARG, std::string(what) + ": " + item + " " + std::to_string(bad) + " has node id " + std::to_string(id) + ", which the tree lacks"};
+}
+
+// bins (device, n + 2) = the tally of z classes
+void taxo_tally(goss_gpu_object* o, const uint32_t* classes, uint64_t z)
+{
+    HIP_TRY(hipMemsetAsync(o->taxo_bins, 0, ((uint64_t)o->taxo_n + 2) * 8, o->stream));
+    if (z) hipLaunchKernelGGL(taxo_tally_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, classes, z, o->taxo_n, o->taxo_bins);
+}
+
+// counts[i] = the bin of the i-th node as given, then none and many
+void taxo_bins_out(goss_gpu_object* o, uint64_t* counts)
+{
+    std::vector<unsigned long long> bins((uint64_t)o->taxo_n + 2);
+    HIP_TRY(hipMemcpyAsync(bins.data(), o->taxo_bins, bins.size() * 8, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    for (uint32_t i = 0; i < o->taxo_n; ++i) counts[i] = bins[o->taxo_pre[i]];
+    counts[o->taxo_n] = bins[o->taxo_n];
+    counts[o->taxo_n + 1] = bins[o->taxo_n + 1];
+}
+
+}  // namespace
+
+extern "C" int goss_gpu_object_taxo_tree_host(goss_gpu_object* o, uint32_t n, const uint32_t* ids, const uint32_t* parent_index)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_tree needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (!n || !ids || !parent_index) { o->last_error = "taxo_tree: no nodes"; return GOSS_ERR_INVALID_ARG; }
+    if (n >= 0xFFFFFFFEu) { o->last_error = "taxo_tree: too many nodes"; return GOSS_ERR_INVALID_ARG; }
+    return obj_guarded(o->device, o->last_error, [&]() {
+        auto refuse = [](const std::string& msg) { throw StatusError{GOSS_ERR_INVALID_ARG, "taxo_tree: " + msg}; };
+        // one root, parents in range, ids usable and distinct
+        uint32_t root = n;
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            if (parent_index[i] >= n) refuse("node " + std::to_string(i) + " names parent " + std::to_string(parent_index[i]) + " of " + std::to_string(n));
+            if (ids[i] == GOSS_TAXO_NONE || ids[i] == GOSS_TAXO_MANY) refuse("node " + std::to_string(i) + " has the reserved id " + std::to_string(ids[i]));
+            if (parent_index[i] != i) continue;
+            if (root != n) refuse("nodes " + std::to_string(root) + " and " + std::to_string(i) + " are both their own parent");
+            root = i;
+        }
+        if (root == n) refuse("no node is its own parent");
+        std::vector<uint32_t> by_id(n);
+        for (uint32_t i = 0; i < n; ++i) by_id[i] = i;
+        std::sort(by_id.begin(), by_id.end(), [&](uint32_t a, uint32_t b) { return ids[a] < ids[b]; });
+        for (uint32_t i = 1; i < n; ++i)
+            if (ids[by_id[i]] == ids[by_id[i - 1]]) refuse("node id " + std::to_string(ids[by_id[i]]) + " occurs twice");
+        // children in the order given (a counting sort by parent), then pre-order numbers without recursion
+        std::vector<uint32_t> first(n + 1, 0), kids(n ? n - 1 : 0);
+        for (uint32_t i = 0; i < n; ++i) if (i != root) ++first[parent_index[i] + 1];
+        for (uint32_t i = 0; i < n; ++i) first[i + 1] += first[i];
+        {
+            std::vector<uint32_t> at(first.begin(), first.end() - 1);
+            for (uint32_t i = 0; i < n; ++i) if (i != root) kids[at[parent_index[i]]++] = i;
+        }
+        std::vector<uint32_t> pre(n, 0xFFFFFFFFu), tab(5 * (uint64_t)n), next(n, 0), stack;
+        uint32_t* parent = tab.data(); uint32_t* last = parent + n; uint32_t* id = last + n; uint32_t* sid = id + n; uint32_t* scl = sid + n;
+        uint32_t seen = 0;
+        pre[root] = seen++;
+        parent[0] = 0;
+        id[0] = ids[root];
+        stack.push_back(root);
+        while (!stack.empty())
+        {
+            const uint32_t v = stack.back();
+            if (next[v] < first[v + 1] - first[v])
+            {
+                const uint32_t c = kids[first[v] + next[v]++];
+                pre[c] = seen++;
+                parent[pre[c]] = pre[v];
+                id[pre[c]] = ids[c];
+                stack.push_back(c);
+            }
+            else
+            {
+                last[pre[v]] = seen - 1;
+                stack.pop_back();
+            }
+        }
+        if (seen != n)
+            for (uint32_t i = 0; i < n; ++i)
+                if (pre[i] == 0xFFFFFFFFu) refuse("node " + std::to_string(i) + " does not hang under the root");
+        for (uint32_t i = 0; i < n; ++i) { sid[i] = ids[by_id[i]]; scl[i] = pre[by_id[i]] + 1; }
+
+        const uint64_t tab_bytes = (5 * (uint64_t)n * 4 + 7) & ~7ULL;
+        uint32_t* mem = nullptr;
+        if (hipMalloc((void**)&mem, tab_bytes + ((uint64_t)n + 2) * 8) != hipSuccess) { (void)hipGetLastError(); throw StatusError{GOSS_ERR_OOM, "taxo_tree: no device memory for the tree"}; }
+        if (hipMemcpy(mem, tab.data(), 5 * (uint64_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(mem); throw StatusError{GOSS_ERR_HIP, "taxo_tree: the copy of the tree failed"}; }
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        if (o->taxo_tree) (void)hipFree(o->taxo_tree);
+        o->taxo_tree = mem;
+        o->taxo_bins = (unsigned long long*)((uint8_t*)mem + tab_bytes);
+        o->taxo_n = n;
+        o->taxo_pre.swap(pre);
+        o->taxo_ann_kept = false;                // (its classes were the old tree's numbers)
+    });
+}
+
+extern "C" int goss_gpu_object_taxo_annotation_host(goss_gpu_object* o, const uint32_t* ann)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    bool empty = false;
+    const int rc = taxo_ready(o, "taxo_annotation", false, &empty);
+    if (rc != GOSS_OK || empty) return rc;
+    const uint64_t z = o->q.s.count;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        if (!o->taxo_ann && hipMalloc((void**)&o->taxo_ann, z * 4) != hipSuccess) { (void)hipGetLastError(); o->taxo_ann = nullptr; throw StatusError{GOSS_ERR_OOM, "taxo_annotation: no device memory for the annotation"}; }
+        if (!ann) HIP_TRY(hipMemsetAsync(o->taxo_ann, 0, z * 4, o->stream));
+        else
+        {
+            // converted beside the kept one, which an unknown id leaves as it was
+            const uint64_t each = (z * 4 + 255) & ~255ULL;
+            uint8_t* tmp = match_room(o->taxo_tmp, o->taxo_tmp_bytes, 2 * each);
+            HIP_TRY(hipMemcpyAsync(tmp, ann, z * 4, hipMemcpyHostToDevice, o->stream));
+            taxo_dense(o, "taxo_annotation", "rank", (const uint32_t*)tmp, z, kTaxoAllowNone, (uint32_t*)(tmp + each));
+            HIP_TRY(hipMemcpyAsync(o->taxo_ann, tmp + each, z * 4, hipMemcpyDeviceToDevice, o->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        o->taxo_ann_kept = true;
+    });
+}
+
+extern "C" int goss_gpu_object_taxo_annotation_read(goss_gpu_object* o, uint32_t* ann_out, uint64_t* counts_out)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    bool empty = false;
+    const int rc = taxo_ready(o, "taxo_annotation_read", true, &empty);
+    if (rc != GOSS_OK) return rc;
+    if (empty)
+    {
+        if (counts_out) for (uint32_t i = 0; i < o->taxo_n; ++i) counts_out[i] = 0;
+        return GOSS_OK;
+    }
+    const uint64_t z = o->q.s.count;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        if (counts_out)
+        {
+            taxo_tally(o, o->taxo_ann, z);
+            std::vector<uint64_t> counts((uint64_t)o->taxo_n + 2);
+            taxo_bins_out(o, counts.data());
+            std::copy(counts.begin(), counts.end() - 2, counts_out);
+        }
+        if (ann_out)
+        {
+            uint32_t* tmp = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, z * 4);
+            hipLaunchKernelGGL(taxo_ids_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, (const uint32_t*)o->taxo_ann, z, taxo_tables(o).id, tmp);
+            HIP_TRY(hipMemcpyAsync(ann_out, tmp, z * 4, hipMemcpyDeviceToHost, o->stream));
+            HIP_TRY(hipStreamSynchronize(o->stream));
+            check_launch("taxo_annotation_read");
+        }
+    });
+}
+
+namespace {
+
+// the result of a call on an empty set: the reads counted and their windows, no hit anywhere (must_fit: annotate, whose
+// node ids are per read)
+int taxo_empty_pass(goss_gpu_object* o, const char* what, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads, uint32_t* d_result,
+                    uint32_t* d_windows, uint64_t* d_read_starts, bool must_fit, goss_gpu_taxo_info* info)
+{
+    ReadsPass res;
+    int rc = reads_pass(o, what, kModeCount, d_bases, nbytes, flags, max_reads, d_windows, nullptr, d_read_starts, nullptr, nullptr, &res);
+    if (rc == GOSS_OK && must_fit && res.reads > max_reads)
+    {
+        o->last_error = std::string(what) + ": the input holds " + std::to_string(res.reads) + " reads, the output arrays " + std::to_string(max_reads);
+        rc = GOSS_ERR_BUFFER;
+    }
+    if (rc == GOSS_OK && d_result && res.reads)
+        rc = obj_guarded(o->device, o->last_error, [&]() {
+            HIP_TRY(hipMemsetAsync(d_result, 0xFF, res.reads * 4, o->stream));       // (GOSS_TAXO_NONE)
+            HIP_TRY(hipStreamSynchronize(o->stream));
+        });
+    if (info)
+    {
+        info->reads = res.reads;
+        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->none = must_fit ? 0 : res.reads; info->ms = res.ms; }
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int goss_gpu_object_taxo_annotate(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint32_t* d_read_nodes, uint32_t flags,
+                                             uint64_t max_reads, uint32_t* d_windows, goss_gpu_taxo_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)GOSS_TAXO_NORMALIZE) { o->last_error = "taxo_annotate: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    bool empty = false;
+    int rc = taxo_ready(o, "taxo_annotate", true, &empty);
+    if (rc != GOSS_OK) return rc;
+    if (!d_read_nodes && max_reads && nbytes) { o->last_error = "taxo_annotate: no node ids for the reads"; return GOSS_ERR_INVALID_ARG; }
+    if (empty)
+        return taxo_empty_pass(o, "taxo_annotate", d_bases, nbytes, flags, max_reads, nullptr, d_windows, nullptr, true, info);
+    if (nbytes == 0) return GOSS_OK;
+    TaxoView tx;
+    rc = obj_guarded(o->device, o->last_error, [&]() {
+        uint32_t* cls = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, max_reads * 4 + 256);
+        taxo_dense(o, "taxo_annotate", "read", d_read_nodes, max_reads, 0, cls);
+        const TaxoTables t = taxo_tables(o);
+        tx.parent = t.parent; tx.last = t.last; tx.ann = o->taxo_ann; tx.read_class = cls;
+    });
+    if (rc != GOSS_OK) return rc;
+    ReadsPass res;
+    rc = reads_pass(o, "taxo_annotate", kModeAnnotate, d_bases, nbytes, flags, max_reads, d_windows, nullptr, nullptr, nullptr, nullptr, &res, tx);
+    if (info)
+    {
+        info->reads = res.reads;
+        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->hits = res.sums[1]; info->ms = res.ms; }
+    }
+    return rc;
+}
+
+extern "C" int goss_gpu_object_taxo_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                                   uint32_t* d_result, uint32_t* d_windows, uint64_t* d_read_starts, goss_gpu_taxo_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)GOSS_TAXO_NORMALIZE) { o->last_error = "taxo_classify_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    bool empty = false;
+    int rc = taxo_ready(o, "taxo_classify_reads", true, &empty);
+    if (rc != GOSS_OK) return rc;
+    if (empty) return taxo_empty_pass(o, "taxo_classify_reads", d_bases, nbytes, flags, max_reads, d_result, d_windows, d_read_starts, false, info);
+    const TaxoTables t = taxo_tables(o);
+    TaxoView tx;
+    tx.parent = t.parent; tx.last = t.last; tx.ann = o->taxo_ann;
+    ReadsPass res;
+    unsigned long long ends[2] = {0, 0};
+    rc = reads_pass(o, "taxo_classify_reads", kModeTaxon, d_bases, nbytes, flags, max_reads, d_windows, d_result, d_read_starts, nullptr, nullptr, &res, tx,
+                    [&](uint32_t* h, uint64_t reads) {
+                        // the figures from the classes, then the classes become node ids where they lie
+                        taxo_tally(o, h, reads);
+                        hipLaunchKernelGGL(taxo_ids_kernel, taxo_grid(reads), dim3(kTB), 0, o->stream, (const uint32_t*)h, reads, t.id, h);
+                        HIP_TRY(hipMemcpyAsync(ends, o->taxo_bins + o->taxo_n, 16, hipMemcpyDeviceToHost, o->stream));
+                    });
+    if (info)
+    {
+        info->reads = res.reads;
+        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->none = ends[0]; info->many = ends[1]; info->unannotated = res.sums[3]; info->ms = res.ms; }
+    }
+    return rc;
+}
+
+extern "C" int goss_gpu_object_taxo_annotate_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, const uint32_t* read_nodes, uint32_t flags,
+                                                  uint64_t max_reads, uint32_t* windows, goss_gpu_taxo_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (nbytes == 0) return goss_gpu_object_taxo_annotate(o, nullptr, 0, nullptr, flags, max_reads, nullptr, info);
+    if (!read_nodes && max_reads) { o->last_error = "taxo_annotate: no node ids for the reads"; return GOSS_ERR_INVALID_ARG; }
+    // the node ids ride in the slot of the staged form's second array
+    return reads_staged(o, bases, nbytes, max_reads, windows, nullptr, nullptr,
+                        [&](const void* d, uint32_t* dw, uint32_t*, uint64_t*, uint64_t* reads) {
+                            uint32_t* dn = (uint32_t*)(o->match_stage + ((nbytes + 255) & ~255ULL) + ((max_reads * 4 + 255) & ~255ULL));
+                            const int rc0 = obj_guarded(o->device, o->last_error, [&]() {
+                                if (max_reads) HIP_TRY(hipMemcpyAsync(dn, read_nodes, max_reads * 4, hipMemcpyHostToDevice, o->stream));
+                            });
+                            if (rc0 != GOSS_OK) return rc0;
+                            goss_gpu_taxo_info mine;
+                            const int rc = goss_gpu_object_taxo_annotate(o, d, nbytes, dn, flags, max_reads, dw, &mine);
+                            if (info) *info = mine;
+                            *reads = mine.reads;
+                            return rc;
+                        });
+}
+
+extern "C" int goss_gpu_object_taxo_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                                        uint32_t* result, uint32_t* windows, uint64_t* read_starts, goss_gpu_taxo_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (nbytes == 0)
+    {
+        if (read_starts) read_starts[0] = 0;
+        return goss_gpu_object_taxo_classify_reads(o, nullptr, 0, flags, max_reads, nullptr, nullptr, nullptr, info);
+    }
+    return reads_staged(o, bases, nbytes, max_reads, windows, result, read_starts,
+                        [&](const void* d, uint32_t* dw, uint32_t* dr, uint64_t* ds, uint64_t* reads) {
+                            goss_gpu_taxo_info mine;
+                            const int rc = goss_gpu_object_taxo_classify_reads(o, d, nbytes, flags, max_reads, dr, dw, ds, &mine);
+                            if (info) *info = mine;
+                            *reads = mine.reads;
+                            return rc;
+                        });
+}
+
+extern "C" int goss_gpu_object_taxo_pair(goss_gpu_object* o, const uint32_t* d_a, const uint32_t* d_b, uint64_t n, uint32_t* d_out)
+{
+    if (!o || (n && (!d_a || !d_b || !d_out))) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_pair needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (!o->taxo_n) { o->last_error = "taxo_pair: no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
+    if (!n) return GOSS_OK;
+    return obj_guarded(o->device, o->last_error, [&]() {
+        const TaxoTables t = taxo_tables(o);
+        HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
+        hipLaunchKernelGGL(taxo_pair_kernel, taxo_grid(n), dim3(kTB), 0, o->stream, d_a, d_b, n, t.sorted_id, t.sorted_class, t.last, t.id, o->taxo_n, d_out, o->d_bad);
+        HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        check_launch("taxo_pair");
+        if (*o->h_bad != ~0ULL) throw StatusError{GOSS_ERR_INVALID_ARG, "taxo_pair: pair " + std::to_string(*o->h_bad) + " holds a node id the tree lacks"};
+    });
+}
+
+extern "C" int goss_gpu_object_taxo_tally(goss_gpu_object* o, const uint32_t* d_values, uint64_t n, uint64_t* counts)
+{
+    if (!o || !counts || (n && !d_values)) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_tally needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (!o->taxo_n) { o->last_error = "taxo_tally: no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
+    return obj_guarded(o->device, o->last_error, [&]() {
+        uint32_t* cls = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, n * 4 + 256);
+        taxo_dense(o, "taxo_tally", "value", d_values, n, kTaxoAllowNone | kTaxoAllowMany, cls);
+        taxo_tally(o, cls, n);
+        taxo_bins_out(o, counts);
+        check_launch("taxo_tally");
+    });
+}
+
+namespace {
+
+// n values per array staged to the device and `call`ed there: ins host arrays in, then `outs` arrays back
+template <class Call>
+int taxo_staged(goss_gpu_object* o, std::initializer_list<const uint32_t*> ins, uint64_t n, uint32_t* out, Call call)
+{
+    uint32_t* d[3] = {nullptr, nullptr, nullptr};
+    int rc = obj_guarded(o->device, o->last_error, [&]() {
+        const uint64_t each = (n * 4 + 255) & ~255ULL;
+        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, 3 * each + 256);
+        uint32_t k = 0;
+        for (const uint32_t* p : ins)
+        {
+            d[k] = (uint32_t*)(mem + k * each);
+            if (n) HIP_TRY(hipMemcpyAsync(d[k], p, n * 4, hipMemcpyHostToDevice, o->stream));
+            ++k;
+        }
+        d[2] = (uint32_t*)(mem + 2 * each);
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    });
+    if (rc != GOSS_OK) return rc;
+    rc = call(d[0], d[1], d[2]);
+    if (rc != GOSS_OK || !out || !n) return rc;
+    return obj_guarded(o->device, o->last_error, [&]() { HIP_TRY(hipMemcpy(out, d[2], n * 4, hipMemcpyDeviceToHost)); });
+}
+
+}  // namespace
+
+extern "C" int goss_gpu_object_taxo_pair_host(goss_gpu_object* o, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out)
+{
+    if (!o || (n && (!a || !b || !out))) return GOSS_ERR_INVALID_ARG;
+    return taxo_staged(o, {a, b}, n, out, [&](uint32_t* da, uint32_t* db, uint32_t* dout) { return goss_gpu_object_taxo_pair(o, da, db, n, dout); });
+}
+
+extern "C" int goss_gpu_object_taxo_tally_host(goss_gpu_object* o, const uint32_t* values, uint64_t n, uint64_t* counts)
+{
+    if (!o || !counts || (n && !values)) return GOSS_ERR_INVALID_ARG;
+    return taxo_staged(o, {values}, n, nullptr, [&](uint32_t* dv, uint32_t*, uint32_t*) { return goss_gpu_object_taxo_tally(o, dv, n, counts); });
 }

@@ -23,6 +23,7 @@
 #include "kernels_tips.hpp"
 #include "kernels_contigs.hpp"
 #include "kernels_entries.hpp"
+#include "kernels_taxo.hpp"
 #include "kernels_match.hpp"
 #include "kernels_components.hpp"
 #include "kernels_subgraph.hpp"

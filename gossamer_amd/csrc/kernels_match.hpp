@@ -28,6 +28,14 @@
 // of two bitmaps, c = 2 * lhs[r] + rhs[r], and the read's word is the OR of 1 << c over its hits -- four ballots a run
 // cut by the same lane intervals, one LDS atomicOr per interval, one global atomicOr per read and tile.
 //
+// The two taxonomy modes (goss_gpu_object_taxo_annotate / _classify_reads, kernels_taxo.hpp) also keep the rank.  Annotate:
+// the read's class comes from a per-read array, and a hit at rank r joins it into ann[r] by lca with a compare-and-swap
+// loop that does not write where ann[r] already is the join; windows and hits are counted as in count mode.  Taxon: a
+// hit reads ann[r] (a rank without a class is counted and otherwise ignored), the classes of a read's lanes in a run
+// are joined by taxo_combine -- one ballot finds the usual case, all of them the same class, which is one LDS
+// compare-and-swap join by one lane; otherwise the hit lanes join one by one -- and after the tile one global join per
+// read and tile.  Both joins are order-free, so the arrays do not depend on the scheduling.
+//
 // A walk that cannot answer (damaged image) leaves the lowest such byte position in bad[0]; a read whose window
 // count reaches 2^32 - 1 leaves its index in bad[1].
 #pragma once
@@ -39,11 +47,13 @@
 #include "goss_reader.hpp"
 #include "kernels_common.hpp"
 #include "kernels_query.hpp"
+#include "kernels_taxo.hpp"
 
 namespace goss {
 
 enum : uint32_t { kMatchNormalize = 1, kMatchAny = 4 };
-enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2 };      // what hits[] receives: a sum, 1 / 0, a 4-bit mask
+// what hits[] receives: a sum, 1 / 0, a 4-bit mask, a sum (and ann[] the lca), the join of the classes
+enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2, kModeAnnotate = 3, kModeTaxon = 4 };
 constexpr uint32_t kMatchTile = 2048;                    // positions per workgroup: 256 lanes x 8 bytes
 constexpr uint32_t kMatchRuns = kMatchTile / 64;         // runs of 64 positions, 8 per wave
 constexpr uint32_t kMatchGroups = kMatchTile / 8 + 8;    // 8-byte groups staged: the tile and a halo of 64 positions
@@ -144,9 +154,9 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
                                                           const uint64_t* __restrict__ tile_read, uint32_t flags, uint32_t aligned,
                                                           uint32_t* __restrict__ windows, uint32_t* __restrict__ hits,
                                                           uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad,
-                                                          const uint64_t* __restrict__ lhs, const uint64_t* __restrict__ rhs)
+                                                          const uint64_t* __restrict__ lhs, const uint64_t* __restrict__ rhs, TaxoView tx)
 {
-    constexpr bool ANY = MODE == kModeAny, CLS = MODE == kModeClassify;
+    constexpr bool ANY = MODE == kModeAny, CLS = MODE == kModeClassify, ANN = MODE == kModeAnnotate, TAX = MODE == kModeTaxon;
     __shared__ uint64_t s_codes[kMatchGroups / 4];       // 32 bases per word, first base lowest
     __shared__ uint64_t s_inv[kMatchGroups / 8];         // bit = not one of ACGTacgt (or beyond the input)
     __shared__ uint64_t s_nl[kMatchRuns];                // bit = '\n'
@@ -191,6 +201,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
     __syncthreads();
 
     const uint64_t lmask = (1ULL << L) - 1;              // (L <= 63)
+    uint32_t unann = 0;                                  // TAX: this wave's hits at ranks without a class
     for (uint32_t it = 0; it < kMatchRuns / kWaves; ++it)
     {
         const uint32_t run = wave_id() * (kMatchRuns / kWaves) + it;
@@ -217,7 +228,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
 
         bool done = ANY && __atomic_load_n(&s_hit[local], __ATOMIC_RELAXED) != 0;
         uint64_t hb = 0;
-        uint32_t cls = 0;                                // CLS: the class of this lane's hit
+        uint32_t cls = 0;                                // CLS, TAX: the class of this lane's hit
 #pragma unroll
         for (uint32_t ph = 0; ph < (ANY ? 2u : 1u); ++ph)
         {
@@ -244,6 +255,12 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
                     if (r >= o.s.count) { q_fail(bad, p, kQBadWalk); hit = false; }      // (the bitmaps end at count)
                     else cls = (uint32_t)((lhs[r >> 6] >> (r & 63)) & 1) << 1 | (uint32_t)((rhs[r >> 6] >> (r & 63)) & 1);
                 }
+                if ((ANN || TAX) && hit)
+                {
+                    if (r >= o.s.count) { q_fail(bad, p, kQBadWalk); hit = false; }      // (ann[] ends at count)
+                    else if (ANN) taxo_lca_into(&tx.ann[r], tx.parent, tx.last, tx.read_class[read0 + local]);
+                    else cls = __atomic_load_n(&tx.ann[r], __ATOMIC_RELAXED);
+                }
             }
             const uint64_t b = __ballot(hit);
             hb |= b;
@@ -258,15 +275,32 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
             for (uint32_t j = 0; j < 4; ++j)
                 if (__ballot(hit && cls == j) & seg) mask |= 1u << j;
         }
+        if (TAX && hb)
+        {
+            const bool hit = (hb >> lane) & 1;
+            unann += (uint32_t)__popcll(__ballot(hit && cls == 0));
+            const uint64_t cb = __ballot(hit && cls != 0);                   // the lanes that bring a class
+            if (cb)
+            {
+                // every lane learns the class of the first such lane of its read; a read whose lanes all agree sends one
+                const uint64_t mine = cb & seg;
+                const uint32_t lead = mine ? (uint32_t)__ffsll((long long)mine) - 1u : lane;
+                const uint32_t c0 = (uint32_t)__shfl((int)cls, (int)lead, 64);
+                const bool differs = hit && cls != 0 && cls != c0;
+                const bool mixed = (__ballot(differs) & seg) != 0;
+                if (mine && (mixed ? hit && cls != 0 : lane == lead)) taxo_combine_into(&s_hit[local], tx.last, cls);
+            }
+        }
         if (lane == first)
         {
             const uint32_t nw = (uint32_t)__popcll(vb & seg), nh = (uint32_t)__popcll(hb & seg);
             if (nw) atomicAdd(&s_win[local], nw);
             if (CLS) { if (mask) atomicOr(&s_hit[local], mask); }
-            else if (nh) atomicAdd(&s_hit[local], nh);
+            else if (!TAX && nh) atomicAdd(&s_hit[local], nh);
         }
     }
     __syncthreads();
+    if (TAX && lane == 0 && unann) atomicAdd(tx.unann, (unsigned long long)unann);      // (a ballot's count: the same in every lane)
 
     for (uint32_t i = threadIdx.x; i < nloc; i += kTB)
     {
@@ -280,6 +314,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
         {
             if (ANY) atomicOr(&hits[read0 + i], 1u);
             else if (CLS) atomicOr(&hits[read0 + i], nh);
+            else if (TAX) taxo_combine_into(&hits[read0 + i], tx.last, nh);
             else atomicAdd(&hits[read0 + i], nh);
         }
     }

@@ -1933,7 +1933,9 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  extract-reads    extract reads which map on to a graph\n"
               << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n"
               << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n"
-              << "  pool-samples     pool all the samples\n";
+              << "  pool-samples     pool all the samples\n"
+              << "  annotate-kmers   Decorate a graph with an assignment of kmers to graphs.\n"
+              << "  classify-reads   thread the reads through the graph\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -2520,6 +2522,84 @@ int gossMain(int argc, char* argv[])
                 GossCmdGroupReads cmd(in, fastas, fastqs, lines, opts.count("pairs") != 0, M, T, lhsName, rhsName, prefix,
                                       opts.count("dont-write-reads") != 0, opts.count("preserve-read-order") != 0);
                 cmd(cxt);
+            }
+            catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "annotate-kmers" || cmdName == "classify-reads")
+        {
+            // GossCmdFactoryAnnotateKmers::create (GossCmdAnnotateKmers.cc:402-433), GossCmdFactoryClassifyReads::create
+            // (GossCmdClassifyReads.cc:512-557)
+            const bool isAnnotate = cmdName == "annotate-kmers";
+            static const OptDef kAnnotate[] = {
+                {"graph-in", "G", kStrings, "name of the input graph object"},
+                {"annotation-list", "", kString, "A file containing a list of graph names, 1 per line."},
+                {"phylogeny", "", kString, "A file containing a list of merges to perform to construct the phylogenetic tree."},
+            };
+            static const OptDef kClassify[] = {
+                {"buffer-size", "B", kU64, "maximum size (in GB) for in-memory buffers (default: 2)"},
+                {"graph-in", "G", kStrings, "name of the input graph object"},
+                {"fasta-in", "I", kStrings, "input file in FASTA format"},
+                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
+                {"line-in", "", kStrings, "input file with one sequence per line"},
+                {"pairs", "", kFlag, "treat reads as pairs"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            if (isAnnotate) for (auto& d : kAnnotate) t.defs.push_back(d);
+            else for (auto& d : kClassify) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            std::string in;
+            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+            else if (opts.strs("graph-in").size() != 1)
+            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+            else in = opts.str("graph-in");
+            std::string annotList, phylogeny;
+            strings fastas, fastqs, lines;
+            uint64_t B = 2;
+            if (isAnnotate)
+            {
+                for (const auto& m : {std::make_pair("annotation-list", &annotList), std::make_pair("phylogeny", &phylogeny)})
+                {
+                    if (!opts.count(m.first)) { chk.errors += std::string("mandatory option ") + m.first + " was not given.\n"; chk.suggestUsage = true; }
+                    else *m.second = opts.str(m.first);
+                }
+            }
+            else
+            {
+                chk.repeatingIn("fasta-in", fastas);
+                chk.repeatingIn("fastq-in", fastqs);
+                chk.repeatingIn("line-in", lines);
+                chk.optionalU64("buffer-size", B);
+            }
+            uint64_t T = 4;
+            chk.optionalU64("num-threads", T);
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            try
+            {
+                if (isAnnotate) { GossCmdAnnotateKmers cmd(in, annotList, phylogeny, T); cmd(cxt); }
+                else { GossCmdClassifyReads cmd(in, fastas, fastqs, lines, B << 30, T, opts.count("pairs") != 0); cmd(cxt); }
             }
             catch (Error& e) { e.cmd = cmdName; throw; }
             return 0;

@@ -406,6 +406,39 @@ private:
     const bool mPairs, mDontWriteReads, mPreserveReadOrder; const double mMaxMemory; const uint64_t mNumThreads;
 };
 
+// GossCmdAnnotateKmers (GossCmdAnnotateKmers.{hh,cc}): every k-mer of the set gets the lowest common ancestor, in the
+// phylogeny pPhylogeny, of the nodes whose FASTA files (pAnnotList: whitespace-separated `file id` pairs, a repeated file
+// keeping its last id) hold it; <set>.annotation receives a raw uint32 per rank, 0xFFFFFFFF for a k-mer nothing holds, and
+// the phylogeny is written back over pPhylogeny with `count` (ranks whose class is exactly the node) and `total` (the sum
+// over its subtree) on every node.  Departures: a node without `node` or `name`, an id that occurs twice, the ids
+// 0xFFFFFFFF / 0xFFFFFFFE and an id in the list that the phylogeny lacks are errors raised before any device work (the
+// reference throws the integer 42 or walks off its maps); pNumThreads is unused.
+class GossCmdAnnotateKmers {
+public:
+    GossCmdAnnotateKmers(const std::string& pRef, const std::string& pAnnotList, const std::string& pPhylogeny, uint64_t pNumThreads)
+        : mRef(pRef), mAnnotList(pAnnotList), mPhylogeny(pPhylogeny), mNumThreads(pNumThreads) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mRef, mAnnotList, mPhylogeny; const uint64_t mNumThreads;
+};
+
+// GossCmdClassifyReads (GossCmdClassifyReads.{hh,cc}): every read (or, pPairs, every pair of reads of files 2i and 2i + 1,
+// their k-mers pooled) whose k-mers' classes in <set>.annotation lie on one root-to-leaf path of <set>.taxo is counted for
+// the deepest of them; standard output gets, in post-order, `sum TAB kind TAB name` for every node whose subtree sum is
+// not zero.  Departures: a k-mer whose annotation is 0xFFFFFFFF is ignored as if absent (the reference looks up a parent
+// that does not exist); an id in the annotation that the phylogeny lacks is an error naming the id and the rank; a node
+// without `node`, `name` or `kind` is an error at load; line, FASTA and FASTQ inputs are all read, in that order;
+// pBufferSize and pNumThreads are accepted and unused; pair files of unequal length are an error.
+class GossCmdClassifyReads {
+public:
+    GossCmdClassifyReads(const std::string& pIn, const strings& pFastas, const strings& pFastqs, const strings& pLines, uint64_t pBufferSize,
+                         uint64_t pNumThreads, bool pPairs)
+        : mIn(pIn), mFastas(pFastas), mFastqs(pFastqs), mLines(pLines), mBufferSize(pBufferSize), mNumThreads(pNumThreads), mPairs(pPairs) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn; const strings mFastas, mFastqs, mLines; const uint64_t mBufferSize, mNumThreads; const bool mPairs;
+};
+
 // Bytes of reads in byte form ('\n' after each) handed to the device per batch by the commands that look reads up in a
 // graph or k-mer set: GossCmdContext::batchBytes, or GOSS_MATCH_BATCH=<bytes> (tests).
 size_t matchBatchBytes(const GossCmdContext& cxt);

@@ -3,7 +3,8 @@
 //
 // The object is opened on the device as it lies on disk (goss_gpu_object_open).  The reads are parsed in order, batched
 // ('\n' after each), and each batch is answered by goss_gpu_object_match_reads_host with GOSS_MATCH_ANY; what comes back
-// is one word per read, and the reads are written from the host's copy of the batch, in input order.
+// is one word per read, and the reads are written from the host's copy of the batch, in input order.  The object and the
+// batching are GossReads.hpp's, shared with GossTaxo.cpp.
 //
 // `goss group-reads` (GossCmdGroupReads.cc, what `xenome classify` runs) is the same pipeline over
 // goss_gpu_object_classify_reads_host: the word per read is then the 4-bit mask of the classes its k-mers fall into, which
@@ -25,133 +26,13 @@
 
 #include "../../include/goss_gpu.h"
 #include "GossHost.hpp"
+#include "GossReads.hpp"
 
 namespace gosshost {
 
+using namespace reads;
+
 namespace {
-
-std::string num(uint64_t v) { return std::to_string(v); }
-
-// An object's files, mapped, under the names they have on disk.
-struct ObjectFiles {
-    std::vector<std::string> names;
-    std::vector<std::pair<const void*, size_t>> maps;
-    ~ObjectFiles() { for (auto& m : maps) if (m.first && m.second) munmap((void*)m.first, m.second); }
-    void add(const std::string& name)
-    {
-        int fd = ::open(name.c_str(), O_RDONLY);
-        if (fd < 0) throw Error::Errno(name, errno);
-        struct stat st;
-        if (fstat(fd, &st) != 0) { int e = errno; ::close(fd); throw Error::Errno(name, e); }
-        const void* p = nullptr;
-        if (S_ISREG(st.st_mode) && st.st_size)
-        {
-            void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { int e = errno; ::close(fd); throw Error::Errno(name, e); }
-            p = m;
-        }
-        ::close(fd);
-        if (!S_ISREG(st.st_mode)) return;
-        names.push_back(name);
-        maps.emplace_back(p, (size_t)st.st_size);
-    }
-};
-
-struct Object {
-    goss_gpu_object* h = nullptr;
-    goss_gpu_object_desc desc{};
-    ~Object() { if (h) goss_gpu_object_close(h); }
-    void check(int rc, const char* what) const
-    {
-        if (rc == GOSS_OK) return;
-        std::string msg = std::string(what) + ": " + goss_gpu_strerror(rc);
-        const char* d = goss_gpu_object_last_error(h);
-        if (d && *d) msg += std::string(" (") + d + ")";
-        throw Error::General(msg + "\n");
-    }
-    // Graph::open(name, fac) / KmerSet(name, fac): every file "<name>." or "<name>-" something
-    void open(const GossCmdContext& cxt, const std::string& name, bool graph)
-    {
-        ObjectFiles files;
-        glob_t g{};
-        std::string pat;
-        for (char c : name) { if (c == '*' || c == '?' || c == '[' || c == '\\') pat += '\\'; pat += c; }
-        pat += "[.-]*";
-        if (::glob(pat.c_str(), 0, nullptr, &g) == 0)
-            for (size_t i = 0; i < g.gl_pathc; ++i)
-            {
-                const std::string f = g.gl_pathv[i];
-                if (f.size() >= 4 && f.compare(f.size() - 4, 4, ".txt") == 0) continue;
-                files.add(f);
-            }
-        globfree(&g);
-        std::vector<goss_gpu_named_file> nf(files.names.size());
-        for (size_t i = 0; i < nf.size(); ++i) nf[i] = goss_gpu_named_file{files.names[i].c_str(), files.maps[i].first, files.maps[i].second};
-        int rc = goss_gpu_object_open(&h, cxt.device, nullptr, graph ? GOSS_OBJECT_GRAPH : GOSS_OBJECT_KMER_SET, name.c_str(), nf.data(), (uint32_t)nf.size());
-        if (rc != GOSS_OK)
-        {
-            std::string msg = "\tunable to open graph '" + name + "'\n\t" + goss_gpu_strerror(rc);
-            const char* d = goss_gpu_object_last_error(nullptr);
-            if (d && *d) msg += std::string(" (") + d + ")";
-            throw Error::General(msg + "\n");
-        }
-        check(goss_gpu_object_info(h, &desc), "describing the object");
-    }
-};
-
-// Reads in, one word per read out, in order: batches end at read boundaries and hold `cap` bytes (one read more than
-// that is a batch of its own).  The word is match_reads' hits (with GOSS_MATCH_ANY 1 / 0) or, pClassify, classify_reads' mask.
-class Matcher {
-public:
-    typedef std::function<void(const char* seq, size_t len, uint32_t word)> Verdict;
-    Matcher(const Object& obj, uint32_t flags, size_t cap, Verdict v, bool pClassify = false)
-        : mObj(obj), mFlags(flags), mCap(cap), mVerdict(std::move(v)), mClassify(pClassify) {}
-    void push(const char* seq, size_t len)
-    {
-        if (!mBuf.empty() && mBuf.size() + len + 1 > mCap) flush();
-        mStart.push_back(mBuf.size());
-        mBuf.insert(mBuf.end(), seq, seq + len);
-        mBuf.push_back('\n');
-    }
-    void flush()
-    {
-        if (mStart.empty()) return;
-        const uint64_t n = mStart.size();
-        mHits.resize(n);
-        uint64_t answered = 0;
-        if (mClassify)
-        {
-            goss_gpu_classify_info info;
-            mObj.check(goss_gpu_object_classify_reads_host(mObj.h, mBuf.data(), mBuf.size(), mFlags, n, mHits.data(), nullptr, nullptr, &info),
-                       "classifying a batch of reads");
-            answered = info.reads;
-        }
-        else
-        {
-            goss_gpu_match_info info;
-            mObj.check(goss_gpu_object_match_reads_host(mObj.h, mBuf.data(), mBuf.size(), mFlags, n, nullptr, mHits.data(), nullptr, &info),
-                       "matching a batch of reads");
-            answered = info.reads;
-        }
-        if (answered != n) throw Error::General("matching a batch of reads: " + num(n) + " reads sent, " + num(answered) + " answered\n");
-        mStart.push_back(mBuf.size());
-        for (uint64_t r = 0; r < n; ++r) mVerdict(mBuf.data() + mStart[r], mStart[r + 1] - mStart[r] - 1, mHits[r]);
-        mBuf.clear();
-        mStart.clear();
-        ++mBatches;
-    }
-    uint64_t batches() const { return mBatches; }
-private:
-    const Object& mObj;
-    const uint32_t mFlags;
-    const size_t mCap;
-    Verdict mVerdict;
-    const bool mClassify;
-    std::vector<char> mBuf;
-    std::vector<uint64_t> mStart;
-    std::vector<uint32_t> mHits;
-    uint64_t mBatches = 0;
-};
 
 // FileFactory::out(name): "-" is standard output
 struct OutFile {
@@ -186,25 +67,6 @@ struct OutFile {
     }
     ~OutFile() { if (fp && fp != stdout) fclose(fp); }
 };
-
-enum Format { kLine, kFasta, kFastq };
-struct Item { std::string name; Format fmt; };
-
-// the reference's item order: all line files, then all FASTA files, then all FASTQ files
-// (GossCmdExtractReads.cc:64-88, GossCmdFilterReads.cc:186-212)
-std::vector<Item> itemsOf(const strings& fastas, const strings& fastqs, const strings& lines)
-{
-    std::vector<Item> items;
-    for (auto& f : lines) items.push_back(Item{f, kLine});
-    for (auto& f : fastas) items.push_back(Item{f, kFasta});
-    for (auto& f : fastqs) items.push_back(Item{f, kFastq});
-    return items;
-}
-
-uint64_t parseItem(const Item& it, const ReadSink& sink)
-{
-    return it.fmt == kLine ? parseLines(it.name, sink) : it.fmt == kFasta ? parseFasta(it.name, sink) : parseFastq(it.name, sink);
-}
 
 }  // namespace
 

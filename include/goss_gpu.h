@@ -1009,6 +1009,12 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * into -- the loop of GossCmdGroupReads.cc:381-485 over the same .lhs-bits / .rhs-bits; likewise a header of its own. */
 #include "goss_gpu_classify.h"
 
+/* annotate-kmers and classify-reads on an object (goss_gpu_object_taxo_*): a class per k-mer, the lowest common
+ * ancestor in a taxonomy of the genomes that hold it, and per read the deepest class of its k-mers when they lie on
+ * one root-to-leaf path -- GossCmdAnnotateKmers.cc:196-320, GossCmdClassifyReads.cc:301-427; likewise a header of its
+ * own. */
+#include "goss_gpu_taxo.h"
+
 #ifdef __cplusplus
 }
 #endif

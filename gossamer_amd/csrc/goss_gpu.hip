@@ -3633,310 +3633,7 @@ int goss_synth_reads_host(char* out, uint64_t nreads, uint32_t read_len, uint64_
 // allocation of its own, outside every context's arena
 // ============================================================================================
 
-struct goss_gpu_object {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int kind = 0;
-    uint32_t K = 0, key_words = 1, node_words = 1;
-    bool asymmetric = false;
-    uint8_t* mem = nullptr;                 // every image, then the query's failure word
-    uint64_t bytes = 0;
-    unsigned long long* d_bad = nullptr;    // [0] the failure word, [1] near_kmers' gray total
-    unsigned long long* h_bad = nullptr;    // (page-locked, two words)
-    QueryObj q{};
-    QueryEntries qe{};                      // an EntryEdgeSet's lengths and ends
-    std::string last_error;
-    // goss_gpu_object_match_reads: grow-only working memory (tile counts and their scan; outputs the caller left out),
-    // a page-locked block for what comes back, the events that time the kernels
-    uint8_t* match_mem = nullptr;
-    uint64_t match_bytes = 0;
-    uint8_t* match_tmp = nullptr;
-    uint64_t match_tmp_bytes = 0;
-    uint8_t* match_stage = nullptr;         // goss_gpu_object_match_reads_host: the batch and its answers on the device
-    uint64_t match_stage_bytes = 0;
-    unsigned long long* h_match = nullptr;
-    hipEvent_t match_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // goss_gpu_object_classify_bits_host: the kept pair, lhs then rhs, (count + 63) / 64 words each
-    uint64_t* classify_bits = nullptr;
-    bool classify_kept = false;
-    // goss_gpu_object_taxo_*: the tree in one allocation -- parent, last, id by pre-order number, then the sorted ids and
-    // their classes, then n + 2 bins --, the annotation (a class per rank), working memory that only grows
-    uint32_t taxo_n = 0;
-    uint32_t* taxo_tree = nullptr;
-    unsigned long long* taxo_bins = nullptr;
-    std::vector<uint32_t> taxo_pre;         // the pre-order number of the i-th node as given
-    uint32_t* taxo_ann = nullptr;
-    bool taxo_ann_kept = false;
-    uint8_t* taxo_tmp = nullptr;
-    uint64_t taxo_tmp_bytes = 0;
-};
-
-namespace {
-
-thread_local std::string t_open_error;      // why the calling thread's last open failed (goss_gpu_object_last_error(NULL))
-
-struct ObjSrc { const uint8_t* p = nullptr; uint64_t n = 0; bool dev = false; };
-typedef std::map<std::string, ObjSrc> ObjFiles;
-
-// The images an object needs, laid out in its one allocation: what is read from where, and which device
-// pointer of the object's view points at it.
-struct ObjPlan {
-    const ObjFiles& files;
-    struct Piece { ObjSrc src; uint64_t bytes, off; const void** dst; };
-    std::vector<Piece> pieces;
-    uint64_t total = 0;
-
-    const ObjSrc& need(const std::string& name) const
-    {
-        auto it = files.find(name);
-        if (it == files.end()) throw StatusError{GOSS_ERR_INVALID_ARG, "missing file " + name};
-        if (!it->second.p && it->second.n) throw StatusError{GOSS_ERR_INVALID_ARG, "no data for file " + name};
-        return it->second;
-    }
-    // the first n bytes of a file on the host
-    std::vector<uint8_t> head(const ObjSrc& s, uint64_t n) const
-    {
-        std::vector<uint8_t> v(n);
-        if (!n) return v;
-        if (s.dev) HIP_TRY(hipMemcpy(v.data(), s.p, n, hipMemcpyDeviceToHost));
-        else std::memcpy(v.data(), s.p, n);
-        return v;
-    }
-    void place(const ObjSrc& s, uint64_t bytes, const void** dst)
-    {
-        pieces.push_back(Piece{s, bytes, total, dst});
-        total = (total + bytes + 16 + 255) & ~255ULL;            // (16: the walkers never read past an image; slack only)
-    }
-};
-
-uint64_t pow4(uint32_t n, uint64_t* hi) { *hi = 2 * n >= 64 ? 1ULL << (2 * n - 64) : 0; return 2 * n < 64 ? 1ULL << (2 * n) : 0; }
-
-// SparseArray(base, fac) (SparseArray.hh:60-72, SparseArray.cc:133-170): header, high-bits, -d0, -d1 and the low-bits
-// columns of quantizedD bits (IntegerArray.cc:259-357), every size checked against the header
-void plan_sparse(ObjPlan& pl, const std::string& sa, RdSparse& s)
-{
-    const ObjSrc& hs = pl.need(sa + ".header");
-    if (hs.n < sizeof(SaHeader)) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header is too short"};
-    SaHeader h;
-    std::memcpy(&h, pl.head(hs, sizeof h).data(), sizeof h);
-    if (h.version != 2012030501ULL) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: SparseArray version mismatch"};
-    std::vector<IaCol> cols;
-    if (h.D == 0 || h.D > 128 || h.quantizedD != 8 * ((h.D + 7) / 8) || !ia_layout((uint32_t)h.quantizedD, "", 0, cols) || cols.size() > 4)
-        throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: corrupt SparseArray header"};
-    s = RdSparse{};
-    s.D = h.D; s.count = h.count; s.size_lo = h.size_lo; s.size_hi = h.size_hi;
-    // N >> D bits of zeros and count ones (SparseArray.cc:79-86)
-    uint64_t nd = 0;
-    if (h.D < 64)
-    {
-        if (h.size_hi >> h.D) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: N >> D does not fit 64 bits"};
-        nd = (h.size_lo >> h.D) | (h.size_hi << (64 - h.D));
-    }
-    else if (h.D < 128) nd = h.size_hi >> (h.D - 64);
-    const ObjSrc& hb = pl.need(sa + ".high-bits");
-    const uint64_t words = hb.n / 8;
-    if (nd > (~0ULL >> 2) || h.count > (~0ULL >> 2) || words < (nd + h.count + 63) / 64)
-        throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".high-bits is shorter than its header says"};
-    s.hi.nwords = words;
-    pl.place(hb, words * 8, (const void**)&s.hi.w);
-    const ObjSrc& d0 = pl.need(sa + "-d0");
-    const ObjSrc& d1 = pl.need(sa + "-d1");
-    s.d0 = parse_dense_select(pl.head(d0, std::min<uint64_t>(d0.n, sizeof(DsHeader))).data(), d0.n, 1, sa + "-d0");
-    s.d1 = parse_dense_select(pl.head(d1, std::min<uint64_t>(d1.n, sizeof(DsHeader))).data(), d1.n, 0, sa + "-d1");
-    pl.place(d0, d0.n, (const void**)&s.d0.data);
-    pl.place(d1, d1.n, (const void**)&s.d1.data);
-    s.ncols = (uint32_t)cols.size();
-    for (size_t i = 0; i < cols.size(); ++i)
-    {
-        const std::string name = sa + ".low-bits" + cols[i].suffix;
-        const ObjSrc& c = pl.need(name);
-        if (h.count > c.n / cols[i].bytes) throw StatusError{GOSS_ERR_INVALID_ARG, name + " is shorter than its header's count"};
-        s.col_bytes[i] = cols[i].bytes; s.col_shift[i] = cols[i].shift;
-        pl.place(c, h.count * cols[i].bytes, (const void**)&s.col[i]);
-    }
-}
-
-// Graph::open / Graph::Graph (Graph.cc:366-410), KmerSet's constructor (KmerSet.hh:170-190), SparseArray(base, fac)
-void open_object(goss_gpu_object* o, int kind, const std::string& base, const ObjFiles& files)
-{
-    ObjPlan pl{files};
-    QueryObj& q = o->q;
-    o->kind = kind;
-    // VariableByteArray(base, fac) (VariableByteArray.hh:120-160) of `items` values
-    auto plan_vba = [&](const std::string& vb, RdVba& v, uint64_t items) {
-        const ObjSrc& o0 = pl.need(vb + ".ord0");
-        if (o0.n < items) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord0 is shorter than the item count"};
-        pl.place(o0, items, (const void**)&v.ord0);
-        plan_sparse(pl, vb + ".ord1p", v.p1);
-        plan_sparse(pl, vb + ".ord2p", v.p2);
-        if (v.p1.size_hi || v.p2.size_hi) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ": presence arrays wider than 64 bits"};
-        const ObjSrc& o1 = pl.need(vb + ".ord1");
-        const ObjSrc& o2 = pl.need(vb + ".ord2");
-        if (o1.n < v.p1.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord1 is shorter than the ord1p count"};
-        if (o2.n / 2 < v.p2.count) throw StatusError{GOSS_ERR_INVALID_ARG, vb + ".ord2 is shorter than the ord2p count"};
-        pl.place(o1, v.p1.count, (const void**)&v.ord1);
-        pl.place(o2, v.p2.count * 2, (const void**)&v.ord2);
-    };
-    if (kind == GOSS_OBJECT_SPARSE_ARRAY)
-    {
-        plan_sparse(pl, base, q.s);
-        o->key_words = q.s.size_hi ? 2 : 1;
-    }
-    else if (kind == GOSS_OBJECT_ENTRY_EDGE_SET)
-    {
-        // EntryEdgeSet(baseName, fac) (EntryEdgeSet.cc:139-152, 299-306): header, .edges, .counts, .lengths, .ends
-        const ObjSrc& hs = pl.need(base + ".header");
-        if (hs.n < 16) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header is too short"};
-        uint64_t h[2];
-        std::memcpy(h, pl.head(hs, 16).data(), 16);
-        if (h[0] != 2011041901ULL) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: EntryEdgeSet version mismatch"};
-        if (h[1] == 0 || h[1] > 62u) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: K out of range"};
-        o->K = (uint32_t)h[1];
-        q.len = o->K + 1;
-        q.graph = 1;                                              // (a count per element: lookup answers it)
-        o->key_words = 2 * q.len <= 62 ? 1 : 2;
-        o->node_words = 2 * o->K <= 62 ? 1 : 2;
-        plan_sparse(pl, base + ".edges", q.s);
-        uint64_t nhi, nlo = pow4(q.len, &nhi);
-        if (q.s.size_lo != nlo || q.s.size_hi != nhi) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".edges.header: the universe is not 4^len"};
-        plan_vba(base + ".counts", q.v, q.s.count);
-        plan_vba(base + ".lengths", o->qe.lengths, q.s.count);
-        o->qe.count = q.s.count;
-        const ObjSrc& up = pl.need(base + ".ends.upr");
-        const ObjSrc& lw = pl.need(base + ".ends.lwr");
-        if (up.n < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".ends.upr is shorter than the entry count"};
-        if (lw.n / 4 < q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".ends.lwr is shorter than the entry count"};
-        pl.place(up, q.s.count, (const void**)&o->qe.ends_upr);
-        pl.place(lw, q.s.count * 4, (const void**)&o->qe.ends_lwr);
-    }
-    else
-    {
-        const ObjSrc& hs = pl.need(base + ".header");
-        if (hs.n < 24) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header is too short"};
-        uint64_t h[3];
-        std::memcpy(h, pl.head(hs, 24).data(), 24);
-        const bool graph = kind == GOSS_OBJECT_GRAPH;
-        if (h[0] != (graph ? 2011101014ULL : 2011101701ULL))
-            throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: " + (graph ? "Graph" : "KmerSet") + " version mismatch"};
-        if (h[1] == 0 || h[1] > (graph ? 62u : 63u)) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: K out of range"};
-        o->K = (uint32_t)h[1];
-        q.len = graph ? o->K + 1 : o->K;
-        q.graph = graph;
-        o->key_words = 2 * q.len <= 62 ? 1 : 2;
-        o->node_words = 2 * o->K <= 62 ? 1 : 2;
-        o->asymmetric = graph && (h[2] & 1);
-        const std::string sa = base + (graph ? "-edges" : ".kmers");
-        plan_sparse(pl, sa, q.s);
-        uint64_t nhi, nlo = pow4(q.len, &nhi);
-        if (q.s.size_lo != nlo || q.s.size_hi != nhi) throw StatusError{GOSS_ERR_INVALID_ARG, sa + ".header: the universe is not 4^len"};
-        if (!graph && h[2] != q.s.count) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: count differs from " + sa};
-        if (graph)
-        {
-            plan_vba(base + "-counts", q.v, q.s.count);
-        }
-    }
-    // one allocation: the images, then the failure word
-    const uint64_t bad_off = pl.total;
-    o->bytes = pl.total + 256;
-    HIP_TRY(hipMalloc((void**)&o->mem, o->bytes));
-    o->d_bad = (unsigned long long*)(o->mem + bad_off);
-    for (auto& pc : pl.pieces)
-    {
-        *pc.dst = o->mem + pc.off;
-        if (pc.bytes)
-            HIP_TRY(hipMemcpyAsync(o->mem + pc.off, pc.src.p, pc.bytes, pc.src.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(o->stream));
-}
-
-int usable_device(int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return GOSS_ERR_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return GOSS_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GOSS_ERR_NO_DEVICE;
-    return GOSS_OK;
-}
-
-// guarded() for objects: no exception crosses the ABI; the message goes to `err`
-template <class F>
-int obj_guarded(int device, std::string& err, F&& f)
-{
-    try
-    {
-        HIP_TRY(hipSetDevice(device));
-        (void)hipGetLastError();
-        f();
-        check_launch("a kernel launch was refused");
-        return GOSS_OK;
-    }
-    catch (const HipError& e) { err = std::string(e.what) + ": " + hipGetErrorString(e.e); return GOSS_ERR_HIP; }
-    catch (const StatusError& e) { err = e.msg; return e.status; }
-    catch (const std::bad_alloc&) { err = "host allocation failed"; return GOSS_ERR_OOM; }
-    catch (const std::exception& e) { err = std::string("unexpected failure: ") + e.what(); return GOSS_ERR_STATE; }
-}
-
-void object_free(goss_gpu_object* o)
-{
-    if (!o) return;
-    (void)hipSetDevice(o->device);
-    if (o->stream) (void)hipStreamSynchronize(o->stream);
-    if (o->mem) (void)hipFree(o->mem);
-    if (o->h_bad) (void)hipHostFree(o->h_bad);
-    if (o->match_mem) (void)hipFree(o->match_mem);
-    if (o->match_tmp) (void)hipFree(o->match_tmp);
-    if (o->match_stage) (void)hipFree(o->match_stage);
-    if (o->h_match) (void)hipHostFree(o->h_match);
-    if (o->classify_bits) (void)hipFree(o->classify_bits);
-    if (o->taxo_tree) (void)hipFree(o->taxo_tree);
-    if (o->taxo_ann) (void)hipFree(o->taxo_ann);
-    if (o->taxo_tmp) (void)hipFree(o->taxo_tmp);
-    for (hipEvent_t e : o->match_ev) if (e) (void)hipEventDestroy(e);
-    if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
-    delete o;
-}
-
-int object_open(goss_gpu_object** out, int device, void* stream, int kind, const std::string& base, const ObjFiles& files)
-{
-    goss_gpu_object* o = new (std::nothrow) goss_gpu_object();
-    if (!o) return GOSS_ERR_OOM;
-    o->device = device;
-    int rc = obj_guarded(device, t_open_error, [&]() {
-        if (stream) o->stream = (hipStream_t)stream;
-        else { HIP_TRY(hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking)); o->own_stream = true; }
-        HIP_TRY(hipHostMalloc((void**)&o->h_bad, 16, hipHostMallocDefault));    // (the failure word; near_kmers: the gray total)
-        open_object(o, kind, base, files);
-    });
-    if (rc != GOSS_OK) { object_free(o); return rc; }
-    *out = o;
-    return GOSS_OK;
-}
-
-inline dim3 query_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)); }
-
-// one batched query: launch, then the lowest failing query index, if any, becomes the call's error
-template <class L>
-int object_query(goss_gpu_object* o, uint64_t n, L&& launch)
-{
-    if (n == 0) return GOSS_OK;
-    return obj_guarded(o->device, o->last_error, [&]() {
-        HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
-        launch(query_grid(n));
-        HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        const unsigned long long bad = *o->h_bad;
-        if (bad != ~0ULL)
-        {
-            static const char* const why[4] = {"", "a key has bits at or above 2*len (or lies at or past N)",
-                                               "a rank is not below the count", "the index walk cannot answer (damaged object)"};
-            throw StatusError{GOSS_ERR_INVALID_ARG, "query " + std::to_string(bad >> 2) + ": " + why[bad & 3]};
-        }
-    });
-}
-
-}  // namespace
+#include "object_path.hpp"
 
 extern "C" {
 
@@ -4135,249 +3832,47 @@ int goss_gpu_object_near_kmers_host(goss_gpu_object* o, const uint64_t* lhs, con
 }  // extern "C"
 
 // ============================================================================================
-// Reads against an object (goss_gpu_object_match_reads): kernels_match.hpp
+// Reads against an object (goss_gpu_object_match_reads, _classify_reads, _taxo_*): the pass, the staged batch, the
+// classify bitmaps and the taxonomy are reads_path.hpp; what follows checks the arguments and calls it
 // ============================================================================================
 
-namespace {
+#include "reads_path.hpp"
 
-// at least `bytes` of device memory in a buffer that only grows
-uint8_t* match_room(uint8_t*& mem, uint64_t& have, uint64_t bytes)
-{
-    if (bytes > have)
-    {
-        if (mem) { HIP_TRY(hipFree(mem)); mem = nullptr; have = 0; }
-        const uint64_t want = (bytes + (bytes >> 2) + 4095) & ~4095ULL;
-        if (hipMalloc((void**)&mem, want) != hipSuccess) { (void)hipGetLastError(); mem = nullptr; throw StatusError{GOSS_ERR_OOM, "no device memory for the working arrays of match_reads"}; }
-        have = want;
-    }
-    return mem;
-}
+extern "C" {
 
-// exclusive scan of a[0..n) in place; `partial` holds the chunk sums of every level
-void match_scan(hipStream_t st, uint64_t* a, uint64_t n, uint64_t* partial)
-{
-    const uint64_t nchunks = (n + kScanChunk - 1) / kScanChunk;
-    if (nchunks <= 1)
-    {
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(1), dim3(kTB), 0, st, a, n, (const uint64_t*)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, st, (const uint64_t*)a, n, partial);
-    match_scan(st, partial, nchunks, partial + nchunks);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, st, a, n, (const uint64_t*)partial);
-}
-
-template <class K, int MODE>
-void match_launch(goss_gpu_object* o, uint64_t ntiles, const uint8_t* bases, uint64_t nbytes, const uint64_t* tile_read, uint32_t flags,
-                  uint32_t aligned, uint32_t* w, uint32_t* h, uint64_t* starts, unsigned long long* bad, const uint64_t* lhs, const uint64_t* rhs,
-                  const TaxoView& tx)
-{
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(match_reads_kernel<K, MODE>), unit_grid(ntiles), dim3(kTB), 0, o->stream, o->q, bases, nbytes, ntiles,
-                       tile_read, flags, aligned, w, h, starts, bad, lhs, rhs, tx);
-}
-
-// what one pass over the reads leaves on the host
-struct ReadsPass {
-    uint64_t reads = 0;
-    unsigned long long sums[4] = {0, 0, 0, 0};  // windows, hits, reads with a hit; kModeTaxon: hits at a rank without a class
-    unsigned long long counts[16] = {};         // kModeClassify: reads per mask
-    float ms = 0;
-};
-
-// goss_gpu_object_match_reads and goss_gpu_object_classify_reads past their own argument checks: `what` names the call in
-// messages, `mode` is the kernel's (kModeCount / kModeAny / kModeClassify; d_hits then receives the masks, read at lhs / rhs).
-// kModeAnnotate / kModeTaxon read and write what `tx` points at (kernels_taxo.hpp; tx.read_class holds max_reads classes,
-// so the batch must fit); `post(hits, reads)` runs on the stream behind the kernel, inside the timed stretch.
-typedef std::function<void(uint32_t*, uint64_t)> ReadsPost;
-int reads_pass(goss_gpu_object* o, const std::string& what, int mode, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-               uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, const uint64_t* lhs, const uint64_t* rhs, ReadsPass* res,
-               TaxoView tx = TaxoView{}, const ReadsPost& post = ReadsPost())
-{
-    if (nbytes == 0)
-    {
-        if (!d_read_starts) return GOSS_OK;
-        return obj_guarded(o->device, o->last_error, [&]() {
-            HIP_TRY(hipMemsetAsync(d_read_starts, 0, 8, o->stream));
-            HIP_TRY(hipStreamSynchronize(o->stream));
-        });
-    }
-    return obj_guarded(o->device, o->last_error, [&]() {
-        const uint8_t* bases = (const uint8_t*)d_bases;
-        const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
-        // working memory: [0, 256) sums[4], bad[2] at word 4, the classes' counts[16] at word 8; then the tiles' newline
-        // counts (+ 1: the total) and the scan's partial sums
-        const uint64_t npartial = 2 * ((ntiles + 1 + kScanChunk - 1) / kScanChunk) + 64;
-        uint8_t* mem = match_room(o->match_mem, o->match_bytes, 256 + (ntiles + 1 + npartial) * 8);
-        unsigned long long* sums = (unsigned long long*)mem;
-        unsigned long long* bad = sums + 4;
-        unsigned long long* counts = sums + 8;
-        uint64_t* tiles = (uint64_t*)(mem + 256);
-        uint64_t* partial = tiles + ntiles + 1;
-        if (!o->h_match) HIP_TRY(hipHostMalloc((void**)&o->h_match, 256, hipHostMallocDefault));
-        for (hipEvent_t& e : o->match_ev) if (!e) HIP_TRY(hipEventCreate(&e));
-        const uint32_t aligned = ((uintptr_t)bases & 7u) == 0;
-
-        // reads: one '\n' count per tile, scanned; the last byte decides whether a read is left open
-        HIP_TRY(hipMemsetAsync(mem, 0, 256, o->stream));
-        HIP_TRY(hipMemsetAsync(bad, 0xFF, 16, o->stream));
-        HIP_TRY(hipMemsetAsync(tiles + ntiles, 0, 8, o->stream));
-        HIP_TRY(hipEventRecord(o->match_ev[0], o->stream));
-        hipLaunchKernelGGL(match_count_newlines_kernel, unit_grid((ntiles + kWaves - 1) / kWaves), dim3(kTB), 0, o->stream, bases, nbytes, ntiles, tiles, aligned);
-        match_scan(o->stream, tiles, ntiles + 1, partial);
-        HIP_TRY(hipEventRecord(o->match_ev[1], o->stream));
-        HIP_TRY(hipMemcpyAsync(&o->h_match[0], tiles + ntiles, 8, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipMemcpyAsync(&o->h_match[1], bases + nbytes - 1, 1, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        check_launch((what + ": counting the reads").c_str());
-        const bool open_end = (uint8_t)(o->h_match[1] & 0xFF) != (uint8_t)'\n';
-        const uint64_t reads = o->h_match[0] + (open_end ? 1 : 0);
-        res->reads = reads;
-        if ((d_windows || d_hits || d_read_starts || tx.read_class) && reads > max_reads)
-            throw StatusError{GOSS_ERR_BUFFER, what + ": the input holds " + std::to_string(reads) + " reads, the output arrays " + std::to_string(max_reads)};
-
-        // outputs the caller left out are still the kernel's counters
-        uint32_t* w = d_windows;
-        uint32_t* h = d_hits;
-        if (!w || !h)
-        {
-            const uint64_t each = (reads * 4 + 255) & ~255ULL;
-            uint8_t* tmp = match_room(o->match_tmp, o->match_tmp_bytes, 2 * each + 256);
-            if (!w) w = (uint32_t*)tmp;
-            if (!h) h = (uint32_t*)(tmp + each);
-        }
-        if (reads)
-        {
-            HIP_TRY(hipMemsetAsync(w, 0, reads * 4, o->stream));
-            HIP_TRY(hipMemsetAsync(h, 0, reads * 4, o->stream));
-        }
-        HIP_TRY(hipEventRecord(o->match_ev[2], o->stream));
-        auto launch = [&](auto key) {
-            typedef decltype(key) K;
-            if (mode == kModeAny) match_launch<K, kModeAny>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
-            else if (mode == kModeClassify) match_launch<K, kModeClassify>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
-            else if (mode == kModeAnnotate) match_launch<K, kModeAnnotate>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
-            else if (mode == kModeTaxon) match_launch<K, kModeTaxon>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
-            else match_launch<K, kModeCount>(o, ntiles, bases, nbytes, tiles, flags, aligned, w, h, d_read_starts, bad, lhs, rhs, tx);
-        };
-        tx.unann = sums + 3;
-        if (o->key_words == 1) launch(Key1{});
-        else launch(Key2{});
-        if (mode == kModeClassify && reads)
-            hipLaunchKernelGGL(classify_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256, 2048)), dim3(kTB), 0, o->stream,
-                               (const uint32_t*)h, reads, counts);
-        hipLaunchKernelGGL(match_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256 + 1, 2048)), dim3(kTB), 0, o->stream,
-                           (const uint32_t*)w, (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
-        if (post && reads) post(h, reads);
-        HIP_TRY(hipEventRecord(o->match_ev[3], o->stream));
-        HIP_TRY(hipMemcpyAsync(o->h_match, mem, 192, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        check_launch((what + ": matching").c_str());
-        if (o->h_match[4] != ~0ULL)
-            throw StatusError{GOSS_ERR_INVALID_ARG, what + ": the window at byte " + std::to_string(o->h_match[4] >> 2) + ": the index walk cannot answer (damaged object)"};
-        if (o->h_match[5] != ~0ULL)
-            throw StatusError{GOSS_ERR_INVALID_ARG, what + ": read " + std::to_string(o->h_match[5]) + " has 2^32 - 1 windows or more"};
-        float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, o->match_ev[0], o->match_ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, o->match_ev[2], o->match_ev[3]));
-        for (int i = 0; i < 4; ++i) res->sums[i] = o->h_match[i];
-        for (int i = 0; i < 16; ++i) res->counts[i] = o->h_match[8 + i];
-        res->ms = a + b;
-    });
-}
-
-}  // namespace
-
-extern "C" int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                           uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, goss_gpu_match_info* info)
+int goss_gpu_object_match_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                uint32_t* d_windows, uint32_t* d_hits, uint64_t* d_read_starts, goss_gpu_match_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
     if (flags & ~(uint32_t)(GOSS_MATCH_NORMALIZE | GOSS_MATCH_ANY)) { o->last_error = "match_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
     if (o->kind == GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "match_reads needs a KmerSet or a Graph: a bare SparseArray has no key length"; return GOSS_ERR_INVALID_ARG; }
     ReadsPass res;
-    const int rc = reads_pass(o, "match_reads", flags & GOSS_MATCH_ANY ? kModeAny : kModeCount, d_bases, nbytes, flags, max_reads, d_windows, d_hits,
-                              d_read_starts, nullptr, nullptr, &res);
-    if (info)
-    {
-        info->reads = res.reads;
-        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->hits = res.sums[1]; info->matched_reads = res.sums[2]; info->ms = res.ms; }
-    }
-    return rc;
+    const int rc = reads_pass(o, ReadsJob{"match_reads", flags & GOSS_MATCH_ANY ? kModeAny : kModeCount, d_bases, nbytes, flags, max_reads, d_windows, d_hits, d_read_starts}, &res);
+    return pass_report(rc, res, info, [&](goss_gpu_match_info& i) { i.windows = res.sums[0]; i.hits = res.sums[1]; i.matched_reads = res.sums[2]; });
 }
 
-namespace {
-
-// The host forms: the batch goes to a buffer the object keeps, `call(d_bases, d_a, d_b, d_starts, &reads)` answers it there,
-// and 4 bytes per read and array come back (a: windows, b: hits / classes).
-template <class Call>
-int reads_staged(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint64_t max_reads, uint32_t* a, uint32_t* b, uint64_t* read_starts, Call call)
-{
-    uint32_t* da = nullptr; uint32_t* db = nullptr; uint64_t* ds = nullptr;
-    int rc = obj_guarded(o->device, o->last_error, [&]() {
-        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL;
-        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, b0 + 2 * each + (max_reads + 1) * 8);
-        da = (uint32_t*)(mem + b0); db = (uint32_t*)(mem + b0 + each); ds = (uint64_t*)(mem + b0 + 2 * each);
-        HIP_TRY(hipMemcpyAsync(mem, bases, nbytes, hipMemcpyHostToDevice, o->stream));
-    });
-    if (rc != GOSS_OK) return rc;
-    uint64_t reads = 0;
-    rc = call(o->match_stage, a ? da : nullptr, b ? db : nullptr, read_starts ? ds : nullptr, &reads);
-    if (rc != GOSS_OK) return rc;
-    return obj_guarded(o->device, o->last_error, [&]() {
-        if (a && reads) HIP_TRY(hipMemcpyAsync(a, da, reads * 4, hipMemcpyDeviceToHost, o->stream));
-        if (b && reads) HIP_TRY(hipMemcpyAsync(b, db, reads * 4, hipMemcpyDeviceToHost, o->stream));
-        if (read_starts) HIP_TRY(hipMemcpyAsync(read_starts, ds, (reads + 1) * 8, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-    });
-}
-
-}  // namespace
-
-extern "C" int goss_gpu_object_match_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                                uint32_t* windows, uint32_t* hits, uint64_t* read_starts, goss_gpu_match_info* info)
+int goss_gpu_object_match_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                     uint32_t* windows, uint32_t* hits, uint64_t* read_starts, goss_gpu_match_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (nbytes == 0)
-    {
-        if (read_starts) read_starts[0] = 0;
-        return goss_gpu_object_match_reads(o, nullptr, 0, flags, max_reads, nullptr, nullptr, nullptr, info);
-    }
-    return reads_staged(o, bases, nbytes, max_reads, windows, hits, read_starts,
-                        [&](const void* d, uint32_t* dw, uint32_t* dh, uint64_t* ds, uint64_t* reads) {
-                            goss_gpu_match_info mine;
-                            const int rc = goss_gpu_object_match_reads(o, d, nbytes, flags, max_reads, dw, dh, ds, &mine);
-                            if (info) *info = mine;
-                            *reads = mine.reads;
-                            return rc;
-                        });
-}
-
-// ============================================================================================
-// Reads classified against an annotated KmerSet (goss_gpu_object_classify_reads): the classify mode of kernels_match.hpp
-// ============================================================================================
-
-extern "C" int goss_gpu_object_classify_bits_host(goss_gpu_object* o, const uint64_t* lhs, const uint64_t* rhs)
-{
-    if (!o) return GOSS_ERR_INVALID_ARG;
-    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "classify_bits needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
-    const uint64_t nwords = (o->q.s.count + 63) / 64, bytes = nwords * 8;
-    if (nwords && (!lhs || !rhs)) { o->last_error = "classify_bits: a bitmap pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
-    return obj_guarded(o->device, o->last_error, [&]() {
-        if (nwords && !o->classify_bits) HIP_TRY(hipMalloc((void**)&o->classify_bits, 2 * bytes));      // (count never changes)
-        if (nwords)
-        {
-            HIP_TRY(hipMemcpyAsync(o->classify_bits, lhs, bytes, hipMemcpyHostToDevice, o->stream));
-            HIP_TRY(hipMemcpyAsync(o->classify_bits + nwords, rhs, bytes, hipMemcpyHostToDevice, o->stream));
-            HIP_TRY(hipStreamSynchronize(o->stream));
-        }
-        o->classify_kept = true;
+    return reads_staged(o, bases, nbytes, max_reads, windows, hits, read_starts, nullptr, info, [&](const StagedBatch& s, goss_gpu_match_info* mine) {
+        return goss_gpu_object_match_reads(o, s.bases, nbytes, flags, max_reads, s.a, s.b, s.starts, mine);
     });
 }
 
-extern "C" int goss_gpu_object_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint64_t* d_lhs, const uint64_t* d_rhs,
-                                              uint32_t flags, uint64_t max_reads, uint32_t* d_classes, uint32_t* d_windows, uint64_t* d_read_starts,
-                                              goss_gpu_classify_info* info)
+int goss_gpu_object_classify_bits_host(goss_gpu_object* o, const uint64_t* lhs, const uint64_t* rhs)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "classify_bits needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (o->q.s.count && (!lhs || !rhs)) { o->last_error = "classify_bits: a bitmap pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
+    return obj_guarded(o->device, o->last_error, [&]() { classify_keep_bits(o, lhs, rhs); });
+}
+
+int goss_gpu_object_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint64_t* d_lhs, const uint64_t* d_rhs,
+                                   uint32_t flags, uint64_t max_reads, uint32_t* d_classes, uint32_t* d_windows, uint64_t* d_read_starts,
+                                   goss_gpu_classify_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
@@ -4396,207 +3891,43 @@ extern "C" int goss_gpu_object_classify_reads(goss_gpu_object* o, const void* d_
         d_rhs = o->classify_bits + nwords;
     }
     ReadsPass res;
-    const int rc = reads_pass(o, "classify_reads", kModeClassify, d_bases, nbytes, flags, max_reads, d_windows, d_classes, d_read_starts, d_lhs, d_rhs, &res);
-    if (info)
-    {
-        info->reads = res.reads;
-        if (rc == GOSS_OK)
-        {
-            info->windows = res.sums[0];
-            for (int i = 0; i < 16; ++i) info->counts[i] = res.counts[i];
-            info->ms = res.ms;
-        }
-    }
-    return rc;
+    const int rc = reads_pass(o, ReadsJob{"classify_reads", kModeClassify, d_bases, nbytes, flags, max_reads, d_windows, d_classes, d_read_starts, false,
+                                          MatchAux{d_lhs, d_rhs, TaxoView{}}}, &res);
+    return pass_report(rc, res, info, [&](goss_gpu_classify_info& i) {
+        i.windows = res.sums[0];
+        for (int k = 0; k < 16; ++k) i.counts[k] = res.counts[k];
+    });
 }
 
-extern "C" int goss_gpu_object_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                                   uint32_t* classes, uint32_t* windows, uint64_t* read_starts, goss_gpu_classify_info* info)
+int goss_gpu_object_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                        uint32_t* classes, uint32_t* windows, uint64_t* read_starts, goss_gpu_classify_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (nbytes == 0)
-    {
-        if (read_starts) read_starts[0] = 0;
-        return goss_gpu_object_classify_reads(o, nullptr, 0, nullptr, nullptr, flags, max_reads, nullptr, nullptr, nullptr, info);
-    }
-    return reads_staged(o, bases, nbytes, max_reads, windows, classes, read_starts,
-                        [&](const void* d, uint32_t* dw, uint32_t* dc, uint64_t* ds, uint64_t* reads) {
-                            goss_gpu_classify_info mine;
-                            const int rc = goss_gpu_object_classify_reads(o, d, nbytes, nullptr, nullptr, flags, max_reads, dc, dw, ds, &mine);
-                            if (info) *info = mine;
-                            *reads = mine.reads;
-                            return rc;
-                        });
+    return reads_staged(o, bases, nbytes, max_reads, windows, classes, read_starts, nullptr, info, [&](const StagedBatch& s, goss_gpu_classify_info* mine) {
+        return goss_gpu_object_classify_reads(o, s.bases, nbytes, nullptr, nullptr, flags, max_reads, s.b, s.a, s.starts, mine);
+    });
 }
 
-// ============================================================================================
-// A taxonomy over a KmerSet's k-mers (goss_gpu_object_taxo_*): kernels_taxo.hpp and the annotate / taxon modes of
-// kernels_match.hpp
-// ============================================================================================
-
-namespace {
-
-inline dim3 taxo_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 2048)); }
-
-struct TaxoTables {
-    const uint32_t *parent, *last, *id, *sorted_id, *sorted_class;
-};
-TaxoTables taxo_tables(const goss_gpu_object* o)
-{
-    const uint32_t* t = o->taxo_tree;
-    const uint64_t n = o->taxo_n;
-    return TaxoTables{t, t + n, t + 2 * n, t + 3 * n, t + 4 * n};
-}
-
-// the checks every taxo call but the tree's begins with; *empty: the set has no k-mers, and the call has nothing to do
-int taxo_ready(goss_gpu_object* o, const char* what, bool need_ann, bool* empty)
-{
-    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = std::string(what) + " needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
-    *empty = o->q.s.count == 0;
-    if (*empty) return GOSS_OK;
-    if (!o->taxo_n) { o->last_error = std::string(what) + ": no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
-    if (need_ann && !o->taxo_ann_kept) { o->last_error = std::string(what) + ": no annotation (goss_gpu_object_taxo_annotation_host)"; return GOSS_ERR_STATE; }
-    return GOSS_OK;
-}
-
-// out[0..z) = the classes of the node ids in[0..z) (device arrays); an id the tree lacks throws, `item` naming what i counts
-void taxo_dense(goss_gpu_object* o, const char* what, const char* item, const uint32_t* in, uint64_t z, uint32_t allow, uint32_t* out)
-{
-    if (!z) return;
-    const TaxoTables t = taxo_tables(o);
-    HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
-    hipLaunchKernelGGL(taxo_dense_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, in, z, t.sorted_id, t.sorted_class, o->taxo_n, allow, out, o->d_bad);
-    HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    check_launch(what);
-    const unsigned long long bad = *o->h_bad;
-    if (bad == ~0ULL) return;
-    uint32_t id = 0;
-    HIP_TRY(hipMemcpy(&id, in + bad, 4, hipMemcpyDeviceToHost));
-    throw StatusError{GOSS_ERR_INVALID_ARG, std::string(what) + ": " + item + " " + std::to_string(bad) + " has node id " + std::to_string(id) + ", which the tree lacks"};
-}
-
-// bins (device, n + 2) = the tally of z classes
-void taxo_tally(goss_gpu_object* o, const uint32_t* classes, uint64_t z)
-{
-    HIP_TRY(hipMemsetAsync(o->taxo_bins, 0, ((uint64_t)o->taxo_n + 2) * 8, o->stream));
-    if (z) hipLaunchKernelGGL(taxo_tally_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, classes, z, o->taxo_n, o->taxo_bins);
-}
-
-// counts[i] = the bin of the i-th node as given, then none and many
-void taxo_bins_out(goss_gpu_object* o, uint64_t* counts)
-{
-    std::vector<unsigned long long> bins((uint64_t)o->taxo_n + 2);
-    HIP_TRY(hipMemcpyAsync(bins.data(), o->taxo_bins, bins.size() * 8, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    for (uint32_t i = 0; i < o->taxo_n; ++i) counts[i] = bins[o->taxo_pre[i]];
-    counts[o->taxo_n] = bins[o->taxo_n];
-    counts[o->taxo_n + 1] = bins[o->taxo_n + 1];
-}
-
-}  // namespace
-
-extern "C" int goss_gpu_object_taxo_tree_host(goss_gpu_object* o, uint32_t n, const uint32_t* ids, const uint32_t* parent_index)
+int goss_gpu_object_taxo_tree_host(goss_gpu_object* o, uint32_t n, const uint32_t* ids, const uint32_t* parent_index)
 {
     if (!o) return GOSS_ERR_INVALID_ARG;
     if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_tree needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
     if (!n || !ids || !parent_index) { o->last_error = "taxo_tree: no nodes"; return GOSS_ERR_INVALID_ARG; }
     if (n >= 0xFFFFFFFEu) { o->last_error = "taxo_tree: too many nodes"; return GOSS_ERR_INVALID_ARG; }
-    return obj_guarded(o->device, o->last_error, [&]() {
-        auto refuse = [](const std::string& msg) { throw StatusError{GOSS_ERR_INVALID_ARG, "taxo_tree: " + msg}; };
-        // one root, parents in range, ids usable and distinct
-        uint32_t root = n;
-        for (uint32_t i = 0; i < n; ++i)
-        {
-            if (parent_index[i] >= n) refuse("node " + std::to_string(i) + " names parent " + std::to_string(parent_index[i]) + " of " + std::to_string(n));
-            if (ids[i] == GOSS_TAXO_NONE || ids[i] == GOSS_TAXO_MANY) refuse("node " + std::to_string(i) + " has the reserved id " + std::to_string(ids[i]));
-            if (parent_index[i] != i) continue;
-            if (root != n) refuse("nodes " + std::to_string(root) + " and " + std::to_string(i) + " are both their own parent");
-            root = i;
-        }
-        if (root == n) refuse("no node is its own parent");
-        std::vector<uint32_t> by_id(n);
-        for (uint32_t i = 0; i < n; ++i) by_id[i] = i;
-        std::sort(by_id.begin(), by_id.end(), [&](uint32_t a, uint32_t b) { return ids[a] < ids[b]; });
-        for (uint32_t i = 1; i < n; ++i)
-            if (ids[by_id[i]] == ids[by_id[i - 1]]) refuse("node id " + std::to_string(ids[by_id[i]]) + " occurs twice");
-        // children in the order given (a counting sort by parent), then pre-order numbers without recursion
-        std::vector<uint32_t> first(n + 1, 0), kids(n ? n - 1 : 0);
-        for (uint32_t i = 0; i < n; ++i) if (i != root) ++first[parent_index[i] + 1];
-        for (uint32_t i = 0; i < n; ++i) first[i + 1] += first[i];
-        {
-            std::vector<uint32_t> at(first.begin(), first.end() - 1);
-            for (uint32_t i = 0; i < n; ++i) if (i != root) kids[at[parent_index[i]]++] = i;
-        }
-        std::vector<uint32_t> pre(n, 0xFFFFFFFFu), tab(5 * (uint64_t)n), next(n, 0), stack;
-        uint32_t* parent = tab.data(); uint32_t* last = parent + n; uint32_t* id = last + n; uint32_t* sid = id + n; uint32_t* scl = sid + n;
-        uint32_t seen = 0;
-        pre[root] = seen++;
-        parent[0] = 0;
-        id[0] = ids[root];
-        stack.push_back(root);
-        while (!stack.empty())
-        {
-            const uint32_t v = stack.back();
-            if (next[v] < first[v + 1] - first[v])
-            {
-                const uint32_t c = kids[first[v] + next[v]++];
-                pre[c] = seen++;
-                parent[pre[c]] = pre[v];
-                id[pre[c]] = ids[c];
-                stack.push_back(c);
-            }
-            else
-            {
-                last[pre[v]] = seen - 1;
-                stack.pop_back();
-            }
-        }
-        if (seen != n)
-            for (uint32_t i = 0; i < n; ++i)
-                if (pre[i] == 0xFFFFFFFFu) refuse("node " + std::to_string(i) + " does not hang under the root");
-        for (uint32_t i = 0; i < n; ++i) { sid[i] = ids[by_id[i]]; scl[i] = pre[by_id[i]] + 1; }
-
-        const uint64_t tab_bytes = (5 * (uint64_t)n * 4 + 7) & ~7ULL;
-        uint32_t* mem = nullptr;
-        if (hipMalloc((void**)&mem, tab_bytes + ((uint64_t)n + 2) * 8) != hipSuccess) { (void)hipGetLastError(); throw StatusError{GOSS_ERR_OOM, "taxo_tree: no device memory for the tree"}; }
-        if (hipMemcpy(mem, tab.data(), 5 * (uint64_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(mem); throw StatusError{GOSS_ERR_HIP, "taxo_tree: the copy of the tree failed"}; }
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        if (o->taxo_tree) (void)hipFree(o->taxo_tree);
-        o->taxo_tree = mem;
-        o->taxo_bins = (unsigned long long*)((uint8_t*)mem + tab_bytes);
-        o->taxo_n = n;
-        o->taxo_pre.swap(pre);
-        o->taxo_ann_kept = false;                // (its classes were the old tree's numbers)
-    });
+    return obj_guarded(o->device, o->last_error, [&]() { taxo_build_tree(o, n, ids, parent_index); });
 }
 
-extern "C" int goss_gpu_object_taxo_annotation_host(goss_gpu_object* o, const uint32_t* ann)
+int goss_gpu_object_taxo_annotation_host(goss_gpu_object* o, const uint32_t* ann)
 {
     if (!o) return GOSS_ERR_INVALID_ARG;
     bool empty = false;
     const int rc = taxo_ready(o, "taxo_annotation", false, &empty);
     if (rc != GOSS_OK || empty) return rc;
-    const uint64_t z = o->q.s.count;
-    return obj_guarded(o->device, o->last_error, [&]() {
-        if (!o->taxo_ann && hipMalloc((void**)&o->taxo_ann, z * 4) != hipSuccess) { (void)hipGetLastError(); o->taxo_ann = nullptr; throw StatusError{GOSS_ERR_OOM, "taxo_annotation: no device memory for the annotation"}; }
-        if (!ann) HIP_TRY(hipMemsetAsync(o->taxo_ann, 0, z * 4, o->stream));
-        else
-        {
-            // converted beside the kept one, which an unknown id leaves as it was
-            const uint64_t each = (z * 4 + 255) & ~255ULL;
-            uint8_t* tmp = match_room(o->taxo_tmp, o->taxo_tmp_bytes, 2 * each);
-            HIP_TRY(hipMemcpyAsync(tmp, ann, z * 4, hipMemcpyHostToDevice, o->stream));
-            taxo_dense(o, "taxo_annotation", "rank", (const uint32_t*)tmp, z, kTaxoAllowNone, (uint32_t*)(tmp + each));
-            HIP_TRY(hipMemcpyAsync(o->taxo_ann, tmp + each, z * 4, hipMemcpyDeviceToDevice, o->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        o->taxo_ann_kept = true;
-    });
+    return obj_guarded(o->device, o->last_error, [&]() { taxo_keep_annotation(o, ann); });
 }
 
-extern "C" int goss_gpu_object_taxo_annotation_read(goss_gpu_object* o, uint32_t* ann_out, uint64_t* counts_out)
+int goss_gpu_object_taxo_annotation_read(goss_gpu_object* o, uint32_t* ann_out, uint64_t* counts_out)
 {
     if (!o) return GOSS_ERR_INVALID_ARG;
     bool empty = false;
@@ -4607,57 +3938,11 @@ extern "C" int goss_gpu_object_taxo_annotation_read(goss_gpu_object* o, uint32_t
         if (counts_out) for (uint32_t i = 0; i < o->taxo_n; ++i) counts_out[i] = 0;
         return GOSS_OK;
     }
-    const uint64_t z = o->q.s.count;
-    return obj_guarded(o->device, o->last_error, [&]() {
-        if (counts_out)
-        {
-            taxo_tally(o, o->taxo_ann, z);
-            std::vector<uint64_t> counts((uint64_t)o->taxo_n + 2);
-            taxo_bins_out(o, counts.data());
-            std::copy(counts.begin(), counts.end() - 2, counts_out);
-        }
-        if (ann_out)
-        {
-            uint32_t* tmp = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, z * 4);
-            hipLaunchKernelGGL(taxo_ids_kernel, taxo_grid(z), dim3(kTB), 0, o->stream, (const uint32_t*)o->taxo_ann, z, taxo_tables(o).id, tmp);
-            HIP_TRY(hipMemcpyAsync(ann_out, tmp, z * 4, hipMemcpyDeviceToHost, o->stream));
-            HIP_TRY(hipStreamSynchronize(o->stream));
-            check_launch("taxo_annotation_read");
-        }
-    });
+    return obj_guarded(o->device, o->last_error, [&]() { taxo_read_annotation(o, ann_out, counts_out); });
 }
 
-namespace {
-
-// the result of a call on an empty set: the reads counted and their windows, no hit anywhere (must_fit: annotate, whose
-// node ids are per read)
-int taxo_empty_pass(goss_gpu_object* o, const char* what, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads, uint32_t* d_result,
-                    uint32_t* d_windows, uint64_t* d_read_starts, bool must_fit, goss_gpu_taxo_info* info)
-{
-    ReadsPass res;
-    int rc = reads_pass(o, what, kModeCount, d_bases, nbytes, flags, max_reads, d_windows, nullptr, d_read_starts, nullptr, nullptr, &res);
-    if (rc == GOSS_OK && must_fit && res.reads > max_reads)
-    {
-        o->last_error = std::string(what) + ": the input holds " + std::to_string(res.reads) + " reads, the output arrays " + std::to_string(max_reads);
-        rc = GOSS_ERR_BUFFER;
-    }
-    if (rc == GOSS_OK && d_result && res.reads)
-        rc = obj_guarded(o->device, o->last_error, [&]() {
-            HIP_TRY(hipMemsetAsync(d_result, 0xFF, res.reads * 4, o->stream));       // (GOSS_TAXO_NONE)
-            HIP_TRY(hipStreamSynchronize(o->stream));
-        });
-    if (info)
-    {
-        info->reads = res.reads;
-        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->none = must_fit ? 0 : res.reads; info->ms = res.ms; }
-    }
-    return rc;
-}
-
-}  // namespace
-
-extern "C" int goss_gpu_object_taxo_annotate(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint32_t* d_read_nodes, uint32_t flags,
-                                             uint64_t max_reads, uint32_t* d_windows, goss_gpu_taxo_info* info)
+int goss_gpu_object_taxo_annotate(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, const uint32_t* d_read_nodes, uint32_t flags,
+                                  uint64_t max_reads, uint32_t* d_windows, goss_gpu_taxo_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
@@ -4669,26 +3954,21 @@ extern "C" int goss_gpu_object_taxo_annotate(goss_gpu_object* o, const void* d_b
     if (empty)
         return taxo_empty_pass(o, "taxo_annotate", d_bases, nbytes, flags, max_reads, nullptr, d_windows, nullptr, true, info);
     if (nbytes == 0) return GOSS_OK;
-    TaxoView tx;
+    ReadsJob job{"taxo_annotate", kModeAnnotate, d_bases, nbytes, flags, max_reads, d_windows, nullptr, nullptr, true};
     rc = obj_guarded(o->device, o->last_error, [&]() {
-        uint32_t* cls = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, max_reads * 4 + 256);
+        uint32_t* cls = (uint32_t*)o->taxo_scratch.room(max_reads * 4 + 256);
         taxo_dense(o, "taxo_annotate", "read", d_read_nodes, max_reads, 0, cls);
-        const TaxoTables t = taxo_tables(o);
-        tx.parent = t.parent; tx.last = t.last; tx.ann = o->taxo_ann; tx.read_class = cls;
+        job.aux.tx = taxo_view(o);
+        job.aux.tx.read_class = cls;
     });
     if (rc != GOSS_OK) return rc;
     ReadsPass res;
-    rc = reads_pass(o, "taxo_annotate", kModeAnnotate, d_bases, nbytes, flags, max_reads, d_windows, nullptr, nullptr, nullptr, nullptr, &res, tx);
-    if (info)
-    {
-        info->reads = res.reads;
-        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->hits = res.sums[1]; info->ms = res.ms; }
-    }
-    return rc;
+    rc = reads_pass(o, job, &res);
+    return pass_report(rc, res, info, [&](goss_gpu_taxo_info& i) { i.windows = res.sums[0]; i.hits = res.sums[1]; });
 }
 
-extern "C" int goss_gpu_object_taxo_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                                   uint32_t* d_result, uint32_t* d_windows, uint64_t* d_read_starts, goss_gpu_taxo_info* info)
+int goss_gpu_object_taxo_classify_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                        uint32_t* d_result, uint32_t* d_windows, uint64_t* d_read_starts, goss_gpu_taxo_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
@@ -4697,93 +3977,52 @@ extern "C" int goss_gpu_object_taxo_classify_reads(goss_gpu_object* o, const voi
     int rc = taxo_ready(o, "taxo_classify_reads", true, &empty);
     if (rc != GOSS_OK) return rc;
     if (empty) return taxo_empty_pass(o, "taxo_classify_reads", d_bases, nbytes, flags, max_reads, d_result, d_windows, d_read_starts, false, info);
-    const TaxoTables t = taxo_tables(o);
-    TaxoView tx;
-    tx.parent = t.parent; tx.last = t.last; tx.ann = o->taxo_ann;
     ReadsPass res;
-    unsigned long long ends[2] = {0, 0};
-    rc = reads_pass(o, "taxo_classify_reads", kModeTaxon, d_bases, nbytes, flags, max_reads, d_windows, d_result, d_read_starts, nullptr, nullptr, &res, tx,
-                    [&](uint32_t* h, uint64_t reads) {
-                        // the figures from the classes, then the classes become node ids where they lie
-                        taxo_tally(o, h, reads);
-                        hipLaunchKernelGGL(taxo_ids_kernel, taxo_grid(reads), dim3(kTB), 0, o->stream, (const uint32_t*)h, reads, t.id, h);
-                        HIP_TRY(hipMemcpyAsync(ends, o->taxo_bins + o->taxo_n, 16, hipMemcpyDeviceToHost, o->stream));
-                    });
-    if (info)
-    {
-        info->reads = res.reads;
-        if (rc == GOSS_OK) { info->windows = res.sums[0]; info->none = ends[0]; info->many = ends[1]; info->unannotated = res.sums[3]; info->ms = res.ms; }
-    }
-    return rc;
+    rc = reads_pass(o, ReadsJob{"taxo_classify_reads", kModeTaxon, d_bases, nbytes, flags, max_reads, d_windows, d_result, d_read_starts, false,
+                                MatchAux{nullptr, nullptr, taxo_view(o)}}, &res);
+    return pass_report(rc, res, info, [&](goss_gpu_taxo_info& i) {
+        i.windows = res.sums[0]; i.none = res.counts[0]; i.many = res.counts[1]; i.unannotated = res.sums[3];
+    });
 }
 
-extern "C" int goss_gpu_object_taxo_annotate_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, const uint32_t* read_nodes, uint32_t flags,
-                                                  uint64_t max_reads, uint32_t* windows, goss_gpu_taxo_info* info)
+int goss_gpu_object_taxo_annotate_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, const uint32_t* read_nodes, uint32_t flags,
+                                       uint64_t max_reads, uint32_t* windows, goss_gpu_taxo_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (nbytes == 0) return goss_gpu_object_taxo_annotate(o, nullptr, 0, nullptr, flags, max_reads, nullptr, info);
-    if (!read_nodes && max_reads) { o->last_error = "taxo_annotate: no node ids for the reads"; return GOSS_ERR_INVALID_ARG; }
-    // the node ids ride in the slot of the staged form's second array
-    return reads_staged(o, bases, nbytes, max_reads, windows, nullptr, nullptr,
-                        [&](const void* d, uint32_t* dw, uint32_t*, uint64_t*, uint64_t* reads) {
-                            uint32_t* dn = (uint32_t*)(o->match_stage + ((nbytes + 255) & ~255ULL) + ((max_reads * 4 + 255) & ~255ULL));
-                            const int rc0 = obj_guarded(o->device, o->last_error, [&]() {
-                                if (max_reads) HIP_TRY(hipMemcpyAsync(dn, read_nodes, max_reads * 4, hipMemcpyHostToDevice, o->stream));
-                            });
-                            if (rc0 != GOSS_OK) return rc0;
-                            goss_gpu_taxo_info mine;
-                            const int rc = goss_gpu_object_taxo_annotate(o, d, nbytes, dn, flags, max_reads, dw, &mine);
-                            if (info) *info = mine;
-                            *reads = mine.reads;
-                            return rc;
-                        });
+    if (!read_nodes && max_reads && nbytes) { o->last_error = "taxo_annotate: no node ids for the reads"; return GOSS_ERR_INVALID_ARG; }
+    // (the node ids are the batch's extra array)
+    return reads_staged(o, bases, nbytes, max_reads, windows, nullptr, nullptr, read_nodes, info, [&](const StagedBatch& s, goss_gpu_taxo_info* mine) {
+        return goss_gpu_object_taxo_annotate(o, s.bases, nbytes, s.extra, flags, max_reads, s.a, mine);
+    });
 }
 
-extern "C" int goss_gpu_object_taxo_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
-                                                        uint32_t* result, uint32_t* windows, uint64_t* read_starts, goss_gpu_taxo_info* info)
+int goss_gpu_object_taxo_classify_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                             uint32_t* result, uint32_t* windows, uint64_t* read_starts, goss_gpu_taxo_info* info)
 {
     if (info) std::memset(info, 0, sizeof *info);
     if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (nbytes == 0)
-    {
-        if (read_starts) read_starts[0] = 0;
-        return goss_gpu_object_taxo_classify_reads(o, nullptr, 0, flags, max_reads, nullptr, nullptr, nullptr, info);
-    }
-    return reads_staged(o, bases, nbytes, max_reads, windows, result, read_starts,
-                        [&](const void* d, uint32_t* dw, uint32_t* dr, uint64_t* ds, uint64_t* reads) {
-                            goss_gpu_taxo_info mine;
-                            const int rc = goss_gpu_object_taxo_classify_reads(o, d, nbytes, flags, max_reads, dr, dw, ds, &mine);
-                            if (info) *info = mine;
-                            *reads = mine.reads;
-                            return rc;
-                        });
+    return reads_staged(o, bases, nbytes, max_reads, windows, result, read_starts, nullptr, info, [&](const StagedBatch& s, goss_gpu_taxo_info* mine) {
+        return goss_gpu_object_taxo_classify_reads(o, s.bases, nbytes, flags, max_reads, s.b, s.a, s.starts, mine);
+    });
 }
 
-extern "C" int goss_gpu_object_taxo_pair(goss_gpu_object* o, const uint32_t* d_a, const uint32_t* d_b, uint64_t n, uint32_t* d_out)
+int goss_gpu_object_taxo_pair(goss_gpu_object* o, const uint32_t* d_a, const uint32_t* d_b, uint64_t n, uint32_t* d_out)
 {
     if (!o || (n && (!d_a || !d_b || !d_out))) return GOSS_ERR_INVALID_ARG;
     if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_pair needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
     if (!o->taxo_n) { o->last_error = "taxo_pair: no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
     if (!n) return GOSS_OK;
-    return obj_guarded(o->device, o->last_error, [&]() {
-        const TaxoTables t = taxo_tables(o);
-        HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
-        hipLaunchKernelGGL(taxo_pair_kernel, taxo_grid(n), dim3(kTB), 0, o->stream, d_a, d_b, n, t.sorted_id, t.sorted_class, t.last, t.id, o->taxo_n, d_out, o->d_bad);
-        HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        check_launch("taxo_pair");
-        if (*o->h_bad != ~0ULL) throw StatusError{GOSS_ERR_INVALID_ARG, "taxo_pair: pair " + std::to_string(*o->h_bad) + " holds a node id the tree lacks"};
-    });
+    return obj_guarded(o->device, o->last_error, [&]() { taxo_pair(o, d_a, d_b, n, d_out); });
 }
 
-extern "C" int goss_gpu_object_taxo_tally(goss_gpu_object* o, const uint32_t* d_values, uint64_t n, uint64_t* counts)
+int goss_gpu_object_taxo_tally(goss_gpu_object* o, const uint32_t* d_values, uint64_t n, uint64_t* counts)
 {
     if (!o || !counts || (n && !d_values)) return GOSS_ERR_INVALID_ARG;
     if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "taxo_tally needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
     if (!o->taxo_n) { o->last_error = "taxo_tally: no tree (goss_gpu_object_taxo_tree_host)"; return GOSS_ERR_STATE; }
     return obj_guarded(o->device, o->last_error, [&]() {
-        uint32_t* cls = (uint32_t*)match_room(o->taxo_tmp, o->taxo_tmp_bytes, n * 4 + 256);
+        uint32_t* cls = (uint32_t*)o->taxo_scratch.room(n * 4 + 256);
         taxo_dense(o, "taxo_tally", "value", d_values, n, kTaxoAllowNone | kTaxoAllowMany, cls);
         taxo_tally(o, cls, n);
         taxo_bins_out(o, counts);
@@ -4791,42 +4030,16 @@ extern "C" int goss_gpu_object_taxo_tally(goss_gpu_object* o, const uint32_t* d_
     });
 }
 
-namespace {
-
-// n values per array staged to the device and `call`ed there: ins host arrays in, then `outs` arrays back
-template <class Call>
-int taxo_staged(goss_gpu_object* o, std::initializer_list<const uint32_t*> ins, uint64_t n, uint32_t* out, Call call)
-{
-    uint32_t* d[3] = {nullptr, nullptr, nullptr};
-    int rc = obj_guarded(o->device, o->last_error, [&]() {
-        const uint64_t each = (n * 4 + 255) & ~255ULL;
-        uint8_t* mem = match_room(o->match_stage, o->match_stage_bytes, 3 * each + 256);
-        uint32_t k = 0;
-        for (const uint32_t* p : ins)
-        {
-            d[k] = (uint32_t*)(mem + k * each);
-            if (n) HIP_TRY(hipMemcpyAsync(d[k], p, n * 4, hipMemcpyHostToDevice, o->stream));
-            ++k;
-        }
-        d[2] = (uint32_t*)(mem + 2 * each);
-        HIP_TRY(hipStreamSynchronize(o->stream));
-    });
-    if (rc != GOSS_OK) return rc;
-    rc = call(d[0], d[1], d[2]);
-    if (rc != GOSS_OK || !out || !n) return rc;
-    return obj_guarded(o->device, o->last_error, [&]() { HIP_TRY(hipMemcpy(out, d[2], n * 4, hipMemcpyDeviceToHost)); });
-}
-
-}  // namespace
-
-extern "C" int goss_gpu_object_taxo_pair_host(goss_gpu_object* o, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out)
+int goss_gpu_object_taxo_pair_host(goss_gpu_object* o, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out)
 {
     if (!o || (n && (!a || !b || !out))) return GOSS_ERR_INVALID_ARG;
     return taxo_staged(o, {a, b}, n, out, [&](uint32_t* da, uint32_t* db, uint32_t* dout) { return goss_gpu_object_taxo_pair(o, da, db, n, dout); });
 }
 
-extern "C" int goss_gpu_object_taxo_tally_host(goss_gpu_object* o, const uint32_t* values, uint64_t n, uint64_t* counts)
+int goss_gpu_object_taxo_tally_host(goss_gpu_object* o, const uint32_t* values, uint64_t n, uint64_t* counts)
 {
     if (!o || !counts || (n && !values)) return GOSS_ERR_INVALID_ARG;
     return taxo_staged(o, {values}, n, nullptr, [&](uint32_t* dv, uint32_t*, uint32_t*) { return goss_gpu_object_taxo_tally(o, dv, n, counts); });
 }
+
+}  // extern "C"

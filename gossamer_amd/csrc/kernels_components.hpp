@@ -1,6 +1,6 @@
 // kernels_components.hpp -- count-components on the decoded edge list of a graph: the connected components of the
 // marked edges, their figures, and the removal bitmap that keeps one component.
-// Part of the kernel set of libgossgpu.so (gfx950); included through goss_kernels.hpp, after kernels_match.hpp.
+// Part of the kernel set of libgossgpu.so (gfx950); included through goss_kernels.hpp.
 //
 // What it replaces: GossCmdCountComponents.cc:37-127, 171-311 -- a serial flood fill (one stack, one dynamic_bitset)
 // whose every step is a rank / select walk of the Elias-Fano index.  Two marked edges belong together when they share
@@ -28,7 +28,7 @@
 
 #include "goss_key.hpp"
 #include "kernels_common.hpp"
-#include "kernels_match.hpp"
+#include "goss_read_tile.hpp"
 #include "kernels_tips.hpp"
 
 namespace goss {
@@ -55,9 +55,9 @@ __device__ __forceinline__ bool comp_marked(const uint32_t* __restrict__ marks, 
 
 // ---- marking the edges that reads touch ----------------------------------------------------------------------------
 
-// One workgroup per tile of kMatchTile byte positions, staged as match_reads_kernel stages it (2-bit codes and
-// non-base flags in LDS bit arrays, a halo of 64 positions).  Every valid forward window of L = K + 1 bases is looked
-// up among the sorted edges -- the forward key only: no reverse complement, no normalisation
+// One workgroup per tile of kMatchTile byte positions, staged by goss_read_tile.hpp without the newline flags (2-bit
+// codes and non-base flags in LDS bit arrays, a halo of 64 positions).  Every valid forward window of L = K + 1 bases is
+// looked up among the sorted edges -- the forward key only: no reverse complement, no normalisation
 // (GossCmdCountComponents.cc:231-239) -- and a hit sets the edge's bit.  rep->windows / hits: once per wave.
 template <class K>
 __global__ __launch_bounds__(kTB) void components_mark_kernel(const K* __restrict__ keys, uint32_t n, uint32_t L, uint32_t bits,
@@ -73,14 +73,7 @@ __global__ __launch_bounds__(kTB) void components_mark_kernel(const K* __restric
     const uint64_t t0 = tile * kMatchTile;
     const uint32_t lane = lane_id();
 
-    for (uint32_t g = threadIdx.x; g < kMatchGroups; g += kTB)
-    {
-        const uint64_t w = match_load8(bases, nbytes, t0 + 8ULL * g, aligned);
-        uint32_t bad0, bad1;
-        const uint32_t x0 = base_codes((uint32_t)w, bad0), x1 = base_codes((uint32_t)(w >> 32), bad1);
-        reinterpret_cast<uint16_t*>(s_codes)[g] = (uint16_t)(pack_codes(x0) | (pack_codes(x1) << 8));
-        reinterpret_cast<uint8_t*>(s_inv)[g] = (uint8_t)(pack_flags(bad0) | (pack_flags(bad1) << 4));
-    }
+    tile_stage<false>(bases, nbytes, t0, aligned, s_codes, s_inv, nullptr);
     __syncthreads();
 
     const uint64_t lmask = (1ULL << L) - 1;              // (L <= 63)
@@ -88,25 +81,14 @@ __global__ __launch_bounds__(kTB) void components_mark_kernel(const K* __restric
     for (uint32_t it = 0; it < kMatchRuns / kWaves; ++it)
     {
         const uint32_t run = wave_id() * (kMatchRuns / kWaves) + it;
-        const uint32_t q = run * 64 + lane;
-        const uint64_t iv = (s_inv[run] >> lane) | (lane ? s_inv[run + 1] << (64 - lane) : 0);
-        const bool valid = (iv & lmask) == 0;
+        const bool valid = tile_window_valid(s_inv, run, lane, lmask);
         const uint64_t vb = __ballot(valid);
         if (!vb) continue;
         bool hit = false;
         if (valid)
         {
-            const uint32_t cw = q >> 5, co = 2 * (q & 31);
-            const uint64_t c0 = s_codes[cw], c1 = s_codes[cw + 1];
-            const uint64_t v0 = co ? (c0 >> co) | (c1 << (64 - co)) : c0;
-            uint64_t v1 = 0;
-            if (K::kWords == 2)
-            {
-                const uint64_t c2 = s_codes[cw + 2];
-                v1 = co ? (c1 >> co) | (c2 << (64 - co)) : c1;
-            }
             K x, rc;
-            match_keys<K>(v0, v1, L, &x, &rc);
+            tile_window_keys<K>(s_codes, run * 64 + lane, L, &x, &rc);
             const uint32_t r = tips_lower_bound(keys, n, L, bits, table, x);
             if (r < n && keys[r] == x)
             {

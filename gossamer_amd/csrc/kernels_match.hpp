@@ -6,14 +6,11 @@
 // (match_count_newlines_kernel), one device scan, and inside the tile a popcount over a 64-bit mask.  A read of a
 // million bases is 489 tiles on 489 workgroups like any other million bytes.
 //
-// A tile is staged once: every lane turns 8 bytes into 16 bits of 2-bit codes, 8 non-base flags and 8 newline flags
-// (base_codes: the extraction kernels' decoder) and stores them into three LDS bit arrays, the tile's 2,048 positions
-// plus a halo of 64 (>= L - 1).  The window that starts at a position is then a funnel shift of two or three LDS
-// words, valid when L flag bits are clear (a '\n' is a non-base, so a valid window lies inside one read).  Stored
-// with the first base in the LOW bits, the shifted words are the window's reverse complement once inverted
-// (GossReadBaseString.hh:133-188 wants the first base on top): normalising costs one more base-4 reversal, no loop
-// over L.  What is left is the walk, rd_sparse_access_rank on the object's k-mers / edges only: the multiplicity
-// arrays are never touched.
+// A tile is staged once, by goss_read_tile.hpp (tile_stage<true>): 2-bit codes, non-base flags and newline flags in
+// three LDS bit arrays, the tile's 2,048 positions plus a halo of 64.  The window that starts at a position is valid
+// when its L flag bits are clear (tile_window_valid) and its key and reverse complement are a funnel shift of two or
+// three LDS words (tile_window_keys): normalising costs one more base-4 reversal, no loop over L.  What is left is the
+// walk, rd_sparse_access_rank on the object's k-mers / edges only: the multiplicity arrays are never touched.
 //
 // A wave takes 8 consecutive runs of 64 positions.  The reads inside a run are lane intervals between newline bits:
 // ballots of "valid" and "present" are cut by each interval's first lane (popcount under the interval's mask) and
@@ -24,13 +21,16 @@
 // for the tile's first read also what earlier tiles left in hits[]), and inside a run every eighth window walks
 // first -- the other seven follow only where their read is still unmatched after that ballot.
 //
-// Classify mode (goss_gpu_object_classify_reads) is the count mode's walk with the rank kept: a hit at rank r reads bit r
-// of two bitmaps, c = 2 * lhs[r] + rhs[r], and the read's word is the OR of 1 << c over its hits -- four ballots a run
-// cut by the same lane intervals, one LDS atomicOr per interval, one global atomicOr per read and tile.
+// What only some modes read arrives in one MatchAux: the two bitmaps, the taxonomy's view.
 //
-// The two taxonomy modes (goss_gpu_object_taxo_annotate / _classify_reads, kernels_taxo.hpp) also keep the rank.  Annotate:
-// the read's class comes from a per-read array, and a hit at rank r joins it into ann[r] by lca with a compare-and-swap
-// loop that does not write where ann[r] already is the join; windows and hits are counted as in count mode.  Taxon: a
+// Classify mode (goss_gpu_object_classify_reads) is the count mode's walk with the rank kept: a hit at rank r reads bit r
+// of the two bitmaps, c = 2 * aux.lhs[r] + aux.rhs[r], and the read's word is the OR of 1 << c over its hits -- four
+// ballots a run cut by the same lane intervals, one LDS atomicOr per interval, one global atomicOr per read and tile.
+//
+// The two taxonomy modes (goss_gpu_object_taxo_annotate / _classify_reads, kernels_taxo.hpp) also keep the rank and read
+// aux.tx.  Annotate: the read's class comes from a per-read array (tx.read_class), and a hit at rank r joins it into
+// ann[r] by lca with a compare-and-swap loop that does not write where ann[r] already is the join; windows and hits
+// are counted as in count mode.  Taxon: a
 // hit reads ann[r] (a rank without a class is counted and otherwise ignored), the classes of a read's lanes in a run
 // are joined by taxo_combine -- one ballot finds the usual case, all of them the same class, which is one LDS
 // compare-and-swap join by one lane; otherwise the hit lanes join one by one -- and after the tile one global join per
@@ -44,6 +44,7 @@
 #include <stdint.h>
 
 #include "goss_key.hpp"
+#include "goss_read_tile.hpp"
 #include "goss_reader.hpp"
 #include "kernels_common.hpp"
 #include "kernels_query.hpp"
@@ -54,26 +55,13 @@ namespace goss {
 enum : uint32_t { kMatchNormalize = 1, kMatchAny = 4 };
 // what hits[] receives: a sum, 1 / 0, a 4-bit mask, a sum (and ann[] the lca), the join of the classes
 enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2, kModeAnnotate = 3, kModeTaxon = 4 };
-constexpr uint32_t kMatchTile = 2048;                    // positions per workgroup: 256 lanes x 8 bytes
-constexpr uint32_t kMatchRuns = kMatchTile / 64;         // runs of 64 positions, 8 per wave
-constexpr uint32_t kMatchGroups = kMatchTile / 8 + 8;    // 8-byte groups staged: the tile and a halo of 64 positions
 
-// 0x80 in every byte of w that is '\n'
-__device__ __forceinline__ uint32_t newline_flags(uint32_t w)
-{
-    const uint32_t v = w ^ 0x0A0A0A0Au;
-    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u;
-}
-
-// bytes [pos, pos + 8) of the input, 0 (no base, no newline) at and beyond nbytes
-__device__ __forceinline__ uint64_t match_load8(const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t pos, bool aligned)
-{
-    if (aligned && pos + 8 <= nbytes) return *reinterpret_cast<const uint64_t*>(bases + pos);
-    uint64_t w = 0;
-    for (uint32_t j = 0; j < 8; ++j)
-        if (pos + j < nbytes) w |= (uint64_t)bases[pos + j] << (8 * j);
-    return w;
-}
+// what only some modes read: kModeClassify the two bitmaps (bit r = rank r), kModeAnnotate / kModeTaxon the taxonomy
+struct MatchAux {
+    const uint64_t* lhs = nullptr;
+    const uint64_t* rhs = nullptr;
+    TaxoView tx;
+};
 
 // tiles[t] = number of '\n' in tile t; one wave per tile
 __global__ __launch_bounds__(256) void match_count_newlines_kernel(const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t ntiles,
@@ -93,20 +81,6 @@ __global__ __launch_bounds__(256) void match_count_newlines_kernel(const uint8_t
 #pragma unroll
     for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
     if (lane_id() == 0) tiles[t] = n;
-}
-
-// the window of L bases whose first base is `v` bit 0..1 (2-bit codes, first base lowest): its key and, for
-// normalising, the key of its reverse complement
-template <class K> __device__ __forceinline__ void match_keys(uint64_t v0, uint64_t v1, uint32_t L, K* fwd, K* rc);
-template <> __device__ __forceinline__ void match_keys<Key1>(uint64_t v0, uint64_t, uint32_t L, Key1* fwd, Key1* rc)
-{
-    *rc = Key1{~v0 & ((1ULL << (2 * L)) - 1)};
-    *fwd = Key1{rev64(v0) >> (64 - 2 * L)};
-}
-template <> __device__ __forceinline__ void match_keys<Key2>(uint64_t v0, uint64_t v1, uint32_t L, Key2* fwd, Key2* rc)
-{
-    *rc = Key2{~v0, ~v1 & ((1ULL << (2 * L - 64)) - 1)};               // (32 <= L <= 63)
-    *fwd = revcomp(*rc, L);
 }
 
 // out[0..2] += sums over the reads: windows, hits, reads with a hit; starts[reads] = end
@@ -153,9 +127,11 @@ template <class K, int MODE>
 __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint8_t* __restrict__ bases, uint64_t nbytes, uint64_t ntiles,
                                                           const uint64_t* __restrict__ tile_read, uint32_t flags, uint32_t aligned,
                                                           uint32_t* __restrict__ windows, uint32_t* __restrict__ hits,
-                                                          uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad,
-                                                          const uint64_t* __restrict__ lhs, const uint64_t* __restrict__ rhs, TaxoView tx)
+                                                          uint64_t* __restrict__ starts, unsigned long long* __restrict__ bad, MatchAux aux)
 {
+    const uint64_t* __restrict__ lhs = aux.lhs;
+    const uint64_t* __restrict__ rhs = aux.rhs;
+    const TaxoView& tx = aux.tx;
     constexpr bool ANY = MODE == kModeAny, CLS = MODE == kModeClassify, ANN = MODE == kModeAnnotate, TAX = MODE == kModeTaxon;
     __shared__ uint64_t s_codes[kMatchGroups / 4];       // 32 bases per word, first base lowest
     __shared__ uint64_t s_inv[kMatchGroups / 8];         // bit = not one of ACGTacgt (or beyond the input)
@@ -171,17 +147,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
     const uint32_t L = o.len;
     const uint32_t lane = lane_id();
 
-    // stage: group g = 8 bytes -> 16 bits of codes, 8 + 8 flags
-    for (uint32_t g = threadIdx.x; g < kMatchGroups; g += kTB)
-    {
-        const uint64_t w = match_load8(bases, nbytes, t0 + 8ULL * g, aligned);
-        uint32_t bad0, bad1;
-        const uint32_t x0 = base_codes((uint32_t)w, bad0), x1 = base_codes((uint32_t)(w >> 32), bad1);
-        reinterpret_cast<uint16_t*>(s_codes)[g] = (uint16_t)(pack_codes(x0) | (pack_codes(x1) << 8));
-        reinterpret_cast<uint8_t*>(s_inv)[g] = (uint8_t)(pack_flags(bad0) | (pack_flags(bad1) << 4));
-        if (g < kMatchTile / 8)
-            reinterpret_cast<uint8_t*>(s_nl)[g] = (uint8_t)(pack_flags(newline_flags((uint32_t)w)) | (pack_flags(newline_flags((uint32_t)(w >> 32))) << 4));
-    }
+    tile_stage<true>(bases, nbytes, t0, aligned, s_codes, s_inv, s_nl);
     if (threadIdx.x == 0) s_prev_nl = t0 && bases[t0 - 1] == '\n';
     __syncthreads();
     if (threadIdx.x < 64)
@@ -221,8 +187,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
             if (begins) starts[read0 + local] = p;
         }
 
-        const uint64_t iv = (s_inv[run] >> lane) | (lane ? s_inv[run + 1] << (64 - lane) : 0);
-        const bool valid = (iv & lmask) == 0;
+        const bool valid = tile_window_valid(s_inv, run, lane, lmask);
         const uint64_t vb = __ballot(valid);
         if (!vb) continue;
 
@@ -236,17 +201,8 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
             bool hit = false;
             if (go)
             {
-                const uint32_t cw = q >> 5, co = 2 * (q & 31);
-                const uint64_t c0 = s_codes[cw], c1 = s_codes[cw + 1];
-                const uint64_t v0 = co ? (c0 >> co) | (c1 << (64 - co)) : c0;
-                uint64_t v1 = 0;
-                if (K::kWords == 2)
-                {
-                    const uint64_t c2 = s_codes[cw + 2];
-                    v1 = co ? (c1 >> co) | (c2 << (64 - co)) : c1;
-                }
                 K x, rc;
-                match_keys<K>(v0, v1, L, &x, &rc);
+                tile_window_keys<K>(s_codes, q, L, &x, &rc);
                 if (flags & kMatchNormalize) x = canonical(x, rc);
                 uint64_t r;
                 if (!rd_sparse_access_rank<K>(o.s, x, &r, &hit)) { q_fail(bad, p, kQBadWalk); hit = false; }

@@ -175,6 +175,34 @@ def test_special_inputs():
             obj.taxo_annotation(b"")
 
 
+def test_annotate_host_form_with_room_to_spare():
+    """goss_gpu_object_taxo_annotate_host where nothing in the staged batch ends on a 256-byte boundary and max_reads
+    exceeds the reads: 70 bytes, three reads, five node ids.  The ids must reach the kernel from their own slot."""
+    import ctypes as C
+    K = 15
+    rng = random.Random(5)
+    first, second = (bytes(rng.choice(b"ACGT") for _ in range(n)) for n in (22, 23))
+    reads, nodes = [first, second, first], [20, 30, 30]      # (the first read's k-mers: lca(20, 30) = 10)
+    data = b"\n".join(reads) + b"\n"
+    assert len(data) == 70
+    t = tm.Tree([10, 20, 30], [0, 0, 0])
+    keys = sorted(set(tm.canonical_windows(first, K) + tm.canonical_windows(second, K)[2:]))
+    items = list(zip(reads, nodes))
+    exp_ann, _ = tm.annotate(t, keys, K, items)
+    assert set(exp_ann) == {10, 30}
+    with open_set(keys, K) as obj:
+        obj.taxo_tree(t.ids, t.parent)
+        obj.taxo_annotation(None)
+        rn = np.array(nodes + [20, 20], dtype=np.uint32)
+        w = np.full(5, 0xDEAD, dtype=np.uint32)
+        info = g.binding.TaxoInfo()
+        rc = obj._L.goss_gpu_object_taxo_annotate_host(obj._h, data, len(data), rn.ctypes.data, g.TAXO_NORMALIZE, 5, w.ctypes.data, C.byref(info))
+        assert rc == 0, obj._L.goss_gpu_object_last_error(obj._h)
+        assert info.reads == 3 and w.tolist() == [len(mm.windows(r, K)) for r in reads] + [0xDEAD] * 2
+        assert info.windows == int(w[:3].sum()) and info.hits == len(tm.touches(keys, K, items))
+        assert obj.taxo_read_annotation()[0].tolist() == exp_ann
+
+
 def refused(call, status, *words):
     with pytest.raises(g.GossGpuError) as e:
         call()

@@ -32,7 +32,7 @@ SYMBOLS = [
     "goss_gpu_object_open", "goss_gpu_object_open_emitted", "goss_gpu_object_close", "goss_gpu_object_last_error",
     "goss_gpu_object_info", "goss_gpu_object_rank", "goss_gpu_object_select", "goss_gpu_object_multiplicity",
     "goss_gpu_object_lookup", "goss_gpu_object_node_ranks",
-    "goss_gpu_prune_tips",
+    "goss_gpu_prune_tips", "goss_gpu_trim_paths", "goss_gpu_clip_links", "goss_gpu_paths_timing",
     "goss_gpu_segments_build", "goss_gpu_segments_table", "goss_gpu_segments_text", "goss_gpu_segments_release",
     "goss_gpu_entries_build", "goss_gpu_entries_release", "goss_gpu_entries_length", "goss_gpu_entries_end_rank",
     "goss_gpu_components_mark_host", "goss_gpu_components_mark_device", "goss_gpu_components_build", "goss_gpu_components_table",
@@ -69,6 +69,12 @@ RELEASE_FN = C.CFUNCTYPE(None, C.c_void_p)
 # goss_gpu_tips_report, in the order of its fields
 TIPS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "tips", "zapped", "too_long", "both_joined", "isolated",
                       "outweighed", "joined_at_begin", "joined_at_end")
+
+# goss_gpu_paths_report and goss_gpu_links_report, in the order of their fields
+PATHS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "paths", "zapped", "too_long", "spared_by_cutoff", "missing_rc")
+LINKS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "links", "edges", "too_long", "major_out", "major_in", "missing_rc")
+PATHS_CUTOFF = 1
+PATHS_NO_EDGE = 0xFFFFFFFFFFFFFFFF
 
 
 # goss_gpu_segments_info and goss_gpu_segment, in the order of their fields
@@ -724,6 +730,38 @@ class Context:
         if iterations and getattr(self, "counts", None) is not None:
             self.counts.distinct = int(reps[iterations - 1].edges_after)       # what result() copies
         return [{name: int(getattr(reps[i], name)) for name in TIPS_REPORT_FIELDS} for i in range(iterations)]
+
+    def _paths_pass(self, fn, fields, *args):
+        class Report(C.Structure):
+            _fields_ = [(name, C.c_uint64) for name in fields]
+        rep = Report()
+        fn.argtypes = [C.c_void_p] + [C.c_uint32] * len(args) + [C.POINTER(Report)]
+        self._check(fn(self._h, *args, C.byref(rep)))
+        if getattr(self, "counts", None) is not None:
+            self.counts.distinct = int(rep.edges_after)                        # what result() copies
+        return {name: int(getattr(rep, name)) for name in fields}
+
+    def trim_paths(self, cutoff=None):
+        """Between finish and emit, graph mode: one pass of trim-paths on the device (goss_gpu_trim_paths): every path
+        of at most 2K edges that starts at a node without incoming edges goes.  `cutoff` spares a path that holds an
+        edge of that multiplicity or more (GOSS_PATHS_CUTOFF); None leaves the flag clear, as the reference's command
+        does whatever -C says.  The context's result becomes the trimmed graph; returns the report dict."""
+        if cutoff is None:
+            return self._paths_pass(self._L.goss_gpu_trim_paths, PATHS_REPORT_FIELDS, 0, 0)
+        return self._paths_pass(self._L.goss_gpu_trim_paths, PATHS_REPORT_FIELDS, PATHS_CUTOFF, cutoff)
+
+    def clip_links(self):
+        """Between finish and emit, graph mode: one pass of clip-links on the device (goss_gpu_clip_links): every path
+        of at most 2K edges that leaves a fork and enters a join as a minor branch (under a third of the node's
+        multiplicity) goes.  The context's result becomes the clipped graph; returns the report dict."""
+        return self._paths_pass(self._L.goss_gpu_clip_links, LINKS_REPORT_FIELDS, 0)
+
+    def paths_timing(self):
+        """{phase: ms} of the last trim_paths / clip_links pass: link, flag, gather, walk, compact (goss_gpu_paths_timing)"""
+        ms = (C.c_float * 5)()
+        self._L.goss_gpu_paths_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(self._L.goss_gpu_paths_timing(self._h, ms))
+        return dict(zip(("link", "flag", "gather", "walk", "compact"), (float(x) for x in ms)))
 
     def segments_build(self, min_length=0, min_coverage=0, line_breaks=True):
         """Between finish and emit, graph mode: build the linear segments on the device (goss_gpu_segments_build) and

@@ -226,6 +226,7 @@ struct goss_gpu_ctx {
     uint64_t M = 0;
     void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
     uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
+    float paths_ms[5] = {};               // link, flag, gather, walk, compact of the last trim-paths / clip-links pass
     // the held result: permanent room above everything else from held.lo on, held until its release entry point or
     // the next call that may allocate (guarded() gives it back first).  goss_gpu_segments_build: the segment table and
     // the text (seg_*); goss_gpu_entries_build: the images of the EntryEdgeSet, which are the file list
@@ -3320,6 +3321,29 @@ int goss_gpu_prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_repo
     if (st != GOSS_ERR_STATE && reports && iterations) std::memset(reports, 0, sizeof(goss_gpu_tips_report) * (size_t)iterations);
     if (st != GOSS_OK) return st;
     return guarded(c, [&]() { prune_tips(c, iterations, reports); });
+}
+
+int goss_gpu_trim_paths(goss_gpu_ctx* c, uint32_t flags, uint32_t cutoff, goss_gpu_paths_report* out)
+{
+    if (!c || !out || (flags & ~(uint32_t)GOSS_PATHS_CUTOFF)) return GOSS_ERR_INVALID_ARG;
+    return paths_entry(c, out, "trim_paths", "trim_paths works on a graph", "trim_paths belongs between finish and emit", [&]() {
+        if (c->words == 1) trim_paths<Key1>(c, flags, cutoff, out); else trim_paths<Key2>(c, flags, cutoff, out);
+    });
+}
+
+int goss_gpu_clip_links(goss_gpu_ctx* c, uint32_t flags, goss_gpu_links_report* out)
+{
+    if (!c || !out || flags) return GOSS_ERR_INVALID_ARG;
+    return paths_entry(c, out, "clip_links", "clip_links works on a graph", "clip_links belongs between finish and emit", [&]() {
+        if (c->words == 1) clip_links<Key1>(c, out); else clip_links<Key2>(c, out);
+    });
+}
+
+int goss_gpu_paths_timing(goss_gpu_ctx* c, float* ms)
+{
+    if (!c || !ms) return GOSS_ERR_INVALID_ARG;
+    for (int i = 0; i < 5; ++i) ms[i] = c->paths_ms[i];
+    return GOSS_OK;
 }
 
 int goss_gpu_segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)

@@ -21,6 +21,7 @@
 #include "kernels_emit.hpp"
 #include "kernels_query.hpp"
 #include "kernels_tips.hpp"
+#include "kernels_paths.hpp"
 #include "kernels_contigs.hpp"
 #include "kernels_entries.hpp"
 #include "kernels_taxo.hpp"

@@ -344,6 +344,145 @@ void prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_report* repo
     }
 }
 
+// ---- trim-paths, clip-links -----------------------------------------------------------------------------------------
+
+// What one pass of either command found, as the device report has it (kernels_paths.hpp).
+struct PathsOutcome { uint64_t before, after, candidates, hits, edges, too_long, why0, why1; };
+constexpr uint64_t kPathsNoEdge = ~0ULL;               // goss_gpu_paths_report::missing_rc of a graph that has them all
+
+// The pass both commands share, in the steps of prune_tips_once: link, flag (`forks`: the starts of clip-links, else
+// those of trim-paths and prune-tips), gather, walk under `rule`, compact.  Nothing of the context changes before the
+// survivors are complete: a failure leaves the result as it was.  *missing: the edge the link pass refused the graph
+// for, where it did.
+template <class K, class Rule>
+PathsOutcome paths_pass(goss_gpu_ctx* c, const char* who, bool forks, Rule rule, uint64_t* missing)
+{
+    PathsOutcome o{};
+    const uint64_t n64 = c->M;
+    o.before = o.after = n64;
+    if (n64 == 0) return o;
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    const uint64_t zap_words = ntiles * (kRedTile / 32), cand_words = (n64 + 63) / 64;
+    {
+        // the links, the two bitmaps, the list of starts (every edge can be one), and the survivors once more
+        const uint64_t need = link_bytes(c, who) + zap_words * 4 + cand_words * 8 + n64 * 4 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    uint32_t* zap = (uint32_t*)c->arena.temp(zap_words * 4);
+    uint64_t* cand = (uint64_t*)c->arena.temp(cand_words * 8);
+    PathsReport* d_rep = (PathsReport*)c->arena.temp(sizeof(PathsReport));
+    PathsReport* h = pinned_report<PathsReport>(c);
+
+    // the phases of this pass for goss_gpu_paths_timing: link, flag, gather, walk, compact
+    EventPair ev, ev_end;
+    auto mark = [&](int i) { HIP_TRY(hipEventRecord(i < 5 ? ev.e[i] : ev_end.e[0], c->stream)); };
+    auto phases = [&](int done) {
+        for (int i = 0; i < 5; ++i)
+        {
+            c->paths_ms[i] = 0.f;
+            if (i < done) HIP_TRY(hipEventElapsedTime(&c->paths_ms[i], ev.e[i], i < 4 ? ev.e[i + 1] : ev_end.e[0]));
+        }
+    };
+    for (float& x : c->paths_ms) x = 0.f;
+    mark(0);
+    HIP_TRY(hipMemsetAsync(zap, 0, zap_words * 4, c->stream));
+    *pinned_words(c) = kPathsNoEdge;
+    auto flag_starts = [&](const GraphLinks<K>& q) {
+        const dim3 few((uint32_t)std::min<uint64_t>(q.grid.x, kTipsGridBlocks));
+        mark(1);
+        if (forks) hipLaunchKernelGGL(paths_flag_kernel, few, q.block, 0, c->stream, (const uint8_t*)q.info, q.n, cand, d_rep);
+        else hipLaunchKernelGGL(tips_flag_kernel, few, q.block, 0, c->stream, (const uint32_t*)q.rcr, (const uint8_t*)q.info, q.n, cand, (TipsReport*)d_rep);
+        mark(2);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(PathsReport), hipMemcpyDeviceToHost, c->stream));
+    };
+    GraphLinks<K> l{};
+    try { l = link_graph<K>(c, who, (TipsReport*)d_rep, flag_starts); }
+    catch (...) { *missing = *pinned_words(c); throw; }     // (the edge link_graph refuses the graph for, where that is why)
+    const uint32_t n = l.n;
+    const dim3 block = l.block;
+    const uint64_t ncand = h->candidates;
+    o.candidates = ncand;
+    if (ncand == 0) { phases(2); return o; }
+
+    uint32_t* list = (uint32_t*)c->arena.temp(ncand * 4);
+    HIP_TRY(hipMemsetAsync(list, 0xFF, ncand * 4, c->stream));
+    const uint64_t words_per_block = (cand_words + kTipsGridBlocks - 1) / kTipsGridBlocks;
+    hipLaunchKernelGGL(tips_gather_kernel, dim3(grid_for(cand_words, (uint32_t)std::max<uint64_t>(words_per_block, 1))), block, 0, c->stream,
+                       (const uint64_t*)cand, cand_words, words_per_block, list, ncand, (TipsReport*)d_rep);
+    mark(3);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(paths_walk_kernel<Rule>), dim3(grid_for(ncand, kTB)), block, 0, c->stream, (const uint32_t*)list, ncand, n,
+                       c->k, (const uint32_t*)l.rcr, (const uint32_t*)l.nxt, (const uint8_t*)l.info, l.counts, zap, d_rep, rule);
+    mark(4);
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)ntiles), block, 0, c->stream, (const uint32_t*)zap, n64, tile_counts);
+    uint64_t* hm = pinned_words(c);
+    scan_with_total(c, tile_counts, ntiles, hm);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(PathsReport), hipMemcpyDeviceToHost, c->stream));
+    sync_checked(c);
+    o.hits = h->hits; o.edges = h->edges; o.too_long = h->too_long; o.why0 = h->why[0]; o.why1 = h->why[1];
+    const uint64_t m = hm[0];
+    o.after = m;
+    if (m != n64) replace_result<K>(c, l.keys, l.counts, n64, zap, tile_counts, ntiles, m);
+    mark(5);
+    sync_checked(c);
+    phases(5);
+    return o;
+}
+
+// trim-paths over the result (GossCmdTrimPaths.cc:78-248): a path of at most 2K edges from a node without incoming
+// edges goes, with the reverse complement of each of its edges.  GOSS_PATHS_CUTOFF spares a path that holds an edge
+// of multiplicity >= cutoff (what the reference's visitor was evidently meant to do and never does).
+template <class K>
+void trim_paths(goss_gpu_ctx* c, uint32_t flags, uint32_t cutoff, goss_gpu_paths_report* out)
+{
+    static_assert(sizeof(goss_gpu_paths_report) == 8 * 8 && sizeof(PathsReport) == 13 * 8, "paths report layout");
+    out->missing_rc = kPathsNoEdge;
+    const PathsOutcome o = paths_pass<K>(c, "trim_paths", false, TrimPaths{cutoff, (flags & GOSS_PATHS_CUTOFF) ? 1u : 0u}, &out->missing_rc);
+    goss_gpu_paths_report rep{};
+    rep.edges_before = o.before; rep.edges_after = o.after; rep.candidates = o.candidates;
+    rep.paths = o.hits; rep.zapped = o.edges; rep.too_long = o.too_long; rep.spared_by_cutoff = o.why0;
+    rep.missing_rc = kPathsNoEdge;                      // (an edge without its reverse complement refuses the call)
+    *out = rep;
+}
+
+// clip-links over the result (GossCmdClipLinks.cc:50-174): a path of at most 2K edges that leaves a fork as a minor
+// branch and enters a join as a minor branch goes, with the reverse complement of each of its edges.
+template <class K>
+void clip_links(goss_gpu_ctx* c, goss_gpu_links_report* out)
+{
+    static_assert(sizeof(goss_gpu_links_report) == 9 * 8, "links report layout");
+    out->missing_rc = kPathsNoEdge;
+    const PathsOutcome o = paths_pass<K>(c, "clip_links", true, ClipLinks{}, &out->missing_rc);
+    goss_gpu_links_report rep{};
+    rep.edges_before = o.before; rep.edges_after = o.after; rep.candidates = o.candidates;
+    rep.links = o.hits; rep.edges = o.edges; rep.too_long = o.too_long; rep.major_out = o.why0; rep.major_in = o.why1;
+    rep.missing_rc = kPathsNoEdge;
+    *out = rep;
+}
+
+// goss_gpu_trim_paths and goss_gpu_clip_links: the state checks of goss_gpu_prune_tips, one pass, and after a failure
+// a report that holds nothing but the edge the graph was refused for.
+template <class R, class F>
+int paths_entry(goss_gpu_ctx* c, R* out, const char* who, const char* not_a_graph, const char* out_of_place, F&& pass)
+{
+    std::memset(out, 0, sizeof *out);
+    out->missing_rc = GOSS_PATHS_NO_EDGE;
+    if (const int st = graph_pass_state(c, who, not_a_graph, out_of_place)) return st;
+    const int rc = guarded(c, [&]() {
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        pass();
+        t.stop();
+    });
+    if (rc != GOSS_OK)
+    {
+        const uint64_t missing = out->missing_rc;
+        std::memset(out, 0, sizeof *out);
+        out->missing_rc = missing;
+    }
+    return rc;
+}
+
 // ---- print-contigs --------------------------------------------------------------------------------------------------
 
 // Linear segments of the result (GossCmdPrintContigs.cc:49-193).  Temporaries under an ArenaScope; the table and the

@@ -1926,6 +1926,8 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  graph-to-kmer-set  generate a graph's k-mer set\n"
               << "  trim-graph       create a new graph by trimming low frequency edges\n"
               << "  prune-tips       create a new graph by removing low frequency tips\n"
+              << "  trim-paths       create a new graph by removing low frequency paths\n"
+              << "  clip-links       create a new graph by removing spurious links\n"
               << "  print-contigs    print all the non-branching paths in the given assembly graph\n"
               << "  build-entry-edge-set  build an entry edge set for a graph\n"
               << "  count-components  count connected components in the graph represented by the given reads\n"
@@ -1967,7 +1969,8 @@ int gossMain(int argc, char* argv[])
         const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
         const bool isContigs = cmdName == "print-contigs", isEntries = cmdName == "build-entry-edge-set";
         const bool isNear = cmdName == "compute-near-kmers";
-        if (isNear || isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
+        const bool isPaths = cmdName == "trim-paths", isLinks = cmdName == "clip-links";
+        if (isPaths || isLinks || isNear || isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
         {
             // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
             // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
@@ -1978,7 +1981,9 @@ int gossMain(int argc, char* argv[])
             // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378),
             // GossCmdFactoryTrimGraph::create (GossCmdTrimGraph.cc:130-172), GossCmdFactoryPruneTips::create
             // (GossCmdPruneTips.cc:347-373), GossCmdFactoryBuildEntryEdgeSet::create (GossCmdBuildEntryEdgeSet.cc:68-84),
-            // GossCmdFactoryComputeNearKmers::create (GossCmdComputeNearKmers.cc:230-243)
+            // GossCmdFactoryComputeNearKmers::create (GossCmdComputeNearKmers.cc:230-243),
+            // GossCmdFactoryTrimPaths::create (GossCmdTrimPaths.cc:251-279), GossCmdFactoryClipLinks::create
+            // (GossCmdClipLinks.cc:177-199)
             static const OptDef kTrimPrune[] = {
                 {"cutoff", "C", kU64, "coverage cutoff"},
                 {"estimate-only", "", kFlag, "only estimate the coverage cutoff (trim-graph)"},
@@ -2012,6 +2017,7 @@ int gossMain(int argc, char* argv[])
             for (auto& d : kGlobal) t.defs.push_back(d);
             for (auto& d : kMerge) t.defs.push_back(d);
             if (isTrim || isPrune) for (auto& d : kTrimPrune) t.defs.push_back(d);
+            if (isPaths) t.defs.push_back(kTrimPrune[0]);
             if (isContigs) for (auto& d : kContigs) t.defs.push_back(d);
             for (auto& d : kGpuSpecific) t.defs.push_back(d);
             Parsed opts; std::string bad;
@@ -2121,6 +2127,20 @@ int gossMain(int argc, char* argv[])
                     chk.optionalU64("iterate", iterations);
                 }
             }
+            else if (isPaths || isLinks)
+            {
+                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
+                else if (opts.strs("graph-in").size() != 1)
+                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
+                else ins = opts.strs("graph-in");
+                chk.mandatoryOut("graph-out", outName);
+                if (isPaths)
+                {
+                    chk.mandatoryU64("cutoff", cutoff, ~0ULL);
+                    uint64_t ignoredThreads = 4;            // (the walk is the device's)
+                    chk.optionalU64("num-threads", ignoredThreads);
+                }
+            }
             else if (isAnnotate)
             {
                 if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
@@ -2169,6 +2189,14 @@ int gossMain(int argc, char* argv[])
                 else if (isToKmerSet) { GossCmdGraphToKmerSet cmd(ins[0], outName); cmd(cxt); }
                 else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
                 else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
+                else if (isPaths)
+                {
+                    // numeric_cast<uint32_t>(c) (GossCmdTrimPaths.cc:270), thrown before the command exists
+                    if (cutoff > 0xFFFFFFFFULL) throw std::range_error("bad numeric conversion: positive overflow");
+                    GossCmdTrimPaths cmd(ins[0], outName, (uint32_t)cutoff);
+                    cmd(cxt);
+                }
+                else if (isLinks) { GossCmdClipLinks cmd(ins[0], outName); cmd(cxt); }
                 else if (isEntries) { GossCmdBuildEntryEdgeSet cmd(ins[0]); cmd(cxt); }
                 else if (isNear) { GossCmdComputeNearKmers cmd(ins[0], nearThreads); cmd(cxt); }
                 else if (isContigs)

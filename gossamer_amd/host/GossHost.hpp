@@ -303,6 +303,25 @@ private:
     const std::string mIn, mOut; const uint64_t mIterations;
 };
 
+// GossCmdTrimPaths (GossCmdTrimPaths.{hh,cc}): short paths that start at a node without incoming edges go.  pC is
+// parsed and, as in the reference, decides nothing.
+class GossCmdTrimPaths {
+public:
+    GossCmdTrimPaths(const std::string& pIn, const std::string& pOut, uint32_t pC) : mIn(pIn), mOut(pOut), mC(pC) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const uint32_t mC;
+};
+
+// GossCmdClipLinks (GossCmdClipLinks.{hh,cc}): short paths that leave a fork and enter a join as a minor branch go.
+class GossCmdClipLinks {
+public:
+    GossCmdClipLinks(const std::string& pIn, const std::string& pOut) : mIn(pIn), mOut(pOut) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut;
+};
+
 // GossCmdPrintContigs (GossCmdPrintContigs.{hh,cc}) in its linear-segments form: the non-branching paths of a graph
 // as FASTA (or, with pOmitSequence, as a table of their figures).  Supergraph contigs are not part of this build.
 class GossCmdPrintContigs {

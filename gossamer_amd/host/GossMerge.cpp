@@ -1161,6 +1161,58 @@ void GossCmdPruneTips::operator()(const GossCmdContext& pCxt)
     log(info, "total number of edges removed: " + num(zc));
 }
 
+// GossCmdTrimPaths::operator() (GossCmdTrimPaths.cc:175-248): the pass runs on the device (goss_gpu_trim_paths).  The
+// reference builds its output with the estimate g.count() - zapCount, where zapCount counts a path twice whose mirror
+// image is a start too; the same estimate is given here, so the files are the reference's byte for byte.  Where
+// zapCount exceeds the edge count the reference's difference wraps and its estimate is undefined: the exact number of
+// survivors is the estimate then, and a warning says so.
+void GossCmdTrimPaths::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    log(info, "locating low-coverage paths");
+    goss_gpu_paths_report rep;
+    (void)mC;                                           // (Vis::mOK never turns false: GossCmdTrimPaths.cc:29-43)
+    g.check(goss_gpu_trim_paths(g.h, 0, 0, &rep), "trimming paths");
+    log(info, "writing out graph.");
+    if (rep.zapped > rep.edges_before)
+    {
+        log(warning, "the reference's size estimate, " + num(rep.edges_before) + " - " + num(rep.zapped) + ", is negative; building with the exact number of edges, " + num(rep.edges_after));
+        g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+    }
+    else g.check(goss_gpu_emit_estimate(g.h, rep.edges_before - rep.zapped), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, "number of paths removed: " + num(rep.paths));
+    log(info, "number of edges removed: " + num(rep.zapped));
+    log(info, elapsed(t0));
+}
+
+// GossCmdClipLinks::operator() (GossCmdClipLinks.cc:87-174): the pass runs on the device (goss_gpu_clip_links).  The
+// reference never updates numZapped, so its builder gets the input's edge count as the estimate; so does this one.
+void GossCmdClipLinks::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    log(info, "loading graph");
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    log(info, "scanning for spurious links");
+    goss_gpu_links_report rep;
+    g.check(goss_gpu_clip_links(g.h, 0, &rep), "clipping links");
+    log(info, "removing spurious links");
+    g.check(goss_gpu_emit_estimate(g.h, rep.edges_before), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, "links removed: " + num(rep.links));
+    log(info, "edges removed: " + num(rep.edges));
+    log(info, elapsed(t0));
+}
+
 // GossCmdPrintContigs::operator() -> printLinearSegments (GossCmdPrintContigs.cc:49-193).  The device finds the
 // segments, their figures and the bodies (goss_gpu_segments_build); the header lines are formatted here, doubles
 // through the stream as the reference prints them.  The table is read 64 K segments at a time and the text in pieces

@@ -558,6 +558,54 @@ typedef struct {
 int goss_gpu_prune_tips(goss_gpu_ctx* ctx, uint32_t iterations, goss_gpu_tips_report* reports);
 
 /*
+ * Between finish and emit, graph mode: the two other per-path cleaners of the reference, each decided against
+ * the graph as it stands and applied afterwards, the reverse complement of every removed edge with it.  The
+ * walk is Graph::linearPath (Graph.tcc:19-46), followed for at most 2K + 1 edges over the link arrays of
+ * goss_gpu_prune_tips; state errors, refusals and what the context holds afterwards are as stated there.
+ *
+ * goss_gpu_trim_paths (GossCmdTrimPaths.cc:78-248): a start is every edge whose from-node has no incoming
+ * edge; its path of l edges goes iff l <= 2K.  The reference's mandatory cutoff decides nothing (its visitor
+ * never turns false) and `cutoff` is ignored likewise unless flags has GOSS_PATHS_CUTOFF, which spares a path
+ * that holds an edge of multiplicity >= cutoff (a path longer than 2K counts as too_long either way).
+ * `zapped` is the reference's zapCount, the sum of 2 l over the removed starts: it counts a path twice whose
+ * mirror image is a start as well (an isolated path, a path open at both ends, a path that holds its own
+ * reverse complement).  edges_before - edges_after is what really went.
+ *
+ * goss_gpu_clip_links (GossCmdClipLinks.cc:50-174): a start is every edge e whose from-node has two or more
+ * outgoing edges; its path, of l edges and last edge `last`, goes iff l <= 2K, c(e) / S_out < 1/3 and
+ * c(last) / S_in < 1/3, where S_out sums the multiplicities of the edges that leave from(e) and S_in of
+ * those that enter to(last).  Both sums are 32 bits wide and wrap as the reference's; the test is 3 c < S in
+ * 64 bits, a wrapped sum of 0 meaning "not minor" (the reference's double quotient is then inf or NaN).  A
+ * start that fails several tests is counted under the first it fails, in the order length (too_long), fork
+ * (major_out), join (major_in).  `links` counts starts and `edges` the sum of l (not 2 l), as the reference
+ * logs them: a link whose mirror image passes as well counts twice.
+ *
+ * missing_rc: GOSS_PATHS_NO_EDGE, or, where the call is refused with GOSS_ERR_INVALID_ARG for it, the index
+ * of the first edge whose reverse complement the graph lacks (the other fields are then zero).
+ */
+#define GOSS_PATHS_CUTOFF 1u
+#define GOSS_PATHS_NO_EDGE UINT64_MAX
+typedef struct {
+    uint64_t edges_before, edges_after;            /* distinct edges; before - after = really removed */
+    uint64_t candidates;                           /* edges with in(from) == 0 */
+    uint64_t paths, zapped;                        /* as the reference logs them: zapped = sum of 2 * path length */
+    uint64_t too_long, spared_by_cutoff;           /* why the other candidates stayed */
+    uint64_t missing_rc;
+} goss_gpu_paths_report;
+typedef struct {
+    uint64_t edges_before, edges_after;
+    uint64_t candidates;                           /* edges with out(from) >= 2 */
+    uint64_t links, edges;                         /* as the reference logs them: edges = sum of path length */
+    uint64_t too_long, major_out, major_in;        /* why the other candidates stayed: the first test failed */
+    uint64_t missing_rc;
+} goss_gpu_links_report;
+int goss_gpu_trim_paths(goss_gpu_ctx* ctx, uint32_t flags, uint32_t cutoff, goss_gpu_paths_report* out);
+int goss_gpu_clip_links(goss_gpu_ctx* ctx, uint32_t flags, goss_gpu_links_report* out);
+/* ms[5]: device time of the phases of the last of the two calls above that got past its state checks -- link,
+ * flag, gather, walk, compact -- in milliseconds; 0 for a phase it did not reach. */
+int goss_gpu_paths_timing(goss_gpu_ctx* ctx, float* ms);
+
+/*
  * Between finish and emit, graph mode: the linear segments of the graph the context holds, as
  * `goss print-contigs` prints them (printLinearSegments, GossCmdPrintContigs.cc:49-193; the walk is
  * Graph::linearPath, Graph.tcc:21-46).  An edge starts a path unless its from-node has exactly one

@@ -49,6 +49,10 @@ MATCH_SYMBOLS = ["goss_gpu_object_match_reads", "goss_gpu_object_match_reads_hos
 NEAR_SYMBOLS = ["goss_gpu_object_near_kmers", "goss_gpu_object_near_kmers_host"]
 CLASSIFY_SYMBOLS = ["goss_gpu_object_classify_reads", "goss_gpu_object_classify_bits_host", "goss_gpu_object_classify_reads_host"]
 
+# every symbol include/goss_gpu_elect.h declares (reads against up to 64 references: colour words on a KmerSet)
+ELECT_SYMBOLS = ["goss_gpu_object_colours_host", "goss_gpu_object_colours_from_index", "goss_gpu_object_colour_reads",
+                 "goss_gpu_object_colour_reads_host"]
+
 # every symbol include/goss_gpu_taxo.h declares (annotate-kmers and classify-reads on an object)
 TAXO_SYMBOLS = ["goss_gpu_object_taxo_tree_host", "goss_gpu_object_taxo_annotation_host", "goss_gpu_object_taxo_annotation_read",
                 "goss_gpu_object_taxo_annotate", "goss_gpu_object_taxo_annotate_host", "goss_gpu_object_taxo_classify_reads",
@@ -1038,6 +1042,8 @@ QUERY_NORMALIZE, QUERY_INCOMING = 1, 2
 MATCH_NORMALIZE, MATCH_ANY = 1, 4
 NEAR_WHOLE_BASES, NEAR_NORMALIZE = 1, 2          # Object.near_kmers: the two departures from the reference's loop
 CLASSIFY_NORMALIZE = 1                           # Object.classify_reads: look up each window's canonical form
+ELECT_NORMALIZE = 1                              # Object.colour_reads: look up each window's canonical form
+ELECT_MAX_COLOURS = 64                           # Object.colours: the references a colour word can speak of
 TAXO_NORMALIZE = 1                               # Object.taxo_annotate / taxo_classify_reads: canonical windows
 TAXO_NONE, TAXO_MANY = 0xFFFFFFFF, 0xFFFFFFFE    # Object.taxo_classify_reads: no class / classes on more than one path
 ERR_BUFFER = -9
@@ -1091,6 +1097,41 @@ class ClassifyInfo(C.Structure):
 
     def as_dict(self):
         return {"reads": self.reads, "windows": self.windows, "counts": list(self.counts), "ms": self.ms}
+
+
+class ElectInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("windows", C.c_uint64), ("by_count", C.c_uint64 * 65), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {"reads": self.reads, "windows": self.windows, "by_count": list(self.by_count), "ms": self.ms}
+
+
+def elect(colours, windows, threshold, pairs=False, numeric_second_mate=True):
+    """The decision of `electus classify` (KmerFilter, ElectApp.cc:406-451) over what Object.colour_reads gave: a list of
+    bools, one per read, or with pairs=True one per pair, the mates being reads 2i and 2i + 1.  A single read matches
+    when it has a window and its word has at least `threshold` bits.  A pair matches when the first mate does, or when
+    the second mate has a window and the OR of both words reaches the threshold -- as a number, which is what the
+    reference compares (ElectApp.cc:443); numeric_second_mate=False counts that word's bits instead."""
+    import numpy as np
+    def ints(a):                                 # numpy, a torch tensor (int64 with the same bits) or a plain sequence
+        a = a.cpu().numpy() if hasattr(a, "cpu") else a
+        return [int(x) & 0xFFFFFFFFFFFFFFFF for x in (np.asarray(a).reshape(-1).tolist() if hasattr(a, "dtype") else a)]
+    c, w = ints(colours), [x & 0xFFFFFFFF for x in ints(windows)]
+    if len(c) != len(w):
+        raise ValueError("colours and windows differ in length")
+    t = int(threshold)
+
+    def bits(x):
+        return bin(x).count("1")
+    if not pairs:
+        return [wi >= 1 and bits(ci) >= t for ci, wi in zip(c, w)]
+    if len(c) % 2:
+        raise ValueError("pairs need an even number of reads")
+    out = []
+    for i in range(0, len(c), 2):
+        both = c[i] | c[i + 1]
+        out.append((w[i] >= 1 and bits(c[i]) >= t) or (w[i + 1] >= 1 and (both if numeric_second_mate else bits(both)) >= t))
+    return out
 
 
 class TaxoInfo(C.Structure):
@@ -1193,6 +1234,10 @@ def _declare_object(L):
     L.goss_gpu_object_classify_reads.argtypes = [P, P, U64, P, P, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
     L.goss_gpu_object_classify_bits_host.argtypes = [P, P, P]
     L.goss_gpu_object_classify_reads_host.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(ClassifyInfo)]
+    L.goss_gpu_object_colours_host.argtypes = [P, P, C.c_uint32]
+    L.goss_gpu_object_colours_from_index.argtypes = [P, P, C.POINTER(C.c_uint32)]
+    L.goss_gpu_object_colour_reads.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(ElectInfo)]
+    L.goss_gpu_object_colour_reads_host.argtypes = [P, P, U64, C.c_uint32, U64, P, P, P, C.POINTER(ElectInfo)]
     U32 = C.c_uint32
     L.goss_gpu_object_taxo_tree_host.argtypes = [P, U32, P, P]
     L.goss_gpu_object_taxo_annotation_host.argtypes = [P, P]
@@ -1503,6 +1548,51 @@ class Object:
         self._check(rc)
         r = info.reads
         out = [self._back(c[:r], staged, np.uint32), self._back(w[:r], staged, np.uint32)]
+        if starts:
+            out.append(self._back(s[:r + 1], staged, np.uint64))
+        return tuple(out) + (info.as_dict(),)
+
+    # -- up to 64 references in one pass (goss_gpu_object_colour*) --
+    def colours(self, array, ncolours):
+        """Keeps one colour word per k-mer of a KmerSet on the device for later colour_reads calls
+        (goss_gpu_object_colours_host): bit i of array[r] says that reference i holds the k-mer at rank r.  array: count
+        uint64 values; ncolours: 1 .. 64, and no word may have a bit at or above it.  A second call replaces the words."""
+        import numpy as np
+        a = np.ascontiguousarray(array, dtype=np.uint64).reshape(-1)
+        if a.size != self.count:
+            raise ValueError("the colours must hold %d words" % self.count)
+        self._check(self._L.goss_gpu_object_colours_host(self._h, a.ctypes.data if a.size else None, ncolours))
+
+    def colours_from_index(self, index_obj):
+        """The colour words made on the device from a pool's index (goss_gpu_object_colours_from_index): self is the
+        KmerSet opened from <out>-union, index_obj the OBJECT_SPARSE_ARRAY opened from <out>-index.  Returns S, the number
+        of samples the index speaks of."""
+        s = C.c_uint32(0)
+        self._check(self._L.goss_gpu_object_colours_from_index(self._h, getattr(index_obj, "_h", None), C.byref(s)))
+        return s.value
+
+    def colour_reads(self, bases, normalize=True, starts=False, max_reads=None):
+        """(colours, windows[, starts], info) per read of `bases` (reads separated by '\\n'): goss_gpu_object_colour_reads.
+        colours[r]: the OR of the kept colour words over the windows of read r that are in the set (uint64; torch: int64
+        with the same bits); windows[r]: its valid K-windows.  bases and what comes back: as match_reads.  info: reads,
+        windows, by_count (reads per number of bits in their word, a list of 65) and ms."""
+        import numpy as np
+        import torch
+        t, staged = self._bases(bases)
+        n = t.numel()
+        info = ElectInfo()
+        if max_reads is None:
+            max_reads = self._count_reads(t)
+        c = self._out(t, max_reads, torch.int64)
+        w = self._out(t, max_reads, torch.int32)
+        s = self._out(t, max_reads + 1, torch.int64) if starts else None
+        rc = self._L.goss_gpu_object_colour_reads(self._h, t.data_ptr() if n else None, n, ELECT_NORMALIZE if normalize else 0, max_reads,
+                                                  c.data_ptr(), w.data_ptr(), s.data_ptr() if starts else None, C.byref(info))
+        if rc == ERR_BUFFER:
+            raise GossGpuError(rc, self._L.goss_gpu_strerror(rc).decode(), "needs max_reads = %d" % info.reads)
+        self._check(rc)
+        r = info.reads
+        out = [self._back(c[:r], staged, np.uint64), self._back(w[:r], staged, np.uint32)]
         if starts:
             out.append(self._back(s[:r + 1], staged, np.uint64))
         return tuple(out) + (info.as_dict(),)

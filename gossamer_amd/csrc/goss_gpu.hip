@@ -3856,8 +3856,9 @@ int goss_gpu_object_near_kmers_host(goss_gpu_object* o, const uint64_t* lhs, con
 }  // extern "C"
 
 // ============================================================================================
-// Reads against an object (goss_gpu_object_match_reads, _classify_reads, _taxo_*): the pass, the staged batch, the
-// classify bitmaps and the taxonomy are reads_path.hpp; what follows checks the arguments and calls it
+// Reads against an object (goss_gpu_object_match_reads, _classify_reads, _taxo_*, _colour_reads): the pass, the staged
+// batch, the classify bitmaps, the taxonomy and the colour words are reads_path.hpp; what follows checks the arguments
+// and calls it
 // ============================================================================================
 
 #include "reads_path.hpp"
@@ -3931,6 +3932,61 @@ int goss_gpu_object_classify_reads_host(goss_gpu_object* o, const void* bases, u
     return reads_staged(o, bases, nbytes, max_reads, windows, classes, read_starts, nullptr, info, [&](const StagedBatch& s, goss_gpu_classify_info* mine) {
         return goss_gpu_object_classify_reads(o, s.bases, nbytes, nullptr, nullptr, flags, max_reads, s.b, s.a, s.starts, mine);
     });
+}
+
+int goss_gpu_object_colours_host(goss_gpu_object* o, const uint64_t* colours, uint32_t ncolours)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "colours needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (ncolours < 1 || ncolours > GOSS_ELECT_MAX_COLOURS) { o->last_error = "colours: ncolours must be 1 .. 64"; return GOSS_ERR_INVALID_ARG; }
+    if (o->q.s.count && !colours) { o->last_error = "colours: the pointer is NULL"; return GOSS_ERR_INVALID_ARG; }
+    return obj_guarded(o->device, o->last_error, [&]() { colours_keep_host(o, colours, ncolours); });
+}
+
+int goss_gpu_object_colours_from_index(goss_gpu_object* o, goss_gpu_object* index, uint32_t* ncolours_out)
+{
+    if (!o) return GOSS_ERR_INVALID_ARG;
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "colours_from_index needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (!index || index->kind != GOSS_OBJECT_SPARSE_ARRAY) { o->last_error = "colours_from_index: the index must be a SparseArray"; return GOSS_ERR_INVALID_ARG; }
+    if (index->device != o->device) { o->last_error = "colours_from_index: the index lies on another device"; return GOSS_ERR_INVALID_ARG; }
+    return obj_guarded(o->device, o->last_error, [&]() {
+        const uint32_t S = colours_keep_index(o, index);
+        if (ncolours_out) *ncolours_out = S;
+    });
+}
+
+int goss_gpu_object_colour_reads(goss_gpu_object* o, const void* d_bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                 uint64_t* d_colours, uint32_t* d_windows, uint64_t* d_read_starts, goss_gpu_elect_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)GOSS_ELECT_NORMALIZE) { o->last_error = "colour_reads: unknown flag bits"; return GOSS_ERR_INVALID_ARG; }
+    if (o->kind != GOSS_OBJECT_KMER_SET) { o->last_error = "colour_reads needs a KmerSet"; return GOSS_ERR_INVALID_ARG; }
+    if (o->q.s.count && !o->colours_kept)
+    {
+        o->last_error = "colour_reads: no colours kept (goss_gpu_object_colours_host, goss_gpu_object_colours_from_index)";
+        return GOSS_ERR_INVALID_ARG;
+    }
+    MatchAux aux;
+    aux.colours = o->colours;
+    ReadsPass res;
+    const int rc = reads_pass(o, ReadsJob{"colour_reads", kModeColour, d_bases, nbytes, flags, max_reads, d_windows, reinterpret_cast<uint32_t*>(d_colours),
+                                          d_read_starts, false, aux}, &res);
+    return pass_report(rc, res, info, [&](goss_gpu_elect_info& i) {
+        i.windows = res.sums[0];
+        for (int k = 0; k < 65; ++k) i.by_count[k] = res.by_count[k];
+    });
+}
+
+int goss_gpu_object_colour_reads_host(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint32_t flags, uint64_t max_reads,
+                                      uint64_t* colours, uint32_t* windows, uint64_t* read_starts, goss_gpu_elect_info* info)
+{
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!o || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
+    return reads_staged(o, bases, nbytes, max_reads, windows, reinterpret_cast<uint32_t*>(colours), read_starts, nullptr, info,
+                        [&](const StagedBatch& s, goss_gpu_elect_info* mine) {
+                            return goss_gpu_object_colour_reads(o, s.bases, nbytes, flags, max_reads, reinterpret_cast<uint64_t*>(s.b), s.a, s.starts, mine);
+                        }, 8);
 }
 
 int goss_gpu_object_taxo_tree_host(goss_gpu_object* o, uint32_t n, const uint32_t* ids, const uint32_t* parent_index)

@@ -26,6 +26,7 @@
 #include "kernels_entries.hpp"
 #include "kernels_taxo.hpp"
 #include "kernels_match.hpp"
+#include "kernels_elect.hpp"
 #include "kernels_components.hpp"
 #include "kernels_subgraph.hpp"
 #include "kernels_near.hpp"

@@ -36,6 +36,14 @@
 // compare-and-swap join by one lane; otherwise the hit lanes join one by one -- and after the tile one global join per
 // read and tile.  Both joins are order-free, so the arrays do not depend on the scheduling.
 //
+// Colour mode (goss_gpu_object_colour_reads) is the classify mode's walk with one 8-byte load per hit, aux.colours[r],
+// and a 64-bit word per read: s_hit holds 64-bit words in this instantiation only (MatchHitWord).  The OR over a lane
+// interval takes the taxon mode's shape: consecutive windows of a read usually bring the same word, so one ballot asks
+// whether any hit lane differs from the first hit lane of its interval; if none does, that lane ORs its word into LDS.
+// Otherwise an inclusive OR scan runs up the lanes in six shuffle steps on both halves, a step taken only from a lane
+// of the same interval, and the interval's last lane ORs what it holds.  After the tile one global 64-bit atomicOr per
+// read and tile with a non-zero word.  hits[] is then an array of 64-bit words.
+//
 // A walk that cannot answer (damaged image) leaves the lowest such byte position in bad[0]; a read whose window
 // count reaches 2^32 - 1 leaves its index in bad[1].
 #pragma once
@@ -53,14 +61,20 @@
 namespace goss {
 
 enum : uint32_t { kMatchNormalize = 1, kMatchAny = 4 };
-// what hits[] receives: a sum, 1 / 0, a 4-bit mask, a sum (and ann[] the lca), the join of the classes
-enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2, kModeAnnotate = 3, kModeTaxon = 4 };
+// what hits[] receives: a sum, 1 / 0, a 4-bit mask, a sum (and ann[] the lca), the join of the classes, a 64-bit word
+enum : int { kModeCount = 0, kModeAny = 1, kModeClassify = 2, kModeAnnotate = 3, kModeTaxon = 4, kModeColour = 5 };
 
-// what only some modes read: kModeClassify the two bitmaps (bit r = rank r), kModeAnnotate / kModeTaxon the taxonomy
+// a read's accumulator in LDS: 32 bits but for the colour mode's word
+template <int MODE> struct MatchHitWord { typedef uint32_t type; };
+template <> struct MatchHitWord<kModeColour> { typedef unsigned long long type; };
+
+// what only some modes read: kModeClassify the two bitmaps (bit r = rank r), kModeAnnotate / kModeTaxon the taxonomy,
+// kModeColour the word per rank
 struct MatchAux {
     const uint64_t* lhs = nullptr;
     const uint64_t* rhs = nullptr;
     TaxoView tx;
+    const uint64_t* colours = nullptr;
 };
 
 // tiles[t] = number of '\n' in tile t; one wave per tile
@@ -83,7 +97,7 @@ __global__ __launch_bounds__(256) void match_count_newlines_kernel(const uint8_t
     if (lane_id() == 0) tiles[t] = n;
 }
 
-// out[0..2] += sums over the reads: windows, hits, reads with a hit; starts[reads] = end
+// out[0..2] += sums over the reads: windows, hits, reads with a hit (hits NULL: the windows only); starts[reads] = end
 __global__ __launch_bounds__(256) void match_sums_kernel(const uint32_t* __restrict__ windows, const uint32_t* __restrict__ hits, uint64_t reads,
                                                          unsigned long long* __restrict__ out, uint64_t* __restrict__ starts, uint64_t end)
 {
@@ -91,8 +105,9 @@ __global__ __launch_bounds__(256) void match_sums_kernel(const uint32_t* __restr
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < reads; i += (uint64_t)gridDim.x * blockDim.x)
     {
         w += windows[i];
-        h += hits[i];
-        m += hits[i] ? 1 : 0;
+        const uint32_t x = hits ? hits[i] : 0;
+        h += x;
+        m += x ? 1 : 0;
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1)
@@ -133,11 +148,14 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
     const uint64_t* __restrict__ rhs = aux.rhs;
     const TaxoView& tx = aux.tx;
     constexpr bool ANY = MODE == kModeAny, CLS = MODE == kModeClassify, ANN = MODE == kModeAnnotate, TAX = MODE == kModeTaxon;
+    constexpr bool COL = MODE == kModeColour;
+    typedef typename MatchHitWord<MODE>::type HitWord;
     __shared__ uint64_t s_codes[kMatchGroups / 4];       // 32 bases per word, first base lowest
     __shared__ uint64_t s_inv[kMatchGroups / 8];         // bit = not one of ACGTacgt (or beyond the input)
     __shared__ uint64_t s_nl[kMatchRuns];                // bit = '\n'
     __shared__ uint32_t s_pre[kMatchRuns + 1];           // newlines before each run; [kMatchRuns] = in the tile
-    __shared__ uint32_t s_win[kMatchTile + 1], s_hit[kMatchTile + 1];      // per read that touches the tile
+    __shared__ uint32_t s_win[kMatchTile + 1];           // per read that touches the tile
+    __shared__ HitWord s_hit[kMatchTile + 1];
     __shared__ uint32_t s_prev_nl;                       // the byte before the tile is '\n'
 
     const uint64_t tile = unit_block();
@@ -194,6 +212,7 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
         bool done = ANY && __atomic_load_n(&s_hit[local], __ATOMIC_RELAXED) != 0;
         uint64_t hb = 0;
         uint32_t cls = 0;                                // CLS, TAX: the class of this lane's hit
+        unsigned long long cw = 0;                       // COL: the word of this lane's hit
 #pragma unroll
         for (uint32_t ph = 0; ph < (ANY ? 2u : 1u); ++ph)
         {
@@ -210,6 +229,11 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
                 {
                     if (r >= o.s.count) { q_fail(bad, p, kQBadWalk); hit = false; }      // (the bitmaps end at count)
                     else cls = (uint32_t)((lhs[r >> 6] >> (r & 63)) & 1) << 1 | (uint32_t)((rhs[r >> 6] >> (r & 63)) & 1);
+                }
+                if (COL && hit)
+                {
+                    if (r >= o.s.count) { q_fail(bad, p, kQBadWalk); hit = false; }      // (colours[] ends at count)
+                    else cw = aux.colours[r];
                 }
                 if ((ANN || TAX) && hit)
                 {
@@ -231,7 +255,34 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
             for (uint32_t j = 0; j < 4; ++j)
                 if (__ballot(hit && cls == j) & seg) mask |= 1u << j;
         }
-        if (TAX && hb)
+        if constexpr (COL)
+        {
+            if (hb)
+            {
+                // every lane learns the word of the first hit lane of its read; a wave none of whose hit lanes differs
+                // from that sends one word per read
+                const uint64_t mine = hb & seg;
+                const uint32_t lead = mine ? (uint32_t)__ffsll((long long)mine) - 1u : lane;
+                const unsigned long long c0 = __shfl(cw, (int)lead, 64);
+                if (!__ballot(((hb >> lane) & 1) && cw != c0))
+                {
+                    if (lane == lead && mine && c0) atomicOr(&s_hit[local], c0);
+                }
+                else
+                {
+                    // an inclusive OR scan up the lanes, cut at each read's first lane (a lane without a hit holds 0)
+                    unsigned long long v = cw;
+#pragma unroll
+                    for (uint32_t d = 1; d < 64; d <<= 1)
+                    {
+                        const unsigned long long u = __shfl_up(v, d, 64);
+                        if (lane >= first + d) v |= u;
+                    }
+                    if (lane == last && v) atomicOr(&s_hit[local], v);
+                }
+            }
+        }
+        if constexpr (TAX) if (hb)
         {
             const bool hit = (hb >> lane) & 1;
             unann += (uint32_t)__popcll(__ballot(hit && cls == 0));
@@ -251,8 +302,8 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
         {
             const uint32_t nw = (uint32_t)__popcll(vb & seg), nh = (uint32_t)__popcll(hb & seg);
             if (nw) atomicAdd(&s_win[local], nw);
-            if (CLS) { if (mask) atomicOr(&s_hit[local], mask); }
-            else if (!TAX && nh) atomicAdd(&s_hit[local], nh);
+            if constexpr (CLS) { if (mask) atomicOr(&s_hit[local], mask); }
+            else if constexpr (!TAX && !COL) { if (nh) atomicAdd(&s_hit[local], nh); }
         }
     }
     __syncthreads();
@@ -260,7 +311,8 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
 
     for (uint32_t i = threadIdx.x; i < nloc; i += kTB)
     {
-        const uint32_t nw = s_win[i], nh = s_hit[i];
+        const uint32_t nw = s_win[i];
+        const HitWord nh = s_hit[i];
         if (nw)
         {
             const uint32_t old = atomicAdd(&windows[read0 + i], nw);
@@ -268,9 +320,10 @@ __global__ __launch_bounds__(256) void match_reads_kernel(QueryObj o, const uint
         }
         if (nh)
         {
-            if (ANY) atomicOr(&hits[read0 + i], 1u);
-            else if (CLS) atomicOr(&hits[read0 + i], nh);
-            else if (TAX) taxo_combine_into(&hits[read0 + i], tx.last, nh);
+            if constexpr (ANY) atomicOr(&hits[read0 + i], 1u);
+            else if constexpr (CLS) atomicOr(&hits[read0 + i], nh);
+            else if constexpr (TAX) taxo_combine_into(&hits[read0 + i], tx.last, nh);
+            else if constexpr (COL) atomicOr(reinterpret_cast<unsigned long long*>(hits) + read0 + i, nh);
             else atomicAdd(&hits[read0 + i], nh);
         }
     }

@@ -64,6 +64,11 @@ struct goss_gpu_object {
     uint32_t* taxo_ann = nullptr;
     bool taxo_ann_kept = false;
     DevBuf taxo_scratch;                    // ids on their way to classes and back
+    // goss_gpu_object_colours_host / _from_index: the kept word per rank, how many references it speaks of (new words
+    // are filled in an allocation of their own, which replaces this one only once they are complete)
+    uint64_t* colours = nullptr;
+    uint32_t ncolours = 0;
+    bool colours_kept = false;
 
     // (object_free has set the device and waited for the stream; the buffers above go after this body)
     ~goss_gpu_object()
@@ -74,6 +79,7 @@ struct goss_gpu_object {
         if (classify_bits) (void)hipFree(classify_bits);
         if (taxo_tree) (void)hipFree(taxo_tree);
         if (taxo_ann) (void)hipFree(taxo_ann);
+        if (colours) (void)hipFree(colours);
         for (hipEvent_t e : pass_ev) if (e) (void)hipEventDestroy(e);
     }
 };

@@ -1,6 +1,6 @@
-// reads_path.hpp -- reads against an object (goss_gpu_object_match_reads, _classify_reads, _taxo_*): one pass over the
-// reads whatever it is asked for (kernels_match.hpp), the batch the _host forms stage, the classify bitmaps, and a
-// taxonomy over a KmerSet's k-mers (kernels_taxo.hpp).
+// reads_path.hpp -- reads against an object (goss_gpu_object_match_reads, _classify_reads, _taxo_*, _colour_reads): one
+// pass over the reads whatever it is asked for (kernels_match.hpp), the batch the _host forms stage, the classify
+// bitmaps, a taxonomy over a KmerSet's k-mers (kernels_taxo.hpp), and the colour words (kernels_elect.hpp).
 // Part of goss_gpu.hip, which includes it at file scope behind the objects' query entry points and keeps the entry
 // points of everything here.
 
@@ -94,17 +94,18 @@ void taxo_bins_out(goss_gpu_object* o, uint64_t* counts)
 // what a pass is asked to do
 struct ReadsJob {
     const char* what;                       // names the call in messages
-    int mode;                               // kModeCount / kModeAny / kModeClassify / kModeAnnotate / kModeTaxon (kernels_match.hpp)
+    int mode;                               // kModeCount / kModeAny / kModeClassify / kModeAnnotate / kModeTaxon / kModeColour (kernels_match.hpp)
     const void* d_bases;
     uint64_t nbytes;
     uint32_t flags;
     uint64_t max_reads;                     // what each per-read array holds
     uint32_t* d_windows;                    // per read, on the device; each may be NULL
-    uint32_t* d_hits;                       // by mode: hits, 1 / 0, the 4-bit mask, (annotate: unused), the node id
+    uint32_t* d_hits;                       // by mode: hits, 1 / 0, the 4-bit mask, (annotate: unused), the node id;
+                                            // kModeColour: 8 bytes per read, the word
     uint64_t* d_read_starts;                // reads + 1 values
     bool must_fit = false;                  // more reads than max_reads are refused even where no array is given (annotate:
                                             // aux.tx.read_class holds max_reads classes)
-    MatchAux aux{};                         // kModeClassify: the bitmaps; kModeAnnotate / kModeTaxon: the taxonomy
+    MatchAux aux{};                         // kModeClassify: the bitmaps; kModeAnnotate / kModeTaxon: the taxonomy; kModeColour: the words
 };
 
 // what one pass over the reads leaves on the host
@@ -112,6 +113,7 @@ struct ReadsPass {
     uint64_t reads = 0;
     unsigned long long sums[4] = {0, 0, 0, 0};  // windows, hits, reads with a hit; kModeTaxon: hits at a rank without a class
     unsigned long long counts[16] = {};         // kModeClassify: reads per mask; kModeTaxon: [0] reads without a class, [1] with many
+    unsigned long long by_count[65] = {};       // kModeColour: reads per number of bits in their word
     float ms = 0;
 };
 
@@ -134,15 +136,18 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
         const uint8_t* bases = (const uint8_t*)job.d_bases;
         const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
         // working memory: [0, 256) sums[4], bad[2] at word 4, the classes' counts[16] at word 8; then the tiles' newline
-        // counts (+ 1: the total) and the scan's partial sums
+        // counts (+ 1: the total) and the scan's partial sums, then the colour mode's by_count[65]
         const uint64_t npartial = 2 * ((ntiles + 1 + kScanChunk - 1) / kScanChunk) + 64;
-        uint8_t* mem = o->scan_sums.room(256 + (ntiles + 1 + npartial) * 8);
+        const bool colour = job.mode == kModeColour;
+        const uint64_t hit_bytes = colour ? 8 : 4;
+        uint8_t* mem = o->scan_sums.room(256 + (ntiles + 1 + npartial + 65) * 8);
         unsigned long long* sums = (unsigned long long*)mem;
         unsigned long long* bad = sums + 4;
         unsigned long long* counts = sums + 8;
         uint64_t* tiles = (uint64_t*)(mem + 256);
         uint64_t* partial = tiles + ntiles + 1;
-        if (!o->h_pass) HIP_TRY(hipHostMalloc((void**)&o->h_pass, 256, hipHostMallocDefault));
+        unsigned long long* by_count = (unsigned long long*)(partial + npartial);
+        if (!o->h_pass) HIP_TRY(hipHostMalloc((void**)&o->h_pass, 1024, hipHostMallocDefault));      // (words 32 .. 96: by_count)
         for (hipEvent_t& e : o->pass_ev) if (!e) HIP_TRY(hipEventCreate(&e));
         const uint32_t aligned = ((uintptr_t)bases & 7u) == 0;
 
@@ -170,15 +175,16 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
         if (!w || !h)
         {
             const uint64_t each = (reads * 4 + 255) & ~255ULL;
-            uint8_t* tmp = o->spare_out.room(2 * each + 256);
+            uint8_t* tmp = o->spare_out.room(3 * each + 256);
             if (!w) w = (uint32_t*)tmp;
             if (!h) h = (uint32_t*)(tmp + each);
         }
         if (reads)
         {
             HIP_TRY(hipMemsetAsync(w, 0, reads * 4, o->stream));
-            HIP_TRY(hipMemsetAsync(h, 0, reads * 4, o->stream));
+            HIP_TRY(hipMemsetAsync(h, 0, reads * hit_bytes, o->stream));
         }
+        if (colour) HIP_TRY(hipMemsetAsync(by_count, 0, 65 * 8, o->stream));
         HIP_TRY(hipEventRecord(o->pass_ev[2], o->stream));
         MatchAux aux = job.aux;
         aux.tx.unann = sums + 3;
@@ -194,6 +200,7 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
             case kModeClassify: return launch(match_reads_kernel<K, kModeClassify>);
             case kModeAnnotate: return launch(match_reads_kernel<K, kModeAnnotate>);
             case kModeTaxon: return launch(match_reads_kernel<K, kModeTaxon>);
+            case kModeColour: return launch(match_reads_kernel<K, kModeColour>);
             default: return launch(match_reads_kernel<K, kModeCount>);
             }
         };
@@ -203,8 +210,12 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
         if (job.mode == kModeClassify && reads)
             hipLaunchKernelGGL(classify_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256, 2048)), dim3(kTB), 0, o->stream,
                                (const uint32_t*)h, reads, counts);
+        if (colour && reads)
+            hipLaunchKernelGGL(elect_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256, 2048)), dim3(kTB), 0, o->stream,
+                               (const uint64_t*)h, reads, by_count);
+        // (the colour mode's words are no sums: its hit sums stay 0)
         hipLaunchKernelGGL(match_sums_kernel, dim3((uint32_t)std::min<uint64_t>((reads + 255) / 256 + 1, 2048)), dim3(kTB), 0, o->stream,
-                           (const uint32_t*)w, (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
+                           (const uint32_t*)w, colour ? (const uint32_t*)nullptr : (const uint32_t*)h, reads, sums, d_read_starts, nbytes - (open_end ? 0 : 1));
         if (job.mode == kModeTaxon && reads)
         {
             // the figures from the classes, then the classes become node ids where they lie
@@ -214,6 +225,7 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
         }
         HIP_TRY(hipEventRecord(o->pass_ev[3], o->stream));
         HIP_TRY(hipMemcpyAsync(o->h_pass, mem, 192, hipMemcpyDeviceToHost, o->stream));
+        if (colour) HIP_TRY(hipMemcpyAsync(o->h_pass + 32, by_count, 65 * 8, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
         check_launch((what + ": matching").c_str());
         if (o->h_pass[4] != ~0ULL)
@@ -225,6 +237,7 @@ int reads_pass(goss_gpu_object* o, const ReadsJob& job, ReadsPass* res)
         HIP_TRY(hipEventElapsedTime(&b, o->pass_ev[2], o->pass_ev[3]));
         for (int i = 0; i < 4; ++i) res->sums[i] = o->h_pass[i];
         for (int i = 0; i < 16; ++i) res->counts[i] = o->h_pass[8 + i];
+        if (colour) for (int i = 0; i < 65; ++i) res->by_count[i] = o->h_pass[32 + i];
         res->ms = a + b;
     });
 }
@@ -256,10 +269,11 @@ struct StagedBatch {
 
 // The host forms: the batch goes to the device, and with it `extra`, max_reads values where the caller has some;
 // `device_form(batch, &mine)` answers it there, its info is passed on, and 4 bytes per read and array come back (a:
-// windows, b: hits / classes).  No bytes: the device form on no batch.  The only place that lays the staged buffer out.
+// windows, b: hits / classes; b_bytes = 8: b holds 64-bit words, the colour mode's).  No bytes: the device form on no
+// batch.  The only place that lays the staged buffer out.
 template <class Info, class Call>
 int reads_staged(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint64_t max_reads, uint32_t* a, uint32_t* b, uint64_t* read_starts,
-                 const uint32_t* extra, Info* info, Call device_form)
+                 const uint32_t* extra, Info* info, Call device_form, uint64_t b_bytes = 4)
 {
     StagedBatch s;
     if (nbytes == 0)
@@ -268,12 +282,12 @@ int reads_staged(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint64_
         return device_form(s, info);
     }
     int rc = obj_guarded(o->device, o->last_error, [&]() {
-        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL, narrays = extra ? 3 : 2;
+        const uint64_t b0 = (nbytes + 255) & ~255ULL, each = (max_reads * 4 + 255) & ~255ULL, narrays = (extra ? 3 : 2) + (b_bytes == 8 ? 1 : 0);
         uint8_t* mem = o->staged.room(b0 + narrays * each + (max_reads + 1) * 8);
         s.bases = mem;
         if (a) s.a = (uint32_t*)(mem + b0);
         if (b) s.b = (uint32_t*)(mem + b0 + each);
-        if (extra) s.extra = (uint32_t*)(mem + b0 + 2 * each);
+        if (extra) s.extra = (uint32_t*)(mem + b0 + (narrays - 1) * each);
         if (read_starts) s.starts = (uint64_t*)(mem + b0 + narrays * each);
         HIP_TRY(hipMemcpyAsync(mem, bases, nbytes, hipMemcpyHostToDevice, o->stream));
         if (extra && max_reads) HIP_TRY(hipMemcpyAsync(s.extra, extra, max_reads * 4, hipMemcpyHostToDevice, o->stream));
@@ -286,7 +300,7 @@ int reads_staged(goss_gpu_object* o, const void* bases, uint64_t nbytes, uint64_
     const uint64_t reads = mine.reads;
     return obj_guarded(o->device, o->last_error, [&]() {
         if (a && reads) HIP_TRY(hipMemcpyAsync(a, s.a, reads * 4, hipMemcpyDeviceToHost, o->stream));
-        if (b && reads) HIP_TRY(hipMemcpyAsync(b, s.b, reads * 4, hipMemcpyDeviceToHost, o->stream));
+        if (b && reads) HIP_TRY(hipMemcpyAsync(b, s.b, reads * b_bytes, hipMemcpyDeviceToHost, o->stream));
         if (read_starts) HIP_TRY(hipMemcpyAsync(read_starts, s.starts, (reads + 1) * 8, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
     });
@@ -330,6 +344,70 @@ void classify_keep_bits(goss_gpu_object* o, const uint64_t* lhs, const uint64_t*
         HIP_TRY(hipStreamSynchronize(o->stream));
     }
     o->classify_kept = true;
+}
+
+// ---- the colour words -------------------------------------------------------------------------------------------------------
+
+// count words on the device, not yet the object's: freed unless adopt() makes them the kept ones, so a call that
+// fails on the way leaves the old words, and the object never holds a second copy
+struct FreshColours {
+    goss_gpu_object* o;
+    unsigned long long* p = nullptr;
+    explicit FreshColours(goss_gpu_object* obj) : o(obj)
+    {
+        const uint64_t z = o->q.s.count;
+        if (z && hipMalloc((void**)&p, z * 8) != hipSuccess) { (void)hipGetLastError(); p = nullptr; throw StatusError{GOSS_ERR_OOM, "colours: no device memory for the words"}; }
+    }
+    FreshColours(const FreshColours&) = delete;
+    FreshColours& operator=(const FreshColours&) = delete;
+    ~FreshColours() { if (p) (void)hipFree(p); }
+    // (the stream is idle: every call on the object is synchronous, so nothing still reads the old words)
+    void adopt(uint32_t ncolours)
+    {
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        if (o->colours) (void)hipFree(o->colours);
+        o->colours = (uint64_t*)p;
+        p = nullptr;
+        o->ncolours = ncolours;
+        o->colours_kept = true;
+    }
+};
+
+// goss_gpu_object_colours_host past its argument checks
+void colours_keep_host(goss_gpu_object* o, const uint64_t* colours, uint32_t ncolours)
+{
+    const uint64_t z = o->q.s.count;
+    if (ncolours < 64)
+        for (uint64_t r = 0; r < z; ++r)
+            if (colours[r] >> ncolours)
+                throw StatusError{GOSS_ERR_INVALID_ARG, "colours: the word of rank " + std::to_string(r) + " has a bit at or above ncolours = " + std::to_string(ncolours)};
+    FreshColours fresh(o);
+    if (z) HIP_TRY(hipMemcpyAsync(fresh.p, colours, z * 8, hipMemcpyHostToDevice, o->stream));
+    fresh.adopt(ncolours);
+}
+
+// goss_gpu_object_colours_from_index past its argument checks: S = N / z words' worth of positions ORed into place
+uint32_t colours_keep_index(goss_gpu_object* o, goss_gpu_object* index)
+{
+    const uint64_t z = o->q.s.count;
+    const RdSparse& idx = index->q.s;
+    if (!z) throw StatusError{GOSS_ERR_INVALID_ARG, "colours_from_index: the set is empty, so the index's universe cannot be S * count"};
+    if (idx.size_hi || idx.size_lo % z) throw StatusError{GOSS_ERR_INVALID_ARG, "colours_from_index: the index's universe is not S * count (count = " + std::to_string(z) + ")"};
+    const uint64_t S = idx.size_lo / z;
+    if (S < 1 || S > GOSS_ELECT_MAX_COLOURS)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "colours_from_index: the index speaks of S = " + std::to_string(S) + " references; S must be 1 .. 64"};
+    HIP_TRY(hipStreamSynchronize(index->stream));
+    FreshColours fresh(o);
+    HIP_TRY(hipMemsetAsync(fresh.p, 0, z * 8, o->stream));
+    HIP_TRY(hipMemsetAsync(o->d_bad, 0xFF, 8, o->stream));
+    if (idx.count) hipLaunchKernelGGL(elect_colours_from_index_kernel, query_grid(idx.count), dim3(kTB), 0, o->stream, idx, z, (uint32_t)S, fresh.p, o->d_bad);
+    HIP_TRY(hipMemcpyAsync(o->h_bad, o->d_bad, 8, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    check_launch("colours_from_index");
+    if (*o->h_bad != ~0ULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "colours_from_index: stored position " + std::to_string(*o->h_bad >> 2) + " of the index cannot be read, or lies at or past S * count (damaged object)"};
+    fresh.adopt((uint32_t)S);
+    return (uint32_t)S;
 }
 
 // ---- the taxonomy: the tree, the annotation, the empty set -------------------------------------------------------------------

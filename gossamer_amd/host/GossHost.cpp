@@ -1937,7 +1937,8 @@ void printHelp(const std::string& cmdName, const OptTable* t)
               << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n"
               << "  pool-samples     pool all the samples\n"
               << "  annotate-kmers   Decorate a graph with an assignment of kmers to graphs.\n"
-              << "  classify-reads   thread the reads through the graph\n";
+              << "  classify-reads   thread the reads through the graph\n"
+              << "  elect-reads      classify reads according to reference\n";
     if (t)
     {
         std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
@@ -2552,6 +2553,93 @@ int gossMain(int argc, char* argv[])
                 cmd(cxt);
             }
             catch (Error& e) { e.cmd = cmdName; throw; }
+            return 0;
+        }
+        if (cmdName == "elect-reads")
+        {
+            // ElectCmdFactoryGroup::create (ElectApp.cc:703-783) with electus' own option names (:806-820)
+            static const OptDef kElect[] = {
+                {"ref-fasta", "", kStrings, "reference file in FASTA format"},
+                {"ref-index", "", kStrings, "prefix of reference index"},
+                {"pool", "", kString, "prefix of a pool written by pool-samples, used as the references"},
+                {"fasta-in", "I", kStrings, "input file in FASTA format"},
+                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
+                {"line-in", "", kStrings, "input file with one sequence per line"},
+                {"max-memory", "M", kString, "maximum memory (in GB) to use"},
+                {"kmer-size", "K", kU64, "kmer size to use (default 25)"},
+                {"pairs", "", kFlag, "treat reads as pairs"},
+                {"dont-write-reads", "", kFlag, "do not produce any output read files"},
+                {"preserve-read-order", "", kFlag, "maintain the same relative ordering of reads in output files"},
+                {"ref-threshold", "", kU64, "the minimum number of references a read must match (default: all of them)"},
+                {"match-prefix", "", kString, "filename prefix for matching reads"},
+                {"non-match-prefix", "", kString, "filename prefix for non-matching reads"},
+            };
+            OptTable t;
+            for (auto& d : kGlobal) t.defs.push_back(d);
+            for (auto& d : kElect) t.defs.push_back(d);
+            for (auto& d : kGpuSpecific) t.defs.push_back(d);
+            Parsed opts; std::string bad;
+            parseArgs(argc, argv, 2, t, opts, bad);
+            if (!bad.empty())
+            {
+                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
+                throw Error::Usage(bad);
+            }
+            Severity sev = opts.count("verbose") ? info : warning;
+            std::unique_ptr<Logger> logger;
+            if (opts.count("log-file"))
+            {
+                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
+                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
+                logger.reset(new Logger(fp, sev, true));
+            }
+            else logger.reset(new Logger(stderr, sev));
+            Checker chk{opts, std::string(), false};
+            strings refFastas, refIndexes, fastas, fastqs, lines;
+            chk.repeatingIn("ref-fasta", refFastas);
+            if (opts.count("ref-index")) refIndexes = opts.strs("ref-index");
+            chk.repeatingIn("fasta-in", fastas);
+            chk.repeatingIn("fastq-in", fastqs);
+            chk.repeatingIn("line-in", lines);
+            uint64_t K = 25;
+            if (opts.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
+            if (K == 0) { chk.errors += "The given value of the option kmer-size was invalid.\n\tvalue 0 is out of range.\n"; chk.suggestUsage = true; }
+            double M = 1.0e9;
+            if (opts.count("max-memory"))
+            {
+                const std::string& v = opts.str("max-memory");
+                char* end = nullptr;
+                errno = 0;
+                M = strtod(v.c_str(), &end);
+                if (v.empty() || errno || *end) throw Error::Usage("the argument ('" + v + "') for option '--max-memory' is invalid\n");
+            }
+            uint64_t T = 4;
+            chk.optionalU64("num-threads", T);
+            uint64_t refThreshold = ~0ULL;
+            chk.optionalU64("ref-threshold", refThreshold);
+            std::string match, nonMatch, pool;
+            if (opts.count("match-prefix")) match = opts.str("match-prefix");
+            if (opts.count("non-match-prefix")) nonMatch = opts.str("non-match-prefix");
+            if (opts.count("pool")) pool = opts.str("pool");
+            const size_t nrefs = refFastas.size() + refIndexes.size();
+            if (pool.empty() && nrefs == 0) { chk.errors += "no references: give ref-fasta, ref-index or pool.\n"; chk.suggestUsage = true; }
+            if (!pool.empty() && nrefs) { chk.errors += "pool stands in for the references: ref-fasta and ref-index cannot be given with it.\n"; chk.suggestUsage = true; }
+            if (nrefs > 64)
+            { chk.errors += num(nrefs) + " references were given; a read's word holds at most 64.\n"; chk.suggestUsage = true; }
+            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
+            chk.throwIfNecessary();
+            GossCmdContext cxt{*logger, cmdName};
+            uint64_t dev = 0, budgetGb = 0;
+            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
+            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
+            cxt.tmpDir = tmpDirOption(opts.vals);
+            try
+            {
+                GossCmdElectReads cmd(K, refThreshold, refFastas, refIndexes, pool, fastas, fastqs, lines, opts.count("pairs") != 0, M, T, match, nonMatch,
+                                      opts.count("preserve-read-order") != 0);
+                cmd(cxt);
+            }
+            catch (Error& e) { if (e.usage.empty()) e.cmd = cmdName; throw; }      // (a reference of another K is a usage error)
             return 0;
         }
         if (cmdName == "annotate-kmers" || cmdName == "classify-reads")

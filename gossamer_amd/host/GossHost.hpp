@@ -458,6 +458,35 @@ private:
     const std::string mIn; const strings mFastas, mFastqs, mLines; const uint64_t mBufferSize, mNumThreads; const bool mPairs;
 };
 
+// GossCmdElectReads (`electus classify`, ElectApp.cc:150-701): every read (or, pPairs, every pair of reads of files 2i and
+// 2i + 1) is looked up in up to 64 references at once -- a k-mer set built per pRefFastas file, then every pRefIndexes set as
+// it is, pooled by GossCmdPoolSamples into a union whose k-mers carry one colour bit per reference; or pPool, what
+// pool-samples wrote -- and goes to <pMatch>{.fasta,.fastq,.txt} when at least pRefThreshold references are hit (~0: all of
+// them), else to <pNonMatch>...; with pPairs the mates go to ..._1 / ..._2 before the suffix.  A prefix that is empty
+// writes nothing.  The pair rule compares the second mate's word as a number, as the reference does (ElectApp.cc:443).
+// Departures: the output keeps the input's order whatever pPreserveReadOrder says; pMaxMemory and pNumThreads are
+// accepted and unused (pNumThreads reaches the builds of the per-file sets); more than 64 references and a reference
+// index whose K differs are usage errors; pair files of unequal length are an error naming both.
+class GossCmdElectReads {
+public:
+    GossCmdElectReads(uint64_t pK, uint64_t pRefThreshold, const strings& pRefFastas, const strings& pRefIndexes, const std::string& pPool,
+                      const strings& pFastas, const strings& pFastqs, const strings& pLines, bool pPairs, double pMaxMemory,
+                      uint64_t pNumThreads, const std::string& pMatch, const std::string& pNonMatch, bool pPreserveReadOrder)
+        : mK(pK), mRefThreshold(pRefThreshold), mRefFastas(pRefFastas), mRefIndexes(pRefIndexes), mPool(pPool), mFastas(pFastas),
+          mFastqs(pFastqs), mLines(pLines), mPairs(pPairs), mMaxMemory(pMaxMemory), mNumThreads(pNumThreads), mMatch(pMatch),
+          mNonMatch(pNonMatch), mPreserveReadOrder(pPreserveReadOrder) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const uint64_t mK, mRefThreshold; const strings mRefFastas, mRefIndexes; const std::string mPool; const strings mFastas, mFastqs, mLines;
+    const bool mPairs; const double mMaxMemory; const uint64_t mNumThreads; const std::string mMatch, mNonMatch; const bool mPreserveReadOrder;
+};
+
+// the decision of elect-reads (KmerFilter, ElectApp.cc:406-451) from a read's word and window count, and the name of an
+// output file: <prefix>[_1|_2]<suffix>, half = 0 for single reads
+bool electSingle(uint64_t word, uint32_t windows, uint64_t threshold);
+bool electPair(uint64_t word1, uint32_t windows1, uint64_t word2, uint32_t windows2, uint64_t threshold);
+std::string electFileName(const std::string& prefix, int half, const std::string& suffix);
+
 // Bytes of reads in byte form ('\n' after each) handed to the device per batch by the commands that look reads up in a
 // graph or k-mer set: GossCmdContext::batchBytes, or GOSS_MATCH_BATCH=<bytes> (tests).
 size_t matchBatchBytes(const GossCmdContext& cxt);

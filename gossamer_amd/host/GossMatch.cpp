@@ -32,44 +32,6 @@ namespace gosshost {
 
 using namespace reads;
 
-namespace {
-
-// FileFactory::out(name): "-" is standard output
-struct OutFile {
-    std::string name;
-    FILE* fp = nullptr;
-    std::string pending;
-    void open(const std::string& n)
-    {
-        name = n;
-        fp = n == "-" ? stdout : fopen(n.c_str(), "wb");
-        if (!fp) throw Error::Errno(n, errno);
-    }
-    // GossReadBaseString::print (GossReadBaseString.hh:115-118): the bases as parsed, then '\n'
-    void print(const char* seq, size_t len)
-    {
-        pending.append(seq, len);
-        pending += '\n';
-        if (pending.size() >= (4u << 20)) drain();
-    }
-    void drain()
-    {
-        if (!pending.empty() && fwrite(pending.data(), 1, pending.size(), fp) != pending.size()) throw Error::Write(name);
-        pending.clear();
-    }
-    void close()
-    {
-        if (!fp) return;
-        drain();
-        if (fp == stdout) fflush(stdout);
-        else if (fclose(fp) != 0) { fp = nullptr; throw Error::Write(name); }
-        fp = nullptr;
-    }
-    ~OutFile() { if (fp && fp != stdout) fclose(fp); }
-};
-
-}  // namespace
-
 size_t matchBatchBytes(const GossCmdContext& cxt)
 {
     if (const char* e = std::getenv("GOSS_MATCH_BATCH"))

@@ -1,6 +1,7 @@
 // GossReads.hpp -- what the commands that look reads up in an object resident on the device share: the object as it lies
 // on disk (Object), the reads in and one word per read out in batches (Matcher), and the input files in the reference's
-// order.  Used by GossMatch.cpp (extract-reads, filter-reads, group-reads) and GossTaxo.cpp (annotate-kmers, classify-reads).
+// order, and the files the reads are written to (OutFile).  Used by GossMatch.cpp (extract-reads, filter-reads,
+// group-reads), GossTaxo.cpp (annotate-kmers, classify-reads) and GossElect.cpp (elect-reads).
 #pragma once
 
 #include <fcntl.h>
@@ -10,6 +11,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cstdio>
 #include <functional>
 #include <string>
 #include <vector>
@@ -60,7 +62,9 @@ struct Object {
         throw Error::General(msg + "\n");
     }
     // Graph::open(name, fac) / KmerSet(name, fac): every file "<name>." or "<name>-" something
-    void open(const GossCmdContext& cxt, const std::string& name, bool graph)
+    void open(const GossCmdContext& cxt, const std::string& name, bool graph) { openAs(cxt, name, graph ? GOSS_OBJECT_GRAPH : GOSS_OBJECT_KMER_SET); }
+    // the same for any kind of object (GOSS_OBJECT_*)
+    void openAs(const GossCmdContext& cxt, const std::string& name, int kind)
     {
         ObjectFiles files;
         glob_t g{};
@@ -77,7 +81,7 @@ struct Object {
         globfree(&g);
         std::vector<goss_gpu_named_file> nf(files.names.size());
         for (size_t i = 0; i < nf.size(); ++i) nf[i] = goss_gpu_named_file{files.names[i].c_str(), files.maps[i].first, files.maps[i].second};
-        int rc = goss_gpu_object_open(&h, cxt.device, nullptr, graph ? GOSS_OBJECT_GRAPH : GOSS_OBJECT_KMER_SET, name.c_str(), nf.data(), (uint32_t)nf.size());
+        int rc = goss_gpu_object_open(&h, cxt.device, nullptr, kind, name.c_str(), nf.data(), (uint32_t)nf.size());
         if (rc != GOSS_OK)
         {
             std::string msg = "\tunable to open graph '" + name + "'\n\t" + goss_gpu_strerror(rc);
@@ -91,15 +95,17 @@ struct Object {
 
 // Reads in, one word per read out, in order: batches end at read boundaries and hold `cap` bytes (one read more than
 // that is a batch of its own).  The word is what the Answer makes of a read: match_reads' hits (with GOSS_MATCH_ANY 1 / 0),
-// pClassify: classify_reads' mask, or whatever a command's own Answer gives.
-class Matcher {
+// pClassify: classify_reads' mask, or whatever a command's own Answer gives.  Word is uint32_t (Matcher) but where a
+// command needs more per read: elect-reads' Coloured.
+template <class Word>
+class BasicMatcher {
 public:
-    typedef std::function<void(const char* seq, size_t len, uint32_t word)> Verdict;
+    typedef std::function<void(const char* seq, size_t len, Word word)> Verdict;
     // the reads of a batch answered: `bytes` of reads ('\n' after each), n of them, one word each; returns the reads seen
-    typedef std::function<uint64_t(const char* buf, size_t bytes, uint64_t n, uint32_t* words)> Answer;
-    Matcher(size_t cap, Answer a, Verdict v) : mCap(cap), mAnswer(std::move(a)), mVerdict(std::move(v)) {}
-    Matcher(const Object& obj, uint32_t flags, size_t cap, Verdict v, bool pClassify = false)
-        : Matcher(cap, pClassify ? classifyAnswer(obj, flags) : matchAnswer(obj, flags), std::move(v)) {}
+    typedef std::function<uint64_t(const char* buf, size_t bytes, uint64_t n, Word* words)> Answer;
+    BasicMatcher(size_t cap, Answer a, Verdict v) : mCap(cap), mAnswer(std::move(a)), mVerdict(std::move(v)) {}
+    BasicMatcher(const Object& obj, uint32_t flags, size_t cap, Verdict v, bool pClassify = false)
+        : BasicMatcher(cap, pClassify ? classifyAnswer(obj, flags) : matchAnswer(obj, flags), std::move(v)) {}
     static Answer matchAnswer(const Object& obj, uint32_t flags)
     {
         return [&obj, flags](const char* buf, size_t bytes, uint64_t n, uint32_t* words) {
@@ -143,8 +149,43 @@ private:
     Verdict mVerdict;
     std::vector<char> mBuf;
     std::vector<uint64_t> mStart;
-    std::vector<uint32_t> mHits;
+    std::vector<Word> mHits;
     uint64_t mBatches = 0;
+};
+typedef BasicMatcher<uint32_t> Matcher;
+
+// FileFactory::out(name): "-" is standard output
+struct OutFile {
+    std::string name;
+    FILE* fp = nullptr;
+    std::string pending;
+    void open(const std::string& n)
+    {
+        name = n;
+        fp = n == "-" ? stdout : fopen(n.c_str(), "wb");
+        if (!fp) throw Error::Errno(n, errno);
+    }
+    // GossReadBaseString::print (GossReadBaseString.hh:115-118): the bases as parsed, then '\n'
+    void print(const char* seq, size_t len)
+    {
+        pending.append(seq, len);
+        pending += '\n';
+        if (pending.size() >= (4u << 20)) drain();
+    }
+    void drain()
+    {
+        if (!pending.empty() && fwrite(pending.data(), 1, pending.size(), fp) != pending.size()) throw Error::Write(name);
+        pending.clear();
+    }
+    void close()
+    {
+        if (!fp) return;
+        drain();
+        if (fp == stdout) fflush(stdout);
+        else if (fclose(fp) != 0) { fp = nullptr; throw Error::Write(name); }
+        fp = nullptr;
+    }
+    ~OutFile() { if (fp && fp != stdout) fclose(fp); }
 };
 
 enum Format { kLine, kFasta, kFastq };

@@ -1063,6 +1063,12 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * own. */
 #include "goss_gpu_taxo.h"
 
+/* elect-reads on an object (goss_gpu_object_colours_host, goss_gpu_object_colours_from_index,
+ * goss_gpu_object_colour_reads, goss_gpu_object_colour_reads_host): per read, which of up to 64 references its k-mers
+ * fall into -- the loop of ElectApp.cc:406-451 over one colour word per k-mer of the references' union; likewise a
+ * header of its own. */
+#include "goss_gpu_elect.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1681,1252 +1681,36 @@ void GossCmdBuildGraph::operator()(const GossCmdContext& pCxt)
     runBuild(pCxt, mK, GOSS_MODE_GRAPH, mGraphName, mFastaNames, mFastqNames, mLineNames, mT, mStats);
 }
 
-// --------------------------------------------------------------------------------------
-// command line (App.cc:176-417, GossApp.cc:145-202, GossOptionChecker.hh)
-// --------------------------------------------------------------------------------------
-
-namespace {
-
-enum OptKind { kFlag, kU64, kString, kStrings };
-struct OptDef { const char* lng; const char* sht; OptKind kind; const char* help; };
-
-const OptDef kGlobal[] = {
-    {"debug", "D", kStrings, "enable particular debugging output"},
-    {"help", "h", kFlag, "show a help message"},
-    {"log-file", "l", kString, "place to write messages"},
-    {"tmp-dir", "", kStrings, "a directory to use for temporary files (default /tmp)"},
-    {"num-threads", "T", kU64, "maximum number of worker threads to use, where possible"},
-    {"verbose", "v", kFlag, "show progress messages"},
-    {"version", "V", kFlag, "show the software version"},
-};
-const OptDef kCommon[] = {
-    {"buffer-size", "B", kU64, "maximum size (in GB) for in-memory buffers (default: 2)"},
-    {"fasta-in", "I", kStrings, "input file in FASTA format"},
-    {"fastas-in", "F", kStrings, "input file containing filenames in FASTA format"},
-    {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-    {"fastqs-in", "f", kStrings, "input file containing filenames in FASTQ format"},
-    {"line-in", "", kStrings, "input file with one sequence per line"},
-    {"graph-out", "O", kString, "name of the output graph object"},
-    {"kmer-size", "k", kU64, "kmer size to use"},
-};
-const OptDef kKmerSetSpecific[] = {
-    {"log-hash-slots", "S", kU64, "log2 of the number of hash slots to use (default 24)"},
-};
-// not in the reference: where and how much HBM to use
-const OptDef kGpuSpecific[] = {
-    {"device", "", kU64, "HIP device ordinal (default 0)"},
-    {"devices", "", kString, "build commands: comma-separated HIP device ordinals to count on side by side (one context each)"},
-    {"hbm-budget", "", kU64, "HBM budget in GB for keys and sort workspace (default: 80% of free HBM)"},
-};
-
-// --tmp-dir: the last one given, which must be a directory (the reference fails when it first creates a temporary file
-// there: "PhysicalFileFactory::tmpName"; here the check comes first, with the name in the message)
-std::string tmpDirOption(const std::map<std::string, std::vector<std::string>>& vals)
+// goss dump-bases (diagnostic): print exactly the byte stream the build commands hand to the device
+// (each read's bases followed by '\n'), inputs in the order line, fasta, fastq
+void dumpBases(const strings& fastas, const strings& fastqs, const strings& lines, uint64_t T)
 {
-    auto it = vals.find("tmp-dir");
-    if (it == vals.end() || it->second.empty()) return std::string();
-    const std::string& d = it->second.back();
-    struct stat st;
-    if (::stat(d.c_str(), &st) != 0) throw Error::Errno(d, errno);
-    if (!S_ISDIR(st.st_mode)) throw Error::General("--tmp-dir: " + d + " is not a directory\n");
-    return d;
-}
-
-struct Parsed {
-    std::map<std::string, std::vector<std::string>> vals;
-    size_t count(const std::string& k) const { auto i = vals.find(k); return i == vals.end() ? 0 : i->second.size(); }
-    const std::string& str(const std::string& k) const { return vals.at(k).back(); }
-    const std::vector<std::string>& strs(const std::string& k) const { return vals.at(k); }
-};
-
-struct OptTable {
-    std::vector<OptDef> defs;
-    const OptDef* findLong(const std::string& n, bool& ambiguous) const
+    uint64_t reads = 0;
+    ReadSink sink = [&](const char* seq, size_t len) { fwrite(seq, 1, len, stdout); fputc('\n', stdout); };
+    for (auto& f : lines) reads += parseLines(f, sink);
+    for (auto& f : fastas) reads += parseFasta(f, sink);
+    for (auto& f : fastqs)
     {
-        ambiguous = false;
-        const OptDef* hit = nullptr;
-        for (auto& d : defs) if (n == d.lng) return &d;
-        for (auto& d : defs)                      // unique-prefix guessing, as program_options does
-            if (strncmp(d.lng, n.c_str(), n.size()) == 0) { if (hit) { ambiguous = true; return nullptr; } hit = &d; }
-        return hit;
+        // -T > 1 exercises the parallel parser (same byte stream, file order)
+        HostAlloc heap{[](size_t n) { return malloc(n); }, [](void* p) { free(p); }, false, nullptr, nullptr, nullptr};
+        // GOSS_DUMP_PACKED=1: the chunks go through the workers' 2-bit packer and are unpacked here the
+        // way the device unpacks them (a base letter in upper case, a newline for every non-base)
+        PackedPush viaPacked;
+        viaPacked.push = [&](const uint32_t* codes, const uint16_t* bad, size_t n, std::function<void()> release) {
+            std::string out(n, '\n');
+            for (size_t i = 0; i < n; ++i)
+                if (!((bad[i / 16] >> (i % 16)) & 1u)) out[i] = "ACGT"[(codes[i / 16] >> (2 * (i % 16))) & 3u];
+            fwrite(out.data(), 1, n, stdout);
+            release();
+        };
+        uint64_t r = parseFastqParallel(f, (unsigned)std::min<uint64_t>(T, maxFramers()), parseChunkBytes(),
+                                        [&](const char* p, size_t n) { fwrite(p, 1, n, stdout); }, heap, nullptr,
+                                        std::getenv("GOSS_DUMP_PACKED") ? &viaPacked : nullptr);
+        if (r == ~0ULL) r = parseFastq(f, sink);
+        reads += r;
     }
-    const OptDef* findShort(char c) const
-    {
-        for (auto& d : defs) if (d.sht[0] == c && d.sht[0]) return &d;
-        return nullptr;
-    }
-    std::string describe() const
-    {
-        std::ostringstream os;
-        for (auto& d : defs)
-        {
-            std::string l = "  ";
-            if (d.sht[0]) l += std::string("-") + d.sht + " [ --" + d.lng + " ]"; else l += std::string("--") + d.lng;
-            if (d.kind != kFlag) l += " arg";
-            if (l.size() < 40) l.resize(40, ' '); else l += " ";
-            os << l << d.help << "\n";
-        }
-        return os.str();
-    }
-};
-
-uint64_t toU64(const std::string& opt, const std::string& v)
-{
-    if (v.empty() || v[0] == '-') throw Error::Usage("the argument ('" + v + "') for option '--" + opt + "' is invalid\n");
-    char* end = nullptr;
-    errno = 0;
-    unsigned long long x = strtoull(v.c_str(), &end, 10);
-    if (errno || *end) throw Error::Usage("the argument ('" + v + "') for option '--" + opt + "' is invalid\n");
-    return x;
-}
-
-// Parses argv[first..] against the table; unknown tokens are collected like
-// command_line_parser(...).allow_unregistered() + the check at App.cc:255-262.
-void parseArgs(int argc, char** argv, int first, const OptTable& t, Parsed& out, std::string& badMsg)
-{
-    for (int i = first; i < argc; ++i)
-    {
-        std::string tok = argv[i];
-        const OptDef* d = nullptr;
-        std::string inlineVal; bool hasInline = false;
-        if (tok.size() > 2 && tok[0] == '-' && tok[1] == '-')
-        {
-            std::string name = tok.substr(2);
-            size_t eq = name.find('=');
-            if (eq != std::string::npos) { inlineVal = name.substr(eq + 1); name = name.substr(0, eq); hasInline = true; }
-            bool amb;
-            d = t.findLong(name, amb);
-        }
-        else if (tok.size() >= 2 && tok[0] == '-' && tok[1] != '-')
-        {
-            d = t.findShort(tok[1]);
-            if (d && tok.size() > 2)
-            {
-                if (d->kind == kFlag) d = nullptr;      // grouped flags are not used by goss
-                else { inlineVal = tok.substr(2); hasInline = true; }
-            }
-        }
-        if (!d)
-        {
-            badMsg += "unknown option '" + tok + "'\n";
-            continue;
-        }
-        if (d->kind == kFlag)
-        {
-            out.vals[d->lng].push_back("1");
-            continue;
-        }
-        std::string v;
-        if (hasInline) v = inlineVal;
-        else if (i + 1 < argc) v = argv[++i];
-        else throw Error::Usage(std::string("the required argument for option '--") + d->lng + "' is missing\n");
-        if (d->kind == kU64) toU64(d->lng, v);
-        out.vals[d->lng].push_back(v);
-    }
-}
-
-// GossOptionChecker: accumulates error text, decides usage vs general error.
-struct Checker {
-    const Parsed& o;
-    std::string errors;
-    bool suggestUsage = false;
-    bool mandatoryU64(const std::string& n, uint64_t& v, uint64_t maxv)
-    {
-        if (!o.count(n)) { errors += "mandatory option " + n + " was not given.\n"; suggestUsage = true; return false; }
-        v = toU64(n, o.str(n));
-        if (v > maxv)
-        {
-            errors += "The given value of the option " + n + " was invalid.\n";
-            errors += "\tvalue " + num(v) + " is out of range.\n\tthe maximum allowed value is " + num(maxv) + ".\n";
-            suggestUsage = true;
-            return false;
-        }
-        return true;
-    }
-    bool optionalU64(const std::string& n, uint64_t& v)
-    {
-        if (!o.count(n)) return false;
-        v = toU64(n, o.str(n));
-        return true;
-    }
-    // FileCreateCheck(fac, true): "<name>.test" must be creatable (GossOptionChecker.hh:80-122)
-    bool mandatoryOut(const std::string& n, std::string& v)
-    {
-        if (!o.count(n)) { errors += "mandatory option " + n + " was not given.\n"; suggestUsage = true; return false; }
-        v = o.str(n);
-        std::string probe = v + ".test";
-        FILE* fp = fopen(probe.c_str(), "wb");
-        if (!fp)
-        {
-            errors += "The given value of the option " + n + " was invalid.\n";
-            errors += "\tcannot create filenames with prefix '" + v + "'\n";
-            return false;
-        }
-        fclose(fp);
-        ::remove(probe.c_str());
-        return true;
-    }
-    // FileReadCheck (GossOptionChecker.hh:125-156)
-    void repeatingIn(const std::string& n, strings& vals)
-    {
-        if (!o.count(n)) return;
-        vals = o.strs(n);
-        for (auto& f : vals)
-            if (!InFile::readable(f))
-            {
-                errors += "The given value of the option " + n + " was invalid.\n";
-                errors += "\tcannot open file '" + f + "' for reading\n";
-            }
-    }
-    // expandFilenames (GossOptionChecker.hh:405-430): one name per '\n'-terminated line
-    void expand(const std::string& n, strings& names)
-    {
-        if (!o.count(n)) return;
-        for (auto& lf : o.strs(n))
-        {
-            InFile in(lf);
-            std::string all; char buf[65536]; size_t got;
-            while ((got = in.read(buf, sizeof buf)) > 0) all.append(buf, got);
-            size_t b = 0;
-            for (;;)
-            {
-                size_t e = all.find('\n', b);
-                if (e == std::string::npos) break;      // a last line without '\n' is dropped
-                names.push_back(all.substr(b, e - b));
-                b = e + 1;
-            }
-        }
-    }
-    void throwIfNecessary()
-    {
-        if (errors.empty()) return;
-        if (suggestUsage) throw Error::Usage(errors);
-        throw Error::General(errors);
-    }
-};
-
-const char* kVersion = "1.3.0-mi355x";
-
-void printHelp(const std::string& cmdName, const OptTable* t)
-{
-    std::cerr << "goss <command> [options]\n\ncommands implemented by this build:\n"
-              << "  build-graph      create a new graph\n"
-              << "  build-kmer-set   create a new graph\n"
-              << "  dump-graph       write out the graph in a robust text representation.\n"
-              << "  dump-kmer-set    write out the graph in a robust text representation.\n"
-              << "  help             print a summary of all the commands.\n"
-              << "  lint-graph       verify that a graph structure is internally consistent\n"
-              << "  restore-graph    read in a graph from a robust text representation.\n"
-              << "  intersect-kmer-sets  generate the intersection of the given k-mer sets\n"
-              << "  merge-and-annotate-kmer-sets  Decorate a graph with an assignment of kmers to graphs.\n"
-              << "  compute-near-kmers  Decorate a graph with an assignment of kmers to graphs.\n"
-              << "  merge-graphs     create a new graph by merging zero or more existing graphs\n"
-              << "  merge-kmer-sets  create a new graph by merging zero or more existing graphs\n"
-              << "  subtract-kmer-set  subtract the second k-mer set from the first\n"
-              << "  graph-to-kmer-set  generate a graph's k-mer set\n"
-              << "  trim-graph       create a new graph by trimming low frequency edges\n"
-              << "  prune-tips       create a new graph by removing low frequency tips\n"
-              << "  trim-paths       create a new graph by removing low frequency paths\n"
-              << "  clip-links       create a new graph by removing spurious links\n"
-              << "  print-contigs    print all the non-branching paths in the given assembly graph\n"
-              << "  build-entry-edge-set  build an entry edge set for a graph\n"
-              << "  count-components  count connected components in the graph represented by the given reads\n"
-              << "  build-subgraph   generate a subgraph of an existing graph\n"
-              << "  extract-reads    extract reads which map on to a graph\n"
-              << "  filter-reads     filter reads keeping/discarding those that coincide with a graph.\n"
-              << "  group-reads      filter reads keeping/discarding those that coincide with a graph.\n"
-              << "  pool-samples     pool all the samples\n"
-              << "  annotate-kmers   Decorate a graph with an assignment of kmers to graphs.\n"
-              << "  classify-reads   thread the reads through the graph\n"
-              << "  elect-reads      classify reads according to reference\n";
-    if (t)
-    {
-        std::cerr << "\n" << cmdName << "\n" << t->describe() << std::endl;
-    }
-}
-
-}  // namespace
-
-int gossMain(int argc, char* argv[])
-{
-    std::string cmdName;
-    try
-    {
-        for (int i = 1; i < argc; ++i)
-            if (!strcmp(argv[i], "--version")) { std::cout << "goss version " << kVersion << std::endl; return 0; }
-
-        int argsToSkip = 0;
-        if (argc < 2) cmdName = "help";
-        else if (argc == 2 && (!strcmp(argv[1], "--help") || !strcmp(argv[1], "-h"))) cmdName = "help";
-        else { cmdName = argv[1]; if (argv[1][0] != '-') argsToSkip = 1; }
-
-        const bool isKmerSet = cmdName == "build-kmer-set", isGraph = cmdName == "build-graph";
-        const bool isMerge = cmdName == "merge-kmer-sets" || cmdName == "merge-graphs";
-        const bool isIntersect = cmdName == "intersect-kmer-sets", isSubtract = cmdName == "subtract-kmer-set";
-        const bool isAnnotate = cmdName == "merge-and-annotate-kmer-sets";
-        const bool isToKmerSet = cmdName == "graph-to-kmer-set";
-        const bool isDump = cmdName == "dump-kmer-set" || cmdName == "dump-graph";
-        const bool isRestore = cmdName == "restore-graph", isLint = cmdName == "lint-graph";
-        const bool isTrim = cmdName == "trim-graph", isPrune = cmdName == "prune-tips";
-        const bool isContigs = cmdName == "print-contigs", isEntries = cmdName == "build-entry-edge-set";
-        const bool isNear = cmdName == "compute-near-kmers";
-        const bool isPaths = cmdName == "trim-paths", isLinks = cmdName == "clip-links";
-        if (isPaths || isLinks || isNear || isMerge || isIntersect || isSubtract || isAnnotate || isDump || isRestore || isLint || isToKmerSet || isTrim || isPrune || isContigs || isEntries)
-        {
-            // GossCmdFactoryDumpKmerSet/DumpGraph::create (GossCmdDumpKmerSet.cc:58-73,
-            // GossCmdDumpGraph.cc:64-79), GossCmdFactoryRestoreGraph::create (GossCmdRestoreGraph.cc:138-152),
-            // GossCmdFactoryLintGraph::create (GossCmdLintGraph.cc:278-292),
-            // GossCmdFactoryIntersectKmerSets::create (GossCmdIntersectKmerSets.cc:131-150),
-            // GossCmdFactorySubtractKmerSet::create (GossCmdSubtractKmerSet.cc:88-113),
-            // GossCmdFactoryMergeAndAnnotateKmerSets::create (GossCmdMergeAndAnnotateKmerSets.cc:209-224),
-            // GossCmdFactoryMerge<T>::create (GossCmdMerge.tcc:329-378),
-            // GossCmdFactoryTrimGraph::create (GossCmdTrimGraph.cc:130-172), GossCmdFactoryPruneTips::create
-            // (GossCmdPruneTips.cc:347-373), GossCmdFactoryBuildEntryEdgeSet::create (GossCmdBuildEntryEdgeSet.cc:68-84),
-            // GossCmdFactoryComputeNearKmers::create (GossCmdComputeNearKmers.cc:230-243),
-            // GossCmdFactoryTrimPaths::create (GossCmdTrimPaths.cc:251-279), GossCmdFactoryClipLinks::create
-            // (GossCmdClipLinks.cc:177-199)
-            static const OptDef kTrimPrune[] = {
-                {"cutoff", "C", kU64, "coverage cutoff"},
-                {"estimate-only", "", kFlag, "only estimate the coverage cutoff (trim-graph)"},
-                {"scale-cutoff-by-k", "", kU64, "scale the coverage cutoff by k-mer size"},
-                {"relative-cutoff", "", kString, "relative coverage cutoff"},
-                {"iterate", "", kU64, "number of passes to perform"},
-            };
-            // GossCmdFactoryPrintContigs (GossCmdPrintContigs.cc:226-289).  The reference registers
-            // include-entailed-contigs and reads print-entailed-contigs (:260, :285); both belong to the supergraph form
-            static const OptDef kContigs[] = {
-                {"min-length", "", kU64, "minimum length of a printed sequence"},
-                {"min-coverage", "", kU64, "minimum coverage"},
-                {"no-sequence", "", kFlag, "print a table of the segments' figures instead of their sequence"},
-                {"print-linear-segments", "", kFlag, "Only print individual linear paths, even if a supergraph is present."},
-                {"verbose-headers", "", kFlag, "Print additional information in contig headers"},
-                {"no-line-breaks", "", kFlag, "Print contig sequences without line breaks"},
-                {"include-entailed-contigs", "", kFlag, "not offered (supergraph contigs)"},
-                {"print-entailed-contigs", "", kFlag, "not offered (supergraph contigs)"},
-                {"print-rcs", "", kFlag, "Include each sequence's reverse complement."},
-            };
-            static const OptDef kMerge[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"graphs-in", "", kStrings, "read graph names (one per line) from the given file."},
-                {"graph-out", "O", kString, "name of the output graph object"},
-                {"max-merge", "", kU64, "The maximum number of graphs to merge at once."},
-                {"input-file", "f", kString, "input file name ('-' for standard input)"},
-                {"output-file", "o", kString, "output file name ('-' for standard output)"},
-                {"dump-properties", "", kFlag, "show the internal properties of the graph"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kMerge) t.defs.push_back(d);
-            if (isTrim || isPrune) for (auto& d : kTrimPrune) t.defs.push_back(d);
-            if (isPaths) t.defs.push_back(kTrimPrune[0]);
-            if (isContigs) for (auto& d : kContigs) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            strings ins;
-            uint64_t maxMerge = 8;
-            std::string outName;
-            std::string textName = "-";
-            uint64_t cutoff = 0, iterations = 1;
-            std::string notOffered;                 // a part of trim-graph / prune-tips that this build refuses
-            uint64_t minLength = 0, minCoverage = 0;
-            uint64_t nearThreads = 4;                       // (compute-near-kmers: the loop is the device's)
-            if (isDump || isLint || isContigs || isEntries || isNear)
-            {
-                // getRepeatingOnce("graph-in") (GossOptionChecker.hh:235-254)
-                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-                else if (opts.strs("graph-in").size() != 1)
-                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-                else ins = opts.strs("graph-in");
-                if (isEntries)
-                {
-                    uint64_t ignoredThreads = 4;            // (the walk is the device's)
-                    chk.optionalU64("num-threads", ignoredThreads);
-                }
-                if (isNear) chk.optionalU64("num-threads", nearThreads);
-                if (isContigs)
-                {
-                    uint64_t ignoredThreads = 1;
-                    chk.optionalU64("num-threads", ignoredThreads);
-                    chk.optionalU64("min-coverage", minCoverage);
-                    chk.optionalU64("min-length", minLength);
-                    if (opts.count("include-entailed-contigs") || opts.count("print-entailed-contigs"))
-                        notOffered = ("not implemented: --print-entailed-contigs / --include-entailed-contigs (they belong to "
-                                      "supergraph contigs; this build prints linear segments only)\n");
-                }
-                if ((isDump || isContigs) && opts.count("output-file"))
-                {
-                    textName = opts.str("output-file");
-                    if (textName != "-")
-                    {
-                        FILE* fp = fopen(textName.c_str(), "wb");      // FileCreateCheck(fac, false)
-                        if (!fp)
-                        {
-                            chk.errors += "The given value of the option output-file was invalid.\n";
-                            chk.errors += "\tcannot create file '" + textName + "'\n";
-                        }
-                        else fclose(fp);
-                    }
-                }
-            }
-            else if (isRestore)
-            {
-                if (opts.count("input-file")) textName = opts.str("input-file");
-                chk.mandatoryOut("graph-out", outName);
-            }
-            else if (isToKmerSet)
-            {
-                // GossCmdFactoryGraphToKmerSet::create (GossCmdGraphToKmerSet.cc:62-77)
-                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-                else if (opts.strs("graph-in").size() != 1)
-                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-                else ins = opts.strs("graph-in");
-                if (!opts.count("graph-out")) { chk.errors += "mandatory option graph-out was not given.\n"; chk.suggestUsage = true; }
-                else outName = opts.str("graph-out");
-            }
-            else if (isTrim || isPrune)
-            {
-                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-                else if (opts.strs("graph-in").size() != 1)
-                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-                else ins = opts.strs("graph-in");
-                chk.mandatoryOut("graph-out", outName);
-                if (isTrim)
-                {
-                    const bool inferCutoff = !chk.optionalU64("cutoff", cutoff);
-                    if (opts.count("estimate-only") && !inferCutoff)
-                        throw Error::Usage("cannot estimate cutoff unless it is also being inferred");
-                    if (inferCutoff && opts.count("scale-cutoff-by-k")) throw Error::Usage("cannot scale an inferred cutoff");
-                    // the inferred cutoff (EstimateGraphStatistics, a Levenberg-Marquardt fit of the multiplicity histogram)
-                    // and what hangs on it are not part of this build
-                    if (inferCutoff || opts.count("scale-cutoff-by-k"))
-                        notOffered = ("not implemented: give -C (the cutoff is not inferred by this build; --estimate-only and "
-                                           "--scale-cutoff-by-k are not offered)\n");
-                }
-                else
-                {
-                    // the reference reads both optionals whether given or not (GossCmdPruneTips.cc:79-80) and compares
-                    // the count with the relative cutoff (:172): defined only when both are given -- neither is offered
-                    if (opts.count("cutoff") || opts.count("relative-cutoff"))
-                        notOffered = ("not implemented: --cutoff and --relative-cutoff (the reference reads them unset "
-                                           "unless both are given, so their behaviour is undefined)\n");
-                    chk.optionalU64("iterate", iterations);
-                }
-            }
-            else if (isPaths || isLinks)
-            {
-                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-                else if (opts.strs("graph-in").size() != 1)
-                { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-                else ins = opts.strs("graph-in");
-                chk.mandatoryOut("graph-out", outName);
-                if (isPaths)
-                {
-                    chk.mandatoryU64("cutoff", cutoff, ~0ULL);
-                    uint64_t ignoredThreads = 4;            // (the walk is the device's)
-                    chk.optionalU64("num-threads", ignoredThreads);
-                }
-            }
-            else if (isAnnotate)
-            {
-                if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-                else if (opts.strs("graph-in").size() != 2)
-                { chk.errors += "mandatory option graph-in must be supplied exactly twice.\n"; chk.suggestUsage = true; }
-                else ins = opts.strs("graph-in");
-                if (!opts.count("graph-out")) { chk.errors += "mandatory option graph-out was not given.\n"; chk.suggestUsage = true; }
-                else outName = opts.str("graph-out");
-            }
-            else
-            {
-                if (opts.count("graph-in")) ins = opts.strs("graph-in");
-                chk.expand("graphs-in", ins);
-                if (isMerge && ins.empty())
-                    chk.errors += "At least one input graph must be supplied either using --graph-in or --graphs-in.\n";
-                if (isMerge) chk.optionalU64("max-merge", maxMerge);
-                chk.mandatoryOut("graph-out", outName);
-                if (isSubtract && ins.size() != 2) chk.errors += "Exactly two input k-mer sets required!";
-            }
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            if (!notOffered.empty()) throw Error::Usage(notOffered);
-            if (isContigs && !opts.count("print-linear-segments") && ::access((ins[0] + "-supergraph.header").c_str(), F_OK) == 0)
-            {
-                // the reference would print the supergraph's contigs here (GossCmdPrintContigs.cc:208-221)
-                Error e = Error::General("\t'" + ins[0] + "' has a supergraph: supergraph contigs are not implemented by this build; "
-                                         "give --print-linear-segments to print the graph's linear segments\n");
-                e.cmd = cmdName;
-                throw e;
-            }
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0, budgetGb = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-            cxt.tmpDir = tmpDirOption(opts.vals);
-            try
-            {
-                if (cmdName == "merge-kmer-sets") { GossCmdMergeKmerSets cmd(ins, maxMerge, outName); cmd(cxt); }
-                else if (isMerge) { GossCmdMergeGraphs cmd(ins, maxMerge, outName); cmd(cxt); }
-                else if (isIntersect) { GossCmdIntersectKmerSets cmd(ins, outName); cmd(cxt); }
-                else if (isSubtract) { GossCmdSubtractKmerSet cmd(ins, outName); cmd(cxt); }
-                else if (cmdName == "dump-kmer-set") { GossCmdDumpKmerSet cmd(ins[0], textName); cmd(cxt); }
-                else if (cmdName == "dump-graph") { GossCmdDumpGraph cmd(ins[0], textName); cmd(cxt); }
-                else if (isRestore) { GossCmdRestoreGraph cmd(textName, outName); cmd(cxt); }
-                else if (isLint) { GossCmdLintGraph cmd(ins[0], opts.count("dump-properties") != 0); cmd(cxt); }
-                else if (isToKmerSet) { GossCmdGraphToKmerSet cmd(ins[0], outName); cmd(cxt); }
-                else if (isTrim) { GossCmdTrimGraph cmd(ins[0], outName, cutoff); cmd(cxt); }
-                else if (isPrune) { GossCmdPruneTips cmd(ins[0], outName, iterations); cmd(cxt); }
-                else if (isPaths)
-                {
-                    // numeric_cast<uint32_t>(c) (GossCmdTrimPaths.cc:270), thrown before the command exists
-                    if (cutoff > 0xFFFFFFFFULL) throw std::range_error("bad numeric conversion: positive overflow");
-                    GossCmdTrimPaths cmd(ins[0], outName, (uint32_t)cutoff);
-                    cmd(cxt);
-                }
-                else if (isLinks) { GossCmdClipLinks cmd(ins[0], outName); cmd(cxt); }
-                else if (isEntries) { GossCmdBuildEntryEdgeSet cmd(ins[0]); cmd(cxt); }
-                else if (isNear) { GossCmdComputeNearKmers cmd(ins[0], nearThreads); cmd(cxt); }
-                else if (isContigs)
-                {
-                    GossCmdPrintContigs cmd(ins[0], minCoverage, minLength, opts.count("no-sequence") != 0, opts.count("verbose-headers") != 0,
-                                            opts.count("no-line-breaks") != 0, textName);
-                    cmd(cxt);
-                }
-                else { GossCmdMergeAndAnnotateKmerSets cmd(ins[0], ins[1], outName); cmd(cxt); }
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "pool-samples")
-        {
-            // GossCmdFactoryPoolSamples::create (GossCmdPoolSamples.cc:255-318)
-            static const OptDef kPool[] = {
-                {"kmer-set-in", "", kStrings, "input k-mer set"},
-                {"kmer-sets-in", "", kStrings, "input file containing k-mer sets"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kCommon) if (std::string(d.lng) != "line-in") t.defs.push_back(d);
-            for (auto& d : kPool) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            uint64_t K = 25;
-            if (opts.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
-            uint64_t B = 2;
-            chk.optionalU64("buffer-size", B);
-            uint64_t S = 0;
-            { uint64_t slots = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16)); S = (uint64_t)std::log2((double)slots); }
-            uint64_t N = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16));
-            uint64_t T = 4;
-            chk.optionalU64("num-threads", T);
-            std::string outName;
-            chk.mandatoryOut("graph-out", outName);          // (optional in the reference: see GossCmdPoolSamples)
-            strings kmerSets, fastas, fastqs;
-            if (opts.count("kmer-set-in")) kmerSets = opts.strs("kmer-set-in");
-            chk.expand("kmer-sets-in", kmerSets);
-            chk.repeatingIn("fasta-in", fastas);
-            chk.expand("fastas-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.expand("fastqs-in", fastqs);
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0, budgetGb = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-            cxt.tmpDir = tmpDirOption(opts.vals);
-            try
-            {
-                GossCmdPoolSamples cmd(K, S, N, T, outName, fastas, fastqs, kmerSets);
-                cmd(cxt);
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "count-components")
-        {
-            // GossCmdFactoryCountComponents::create (GossCmdCountComponents.cc:314-350)
-            static const OptDef kComponents[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"graph-out", "O", kString, "name of the output graph object"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kComponents) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            std::string in, outName;
-            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-            else if (opts.strs("graph-in").size() != 1)
-            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-            else in = opts.str("graph-in");
-            if (opts.count("graph-out")) outName = opts.str("graph-out");
-            strings fastas, fastqs, lines;
-            chk.repeatingIn("fasta-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0, budgetGb = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-            try
-            {
-                GossCmdCountComponents cmd(in, outName, fastas, fastqs, lines);
-                cmd(cxt);
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "build-subgraph")
-        {
-            // GossCmdFactoryBuildSubgraph::create (GossCmdBuildSubgraph.cc:215-268)
-            static const OptDef kSubgraph[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"graph-out", "O", kString, "name of the output graph object"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-                {"buffer-size", "B", kU64, "maximum size (in GB) for in-memory buffers (default: 2)"},
-                {"radius", "", kU64, "distance of the furthest node to include from any source"},
-                {"linear-paths", "", kFlag, "interpret radius in terms of linear paths, not nodes"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kSubgraph) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            std::string in, outName;
-            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-            else if (opts.strs("graph-in").size() != 1)
-            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-            else in = opts.str("graph-in");
-            chk.mandatoryOut("graph-out", outName);
-            strings fastas, fastqs, lines;
-            chk.repeatingIn("fasta-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            uint64_t radius = 1, B = 2;
-            chk.optionalU64("radius", radius);
-            chk.optionalU64("buffer-size", B);
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0, budgetGb = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-            try
-            {
-                GossCmdBuildSubgraph cmd(in, outName, fastas, fastqs, lines, radius, opts.count("linear-paths") != 0, B << 30);
-                cmd(cxt);
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "extract-reads" || cmdName == "filter-reads")
-        {
-            // GossCmdFactoryExtractReads::create (GossCmdExtractReads.cc:113-139), GossCmdFactoryFilterReads::create
-            // (GossCmdFilterReads.cc:312-349)
-            const bool isFilter = cmdName == "filter-reads";
-            static const OptDef kReads[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-            };
-            static const OptDef kExtract[] = {
-                {"output-file", "o", kString, "output file name ('-' for standard output)"},
-            };
-            static const OptDef kFilter[] = {
-                {"match-file", "", kString, "a file to put matching reads into"},
-                {"non-match-file", "", kString, "a file to put non-matching reads into"},
-                {"pairs", "", kFlag, "treat reads as pairs"},
-                {"count", "", kFlag, "generate histogram of matching kmers per read"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kReads) t.defs.push_back(d);
-            if (isFilter) for (auto& d : kFilter) t.defs.push_back(d);
-            else for (auto& d : kExtract) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            std::string in;
-            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-            else if (opts.strs("graph-in").size() != 1)
-            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-            else in = opts.str("graph-in");
-            strings fastas, fastqs, lines;
-            chk.repeatingIn("fasta-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            std::string outName = "-", matchName, nonMatchName;
-            uint64_t T = 4;
-            if (isFilter)
-            {
-                if (opts.count("match-file")) matchName = opts.str("match-file");
-                if (opts.count("non-match-file")) nonMatchName = opts.str("non-match-file");
-                chk.optionalU64("num-threads", T);
-            }
-            else if (opts.count("output-file"))
-            {
-                outName = opts.str("output-file");
-                if (outName != "-")
-                {
-                    FILE* fp = fopen(outName.c_str(), "wb");      // FileCreateCheck(fac, false)
-                    if (!fp)
-                    {
-                        chk.errors += "The given value of the option output-file was invalid.\n";
-                        chk.errors += "\tcannot create file '" + outName + "'\n";
-                    }
-                    else fclose(fp);
-                }
-            }
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            try
-            {
-                if (isFilter)
-                {
-                    GossCmdFilterReads cmd(in, fastas, fastqs, lines, opts.count("pairs") != 0, opts.count("count") != 0, T, matchName, nonMatchName);
-                    cmd(cxt);
-                }
-                else { GossCmdExtractReads cmd(in, fastas, fastqs, lines, outName); cmd(cxt); }
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "group-reads")
-        {
-            // GossCmdFactoryGroupReads::create (GossCmdGroupReads.cc:1037-1084)
-            static const OptDef kGroup[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-                {"max-memory", "M", kString, "maximum memory (in GB) to use (default: unlimited)"},
-                {"pairs", "", kFlag, "treat reads as pairs"},
-                {"lhs-name", "", kString, "name for left-hand side reads"},
-                {"rhs-name", "", kString, "name for right-hand side reads"},
-                {"output-filename-prefix", "", kString, "prefix for output files"},
-                {"dont-write-reads", "", kFlag, "do not produce any output read files"},
-                {"preserve-read-order", "", kFlag, "maintain the same relative ordering of reads in output files"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kGroup) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            std::string in;
-            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-            else if (opts.strs("graph-in").size() != 1)
-            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-            else in = opts.str("graph-in");
-            strings fastas, fastqs, lines;
-            chk.repeatingIn("fasta-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            double M = 1.0e9;
-            if (opts.count("max-memory"))
-            {
-                const std::string& v = opts.str("max-memory");
-                char* end = nullptr;
-                errno = 0;
-                M = strtod(v.c_str(), &end);
-                if (v.empty() || errno || *end) throw Error::Usage("the argument ('" + v + "') for option '--max-memory' is invalid\n");
-            }
-            uint64_t T = 4;
-            chk.optionalU64("num-threads", T);
-            std::string lhsName = "lhs", rhsName = "rhs", prefix;
-            if (opts.count("lhs-name")) lhsName = opts.str("lhs-name");
-            if (opts.count("rhs-name")) rhsName = opts.str("rhs-name");
-            if (opts.count("output-filename-prefix")) prefix = opts.str("output-filename-prefix");
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            try
-            {
-                GossCmdGroupReads cmd(in, fastas, fastqs, lines, opts.count("pairs") != 0, M, T, lhsName, rhsName, prefix,
-                                      opts.count("dont-write-reads") != 0, opts.count("preserve-read-order") != 0);
-                cmd(cxt);
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "elect-reads")
-        {
-            // ElectCmdFactoryGroup::create (ElectApp.cc:703-783) with electus' own option names (:806-820)
-            static const OptDef kElect[] = {
-                {"ref-fasta", "", kStrings, "reference file in FASTA format"},
-                {"ref-index", "", kStrings, "prefix of reference index"},
-                {"pool", "", kString, "prefix of a pool written by pool-samples, used as the references"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-                {"max-memory", "M", kString, "maximum memory (in GB) to use"},
-                {"kmer-size", "K", kU64, "kmer size to use (default 25)"},
-                {"pairs", "", kFlag, "treat reads as pairs"},
-                {"dont-write-reads", "", kFlag, "do not produce any output read files"},
-                {"preserve-read-order", "", kFlag, "maintain the same relative ordering of reads in output files"},
-                {"ref-threshold", "", kU64, "the minimum number of references a read must match (default: all of them)"},
-                {"match-prefix", "", kString, "filename prefix for matching reads"},
-                {"non-match-prefix", "", kString, "filename prefix for non-matching reads"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kElect) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            strings refFastas, refIndexes, fastas, fastqs, lines;
-            chk.repeatingIn("ref-fasta", refFastas);
-            if (opts.count("ref-index")) refIndexes = opts.strs("ref-index");
-            chk.repeatingIn("fasta-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            uint64_t K = 25;
-            if (opts.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
-            if (K == 0) { chk.errors += "The given value of the option kmer-size was invalid.\n\tvalue 0 is out of range.\n"; chk.suggestUsage = true; }
-            double M = 1.0e9;
-            if (opts.count("max-memory"))
-            {
-                const std::string& v = opts.str("max-memory");
-                char* end = nullptr;
-                errno = 0;
-                M = strtod(v.c_str(), &end);
-                if (v.empty() || errno || *end) throw Error::Usage("the argument ('" + v + "') for option '--max-memory' is invalid\n");
-            }
-            uint64_t T = 4;
-            chk.optionalU64("num-threads", T);
-            uint64_t refThreshold = ~0ULL;
-            chk.optionalU64("ref-threshold", refThreshold);
-            std::string match, nonMatch, pool;
-            if (opts.count("match-prefix")) match = opts.str("match-prefix");
-            if (opts.count("non-match-prefix")) nonMatch = opts.str("non-match-prefix");
-            if (opts.count("pool")) pool = opts.str("pool");
-            const size_t nrefs = refFastas.size() + refIndexes.size();
-            if (pool.empty() && nrefs == 0) { chk.errors += "no references: give ref-fasta, ref-index or pool.\n"; chk.suggestUsage = true; }
-            if (!pool.empty() && nrefs) { chk.errors += "pool stands in for the references: ref-fasta and ref-index cannot be given with it.\n"; chk.suggestUsage = true; }
-            if (nrefs > 64)
-            { chk.errors += num(nrefs) + " references were given; a read's word holds at most 64.\n"; chk.suggestUsage = true; }
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0, budgetGb = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-            cxt.tmpDir = tmpDirOption(opts.vals);
-            try
-            {
-                GossCmdElectReads cmd(K, refThreshold, refFastas, refIndexes, pool, fastas, fastqs, lines, opts.count("pairs") != 0, M, T, match, nonMatch,
-                                      opts.count("preserve-read-order") != 0);
-                cmd(cxt);
-            }
-            catch (Error& e) { if (e.usage.empty()) e.cmd = cmdName; throw; }      // (a reference of another K is a usage error)
-            return 0;
-        }
-        if (cmdName == "annotate-kmers" || cmdName == "classify-reads")
-        {
-            // GossCmdFactoryAnnotateKmers::create (GossCmdAnnotateKmers.cc:402-433), GossCmdFactoryClassifyReads::create
-            // (GossCmdClassifyReads.cc:512-557)
-            const bool isAnnotate = cmdName == "annotate-kmers";
-            static const OptDef kAnnotate[] = {
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"annotation-list", "", kString, "A file containing a list of graph names, 1 per line."},
-                {"phylogeny", "", kString, "A file containing a list of merges to perform to construct the phylogenetic tree."},
-            };
-            static const OptDef kClassify[] = {
-                {"buffer-size", "B", kU64, "maximum size (in GB) for in-memory buffers (default: 2)"},
-                {"graph-in", "G", kStrings, "name of the input graph object"},
-                {"fasta-in", "I", kStrings, "input file in FASTA format"},
-                {"fastq-in", "i", kStrings, "input file in FASTQ format"},
-                {"line-in", "", kStrings, "input file with one sequence per line"},
-                {"pairs", "", kFlag, "treat reads as pairs"},
-            };
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            if (isAnnotate) for (auto& d : kAnnotate) t.defs.push_back(d);
-            else for (auto& d : kClassify) t.defs.push_back(d);
-            for (auto& d : kGpuSpecific) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty())
-            {
-                if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-                throw Error::Usage(bad);
-            }
-            Severity sev = opts.count("verbose") ? info : warning;
-            std::unique_ptr<Logger> logger;
-            if (opts.count("log-file"))
-            {
-                FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-                if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-                logger.reset(new Logger(fp, sev, true));
-            }
-            else logger.reset(new Logger(stderr, sev));
-            Checker chk{opts, std::string(), false};
-            std::string in;
-            if (!opts.count("graph-in")) { chk.errors += "mandatory option graph-in was not given.\n"; chk.suggestUsage = true; }
-            else if (opts.strs("graph-in").size() != 1)
-            { chk.errors += "mandatory option graph-in must be supplied exactly once.\n"; chk.suggestUsage = true; }
-            else in = opts.str("graph-in");
-            std::string annotList, phylogeny;
-            strings fastas, fastqs, lines;
-            uint64_t B = 2;
-            if (isAnnotate)
-            {
-                for (const auto& m : {std::make_pair("annotation-list", &annotList), std::make_pair("phylogeny", &phylogeny)})
-                {
-                    if (!opts.count(m.first)) { chk.errors += std::string("mandatory option ") + m.first + " was not given.\n"; chk.suggestUsage = true; }
-                    else *m.second = opts.str(m.first);
-                }
-            }
-            else
-            {
-                chk.repeatingIn("fasta-in", fastas);
-                chk.repeatingIn("fastq-in", fastqs);
-                chk.repeatingIn("line-in", lines);
-                chk.optionalU64("buffer-size", B);
-            }
-            uint64_t T = 4;
-            chk.optionalU64("num-threads", T);
-            if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-            chk.throwIfNecessary();
-            GossCmdContext cxt{*logger, cmdName};
-            uint64_t dev = 0;
-            if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-            try
-            {
-                if (isAnnotate) { GossCmdAnnotateKmers cmd(in, annotList, phylogeny, T); cmd(cxt); }
-                else { GossCmdClassifyReads cmd(in, fastas, fastqs, lines, B << 30, T, opts.count("pairs") != 0); cmd(cxt); }
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            return 0;
-        }
-        if (cmdName == "synth-reads")
-        {
-            // goss synth-reads <nreads> <read_len> <genome_len> <seed> <out.fq>: the bench's
-            // deterministic synthetic read set as 4-line FASTQ
-            if (argc != 7) throw Error::Usage("usage: goss synth-reads <nreads> <read-len> <genome-len> <seed> <out.fq>\n");
-            uint64_t n = toU64("nreads", argv[2]), L = toU64("read-len", argv[3]), G = toU64("genome-len", argv[4]);
-            uint64_t seed = toU64("seed", argv[5]);
-            FILE* fp = fopen(argv[6], "wb");
-            if (!fp) throw Error::Errno(argv[6], errno);
-            const uint64_t per = 65536;
-            std::vector<char> bases(per * (L + 1));
-            std::string out;
-            std::string qual(L, 'I');
-            for (uint64_t r0 = 0; r0 < n; r0 += per)
-            {
-                uint64_t m = std::min(per, n - r0);
-                if (goss_synth_reads_host(bases.data(), m, (uint32_t)L, G, seed, r0) != GOSS_OK)
-                    throw Error::General("synth-reads: invalid arguments\n");
-                out.clear();
-                for (uint64_t i = 0; i < m; ++i)
-                {
-                    out += "@r"; out += std::to_string(r0 + i); out += '\n';
-                    out.append(bases.data() + i * (L + 1), L + 1);
-                    out += "+\n"; out += qual; out += '\n';
-                }
-                if (fwrite(out.data(), 1, out.size(), fp) != out.size()) { fclose(fp); throw Error::Write(argv[6]); }
-            }
-            fclose(fp);
-            return 0;
-        }
-        if (cmdName == "dump-bases")
-        {
-            // diagnostic: print exactly the byte stream the build commands hand to the device
-            // (each read's bases followed by '\n'), inputs in the order line, fasta, fastq
-            OptTable t;
-            for (auto& d : kGlobal) t.defs.push_back(d);
-            for (auto& d : kCommon) t.defs.push_back(d);
-            Parsed opts; std::string bad;
-            parseArgs(argc, argv, 2, t, opts, bad);
-            if (!bad.empty()) throw Error::Usage(bad);
-            uint64_t reads = 0;
-            ReadSink sink = [&](const char* seq, size_t len) { fwrite(seq, 1, len, stdout); fputc('\n', stdout); };
-            strings fastas, fastqs, lines;
-            Checker chk{opts, std::string(), false};
-            chk.repeatingIn("fasta-in", fastas);
-            chk.expand("fastas-in", fastas);
-            chk.repeatingIn("fastq-in", fastqs);
-            chk.expand("fastqs-in", fastqs);
-            chk.repeatingIn("line-in", lines);
-            chk.throwIfNecessary();
-            try
-            {
-                for (auto& f : lines) reads += parseLines(f, sink);
-                for (auto& f : fastas) reads += parseFasta(f, sink);
-                uint64_t T = 1;
-                chk.optionalU64("num-threads", T);
-                for (auto& f : fastqs)
-                {
-                    // -T > 1 exercises the parallel parser (same byte stream, file order)
-                    HostAlloc heap{[](size_t n) { return malloc(n); }, [](void* p) { free(p); }, false, nullptr, nullptr, nullptr};
-                    // GOSS_DUMP_PACKED=1: the chunks go through the workers' 2-bit packer and are unpacked here the
-                    // way the device unpacks them (a base letter in upper case, a newline for every non-base)
-                    PackedPush viaPacked;
-                    viaPacked.push = [&](const uint32_t* codes, const uint16_t* bad, size_t n, std::function<void()> release) {
-                        std::string out(n, '\n');
-                        for (size_t i = 0; i < n; ++i)
-                            if (!((bad[i / 16] >> (i % 16)) & 1u)) out[i] = "ACGT"[(codes[i / 16] >> (2 * (i % 16))) & 3u];
-                        fwrite(out.data(), 1, n, stdout);
-                        release();
-                    };
-                    uint64_t r = parseFastqParallel(f, (unsigned)std::min<uint64_t>(T, maxFramers()), parseChunkBytes(),
-                                                    [&](const char* p, size_t n) { fwrite(p, 1, n, stdout); }, heap, nullptr,
-                                                    std::getenv("GOSS_DUMP_PACKED") ? &viaPacked : nullptr);
-                    if (r == ~0ULL) r = parseFastq(f, sink);
-                    reads += r;
-                }
-            }
-            catch (Error& e) { e.cmd = cmdName; throw; }
-            fflush(stdout);
-            if (reads == 0) { Error e = Error::General("No valid reads."); e.cmd = cmdName; throw e; }
-            return 0;
-        }
-        if (!isKmerSet && !isGraph)
-        {
-            if (cmdName != "help") std::cerr << "unknown command '" << cmdName << "'" << std::endl;
-            printHelp(cmdName, nullptr);
-            return 0;
-        }
-
-        OptTable t;
-        for (auto& d : kGlobal) t.defs.push_back(d);
-        for (auto& d : kCommon) t.defs.push_back(d);
-        if (isKmerSet) for (auto& d : kKmerSetSpecific) t.defs.push_back(d);
-        for (auto& d : kGpuSpecific) t.defs.push_back(d);
-
-        Parsed opts;
-        std::string bad;
-        parseArgs(argc, argv, 1 + argsToSkip, t, opts, bad);
-        if (!bad.empty())
-        {
-            if (opts.count("help")) { std::cerr << bad; printHelp(cmdName, &t); return 1; }
-            throw Error::Usage(bad);
-        }
-
-        // logging (App.cc:291-301)
-        Severity sev = opts.count("verbose") ? info : warning;
-        std::unique_ptr<Logger> logger;
-        if (opts.count("log-file"))
-        {
-            FILE* fp = fopen(opts.str("log-file").c_str(), "w");
-            if (!fp) throw Error::Errno(opts.str("log-file"), errno);
-            logger.reset(new Logger(fp, sev, true));
-        }
-        else logger.reset(new Logger(stderr, sev));
-        if (opts.count("debug"))
-            for (auto& d : opts.strs("debug")) (*logger)(warning, "unknown debug: " + d);
-
-        // the factory (GossCmdBuildKmerSet.cc:151-198, GossCmdBuildGraph.cc:428-476)
-        Checker chk{opts, std::string(), false};
-        uint64_t K = 0;
-        chk.mandatoryU64("kmer-size", K, isGraph ? 62 : 63);
-        uint64_t B = 2;
-        chk.optionalU64("buffer-size", B);
-        if (isGraph && B > 24)
-        {
-            (*logger)(warning, "Unsupported --buffer-size " + num(B) + ", truncating to 24.");
-            B = 24;
-        }
-        // BackyardHash::maxSlotBits(B << 30) = floor(log2((B<<30)/22)) (BackyardHash.hh:414-418)
-        uint64_t S = 0;
-        { uint64_t slots = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16)); S = (uint64_t)std::log2((double)slots); }
-        if (isKmerSet) chk.optionalU64("log-hash-slots", S);
-        uint64_t N = (uint64_t)((double)(B << 30) / (1.5 * 4 + 16));
-        uint64_t T = 4;
-        chk.optionalU64("num-threads", T);
-        std::string outName;
-        chk.mandatoryOut("graph-out", outName);
-        strings fastas, fastqs, lines;
-        chk.repeatingIn("fasta-in", fastas);
-        chk.expand("fastas-in", fastas);
-        chk.repeatingIn("fastq-in", fastqs);
-        chk.expand("fastqs-in", fastqs);
-        chk.repeatingIn("line-in", lines);
-        if (opts.count("help")) { printHelp(cmdName, &t); return 1; }
-        chk.throwIfNecessary();
-
-        GossCmdContext cxt{*logger, cmdName};
-        uint64_t dev = 0, budgetGb = 0;
-        if (chk.optionalU64("device", dev)) cxt.device = (int)dev;
-        if (chk.optionalU64("hbm-budget", budgetGb)) cxt.hbmBudget = budgetGb << 30;
-        cxt.tmpDir = tmpDirOption(opts.vals);
-        if (!cxt.tmpDir.empty())
-            (*logger)(info, "--tmp-dir " + cxt.tmpDir + ": not needed by this build (the runs of its chunks are held in HBM and merged there; no temporary file is written)");
-        if (opts.count("devices"))
-        {
-            // "0,1,2,3": one context per listed device (an ordinal may appear twice: two contexts share that GPU)
-            const std::string& v = opts.str("devices");
-            size_t at = 0;
-            while (at <= v.size())
-            {
-                const size_t comma = std::min(v.find(',', at), v.size());
-                const std::string item = v.substr(at, comma - at);
-                if (item.empty() || item.find_first_not_of("0123456789") != std::string::npos || item.size() > 3)
-                    throw Error::Usage("--devices takes a comma-separated list of device ordinals, e.g. 0,1,2,3\n");
-                cxt.devices.push_back(atoi(item.c_str()));
-                at = comma + 1;
-            }
-            if (cxt.devices.size() > 64) throw Error::Usage("--devices: at most 64 devices\n");
-        }
-        try
-        {
-            if (isKmerSet) { GossCmdBuildKmerSet cmd(K, S, N, T, outName, fastas, fastqs, lines); cmd(cxt); }
-            else { GossCmdBuildGraph cmd(K, S, N, T, outName, fastas, fastqs, lines); cmd(cxt); }
-        }
-        catch (Error& e) { e.cmd = cmdName; throw; }
-    }
-    catch (const Error& e)
-    {
-        // the printing order of App.cc:328-417
-        if (!e.cmd.empty()) std::cerr << "error performing " << e.cmd << ":" << std::endl;
-        if (!e.parse.empty()) std::cerr << "\t'" << e.file << "': " << e.parse << std::endl;
-        if (!e.write_name.empty()) std::cerr << "\tcannot write to '" << e.write_name << "'" << std::endl;
-        if (!e.general.empty()) std::cerr << e.general;
-        if (e.err_no)
-        {
-            std::cerr << "\t";
-            if (!e.file.empty()) std::cerr << "'" << e.file << "': ";
-            std::cerr << strerror(e.err_no) << std::endl;
-        }
-        if (!e.usage.empty())
-        {
-            std::cerr << e.usage;
-            std::cerr << "use\n\tgoss " << cmdName << " -h\nfor more usage information." << std::endl;
-        }
-        return 1;
-    }
-    catch (std::exception& e)
-    {
-        std::cerr << "caught unexpected exception: " << e.what() << std::endl;
-        return 1;
-    }
-    catch (...)
-    {
-        std::cerr << "caught unknown exception" << std::endl;
-        return 1;
-    }
-    return 0;
+    fflush(stdout);
+    if (reads == 0) throw Error::General("No valid reads.");
 }
 
 }  // namespace gosshost

@@ -1,6 +1,8 @@
-// GossHost.hpp -- host-side C++ for the `goss build-kmer-set` / `goss build-graph` commands:
-// errors, logger, input files, the three read parsers, and the command classes that mirror
-// the reference's operator interface (GossCmdBuildKmerSet.hh:25-38, GossCmdBuildGraph.hh:23-29).
+// GossHost.hpp -- host-side C++ for the `goss` commands: errors, logger, input files, the three
+// read parsers, and the command classes that mirror the reference's operator interface
+// (GossCmdBuildKmerSet.hh:25-38, GossCmdBuildGraph.hh:23-29).  GossHost.cpp holds the files, the
+// parsers, the parallel FASTQ framer and the build commands; the command line -- option parser,
+// checker, the table of commands and its driver -- is GossCli.cpp.
 //
 // The parsers frame records exactly like the reference (FastqParser.hh:78-176,
 // FastaParser.hh:51-87, LineParser.hh:71-82 over PlainLineSource, LineSource.cc:17-48) but
@@ -503,8 +505,12 @@ namespace gosshost {
 void writeObjectFiles(goss_gpu_ctx* h, const std::string& out);
 void writeObjectFiles(const std::vector<goss_gpu_ctx*>& hs, const std::string& out);      // a group after goss_gpu_group_emit
 
-// App::main for the commands of this build (App.cc:176-417).
+// App::main for the commands of this build (App.cc:176-417): GossCli.cpp, one record per command in its table.
 int gossMain(int argc, char* argv[]);
+
+// The body of `goss dump-bases`: the bases of every read of the given files, one read per line, on standard output, in
+// the order line, FASTA, FASTQ; T > 1 sends the FASTQ files through the parallel framer.  Throws when there is no read.
+void dumpBases(const strings& fastas, const strings& fastqs, const strings& lines, uint64_t T);
 
 // Gives back what the parser parked between files (page-locked buffers; registered slabs are unregistered first): the
 // orderly exit's share of the tear-down (`goss` itself ends with _exit once its files are closed).

@@ -1,10 +1,15 @@
 #!/bin/bash
-# The host's framers under AddressSanitizer + UBSan (CPU only: goss dump-bases needs no device), driven by the parser
-# fuzz.  usage: bash tools/host_asan.sh [cases] [seed]
+# The host's framers and command line under AddressSanitizer + UBSan (CPU only: goss dump-bases and the checks of the
+# command line need no device), driven by the parser fuzz and tests/test_cli_surface.py.  goss is built by the Makefile's
+# own rule (its HOST_SRCS), as a stand-alone program linked with the sanitizer; libgossgpu.so is used as built.
+# usage: bash tools/host_asan.sh [cases] [seed]
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p scratch
-(cd gossamer_amd && g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -o ../scratch/goss_asan \
-    host/goss.cpp host/GossHost.cpp host/GossMerge.cpp -L. -lgossgpu -lz -lpthread -ldl -Wl,-rpath,"$PWD" -Wl,-rpath,/opt/rocm/lib)
-export GOSS_BIN="$PWD/scratch/goss_asan" ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
-exec python tools/dbg/parser_fuzz.py "${1:-200}" "${2:-1}"
+mkdir -p scratch/asan
+make -C gossamer_amd/csrc ../libgossgpu.so
+cp -p gossamer_amd/libgossgpu.so scratch/asan/
+make -C gossamer_amd/csrc OUT=../../scratch/asan CXXFLAGS="-O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer" \
+    ../../scratch/asan/goss
+export GOSS_BIN="$PWD/scratch/asan/goss" ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
+python tools/dbg/parser_fuzz.py "${1:-200}" "${2:-1}"
+exec python -m pytest tests/test_cli_surface.py -x -q

@@ -9,4 +9,5 @@ from .binding import (Context, GossGpuError, MODE_GRAPH, MODE_KMER_SET, SYMBOLS,
                       group_emit, group_exchange, group_route_exchange, load, synth_reads_host,
                       POOL_PAIR_WORDS, POOL_POS_WORDS, POOL_TILE, format_double, pool_similarity_text,
                       TAXO_MANY, TAXO_NONE, TAXO_NORMALIZE, TAXO_SYMBOLS, format_phylogeny, parse_phylogeny, phylogeny_nodes,
-                      ELECT_MAX_COLOURS, ELECT_NORMALIZE, ELECT_SYMBOLS, elect)
+                      ELECT_MAX_COLOURS, ELECT_NORMALIZE, ELECT_SYMBOLS, elect,
+                      RECOUNT_REPORT_FIELDS, RELATIVE_REPORT_FIELDS, RELATIVE_SYMBOLS)

@@ -59,6 +59,9 @@ TAXO_SYMBOLS = ["goss_gpu_object_taxo_tree_host", "goss_gpu_object_taxo_annotati
                 "goss_gpu_object_taxo_classify_reads_host", "goss_gpu_object_taxo_pair", "goss_gpu_object_taxo_pair_host",
                 "goss_gpu_object_taxo_tally", "goss_gpu_object_taxo_tally_host"]
 
+# every symbol include/goss_gpu_relative.h declares (trim-relative and merge-graph-with-reference on a finished graph)
+RELATIVE_SYMBOLS = ["goss_gpu_trim_relative", "goss_gpu_recount_from", "goss_gpu_relative_timing"]
+
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
 
@@ -79,6 +82,10 @@ PATHS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "paths", "za
 LINKS_REPORT_FIELDS = ("edges_before", "edges_after", "candidates", "links", "edges", "too_long", "major_out", "major_in", "missing_rc")
 PATHS_CUTOFF = 1
 PATHS_NO_EDGE = 0xFFFFFFFFFFFFFFFF
+
+# goss_gpu_relative_report and goss_gpu_recount_report, in the order of their fields
+RELATIVE_REPORT_FIELDS = ("edges_before", "edges_after", "forks", "below", "mirror_only")
+RECOUNT_REPORT_FIELDS = ("edges_before", "edges_after")
 
 
 # goss_gpu_segments_info and goss_gpu_segment, in the order of their fields
@@ -766,6 +773,37 @@ class Context:
         self._L.goss_gpu_paths_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(self._L.goss_gpu_paths_timing(self._h, ms))
         return dict(zip(("link", "flag", "gather", "walk", "compact"), (float(x) for x in ms)))
+
+    def _relative_pass(self, fn, fields, arg):
+        class Report(C.Structure):
+            _fields_ = [(name, C.c_uint64) for name in fields]
+        rep = Report()
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, type(arg), C.POINTER(Report)]
+        self._check(fn(self._h, arg, C.byref(rep)))
+        if getattr(self, "counts", None) is not None:
+            self.counts.distinct = int(rep.edges_after)                        # what result() copies
+        return {name: int(getattr(rep, name)) for name in fields}
+
+    def trim_relative(self, rel=0.02):
+        """Between finish and emit, graph mode: trim-relative on the device (goss_gpu_trim_relative): at every node with
+        two or more outgoing edges, an edge whose multiplicity is below `rel` times the node's sum goes, and its reverse
+        complement with it.  The context's result becomes the trimmed graph; returns the report dict."""
+        return self._relative_pass(self._L.goss_gpu_trim_relative, RELATIVE_REPORT_FIELDS, C.c_double(rel))
+
+    def recount_from(self, obj):
+        """Between finish and emit, graph mode: merge-graph-with-reference on the device (goss_gpu_recount_from): the
+        edges that the open graph `obj` holds too stay, with its multiplicities.  The context's result becomes the
+        merged graph; emit_estimate(report["edges_before"]) writes the reference's files.  Returns the report dict."""
+        return self._relative_pass(self._L.goss_gpu_recount_from, RECOUNT_REPORT_FIELDS, C.c_void_p(obj._h.value))
+
+    def relative_timing(self):
+        """{phase: ms} of the last trim_relative (judge, mirror, compact) or recount_from (judge = the lookup, mirror 0,
+        compact) pass (goss_gpu_relative_timing)"""
+        ms = (C.c_float * 3)()
+        self._L.goss_gpu_relative_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(self._L.goss_gpu_relative_timing(self._h, ms))
+        return dict(zip(("judge", "mirror", "compact"), (float(x) for x in ms)))
 
     def segments_build(self, min_length=0, min_coverage=0, line_breaks=True):
         """Between finish and emit, graph mode: build the linear segments on the device (goss_gpu_segments_build) and

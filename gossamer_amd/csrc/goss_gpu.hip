@@ -227,6 +227,7 @@ struct goss_gpu_ctx {
     void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
     uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
     float paths_ms[5] = {};               // link, flag, gather, walk, compact of the last trim-paths / clip-links pass
+    float relative_ms[3] = {};            // judge, mirror, compact of the last trim-relative pass; lookup, -, compact of the last recount
     // the held result: permanent room above everything else from held.lo on, held until its release entry point or
     // the next call that may allocate (guarded() gives it back first).  goss_gpu_segments_build: the segment table and
     // the text (seg_*); goss_gpu_entries_build: the images of the EntryEdgeSet, which are the file list
@@ -3346,6 +3347,28 @@ int goss_gpu_paths_timing(goss_gpu_ctx* c, float* ms)
     return GOSS_OK;
 }
 
+int goss_gpu_trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
+{
+    if (!c || !out) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (const int st = graph_pass_state(c, "trim_relative", "trim_relative works on a graph", "trim_relative belongs between finish and emit")) return st;
+    if (!std::isfinite(rel)) { c->last_error = "trim_relative: the relative cutoff must be a finite number"; return GOSS_ERR_INVALID_ARG; }
+    const int rc = guarded(c, [&]() {
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        if (c->words == 1) trim_relative<Key1>(c, rel, out); else trim_relative<Key2>(c, rel, out);
+        t.stop();
+    });
+    if (rc != GOSS_OK) std::memset(out, 0, sizeof *out);
+    return rc;
+}
+
+int goss_gpu_relative_timing(goss_gpu_ctx* c, float* ms)
+{
+    if (!c || !ms) return GOSS_ERR_INVALID_ARG;
+    for (int i = 0; i < 3; ++i) ms[i] = c->relative_ms[i];
+    return GOSS_OK;
+}
+
 int goss_gpu_segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage, uint32_t flags, goss_gpu_segments_info* out)
 {
     if (!c || !out || (flags & ~(uint32_t)GOSS_SEGMENTS_NO_LINE_BREAKS)) return GOSS_ERR_INVALID_ARG;
@@ -3757,6 +3780,32 @@ int goss_gpu_object_lookup(goss_gpu_object* o, const void* d_keys, uint64_t n, u
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(query_lookup_kernel<Key2>), grid, dim3(256), 0, o->stream, o->q, (const Key2*)d_keys, n, flags, d_counts, o->d_bad);
     });
+}
+
+// merge-graph-with-reference (TransCmdMergeGraphWithReference.cc:47-114): recount_from of graph_passes.hpp, over the
+// context's result and an open graph that is only read
+int goss_gpu_recount_from(goss_gpu_ctx* c, goss_gpu_object* ref, goss_gpu_recount_report* out)
+{
+    if (!c || !ref || !out) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (const int st = graph_pass_state(c, "recount_from", "recount_from works on a graph", "recount_from belongs between finish and emit")) return st;
+    if (ref->kind != GOSS_OBJECT_GRAPH) { c->last_error = "recount_from: the reference must be a Graph"; return GOSS_ERR_INVALID_ARG; }
+    if (ref->K != c->k)
+    {
+        c->last_error = "recount_from: graphs involved in a merge must have the same kmer-size: the context has k=" + std::to_string(c->k) +
+                        ", the reference has k=" + std::to_string(ref->K);
+        return GOSS_ERR_INVALID_ARG;
+    }
+    if (ref->asymmetric) { c->last_error = "recount_from: the reference preserves sense; asymmetric graphs are not handled"; return GOSS_ERR_INVALID_ARG; }
+    if (ref->device != c->device) { c->last_error = "recount_from: the reference lives on another device"; return GOSS_ERR_INVALID_ARG; }
+    const int rc = guarded(c, [&]() {
+        HIP_TRY(hipStreamSynchronize(ref->stream));      // (what the reference's own stream still does with its images)
+        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        if (c->words == 1) recount_from<Key1>(c, ref->q, out); else recount_from<Key2>(c, ref->q, out);
+        t.stop();
+    });
+    if (rc != GOSS_OK) std::memset(out, 0, sizeof *out);
+    return rc;
 }
 
 int goss_gpu_object_node_ranks(goss_gpu_object* o, const void* d_nodes, uint64_t n, uint32_t flags, uint64_t* d_begin, uint64_t* d_end)

@@ -29,5 +29,6 @@
 #include "kernels_elect.hpp"
 #include "kernels_components.hpp"
 #include "kernels_subgraph.hpp"
+#include "kernels_relative.hpp"
 #include "kernels_near.hpp"
 #include "kernels_pool.hpp"

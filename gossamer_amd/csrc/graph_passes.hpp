@@ -10,7 +10,9 @@
 // prune_tips_once is link_graph and the tip walk; segments_build and entries_build are link_graph, rank_lists and
 // their own records; components_build and components_keep are link_graph and a union-find over the links;
 // components_grow is link_graph and the passes of build-subgraph over the marks.  What a build leaves behind for
-// later calls is the context's one held result (build_held).
+// later calls is the context's one held result (build_held).  trim_relative and recount_from (kernels_relative.hpp)
+// need no links: a judge or lookup pass over the edges, the bucket table alone where mirror images are looked up,
+// and the compaction of prune-tips.
 #pragma once
 
 // Temporaries of one call, given back on every way out (an exception included).
@@ -1026,4 +1028,138 @@ uint64_t components_keep_marked(goss_gpu_ctx* c)
     const uint64_t m = c->words == 1 ? components_keep_marked<Key1>(c) : components_keep_marked<Key2>(c);
     t.stop();
     return m;
+}
+
+// ---- trim-relative, merge-graph-with-reference ----------------------------------------------------------------------
+
+constexpr uint64_t kRelativeNoEdge = ~0ULL;
+
+struct RelativeBitmaps { uint64_t ntiles, zap_words; };
+inline RelativeBitmaps relative_bitmaps(uint64_t n64)
+{
+    static_assert(kRedTile % 64 == 0, "a wave writes 64 bits of the bitmap");
+    const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
+    return RelativeBitmaps{ntiles, ntiles * (kRedTile / 32)};
+}
+
+// The tail both passes share: the survivors of the removal bitmap `zap`, with `counts`, become the result (always when
+// `counts` are new ones, else only when an edge goes).  Returns their number.
+template <class K>
+uint64_t relative_compact(goss_gpu_ctx* c, const uint32_t* counts, const uint32_t* zap, const RelativeBitmaps& b, bool new_counts)
+{
+    const uint64_t n64 = c->M;
+    uint64_t* tile_counts = (uint64_t*)c->arena.temp((b.ntiles + 1) * 8);
+    hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)b.ntiles), dim3(kTB), 0, c->stream, zap, n64, tile_counts);
+    uint64_t* hm = pinned_words(c);
+    scan_with_total(c, tile_counts, b.ntiles, hm);
+    sync_checked(c);
+    const uint64_t m = hm[0];
+    if (m != n64 || new_counts) replace_result<K>(c, (const K*)c->res_keys, counts, n64, zap, tile_counts, b.ntiles, m);
+    return m;
+}
+
+// trim-relative over the result (TransCmdTrimRelative.cc:81-191; kernels_relative.hpp states what is computed): judge,
+// and where an edge is below its node's threshold the bucket table of the link pass, the mirror pass and the
+// compaction of prune-tips.  Two bitmaps, the table (about four bytes an edge) and the survivors once more are the
+// working room; none of the link arrays is built.  Nothing of the context changes before the survivors are complete.
+template <class K>
+void trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
+{
+    static_assert(sizeof(goss_gpu_relative_report) == 5 * 8 && sizeof(RelativeReport) <= 128, "relative report layout");
+    goss_gpu_relative_report rep{};
+    const uint64_t n64 = c->M;
+    rep.edges_before = rep.edges_after = n64;
+    for (float& x : c->relative_ms) x = 0.f;
+    if (n64 == 0) { *out = rep; return; }
+    const uint32_t n = link_edges(c, "trim_relative");
+    const uint32_t bits = tips_bucket_bits(n, c->len);
+    const RelativeBitmaps b = relative_bitmaps(n64);
+    {
+        const uint64_t need = b.zap_words * 8 + link_table_bytes(bits) + (b.ntiles + 1) * 8 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    const K* keys = (const K*)c->res_keys;
+    uint32_t* below = (uint32_t*)c->arena.temp(b.zap_words * 4);
+    uint32_t* zap = (uint32_t*)c->arena.temp(b.zap_words * 4);
+    RelativeReport* d_rep = (RelativeReport*)c->arena.temp(sizeof(RelativeReport));
+    RelativeReport* h = pinned_report<RelativeReport>(c);
+    const dim3 block(kTB), few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kTipsGridBlocks));
+
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    HIP_TRY(hipMemsetAsync(below, 0, b.zap_words * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(RelativeReport), c->stream));
+    HIP_TRY(hipMemsetAsync(&d_rep->bad, 0xFF, 8, c->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_judge_kernel<K>), few, block, 0, c->stream, keys, (const uint32_t*)c->res_counts, n64, rel, below, d_rep);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(RelativeReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    sync_checked(c);
+    rep.forks = h->forks;
+    rep.below = h->below;
+    HIP_TRY(hipEventElapsedTime(&c->relative_ms[0], ev.e[0], ev.e[1]));
+    if (rep.below == 0) { *out = rep; return; }
+
+    uint32_t* table = bits ? (uint32_t*)c->arena.temp(link_table_bytes(bits)) : nullptr;
+    HIP_TRY(hipMemcpyAsync(zap, below, b.zap_words * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (bits)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_table_kernel<K>), dim3(grid_for(n64, kTB)), block, 0, c->stream, keys, n, c->len, bits, table);
+    const uint64_t nwords = b.zap_words / 2;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_mirror_kernel<K>), dim3((uint32_t)std::min<uint64_t>(grid_for(nwords, kTB), kTipsGridBlocks)), block, 0,
+                       c->stream, (const uint64_t*)below, nwords, keys, n, c->len, bits, (const uint32_t*)table, zap, d_rep);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(RelativeReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    sync_checked(c);
+    if (h->bad != kRelativeNoEdge)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "trim_relative: edge " + std::to_string(h->bad) +
+                                                    " has no reverse complement in the graph (lint-graph reports such edges)"};
+    const uint64_t m = relative_compact<K>(c, c->res_counts, zap, b, false);
+    HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    sync_checked(c);
+    HIP_TRY(hipEventElapsedTime(&c->relative_ms[1], ev.e[1], ev.e[2]));
+    HIP_TRY(hipEventElapsedTime(&c->relative_ms[2], ev.e[2], ev.e[3]));
+    rep.edges_after = m;
+    rep.mirror_only = (n64 - m) - rep.below;
+    *out = rep;
+}
+
+// merge-graph-with-reference over the result (TransCmdMergeGraphWithReference.cc:79-106): the edges the reference `q`
+// holds stay, with its multiplicities.  The new counts (4 bytes an edge), one bitmap and the survivors once more are
+// the working room.  Nothing of the context changes before the survivors are complete; the reference is only read.
+template <class K>
+void recount_from(goss_gpu_ctx* c, const QueryObj& q, goss_gpu_recount_report* out)
+{
+    goss_gpu_recount_report rep{};
+    const uint64_t n64 = c->M;
+    rep.edges_before = rep.edges_after = n64;
+    for (float& x : c->relative_ms) x = 0.f;
+    if (n64 == 0) { *out = rep; return; }
+    const RelativeBitmaps b = relative_bitmaps(n64);
+    {
+        const uint64_t need = b.zap_words * 4 + n64 * 4 + (b.ntiles + 1) * 8 + n64 * (sizeof(K) + 4) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    uint32_t* absent = (uint32_t*)c->arena.temp(b.zap_words * 4);
+    uint32_t* counts = (uint32_t*)c->arena.temp(n64 * 4);
+    RelativeReport* d_rep = (RelativeReport*)c->arena.temp(sizeof(RelativeReport));
+    RelativeReport* h = pinned_report<RelativeReport>(c);
+    const dim3 block(kTB), few((uint32_t)std::min<uint64_t>(grid_for(n64, kTB), kTipsGridBlocks));
+
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    HIP_TRY(hipMemsetAsync(absent, 0, b.zap_words * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep, 0xFF, sizeof(RelativeReport), c->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_recount_kernel<K>), few, block, 0, c->stream, q, (const K*)c->res_keys, n64, counts, absent, d_rep);
+    HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(RelativeReport), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    sync_checked(c);
+    if (h->bad != kRelativeNoEdge)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "recount_from: the reference's index cannot answer for edge " + std::to_string(h->bad) + " (damaged object)"};
+    rep.edges_after = relative_compact<K>(c, counts, absent, b, true);
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    sync_checked(c);
+    HIP_TRY(hipEventElapsedTime(&c->relative_ms[0], ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&c->relative_ms[2], ev.e[1], ev.e[2]));
+    *out = rep;
 }

@@ -1,13 +1,15 @@
 // GossCli.cpp -- the goss command line (App.cc:176-417, GossApp.cc:145-202, GossOptionChecker.hh): the option parser,
 // the checker, one `create` function per command in the manner of the reference's GossCmdFactory...::create, the table
 // of commands (kCommands) and the one driver that takes a command from its arguments to its run.  A new command is one
-// record in kCommands and its create function.
+// record in kCommands and its create function.  The driver takes the executable (App: its name and its table) as a
+// parameter: `translucent` (TranslucentApp.cc) is the same driver over four of goss's records and two of its own.
 #include "GossHost.hpp"
 
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cerrno>
 #include <cmath>
 #include <cstring>
@@ -154,6 +156,14 @@ const OptDef kElectOut[] = {
     {"ref-threshold", "", kU64, "the minimum number of references a read must match (default: all of them)"},
     {"match-prefix", "", kString, "filename prefix for matching reads"},
     {"non-match-prefix", "", kString, "filename prefix for non-matching reads"},
+};
+// translucent's own (TranslucentApp.cc:97, TransCmdMergeGraphWithReference.cc:141-142).  relative-cutoff is text here as
+// in kTrimPrune: the command that takes it converts it
+const OptDef kRelativeCutoff[] = {
+    {"relative-cutoff", "", kString, "relative coverage cutoff"},
+};
+const OptDef kGraphRef[] = {
+    {"graph-ref", "", kString, "name of the reference graph object"},
 };
 const OptDef kAnnotate[] = {
     {"annotation-list", "", kString, "A file containing a list of graph names, 1 per line."},
@@ -765,13 +775,47 @@ Run createClassifyReads(Checker& chk)
     return run(GossCmdClassifyReads(in, fastas, fastqs, lines, B << 30, T, chk.flag("pairs")));
 }
 
+// TransCmdFactoryTrimRelative::create (TransCmdTrimRelative.cc:284-307).  The cutoff is a double as lexical_cast reads
+// it, and must be a finite number: anything else is the usage error of a malformed numeric option.
+Run createTrimRelative(Checker& chk)
+{
+    const std::string in = chk.once("graph-in");
+    std::string outName;
+    chk.mandatoryOut("graph-out", outName);
+    double relCutoff = 0.02;
+    if (chk.o.count("relative-cutoff"))
+    {
+        const std::string& s = chk.o.str("relative-cutoff");
+        char* end = nullptr;
+        errno = 0;
+        relCutoff = strtod(s.c_str(), &end);
+        if (s.empty() || isspace((unsigned char)s[0]) || errno || *end || !std::isfinite(relCutoff))
+            throw Error::Usage("the argument ('" + s + "') for option '--relative-cutoff' is invalid\n");
+    }
+    uint64_t numThreads = 4;                // (the pass is the device's)
+    chk.optionalU64("num-threads", numThreads);
+    return run(TransCmdTrimRelative(in, outName, relCutoff, numThreads));
+}
+
+// TransCmdFactoryMergeGraphWithReference::create (TransCmdMergeGraphWithReference.cc:114-133)
+Run createMergeGraphWithReference(Checker& chk)
+{
+    const std::string in = chk.once("graph-in");
+    std::string ref, outName;
+    chk.mandatory("graph-ref", ref);
+    chk.mandatoryOut("graph-out", outName);
+    return run(TransCmdMergeGraphWithReference(ref, in, outName));
+}
+
 // ---- the commands that are no factory's: their own arguments, no help of their own, no logger ----
 
-int helpCommand(int argc, char** argv);
+struct App;
+
+int helpCommand(const App& app, int argc, char** argv);
 
 // goss synth-reads <nreads> <read_len> <genome_len> <seed> <out.fq>: the bench's
 // deterministic synthetic read set as 4-line FASTQ
-int synthReadsCommand(int argc, char** argv)
+int synthReadsCommand(const App&, int argc, char** argv)
 {
     if (argc != 7) throw Error::Usage("usage: goss synth-reads <nreads> <read-len> <genome-len> <seed> <out.fq>\n");
     uint64_t n = toU64("nreads", argv[2]), L = toU64("read-len", argv[3]), G = toU64("genome-len", argv[4]);
@@ -801,7 +845,7 @@ int synthReadsCommand(int argc, char** argv)
 }
 
 // goss dump-bases: the build commands' inputs (and -T) through the framers to standard output (dumpBases)
-int dumpBasesCommand(int argc, char** argv)
+int dumpBasesCommand(const App&, int argc, char** argv)
 {
     OptTable t;
     for (auto& g : {group(kGlobal), group(kBufferSize), group(kReadLists), group(kLineIn), group(kOutAndK)}) t.add(g);
@@ -835,7 +879,18 @@ struct Command {
     std::vector<OptGroup> groups;
     unsigned flags;
     Run (*create)(Checker&);
-    int (*plain)(int argc, char** argv);    // set: run instead of the driver
+    int (*plain)(const App& app, int argc, char** argv);    // set: run instead of the driver
+};
+
+// An executable: the name its help and its errors speak under, and its commands in help order.
+struct App {
+    const char* name;
+    std::vector<const Command*> commands;
+    const Command* find(const std::string& n) const
+    {
+        for (const Command* c : commands) if (n == c->name) return c;
+        return nullptr;
+    }
 };
 
 const unsigned kAll = kHbmBudget | kTmpDir;
@@ -885,17 +940,49 @@ const Command kCommands[] = {
     {"dump-bases", nullptr, {}, 0, nullptr, dumpBasesCommand},
 };
 
+// translucent's own two commands (TranslucentApp.cc:72,76).  Both factories of the reference carry the same summary.
+const char* const kTransSummary = "create a new graph from an existing graph, using coverage information from a reference graph";
+const Command kTransCommands[] = {
+    {"trim-relative", kTransSummary, {group(kGraphIn), group(kGraphOut), group(kRelativeCutoff)}, kAll, createTrimRelative, nullptr},
+    {"merge-graph-with-reference", kTransSummary, {group(kGraphIn), group(kGraphOut), group(kGraphRef)}, kAll, createMergeGraphWithReference, nullptr},
+};
+
+const App& gossApp()
+{
+    static const App app = [] {
+        App a{"goss", {}};
+        for (auto& c : kCommands) a.commands.push_back(&c);
+        return a;
+    }();
+    return app;
+}
+
+// The commands of TranslucentApp.cc:68-76 that this build implements, in its order: goss's records for the four it
+// shares with goss, as they are, and the two above.  pop-bubbles and assemble are not built.
+const App& translucentApp()
+{
+    static const App app = [] {
+        App a{"translucent", {}};
+        for (const char* n : {"help", "build-graph", "lint-graph", "trim-graph"}) a.commands.push_back(gossApp().find(n));
+        a.commands.push_back(&kTransCommands[0]);
+        a.commands.push_back(gossApp().find("prune-tips"));
+        a.commands.push_back(&kTransCommands[1]);
+        return a;
+    }();
+    return app;
+}
+
 const char* kVersion = "1.3.0-mi355x";
 
-void printHelp(const std::string& cmdName, const OptTable* t)
+void printHelp(const App& app, const std::string& cmdName, const OptTable* t)
 {
-    std::cerr << "goss <command> [options]\n\ncommands implemented by this build:\n";
-    for (auto& c : kCommands)
-        if (c.summary)
+    std::cerr << app.name << " <command> [options]\n\ncommands implemented by this build:\n";
+    for (const Command* c : app.commands)
+        if (c->summary)
         {
-            std::string l = c.name;
+            std::string l = c->name;
             l.resize(std::max<size_t>(17, l.size() + 2), ' ');
-            std::cerr << "  " << l << c.summary << "\n";
+            std::cerr << "  " << l << c->summary << "\n";
         }
     if (t)
     {
@@ -903,9 +990,9 @@ void printHelp(const std::string& cmdName, const OptTable* t)
     }
 }
 
-int helpCommand(int, char**)
+int helpCommand(const App& app, int, char**)
 {
-    printHelp("help", nullptr);
+    printHelp(app, "help", nullptr);
     return 0;
 }
 
@@ -926,7 +1013,7 @@ void devicesOption(const std::string& v, std::vector<int>& devices)
 }
 
 // The driver: one command from its arguments to its run, the steps in the order App::main takes them.
-int runCommand(const Command& c, int argc, char** argv)
+int runCommand(const App& app, const Command& c, int argc, char** argv)
 {
     OptTable t;
     t.add(group(kGlobal));
@@ -936,7 +1023,7 @@ int runCommand(const Command& c, int argc, char** argv)
     parseArgs(argc, argv, 2, t, opts, bad);
     if (!bad.empty())
     {
-        if (opts.count("help")) { std::cerr << bad; printHelp(c.name, &t); return 1; }
+        if (opts.count("help")) { std::cerr << bad; printHelp(app, c.name, &t); return 1; }
         throw Error::Usage(bad);
     }
 
@@ -951,7 +1038,7 @@ int runCommand(const Command& c, int argc, char** argv)
 
     Checker chk{opts, logger.get()};
     Run go = c.create(chk);
-    if (opts.count("help")) { printHelp(c.name, &t); return 1; }
+    if (opts.count("help")) { printHelp(app, c.name, &t); return 1; }
     chk.throwIfNecessary();
     if (!chk.notOffered.empty()) throw Error::Usage(chk.notOffered);
     if (!chk.refused.empty())
@@ -981,22 +1068,20 @@ int runCommand(const Command& c, int argc, char** argv)
     return 0;
 }
 
-}  // namespace
-
-int gossMain(int argc, char* argv[])
+// App::main (App.cc:176-417) for one executable: the command named by the first argument, from `app`'s table.
+int appMain(const App& app, int argc, char* argv[])
 {
     std::string cmdName;
     try
     {
         for (int i = 1; i < argc; ++i)
-            if (!strcmp(argv[i], "--version")) { std::cout << "goss version " << kVersion << std::endl; return 0; }
+            if (!strcmp(argv[i], "--version")) { std::cout << app.name << " version " << kVersion << std::endl; return 0; }
 
         if (argc < 2 || (argc == 2 && (!strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")))) cmdName = "help";
         else cmdName = argv[1];
-        for (auto& c : kCommands)
-            if (cmdName == c.name) return c.plain ? c.plain(argc, argv) : runCommand(c, argc, argv);
+        if (const Command* c = app.find(cmdName)) return c->plain ? c->plain(app, argc, argv) : runCommand(app, *c, argc, argv);
         std::cerr << "unknown command '" << cmdName << "'" << std::endl;
-        printHelp(cmdName, nullptr);
+        printHelp(app, cmdName, nullptr);
         return 0;
     }
     catch (const Error& e)
@@ -1015,7 +1100,7 @@ int gossMain(int argc, char* argv[])
         if (!e.usage.empty())
         {
             std::cerr << e.usage;
-            std::cerr << "use\n\tgoss " << cmdName << " -h\nfor more usage information." << std::endl;
+            std::cerr << "use\n\t" << app.name << " " << cmdName << " -h\nfor more usage information." << std::endl;
         }
         return 1;
     }
@@ -1031,5 +1116,11 @@ int gossMain(int argc, char* argv[])
     }
     return 0;
 }
+
+}  // namespace
+
+int gossMain(int argc, char* argv[]) { return appMain(gossApp(), argc, argv); }
+
+int translucentMain(int argc, char* argv[]) { return appMain(translucentApp(), argc, argv); }
 
 }  // namespace gosshost

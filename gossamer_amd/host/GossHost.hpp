@@ -324,6 +324,32 @@ private:
     const std::string mIn, mOut;
 };
 
+// TransCmdTrimRelative (`translucent trim-relative`, TransCmdTrimRelative.cc): at every node with two or more outgoing
+// edges, the edges whose multiplicity is below pRelCoverage times the node's sum go, and their reverse complements
+// with them.  Departures: an empty graph gives the empty graph (the reference calls select(0) on it); pNumThreads is
+// accepted and unused (the reference's result does not depend on it); asymmetric graphs are refused; a non-finite
+// pRelCoverage never reaches the command (the factory refuses it).
+class TransCmdTrimRelative {
+public:
+    TransCmdTrimRelative(const std::string& pIn, const std::string& pOut, double pRelCoverage, uint64_t pNumThreads)
+        : mIn(pIn), mOut(pOut), mRelCoverage(pRelCoverage), mNumThreads(pNumThreads) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mIn, mOut; const double mRelCoverage; const uint64_t mNumThreads;
+};
+
+// TransCmdMergeGraphWithReference (`translucent merge-graph-with-reference`, TransCmdMergeGraphWithReference.cc): the
+// edges of pIn that pReference holds too, each with pReference's multiplicity, built with pIn's edge count as the
+// size estimate as the reference builds them.  Asymmetric graphs are refused.
+class TransCmdMergeGraphWithReference {
+public:
+    TransCmdMergeGraphWithReference(const std::string& pReference, const std::string& pIn, const std::string& pOut)
+        : mReference(pReference), mIn(pIn), mOut(pOut) {}
+    void operator()(const GossCmdContext& pCxt);
+private:
+    const std::string mReference, mIn, mOut;
+};
+
 // GossCmdPrintContigs (GossCmdPrintContigs.{hh,cc}) in its linear-segments form: the non-branching paths of a graph
 // as FASTA (or, with pOmitSequence, as a table of their figures).  Supergraph contigs are not part of this build.
 class GossCmdPrintContigs {
@@ -507,6 +533,8 @@ void writeObjectFiles(const std::vector<goss_gpu_ctx*>& hs, const std::string& o
 
 // App::main for the commands of this build (App.cc:176-417): GossCli.cpp, one record per command in its table.
 int gossMain(int argc, char* argv[]);
+// The same driver under the name `translucent` with the table of TranslucentApp.cc:68-76, less pop-bubbles and assemble.
+int translucentMain(int argc, char* argv[]);
 
 // The body of `goss dump-bases`: the bases of every read of the given files, one read per line, on standard output, in
 // the order line, FASTA, FASTQ; T > 1 sends the FASTQ files through the parallel framer.  Throws when there is no read.

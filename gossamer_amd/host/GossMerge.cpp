@@ -23,6 +23,7 @@
 
 #include "../../include/goss_gpu.h"
 #include "GossHost.hpp"
+#include "GossReads.hpp"
 
 namespace gosshost {
 
@@ -1211,6 +1212,60 @@ void GossCmdClipLinks::operator()(const GossCmdContext& pCxt)
     log(info, "links removed: " + num(rep.links));
     log(info, "edges removed: " + num(rep.edges));
     log(info, elapsed(t0));
+}
+
+// TransCmdTrimRelative::operator() (TransCmdTrimRelative.cc:193-280): the pass runs on the device
+// (goss_gpu_trim_relative); the survivors are built with their exact number as the estimate, as the reference builds
+// them (g.count() - zapped.count()).
+void TransCmdTrimRelative::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    log(info, "locating edges to trim");
+    (void)mNumThreads;                                  // (the blocks of the reference start at a node: their number decides nothing)
+    goss_gpu_relative_report rep;
+    g.check(goss_gpu_trim_relative(g.h, mRelCoverage, &rep), "trimming relative to the forks");
+    log(info, "number of edges removed: " + num(rep.edges_before - rep.edges_after));
+    log(info, "writing out graph.");
+    g.check(goss_gpu_emit(g.h), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, elapsed(t0));
+}
+
+// TransCmdMergeGraphWithReference::operator() (TransCmdMergeGraphWithReference.cc:43-110): the reference graph is
+// opened on the device as it lies on disk and every edge of the input is looked up in it (goss_gpu_recount_from); the
+// builder's estimate is the input's edge count, as there.
+void TransCmdMergeGraphWithReference::operator()(const GossCmdContext& pCxt)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    Logger& log = pCxt.log;
+    const ObjectInfo ri = objectInfo(mReference, true);
+    const ObjectInfo gi = objectInfo(mIn, true);
+    if (ri.K != gi.K)
+        throw Error::General("graphs involved in a merge must have the same kmer-size.\n" + mIn + " has k=" + num(gi.K) + ".\n" + mReference
+                             + " has k=" + num(ri.K) + ".\n");
+    if (ri.asymmetric != gi.asymmetric)
+        throw Error::General("graphs involved in a merge must either all preserve sense or not.\n" + mIn
+                             + (gi.asymmetric ? " preserves sense" : " does not preserve sense") + ".\n" + mReference
+                             + (ri.asymmetric ? " preserves sense" : " does not preserve sense") + ".\n");
+    if (gi.asymmetric) throw Error::General("\tunable to open graph '" + mIn + "'\nAsymmetric graphs not yet handled");
+    log(info, "starting graph merge");
+    GpuCtx g; ObjectInfo o;
+    loadObject(pCxt, g, mIn, true, o);
+    reads::Object ref;
+    ref.open(pCxt, mReference, true);
+    goss_gpu_recount_report rep;
+    g.check(goss_gpu_recount_from(g.h, ref.h, &rep), "merging with the reference");
+    g.check(goss_gpu_emit_estimate(g.h, rep.edges_before), "building the on-disk arrays");
+    writeOut(g, mOut);
+    log(info, "finishing graph merge");
+    std::ostringstream os;
+    os << "total build time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    log(info, os.str());
 }
 
 // GossCmdPrintContigs::operator() -> printLinearSegments (GossCmdPrintContigs.cc:49-193).  The device finds the

@@ -1069,6 +1069,12 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * header of its own. */
 #include "goss_gpu_elect.h"
 
+/* trim-relative and merge-graph-with-reference on a finished graph (goss_gpu_trim_relative, goss_gpu_recount_from,
+ * goss_gpu_relative_timing): an edge goes when it is rare relative to the other edges that leave its node, and a graph
+ * takes the multiplicities of a reference graph for the edges both hold -- TransCmdTrimRelative.cc:81-191,
+ * TransCmdMergeGraphWithReference.cc:47-114; likewise a header of its own. */
+#include "goss_gpu_relative.h"
+
 #ifdef __cplusplus
 }
 #endif

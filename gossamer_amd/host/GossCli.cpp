@@ -2,7 +2,8 @@
 // the checker, one `create` function per command in the manner of the reference's GossCmdFactory...::create, the table
 // of commands (kCommands) and the one driver that takes a command from its arguments to its run.  A new command is one
 // record in kCommands and its create function.  The driver takes the executable (App: its name and its table) as a
-// parameter: `translucent` (TranslucentApp.cc) is the same driver over four of goss's records and two of its own.
+// parameter: `translucent` (TranslucentApp.cc) is the same driver over four of goss's records and two of its own,
+// `xenome` (XenoApp.cc) and `electus` (ElectApp.cc) over two records each.  runAndExit is every executable's main.
 #include "GossHost.hpp"
 
 #include <sys/stat.h>
@@ -11,7 +12,9 @@
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <map>
@@ -164,6 +167,25 @@ const OptDef kRelativeCutoff[] = {
 };
 const OptDef kGraphRef[] = {
     {"graph-ref", "", kString, "name of the reference graph object"},
+};
+// xenome's and electus' own (XenoApp.cc:130-133, 231-236, 300; ElectApp.cc:143)
+const OptDef kIndexPrefix[] = {
+    {"prefix", "P", kString, "filename prefix for index"},
+};
+const OptDef kRefPrefix[] = {
+    {"prefix", "P", kString, "reference output prefix"},
+};
+const OptDef kXenoRefs[] = {
+    {"graft", "G", kString, "graft reference in FASTA format"},
+    {"host", "H", kString, "host reference in FASTA format"},
+};
+const OptDef kXenoNames[] = {
+    {"graft-name", "", kString, "name of graft reads"},
+    {"host-name", "", kString, "name of host reads"},
+    {"output-filename-prefix", "", kString, "prefix for output files"},
+};
+const OptDef kRefFasta[] = {
+    {"ref-fasta", "", kStrings, "reference file in FASTA format"},
 };
 const OptDef kAnnotate[] = {
     {"annotation-list", "", kString, "A file containing a list of graph names, 1 per line."},
@@ -807,6 +829,131 @@ Run createMergeGraphWithReference(Checker& chk)
     return run(TransCmdMergeGraphWithReference(ref, in, outName));
 }
 
+// ---- xenome and electus: the commands of XenoApp.cc and ElectApp.cc, each a few of the commands above in one process ----
+
+// What the reference sizes its BackyardHash with for -M (XenoApp.cc:54-57, ElectApp.cc:84-87): 0.2 GB held back.  The
+// build accepts both and ignores them, so -M changes nothing here.
+void hashSizesOfMemory(double M, uint64_t& S, uint64_t& N)
+{
+    const double bytes = std::max(0.0, M - 0.2) * 1024 * 1024 * 1024;
+    N = (uint64_t)(bytes / (1.5 * 4 + 16));
+    S = N ? (uint64_t)std::log2((double)N) : 0;
+}
+
+std::string elapsedSince(std::chrono::steady_clock::time_point t0)
+{
+    std::ostringstream os;
+    os << "total elapsed time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return os.str();
+}
+
+// bases of a FASTA file, from its size (0: unknown)
+uint64_t fastaBases(const std::string& f)
+{
+    struct stat st;
+    if (f == "-" || ::stat(f.c_str(), &st) != 0) return 0;
+    const size_t n = f.size();
+    const double x = n > 3 && f.compare(n - 3, 3, ".gz") == 0 ? 4.5 : n > 4 && f.compare(n - 4, 4, ".bz2") == 0 ? 5.0 : 1.0;
+    return (uint64_t)((double)st.st_size * x);
+}
+
+// XenoCmdIndex (XenoApp.cc:49-98): the four steps with one GossCmdContext -- and here one goss_gpu_ctx, which the
+// context carries from step to step (SharedContext).  The files go through the file system between the steps.
+class XenoCmdIndex {
+public:
+    XenoCmdIndex(const std::string& pGraft, const std::string& pHost, const std::string& pOut, uint64_t pK, double pM, uint64_t pT)
+        : mGraft(pGraft), mHost(pHost), mOut(pOut), mK(pK), mM(pM), mT(pT) {}
+    void operator()(const GossCmdContext& pCxt)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        Logger& log = pCxt.log;
+        uint64_t S = 0, N = 0;
+        hashSizesOfMemory(mM, S, N);
+        const std::string g = mOut + "-graft", h = mOut + "-host", b = mOut + "-both";
+        GossCmdContext cxt = pCxt;
+        if (!cxt.gpu) cxt.gpu = std::make_shared<SharedContext>();
+        const uint64_t gb = fastaBases(mGraft), hb = fastaBases(mHost);
+        if (gb && hb) cxt.gpu->arenaBytes = sharedArenaBytes(gb + hb);
+
+        log(info, "building graft reference kmer set");
+        GossCmdBuildKmerSet(mK, S, N, mT, g, strings(1, mGraft), strings(), strings())(cxt);
+        log(info, "building host reference kmer set");
+        GossCmdBuildKmerSet(mK, S, N, mT, h, strings(1, mHost), strings(), strings())(cxt);
+        log(info, "merging host and graft reference kmer sets");
+        GossCmdMergeAndAnnotateKmerSets(g, h, b)(cxt);
+        log(info, "computing marginal kmers");
+        GossCmdComputeNearKmers(b, mT)(cxt);
+        log(info, elapsedSince(t0));
+    }
+private:
+    const std::string mGraft, mHost, mOut; const uint64_t mK; const double mM; const uint64_t mT;
+};
+
+// XenoCmdFactoryIndex::create (XenoApp.cc:100-135): kmer-size, graft, host, prefix in the reference's order
+Run createXenoIndex(Checker& chk)
+{
+    uint64_t K = 25;
+    if (chk.o.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
+    std::string graft, host, out;
+    chk.mandatory("graft", graft);
+    chk.mandatory("host", host);
+    chk.mandatory("prefix", out);
+    double M = 2;
+    chk.maxMemory(M);
+    uint64_t T = 4;
+    chk.optionalU64("num-threads", T);
+    return run(XenoCmdIndex(graft, host, out, K, M, T));
+}
+
+// XenoCmdFactoryGroup::create and XenoCmdGroup (XenoApp.cc:137-238): group-reads on <prefix>-both
+Run createXenoClassify(Checker& chk)
+{
+    std::string in;
+    chk.mandatory("prefix", in);
+    strings fastas, fastqs, lines;
+    chk.readsIn(fastas, fastqs, lines);
+    double M = 1.0e9;
+    chk.maxMemory(M);
+    uint64_t T = 4;
+    chk.optionalU64("num-threads", T);
+    std::string graftName = "graft", hostName = "host", prefix;
+    chk.optional("graft-name", graftName);
+    chk.optional("host-name", hostName);
+    chk.optional("output-filename-prefix", prefix);
+    GossCmdGroupReads cmd(in + "-both", fastas, fastqs, lines, chk.flag("pairs"), M, T, graftName, hostName, prefix,
+                          chk.flag("dont-write-reads"), chk.flag("preserve-read-order"));
+    return [cmd](const GossCmdContext& cxt) mutable {
+        const auto t0 = std::chrono::steady_clock::now();
+        cmd(cxt);
+        cxt.log(info, elapsedSince(t0));
+    };
+}
+
+// ElectCmdFactoryIndex::create and ElectCmdIndex (ElectApp.cc:74-146): one k-mer set of all the reference files
+Run createElectIndex(Checker& chk)
+{
+    uint64_t K = 25;
+    if (chk.o.count("kmer-size")) chk.mandatoryU64("kmer-size", K, 63);
+    strings refs;
+    chk.repeatingIn("ref-fasta", refs);
+    if (!chk.o.count("ref-fasta")) { chk.errors += "repeating option ref-fasta must be given at least once.\n"; chk.suggestUsage = true; }      // getRepeating1
+    std::string out;
+    chk.mandatory("prefix", out);
+    double M = 2;
+    chk.maxMemory(M);
+    uint64_t T = 4;
+    chk.optionalU64("num-threads", T);
+    uint64_t S = 0, N = 0;
+    hashSizesOfMemory(M, S, N);
+    GossCmdBuildKmerSet cmd(K, S, N, T, out, refs, strings(), strings());
+    return [cmd](const GossCmdContext& cxt) mutable {
+        const auto t0 = std::chrono::steady_clock::now();
+        cxt.log(info, "building reference kmer set");
+        cmd(cxt);
+        cxt.log(info, elapsedSince(t0));
+    };
+}
+
 // ---- the commands that are no factory's: their own arguments, no help of their own, no logger ----
 
 struct App;
@@ -947,6 +1094,20 @@ const Command kTransCommands[] = {
     {"merge-graph-with-reference", kTransSummary, {group(kGraphIn), group(kGraphOut), group(kGraphRef)}, kAll, createMergeGraphWithReference, nullptr},
 };
 
+// xenome's two commands (XenoApp.cc:274-275) and electus' (ElectApp.cc:802-803).  `electus classify` is goss's
+// elect-reads record under that name: the same groups, the same create.
+const Command kXenoCommands[] = {
+    {"index", "build an index for classifying reads", {group(kIndexPrefix), group(kElectSizes), group(kXenoRefs)}, kAll, createXenoIndex, nullptr},
+    {"classify", "classify reads according to index",
+     {group(kReadsIn), group(kIndexPrefix), group(kGroupMemory), group(kPairs), group(kXenoNames), group(kReadOrder)}, 0, createXenoClassify, nullptr},
+};
+const Command kElectCommands[] = {
+    {"classify", "classify reads according to reference",
+     {group(kElectRefs), group(kReadsIn), group(kElectSizes), group(kPairs), group(kReadOrder), group(kElectOut)}, kAll | kUsageUntagged,
+     createElectReads, nullptr},
+    {"index", "build an index for classifying reads", {group(kRefFasta), group(kElectSizes), group(kRefPrefix)}, kAll, createElectIndex, nullptr},
+};
+
 const App& gossApp()
 {
     static const App app = [] {
@@ -969,6 +1130,19 @@ const App& translucentApp()
         a.commands.push_back(&kTransCommands[1]);
         return a;
     }();
+    return app;
+}
+
+// XenoApp.cc:274-276 and ElectApp.cc:802-804: their commands in their order, then goss's help record
+const App& xenomeApp()
+{
+    static const App app{"xenome", {&kXenoCommands[0], &kXenoCommands[1], gossApp().find("help")}};
+    return app;
+}
+
+const App& electusApp()
+{
+    static const App app{"electus", {&kElectCommands[0], &kElectCommands[1], gossApp().find("help")}};
     return app;
 }
 
@@ -1122,5 +1296,22 @@ int appMain(const App& app, int argc, char* argv[])
 int gossMain(int argc, char* argv[]) { return appMain(gossApp(), argc, argv); }
 
 int translucentMain(int argc, char* argv[]) { return appMain(translucentApp(), argc, argv); }
+
+int xenomeMain(int argc, char* argv[]) { return appMain(xenomeApp(), argc, argv); }
+
+int electusMain(int argc, char* argv[]) { return appMain(electusApp(), argc, argv); }
+
+void runAndExit(int (*appMain)(int, char*[]), int argc, char* argv[])
+{
+    const int rc = appMain(argc, argv);
+    const char* full = std::getenv("GOSS_FULL_EXIT");
+    if ((full && *full == '1') || std::getenv("LD_PRELOAD") || std::getenv("ROCP_TOOL_LIBRARIES") || std::getenv("ROCPROFILER_REGISTER_FORCE_LOAD"))
+    {
+        releaseKeptBuffers();
+        std::exit(rc);
+    }
+    std::fflush(nullptr);
+    _exit(rc);
+}
 
 }  // namespace gosshost

@@ -497,22 +497,54 @@ uint64_t parseLines(const std::string& name, const ReadSink& sink)
 // the build commands
 // --------------------------------------------------------------------------------------
 
-namespace {
+SharedContext::~SharedContext() { if (h) goss_gpu_destroy(h); }
 
-struct GpuCtx {
-    goss_gpu_ctx* h = nullptr;
-    ~GpuCtx() { if (h) goss_gpu_destroy(h); }
-    void check(int rc, const char* what)
+// The largest step of `xenome index` is the merge of the two sets, whose own budget (setBudget, GossMerge.cpp) is six
+// times 24 bytes a k-mer plus the sets' high bits -- below a byte a k-mer -- plus 4 GB; a set has at most a k-mer per
+// base.  The builds before it ask for at most 35 bytes a base and 6 GB.  160 GB at the most: the gray set's object is
+// an allocation of its own beside the arena (under 8 bytes a k-mer), and the library clamps a request to 92 % of what is free.
+uint64_t sharedArenaBytes(uint64_t inputBases)
+{
+    const uint64_t kMax = 160ULL << 30;
+    if (inputBases > kMax / 150) return kMax;
+    return std::min<uint64_t>(kMax, inputBases * 150 + (6ULL << 30));
+}
+
+GpuCtx::~GpuCtx() { if (h && !lent) goss_gpu_destroy(h); }
+
+void GpuCtx::check(int rc, const char* what)
+{
+    if (rc == GOSS_OK) return;
+    std::string msg = std::string(what) + ": " + goss_gpu_strerror(rc);
+    const char* d = h ? goss_gpu_last_error(h) : "";
+    if (d && *d) msg += std::string(" (") + d + ")";
+    throw Error::General(msg + "\n");
+}
+
+void GpuCtx::open(const GossCmdContext& cxt, int device, uint64_t K, int mode, uint64_t budget, bool quiet)
+{
+    SharedContext* s = cxt.gpu.get();
+    const std::string what = " (k=" + num(K) + (mode == GOSS_MODE_GRAPH ? ", graph" : ", k-mer set") + ", device " + num((uint64_t)device) + ")";
+    if (s && s->h && s->device == device && s->k == K && s->mode == mode)
     {
-        if (rc == GOSS_OK) return;
-        std::string msg = std::string(what) + ": " + goss_gpu_strerror(rc);
-        const char* d = h ? goss_gpu_last_error(h) : "";
-        if (d && *d) msg += std::string(" (") + d + ")";
-        throw Error::General(msg + "\n");
+        h = s->h;
+        lent = true;
+        check(goss_gpu_reset(h), "resetting the GPU context");
+        said = "GPU context reused" + what;
+        if (!quiet) cxt.log(info, said);
+        return;
     }
-};
-
-}  // namespace
+    if (s)
+    {
+        // (another device, k or mode: nothing of the old one can be kept)
+        if (s->h) { goss_gpu_destroy(s->h); s->h = nullptr; }
+        if (!cxt.hbmBudget && s->arenaBytes) budget = s->arenaBytes;
+    }
+    check(goss_gpu_create(&h, device, (uint32_t)K, mode, budget, nullptr), "creating the GPU context");
+    said = "GPU context created" + what;
+    if (!quiet) cxt.log(info, said);
+    if (s) { s->h = h; s->device = device; s->k = K; s->mode = mode; lent = true; }
+}
 
 // Every file of the emitted object to "<out><suffix>".  The calling thread (the context's) copies
 // 32 MB pieces from the device into a ring of page-locked buffers; a pool of writer threads pwrites
@@ -1226,6 +1258,8 @@ void runBuild(const GossCmdContext& cxt, uint64_t K, int mode, const std::string
     // with one device the parser's workers read and frame the first chunks meanwhile (into plain pages that are
     // page-locked once the runtime is up: HostAlloc's two-step form).  Whoever needs a context waits for it (needCtx).
     struct CtxState { std::mutex m; std::condition_variable cv; bool done = false; std::exception_ptr err; double readyAt = 0; } cs;
+    GossCmdContext alone = cxt;
+    alone.gpu.reset();
     std::thread ctxThread([&]() {
         std::exception_ptr err;
         try
@@ -1233,7 +1267,7 @@ void runBuild(const GossCmdContext& cxt, uint64_t K, int mode, const std::string
             for (size_t d = 0; d < P; ++d)
             {
                 GpuCtx& g = *gs[d];
-                g.check(goss_gpu_create(&g.h, devs[d], (uint32_t)K, mode, budget, nullptr), "creating the GPU context");
+                g.open(P == 1 ? cxt : alone, devs[d], K, mode, budget, true);          // (a shared context is one device's)
                 // a budget the user did not ask for is a starting size: inputs with little duplication (a
                 // genome in FASTA: every k-mer once) need room for runs that do not shrink
                 if (cxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
@@ -1593,6 +1627,7 @@ void runBuild(const GossCmdContext& cxt, uint64_t K, int mode, const std::string
     if (reads == 0) throw Error::General("No valid reads.");                  // KmerizingAdapter.hh:70-78
     flush();
     needCtx();
+    for (auto& x : gs) log(info, x->said);
     if (beside) { std::ostringstream o; o << "contexts ready at " << cs.readyAt << "s (beside the parser)"; log(info, o.str()); }
     if (fed) drainFeeders();
     auto secs = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };

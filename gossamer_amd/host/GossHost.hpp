@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+struct goss_gpu_ctx;
+
 namespace gosshost {
 
 // ---- errors (role of Gossamer::error + boost::error_info tags, GossamerException.hh:27-40) ----
@@ -112,6 +114,27 @@ uint64_t parseFastq(const std::string& name, const ReadSink& sink);
 uint64_t parseFasta(const std::string& name, const ReadSink& sink);
 uint64_t parseLines(const std::string& name, const ReadSink& sink);
 
+// One goss_gpu_ctx lent from step to step of one process (`xenome index`: two builds, the merge, the gray set; DESIGN.md
+// section 4o).  A command that finds one in its GossCmdContext takes its context from it (GpuCtx::open) -- created by
+// the first step, on its (device, k, mode), with an arena of arenaBytes, and returned to a clean state with
+// goss_gpu_reset for every later step of the same (device, k, mode) -- and leaves it there when it ends; the holder
+// destroys it.  Without a holder, which is every goss command, a command creates and destroys its own as ever.
+struct SharedContext {
+    goss_gpu_ctx* h = nullptr;
+    int device = 0;
+    uint64_t k = 0;
+    int mode = 0;
+    uint64_t arenaBytes = 0;        // what the first step maps (0: what that step would map alone); --hbm-budget wins
+    SharedContext() = default;
+    SharedContext(const SharedContext&) = delete;
+    SharedContext& operator=(const SharedContext&) = delete;
+    ~SharedContext();
+};
+
+// The arena of a shared context, sized once for the largest step of a pipeline over `inputBases` bases of sequence (the
+// one definition: DESIGN.md section 4o).
+uint64_t sharedArenaBytes(uint64_t inputBases);
+
 // ---- command context (GossCmdContext.hh:25-39, minus the FileFactory: files are real) ----
 struct GossCmdContext {
     Logger& log;
@@ -125,6 +148,24 @@ struct GossCmdContext {
     // temporary objects, GossCmdMerge.tcc:176-208); not given: they stay in host memory.  The build commands need no
     // temporary file: the runs of their chunks are held in HBM.
     std::string tmpDir = {};
+    // set by a command that runs several commands in its process: they share one goss_gpu_ctx (SharedContext)
+    std::shared_ptr<SharedContext> gpu = {};
+};
+
+// A command's counting context: its own, destroyed with it, or the one GossCmdContext::gpu lends, which stays.
+struct GpuCtx {
+    goss_gpu_ctx* h = nullptr;
+    bool lent = false;
+    GpuCtx() = default;
+    GpuCtx(const GpuCtx&) = delete;
+    GpuCtx& operator=(const GpuCtx&) = delete;
+    ~GpuCtx();
+    void check(int rc, const char* what);       // throws Error::General with the library's text
+    // goss_gpu_create(device, K, mode, budget), or the shared context after goss_gpu_reset; under -v the log says
+    // which, once: "GPU context created ..." or "GPU context reused ..." (quiet: the caller logs `said` itself -- the
+    // build opens its contexts on a thread beside the parser, and the logger is the command's thread's)
+    void open(const GossCmdContext& cxt, int device, uint64_t K, int mode, uint64_t budget, bool quiet = false);
+    std::string said;
 };
 
 typedef std::vector<std::string> strings;
@@ -535,6 +576,16 @@ void writeObjectFiles(const std::vector<goss_gpu_ctx*>& hs, const std::string& o
 int gossMain(int argc, char* argv[]);
 // The same driver under the name `translucent` with the table of TranslucentApp.cc:68-76, less pop-bubbles and assemble.
 int translucentMain(int argc, char* argv[]);
+// ... under `xenome` (XenoApp.cc:274-276: index, classify, help) and `electus` (ElectApp.cc:802-804: classify, index, help)
+int xenomeMain(int argc, char* argv[]);
+int electusMain(int argc, char* argv[]);
+
+// What every executable's main is: `appMain` from its arguments to the end of the process.  Every file the command
+// wrote is closed when appMain returns; what is left is tearing the device runtime down -- unmapping tens of GB of HBM,
+// unlocking the parser's buffers, unloading the code: 0.05 to 0.1 s of a 1.3 s build that the kernel does anyway when
+// the process ends, so the process ends with _exit.  GOSS_FULL_EXIT=1, or a tool that is loaded with the process and
+// writes its results from an exit handler (rocprofv3, a sanitizer), keeps the orderly exit.
+[[noreturn]] void runAndExit(int (*appMain)(int, char*[]), int argc, char* argv[]);
 
 // The body of `goss dump-bases`: the bases of every read of the given files, one read per line, on standard output, in
 // the order line, FASTA, FASTQ; T > 1 sends the FASTQ files through the parallel framer.  Throws when there is no read.

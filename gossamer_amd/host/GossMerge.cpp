@@ -111,19 +111,6 @@ void openSparse(const std::string& base, SparseFiles& s)
     }
 }
 
-struct GpuCtx {
-    goss_gpu_ctx* h = nullptr;
-    ~GpuCtx() { if (h) goss_gpu_destroy(h); }
-    void check(int rc, const char* what)
-    {
-        if (rc == GOSS_OK) return;
-        std::string msg = std::string(what) + ": " + goss_gpu_strerror(rc);
-        const char* d = h ? goss_gpu_last_error(h) : "";
-        if (d && *d) msg += std::string(" (") + d + ")";
-        throw Error::General(msg + "\n");
-    }
-};
-
 struct ObjectInfo { uint64_t K = 0, count = 0; bool asymmetric = false; };
 
 // Header of an object: T::LazyIterator(name, fac).K() / .count() / .asymmetric().
@@ -246,8 +233,7 @@ void runMerge(const GossCmdContext& cxt, bool graph, const strings& ins, uint64_
 
     uint64_t budget = cxt.hbmBudget ? cxt.hbmBudget : bytes * 6 + (4ULL << 30);
     GpuCtx g;
-    g.check(goss_gpu_create(&g.h, cxt.device, (uint32_t)K, graph ? GOSS_MODE_GRAPH : GOSS_MODE_KMER_SET, budget, nullptr),
-            "creating the GPU context");
+    g.open(cxt, cxt.device, K, graph ? GOSS_MODE_GRAPH : GOSS_MODE_KMER_SET, budget);
     if (cxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     const size_t words = (2 * (K + (graph ? 1 : 0)) <= 62) ? 1 : 2;
 
@@ -398,7 +384,7 @@ void GossCmdIntersectKmerSets::operator()(const GossCmdContext& pCxt)
     const uint64_t K = infos[0].K;
     if (K > 63 || K == 0) throw Error::General("unable to build a graph with k=" + num(K));
     GpuCtx g;
-    g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+    g.open(pCxt, pCxt.device, K, GOSS_MODE_KMER_SET, budget);
     if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     log(info, "counting k-mers");
     uint32_t sets = 0;
@@ -435,7 +421,7 @@ void GossCmdSubtractKmerSet::operator()(const GossCmdContext& pCxt)
     const uint64_t K = infos[0].K;
     if (K > 63 || K == 0) throw Error::General("unable to build a graph with k=" + num(K));
     GpuCtx g;
-    g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+    g.open(pCxt, pCxt.device, K, GOSS_MODE_KMER_SET, budget);
     if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     log(info, "calculating difference");
     pushObject(g, mIns[0], false, 1);
@@ -465,7 +451,7 @@ void GossCmdGraphToKmerSet::operator()(const GossCmdContext& pCxt)
     openSparse(mIn + "-edges", s);
     const uint64_t budget = pCxt.hbmBudget ? pCxt.hbmBudget : s.count * 24 * 6 + s.high.n + (4ULL << 30);
     GpuCtx g;
-    g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)rho, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+    g.open(pCxt, pCxt.device, rho, GOSS_MODE_KMER_SET, budget);
     if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     log(info, "building (k+1)-mer set");
     goss_gpu_sparse_run r{};
@@ -501,7 +487,7 @@ void GossCmdMergeAndAnnotateKmerSets::operator()(const GossCmdContext& pCxt)
     const uint64_t K = infos[0].K;
     if (K > 63 || K == 0) throw Error::General("unable to build a graph with k=" + num(K));
     GpuCtx g;
-    g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+    g.open(pCxt, pCxt.device, K, GOSS_MODE_KMER_SET, budget);
     if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     log(info, "counting kmers.");
     pushObject(g, mLhs, false, 1);
@@ -584,8 +570,9 @@ void GossCmdPoolSamples::operator()(const GossCmdContext& pCxt)
     const uint64_t rowBytes = S * ((z + 63) / 64) * 8;
     log(info, "allocating " + num(rowBytes) + " bytes of sample x k-mer rows");
     GpuCtx pool;
-    pool.check(goss_gpu_create(&pool.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET,
-                               pCxt.hbmBudget ? pCxt.hbmBudget : rowBytes + m * 40 + (1ULL << 30), nullptr), "creating the GPU context");
+    GossCmdContext own = pCxt;          // (the rows live beside the merging context: never the shared one)
+    own.gpu.reset();
+    pool.open(own, pCxt.device, K, GOSS_MODE_KMER_SET, pCxt.hbmBudget ? pCxt.hbmBudget : rowBytes + m * 40 + (1ULL << 30));
     pool.check(goss_gpu_pool_begin(pool.h, (uint32_t)S, z), "allocating the sample x k-mer rows");
     {
         log(info, "merging the samples into membership masks");
@@ -597,7 +584,7 @@ void GossCmdPoolSamples::operator()(const GossCmdContext& pCxt)
             if (::stat((unionName + ".kmers.high-bits").c_str(), &st) == 0) budget += (uint64_t)st.st_size * 6;
             budget += z * 24 * 6;
         }
-        g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)K, GOSS_MODE_KMER_SET, budget, nullptr), "creating the GPU context");
+        g.open(pCxt, pCxt.device, K, GOSS_MODE_KMER_SET, budget);
         if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
         const bool withUnion = S > kPoolSlab;
         for (size_t first = 0; first < S; first += kPoolSlab)
@@ -694,6 +681,12 @@ void GossCmdComputeNearKmers::operator()(const GossCmdContext& pCxt)
         if (f.second->n != nwords * 8)
             throw Error::General("\tfile '" + *f.first + "' holds " + num(f.second->n) + " bytes; the " + num(si.count) + " k-mers of '" + mIn
                                  + "' need " + num(nwords * 8) + "\n");
+    // The set is opened as an object, an allocation of its own.  A context that the steps of this process share is
+    // taken all the same: reset, so that nothing of the step before is held beside the object, and kept, so that no
+    // large mapping is given back inside the process (the next allocations would pay for it).
+    GpuCtx lease;
+    if (const SharedContext* s = pCxt.gpu.get())
+        if (s->h && s->device == pCxt.device && s->k == si.K && s->mode == GOSS_MODE_KMER_SET) lease.open(pCxt, pCxt.device, si.K, GOSS_MODE_KMER_SET, 0);
     struct Obj {
         goss_gpu_object* h = nullptr;
         ~Obj() { if (h) goss_gpu_object_close(h); }
@@ -746,8 +739,7 @@ void loadObject(const GossCmdContext& cxt, GpuCtx& g, const std::string& name, b
     if (::stat((name + (graph ? "-edges.high-bits" : ".kmers.high-bits")).c_str(), &st) == 0) bytes = (uint64_t)st.st_size * 4;
     if (::stat((name + (graph ? "-counts.ord0" : ".kmers.low-bits")).c_str(), &st) == 0) bytes += (uint64_t)st.st_size * 64;
     const uint64_t budget = cxt.hbmBudget ? cxt.hbmBudget : bytes + (4ULL << 30);
-    g.check(goss_gpu_create(&g.h, cxt.device, (uint32_t)o.K, graph ? GOSS_MODE_GRAPH : GOSS_MODE_KMER_SET, budget, nullptr),
-            "creating the GPU context");
+    g.open(cxt, cxt.device, o.K, graph ? GOSS_MODE_GRAPH : GOSS_MODE_KMER_SET, budget);
     if (cxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     pushObject(g, name, graph);
     goss_gpu_counts counts;
@@ -883,7 +875,7 @@ void GossCmdRestoreGraph::operator()(const GossCmdContext& pCxt)
     }
     GpuCtx g;
     const uint64_t budget = pCxt.hbmBudget ? pCxt.hbmBudget : counts.size() * 64 + (4ULL << 30);
-    g.check(goss_gpu_create(&g.h, pCxt.device, (uint32_t)k, GOSS_MODE_GRAPH, budget, nullptr), "creating the GPU context");
+    g.open(pCxt, pCxt.device, k, GOSS_MODE_GRAPH, budget);
     if (pCxt.hbmBudget == 0) g.check(goss_gpu_set_budget_limit(g.h, ~0ULL), "setting the HBM limit");
     g.check(goss_gpu_push_run_host(g.h, keys.data(), counts.data(), counts.size()), "loading the edges");
     goss_gpu_counts gc;

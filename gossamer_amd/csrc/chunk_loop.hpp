@@ -21,11 +21,11 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
         if (c->arena.avail() >= need) ka_slots = basis + extra;
     };
     bool reduced = false;
-    if (c->fused && nstarts >= c->fused_min)
+    if (c->knobs.fused && nstarts >= c->knobs.fused_min)
     {
         // (strand pairs: ONE key per window of a graph on the fused path -- what chunk_capacity cut the chunk for; the
         // sequence a declined chunk falls back to emits both strands and gets its buffers then, below)
-        const uint64_t capf = c->mode == GOSS_MODE_GRAPH && c->graph_rep ? nstarts : cap;
+        const uint64_t capf = c->mode == GOSS_MODE_GRAPH && c->knobs.graph_rep ? nstarts : cap;
         // a chunk whose sample is a set of slices (not the whole chunk): buffers for the expected
         // number of keys -- bucket regions with 6 % of slack, sub-regions with 13 %
         if (c->valid_frac < 0.97 && nstarts > kValidSizingMin)
@@ -42,10 +42,10 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
     K* ka = (K*)c->arena.temp(ka_slots * sizeof(K));
     K* kb = (K*)c->arena.temp(kb_slots * sizeof(K));
     int frc = process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots);
-    if (frc == kFusedDone) { if (reduced) c->valid_sized_chunks++; c->arena.release(mark); return; }
+    if (frc == kFusedDone) { if (reduced) c->stats.valid_sized_chunks++; c->arena.release(mark); return; }
     if (reduced)
     {
-        c->valid_resizes++;
+        c->stats.valid_resizes++;
         // the unfused kernels (and a fused retry) want one slot per window start
         c->arena.release(mark);
         c->valid_frac = 1.0;
@@ -74,10 +74,10 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
     if (n)
     {
         Run r = count_keys<K>(c, ka, kb, n);
-        c->runs.push_back(r);
+        c->build.runs.push_back(r);
     }
-    c->windows += nwin;           // only once the chunk has succeeded (it may be retried)
-    c->keys_total += n;
+    c->build.windows += nwin;           // only once the chunk has succeeded (it may be retried)
+    c->build.keys_total += n;
     c->arena.release(mark);
 }
 
@@ -91,7 +91,7 @@ uint64_t chunk_capacity(goss_gpu_ctx* c, bool optimistic)
     // (keys per window: two for a graph -- but ONE where the fused path counts strand pairs (round 4) and makes the other
     // strand from the counted pairs: sized for two, C4's chunks were half of what the arena holds, seven where four do;
     // a chunk the fused path declines after all asks for its full buffers and is cut in halves if they are not there)
-    const uint32_t S = c->mode == GOSS_MODE_GRAPH && !(optimistic && c->graph_rep && c->fused) ? 2 : 1;
+    const uint32_t S = c->mode == GOSS_MODE_GRAPH && !(optimistic && c->knobs.graph_rep && c->knobs.fused) ? 2 : 1;
     uint64_t avail = c->arena.avail();
     double per_key;
     if (optimistic)
@@ -126,13 +126,12 @@ double estimate_valid_fraction(goss_gpu_ctx* c, const ReadSrc& d, uint64_t nbyte
     if (nbytes < skip + 2 * kSlices * kSlice) return 1.0;
     const uint64_t stride = ((nbytes - skip - kSlice) / (kSlices - 1)) & ~15ULL;
     const ReadSrc::Launch al = d.advance(skip).launch();          // (the first whole sixteen: mis 0)
-    c->mute_timing = true;
+    Scoped<bool> mute(&c->mute_timing, true);
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, 16, c->stream));
     with_bool(d.packed(), [&](auto pk) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(nonbase_sample_kernel<decltype(pk)::value>), dim3(1024), dim3(kTB), 0, c->stream,
                            decltype(pk)::value ? (const uint8_t*)al.bad : al.base, kSlices, stride, kSlice, (unsigned long long*)c->d_ctr);
     });
-    c->mute_timing = false;
     unsigned long long* h = (unsigned long long*)c->h_pinned;
     HIP_TRY(hipMemcpyAsync(h, c->d_ctr, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -151,15 +150,14 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
     if (recs ? n == 0 : n < c->len) return;
     ensure_arena(c);
     const uint64_t nstarts_total = recs ? n * rec_slots(c) : n - c->len + 1;
-    struct FracOff { goss_gpu_ctx* c; ~FracOff() { c->valid_frac = 1.0; } } fracOff{c};
-    c->valid_frac = 1.0;
-    if (c->size_by_valid && c->fused && c->path == 0 && nstarts_total > kValidSizingMin)
+    Scoped<double> frac(&c->valid_frac, 1.0);          // (this push's share, from here on; 1.0 again behind it)
+    if (c->knobs.size_by_valid && c->knobs.fused && c->path == 0 && nstarts_total > kValidSizingMin)
     {
         if (recs) { if (nwindows) c->valid_frac = std::min(1.0, std::max(0.05, (double)nwindows / (double)nstarts_total + 0.01)); }
         else
         {
             c->valid_frac = estimate_valid_fraction(c, src, n);
-            if (c->debug) std::fprintf(stderr, "libgossgpu: valid windows per window start, estimated: %.3f\n", c->valid_frac);
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: valid windows per window start, estimated: %.3f\n", c->valid_frac);
         }
     }
     uint64_t done = 0;
@@ -173,7 +171,7 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
         if (capn < 4096)
         {
             // try to make room by merging what we have
-            if (c->runs.size() > 1) { merge_runs<K>(c); capn = chunk_capacity(c, false); }
+            if (c->build.runs.size() > 1) { merge_runs<K>(c); capn = chunk_capacity(c, false); }
             if (capn < 4096 && grow_arena(c, 0)) capn = chunk_capacity(c, false);
             if (capn < 4096) throw StatusError{GOSS_ERR_OOM, "HBM budget too small for one chunk"};
         }
@@ -191,11 +189,10 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
         const uint64_t ns = std::min(capn, nstarts_total - done);          // (a multiple of 4096 slots = whole records, but for the last)
         const uint64_t navail = recs ? 0 : std::min(n - done, ns + c->len - 1);
         const uint64_t lo0 = c->arena.lo, hi0 = c->arena.hi;
-        const size_t runs0 = c->runs.size();
+        const size_t runs0 = c->build.runs.size();
         // (behind this chunk of a base string: the rest of this push and what the push's own caller has said lies behind
         // IT; a push of records leaves the figure as it is)
-        struct MoreOff { goss_gpu_ctx* c; uint64_t was; ~MoreOff() { c->more_starts = was; } } moreOff{c, c->more_starts};
-        if (!recs) c->more_starts = moreOff.was + (nstarts_total - done - ns);
+        Scoped<uint64_t> more(&c->more_starts, c->more_starts + (recs ? 0 : nstarts_total - done - ns));
         try
         {
             process_chunk<K>(c, src.advance(done), ns, navail);
@@ -206,8 +203,7 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
             // undo the partial chunk; retry it in a larger arena if the budget may grow, else in halves
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->arena.lo = lo0; c->arena.hi = hi0;
-            c->runs.resize(runs0);
-            c->mute_timing = false;             // (a phase that gave up part-way may have left it set)
+            c->build.runs.resize(runs0);
             if (grow_arena(c, 0)) continue;
             limit = (ns / 2) & ~4095ULL;
             continue;
@@ -215,8 +211,8 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
         done += ns;
         // keep the accumulated runs from eating the budget
         uint64_t run_bytes = 0;
-        for (auto& r : c->runs) run_bytes += r.m * (c->words * 8 + 4);
-        if (c->runs.size() > 1 && run_bytes > c->arena.size / 4)
+        for (auto& r : c->build.runs) run_bytes += r.m * (c->words * 8 + 4);
+        if (c->build.runs.size() > 1 && run_bytes > c->arena.size / 4)
         {
             // merging needs two more copies of the runs: possible now, or after growing; else the
             // runs wait for finish

@@ -71,7 +71,7 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
     unsigned long long* cursors = nullptr;
     LookbackCtl* ctl = nullptr;
     LookbackCtl* hctl = (LookbackCtl*)((uint8_t*)c->h_pinned + 128);
-    bool lookback = c->lookback && ndigits <= 16;
+    bool lookback = c->knobs.lookback && ndigits <= 16;
     if (lookback)
     {
         // single-pass form: all digit histograms in one read of the keys, then one look-back
@@ -111,7 +111,7 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
             else HIP_TRY(hipMemsetAsync(status, 0, ntiles * 256 * 8, c->stream));
             {
                 PhaseTimer t(c, GOSS_T_SCATTER, n);
-                if (c->ordered_tiles)
+                if (c->knobs.ordered_tiles)
                 {
                     HIP_TRY(hipMemsetAsync(&ctl->ticket, 0, 4, c->stream));
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_onesweep_kernel<K, HAS_VAL, true>), dim3(grid_for(n, tile)), dim3(kTB), 0,
@@ -136,8 +136,8 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
             if (hctl->error)
             {
                 std::fprintf(stderr, "libgossgpu: radix look-back chain gave up; redoing the pass with histogram tables\n");
-                c->lookback_failures++;
-                if (!c->ordered_tiles) c->ordered_tiles = true;     // next passes take tickets
+                c->stats.lookback_failures++;
+                if (!c->knobs.ordered_tiles) c->knobs.ordered_tiles = true;     // next passes take tickets
                 HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(LookbackCtl), c->stream));
             }
             else done = true;
@@ -222,19 +222,19 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
             for (int b : in_bigs)
                 if (b >= 0)
                 {
-                    auto it = c->big_maps[b].find(kk);
-                    if (it != c->big_maps[b].end()) { exact += it->second; ++markers; }
+                    auto it = c->build.big_maps[b].find(kk);
+                    if (it != c->build.big_maps[b].end()) { exact += it->second; ++markers; }
                 }
             // an entry 0xFFFFFFFF that no input map accounts for came in with a pushed run (goss_gpu_push_run_*: a graph
             // read from disk, a caller's own run), and there it is no marker but the multiplicity 2^32 - 1 itself; where no
             // run was pushed every marker has its map, and one without is a bookkeeping error as before
-            if (markers > hs[nq + q] || (!c->pushed_counts && markers != hs[nq + q]))
+            if (markers > hs[nq + q] || (!c->build.pushed_counts && markers != hs[nq + q]))
                 throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated entry without its exact count"};
             exact += (hs[nq + q] - markers) * 0xFFFFFFFFULL;
             bm[kk] = exact;
         }
-        c->big_maps.push_back(std::move(bm));
-        out.big = (int)c->big_maps.size() - 1;
+        c->build.big_maps.push_back(std::move(bm));
+        out.big = (int)c->build.big_maps.size() - 1;
     }
     HIP_TRY(hipMemsetAsync(c->d_flags, 0, 4, c->stream));
     c->arena.release(mark);
@@ -251,8 +251,8 @@ void adopt_literal_counts(goss_gpu_ctx* c, Run& r)
     if (!sat.n) return;
     BigMap bm;
     for (const auto& kk : sat.key) bm[kk] = 0xFFFFFFFFULL;
-    c->big_maps.push_back(std::move(bm));
-    r.big = (int)c->big_maps.size() - 1;
+    c->build.big_maps.push_back(std::move(bm));
+    r.big = (int)c->build.big_maps.size() - 1;
 }
 
 // ---- run compaction ---------------------------------------------------------------------
@@ -312,7 +312,7 @@ static ReadSrc pk_unpack_temp(goss_gpu_ctx* c, const ReadSrc& p, uint64_t n)
 {
     const ReadSrc::Launch in = p.launch();
     const uint64_t groups = (n + in.mis + 15) / 16;
-    c->pk_unpacked_chunks++;
+    c->stats.pk_unpacked_chunks++;
     uint8_t* out = (uint8_t*)c->arena.temp((groups + 1) * 16 + 64);
     hipLaunchKernelGGL(unpack_bases_kernel, dim3(grid_for(groups + 1, kTB)), dim3(kTB), 0, c->stream, (const uint32_t*)in.base, in.bad, groups,
                        n + in.mis, out);
@@ -548,10 +548,11 @@ uint64_t count_distinct_sample(goss_gpu_ctx* c, const K* keys, uint64_t s)
     HIP_TRY(hipMemcpyAsync(a, keys, s * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
     // auxiliary sort of the sample: histogram-table kernels, kept out of the per-kernel timing
     // so that the partition kernel's launch statistics describe the partition only
-    const bool lb = c->lookback;
-    c->lookback = false; c->mute_timing = true;
-    bool in_b = radix_sort<K, false>(c, a, b, nullptr, nullptr, s, key_digits(c));
-    c->lookback = lb; c->mute_timing = false;
+    bool in_b;
+    {
+        Scoped<bool> plain(&c->knobs.lookback, false), mute(&c->mute_timing, true);
+        in_b = radix_sort<K, false>(c, a, b, nullptr, nullptr, s, key_digits(c));
+    }
     const uint64_t ntiles = (s + kRedTile - 1) / kRedTile;
     uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_count_kernel<K>), dim3(grid_for(s, kRedTile)), dim3(kTB), 0, c->stream,
@@ -610,8 +611,7 @@ uint64_t spectrum_estimate(goss_gpu_ctx* c, const K* keys, uint64_t avail, doubl
     K* b = (K*)c->arena.temp(cap * sizeof(K));
     unsigned long long* ctr = (unsigned long long*)c->arena.temp(64);
     HIP_TRY(hipMemsetAsync(ctr, 0, 64, c->stream));
-    const bool lb = c->lookback, mute = c->mute_timing;
-    c->mute_timing = true;
+    Scoped<bool> mute(&c->mute_timing, true);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(slice_filter_kernel<K>), dim3((uint32_t)std::min<uint64_t>(2048, (scan + kTB - 1) / kTB)), dim3(kTB), 0, c->stream,
                        keys, scan, q - 1, a, ctr, cap);
     unsigned long long* h = (unsigned long long*)c->h_pinned;
@@ -621,9 +621,7 @@ uint64_t spectrum_estimate(goss_gpu_ctx* c, const K* keys, uint64_t avail, doubl
     uint64_t est = 0;
     if (sf >= 2)
     {
-        c->lookback = false;
-        const bool in_b = radix_sort<K, false>(c, a, b, nullptr, nullptr, sf, key_digits(c));
-        c->lookback = lb;
+        const bool in_b = [&]() { Scoped<bool> plain(&c->knobs.lookback, false); return radix_sort<K, false>(c, a, b, nullptr, nullptr, sf, key_digits(c)); }();
         HIP_TRY(hipMemsetAsync(ctr, 0, 64, c->stream));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spectrum_kernel<K>), dim3((uint32_t)std::min<uint64_t>(1024, (sf + kTB - 1) / kTB)), dim3(kTB), 0, c->stream,
                            (const K*)(in_b ? b : a), sf, ctr);
@@ -649,11 +647,10 @@ uint64_t spectrum_estimate(goss_gpu_ctx* c, const K* keys, uint64_t avail, doubl
         est = std::max<uint64_t>(est, (uint64_t)(d * scale_q));
         if (plain == 0 && model == 0) est = 0;                    // no repeated key at all: unknown
         if (rare_out) *rare_out = rare_keys < 0 ? est : std::min<uint64_t>(est, (uint64_t)(rare_keys * scale_q));
-        if (c->debug)
+        if (c->knobs.debug)
             std::fprintf(stderr, "libgossgpu: spectrum of 1/%u of the key space over %llu keys (p = %.4f): d %.0f f1 %.0f f2 %.0f f3 %.0f -> plain %llu, fitted %.0f, estimate %llu\n",
                          q, (unsigned long long)scan, p, d, f1, f2, f3, (unsigned long long)plain, model * scale_q, (unsigned long long)est);
     }
-    c->mute_timing = mute;
     c->arena.release(mark);
     return est;
 }
@@ -746,7 +743,7 @@ int count_overflowed_units(SegStage<K>& st, const uint64_t* d_beg, const uint64_
     const uint64_t need = total * (3 * sizeof(K) + 16) + units.size() * (2 * sizeof(K) + 16) + (64ULL << 20);
     if (c->arena.avail() < need) return 1;
     const uint64_t mark = c->arena.mark(), lo0 = c->arena.lo;
-    const size_t maps0 = c->big_maps.size();
+    const size_t maps0 = c->build.big_maps.size();
     K* a = (K*)c->arena.temp(total * sizeof(K));
     K* b = (K*)c->arena.temp(total * sizeof(K));
     {
@@ -756,13 +753,12 @@ int count_overflowed_units(SegStage<K>& st, const uint64_t* d_beg, const uint64_
     Run r{nullptr, nullptr, 0};
     {
         // (the sort's passes belong to the counting phase that is being timed; put back also when the sort gives up)
-        struct Mute { goss_gpu_ctx* c; bool was; ~Mute() { c->mute_timing = was; } } muted{c, c->mute_timing};
-        c->mute_timing = true;
+        Scoped<bool> mute(&c->mute_timing, true);
         const bool moved = radix_sort<K, false>(c, a, b, nullptr, nullptr, total, key_digits(c));
         r = reduce_runs<K>(c, moved ? b : a, nullptr, total, moved ? a : b);
     }
     int rc = 0;
-    if (r.big >= 0 || c->big_maps.size() != maps0) { c->big_maps.resize(maps0); rc = 1; }          // (a count of 2^32 - 1 or more: the general way keeps those)
+    if (r.big >= 0 || c->build.big_maps.size() != maps0) { c->build.big_maps.resize(maps0); rc = 1; }          // (a count of 2^32 - 1 or more: the general way keeps those)
     else if (st.h.cursor + r.m > st.h.stage_cap) rc = 2;
     else
     {
@@ -790,8 +786,8 @@ int count_overflowed_units(SegStage<K>& st, const uint64_t* d_beg, const uint64_
         HIP_TRY(hipStreamSynchronize(c->stream));          // (the host vectors go)
         st.h.cursor += r.m;
         st.h.overflow = 0;
-        c->overflow_units += nu;
-        if (c->debug) std::fprintf(stderr, "libgossgpu: %u segment(s) with more distinct keys than a table holds counted by sort (%llu keys, %llu distinct)\n",
+        c->stats.overflow_units += nu;
+        if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: %u segment(s) with more distinct keys than a table holds counted by sort (%llu keys, %llu distinct)\n",
                                    nu, (unsigned long long)total, (unsigned long long)r.m);
     }
     c->arena.lo = lo0;               // (the run's storage: it lives on in the staging area)
@@ -808,7 +804,7 @@ int finish_segments(SegStage<K>& st, bool by_sort, const uint64_t* seg_beg, cons
                     Expand expand, UnitLow unit_low)
 {
     goss_gpu_ctx* c = st.c;
-    if (st.h.overflow == 1u && by_sort && c->overflow_by_sort && count_overflowed_units<K>(st, seg_beg, seg_end, expand, unit_low) == 2)
+    if (st.h.overflow == 1u && by_sort && c->knobs.overflow_by_sort && count_overflowed_units<K>(st, seg_beg, seg_end, expand, unit_low) == 2)
         st.h.overflow = 2u;
     if (st.h.overflow)
     {
@@ -884,7 +880,7 @@ int segment_count(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n, uint32_t segbits, b
     const uint32_t npass = (segbits + 7) / 8;
     uint64_t mark = c->arena.mark();
     const unsigned long long* prehist =
-        (segbits == kSegBits && c->extract_hist_shift == shift && c->lookback && !*in_b_out) ? c->d_ctr->hist : nullptr;
+        (segbits == kSegBits && c->extract_hist_shift == shift && c->knobs.lookback && !*in_b_out) ? c->d_ctr->hist : nullptr;
     K* src = *in_b_out ? kb : ka;
     K* dst = *in_b_out ? ka : kb;
     bool moved = radix_sort<K, false>(c, src, dst, nullptr, nullptr, n, npass, shift, prehist);
@@ -974,11 +970,11 @@ Run count_keys(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n)
             {
                 if ((m_est >> segbits) > limit) continue;
                 int rc = segment_count<K>(c, ka, kb, n, segbits, &in_b, &r);
-                if (c->debug) std::fprintf(stderr, "libgossgpu: count_keys: %llu keys, %u segment bits -> %d (%llu distinct)\n",
+                if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: count_keys: %llu keys, %u segment bits -> %d (%llu distinct)\n",
                                            (unsigned long long)n, segbits, rc, (unsigned long long)(rc == 0 ? r.m : 0));
                 if (rc == 0) return r;
                 if (rc == 2) break;
-                c->segment_retries++;
+                c->stats.segment_retries++;
             }
         }
     }
@@ -988,7 +984,7 @@ Run count_keys(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n)
     PhaseTimer t(c, GOSS_T_REDUCE, n);
     r = reduce_runs<K>(c, moved ? dst : src, nullptr, n, moved ? src : dst);
     t.stop();
-    if (c->debug) std::fprintf(stderr, "libgossgpu: count_keys: full sort of %llu keys -> %llu distinct\n", (unsigned long long)n, (unsigned long long)r.m);
+    if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: count_keys: full sort of %llu keys -> %llu distinct\n", (unsigned long long)n, (unsigned long long)r.m);
     return r;
 }
 
@@ -1005,7 +1001,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
     PhaseTimer t(c, GOSS_T_ORDER, m);
     // the run's own storage is one side of the sort's ping-pong, a temporary copy the other
     const uint64_t need = m * sizeof(K) + m * 4 + 512;
-    if (c->arena.avail() < need + (256ULL << 20)) grow_arena(c, need + (256ULL << 20));      // (rebases r: it lives in c->runs)
+    if (c->arena.avail() < need + (256ULL << 20)) grow_arena(c, need + (256ULL << 20));      // (rebases r: it lives in c->build.runs)
     uint64_t mark = c->arena.mark();
     K* ka = (K*)r.keys;
     uint32_t* va = r.counts;
@@ -1013,8 +1009,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
     uint32_t* vb = (uint32_t*)c->arena.temp(m * 4);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(canonical_map_kernel<K>), dim3(grid_for(m, kTB)), dim3(kTB), 0, c->stream,
                        (const K*)ka, ka, m, c->len);
-    const bool mute = c->mute_timing;
-    c->mute_timing = true;                  // the sort's passes belong to this phase, not to the partition classes
+    Scoped<bool> mute(&c->mute_timing, true);          // the sort's passes belong to this phase, not to the partition classes
     bool in_b = false, ordered = false;
     const uint32_t keybits = 2 * c->len;
     if constexpr (std::is_same<K, Key1>::value)
@@ -1025,7 +1020,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
         // (reads with errors; the ranks of a multi-GPU build hold up to the whole k-mer set before the exchange)
         uint32_t sb = 16;
         while (sb < 24 && m > (1ULL << sb) * 2400) ++sb;                // the fewest groups of at most ~2 400 pairs
-        if (c->order_bits) sb = c->order_bits;
+        if (c->knobs.order_bits) sb = c->knobs.order_bits;
         if (keybits >= sb + 10 && m >= (1u << 20) && m <= (1ULL << sb) * 2400)
         {
             const uint32_t nseg = 1u << sb;
@@ -1045,7 +1040,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
             HIP_TRY(hipStreamSynchronize(c->stream));
             ordered = hf[0] == 0;
             c->arena.release(m2);
-            if (c->debug) std::fprintf(stderr, "libgossgpu: canonical order of %llu keys by %u-bit groups: %s\n", (unsigned long long)m, sb, ordered ? "done" : "skewed, full sort");
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: canonical order of %llu keys by %u-bit groups: %s\n", (unsigned long long)m, sb, ordered ? "done" : "skewed, full sort");
             if (!ordered)
             {
                 // skewed bits: order everything by the remaining digits as well (the top bits are in place,
@@ -1056,7 +1051,6 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
         }
     }
     if (!ordered) in_b = radix_sort<K, true>(c, ka, kb, va, vb, m, key_digits(c));
-    c->mute_timing = mute;
     if ((in_b ? kb : ka) != (K*)r.keys)
     {
         HIP_TRY(hipMemcpyAsync(r.keys, in_b ? kb : ka, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
@@ -1074,8 +1068,8 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
 template <class K>
 void expand_graph_run(goss_gpu_ctx* c, size_t ri)
 {
-    const uint64_t m = c->runs[ri].m;
-    c->runs[ri].rep = false;
+    const uint64_t m = c->build.runs[ri].m;
+    c->build.runs[ri].rep = false;
     if (m == 0) return;
     PhaseTimer t(c, GOSS_T_ORDER, m);
     {
@@ -1090,17 +1084,17 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
     unsigned long long* dbig = (unsigned long long*)c->arena.temp((2 + 3 * kMaxBig) * 8);
     unsigned long long* npal = dbig + 1 + 3 * kMaxBig;
     HIP_TRY(hipMemsetAsync(dbig, 0, (2 + 3 * kMaxBig) * 8, c->stream));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(graph_expand_kernel<K>), dim3(grid_for(m, kTB)), dim3(kTB), 0, c->stream, (const K*)c->runs[ri].keys,
-                       c->runs[ri].counts, m, c->len, bk, bc, dbig, kMaxBig, npal);
-    const bool mute = c->mute_timing;
-    c->mute_timing = true;                  // the sort's passes belong to this phase
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(graph_expand_kernel<K>), dim3(grid_for(m, kTB)), dim3(kTB), 0, c->stream, (const K*)c->build.runs[ri].keys,
+                       c->build.runs[ri].counts, m, c->len, bk, bc, dbig, kMaxBig, npal);
     // (the pads -- all ones, in the slots of the palindromes -- must end up BEHIND every key: where the key's 2 len bits
     // fill whole digits (len a multiple of four: 12, 16, .. 28, 32, ..) the edge T..T has every digit a pad has, a stable
     // sort on those digits alone leaves the two kinds in input order, and the cut below dropped T..T for a pad whenever a
     // palindrome stood in front of it: one digit more -- zeros for a key, ones for a pad -- tells them apart)
     const uint32_t nd = key_digits(c) + ((2 * c->len) % 8 == 0 ? 1u : 0u);
-    const bool in_b = radix_sort<K, true>(c, bk, tk, bc, tc, m, nd);
-    c->mute_timing = mute;
+    const bool in_b = [&]() {
+        Scoped<bool> mute(&c->mute_timing, true);          // the sort's passes belong to this phase
+        return radix_sort<K, true>(c, bk, tk, bc, tc, m, nd);
+    }();
     std::vector<unsigned long long> hb(2 + 3 * kMaxBig);
     HIP_TRY(hipMemcpyAsync(hb.data(), dbig, hb.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1109,8 +1103,8 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
     const uint64_t mb = m - npads;
     // exact counts: the representative's entry stays (doubled for a palindrome), its reverse complement gets the same
     BigMap ma, mbm;
-    if (c->runs[ri].big >= 0)
-        for (const auto& kv : c->big_maps[c->runs[ri].big])
+    if (c->build.runs[ri].big >= 0)
+        for (const auto& kv : c->build.big_maps[c->build.runs[ri].big])
         {
             K k;
             if constexpr (sizeof(K) == 8) k = K{kv.first.second}; else k = K{kv.first.second, kv.first.first};
@@ -1119,8 +1113,8 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
             else { ma[kv.first] = kv.second; mbm[std::make_pair((uint64_t)key_hi_word(r), (uint64_t)key_lo_word(r))] = kv.second; }
         }
     for (uint64_t i = 0; i < hb[0]; ++i) ma[std::make_pair((uint64_t)hb[2 + 3 * i], (uint64_t)hb[1 + 3 * i])] = hb[3 + 3 * i];
-    c->runs[ri].big = -1;
-    if (!ma.empty()) { c->big_maps.push_back(std::move(ma)); c->runs[ri].big = (int)c->big_maps.size() - 1; }
+    c->build.runs[ri].big = -1;
+    if (!ma.empty()) { c->build.big_maps.push_back(std::move(ma)); c->build.runs[ri].big = (int)c->build.big_maps.size() - 1; }
     if (mb)
     {
         Run b{nullptr, nullptr, mb};
@@ -1128,13 +1122,13 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
         b.counts = (uint32_t*)c->arena.perm(mb * 4);
         HIP_TRY(hipMemcpyAsync(b.keys, in_b ? tk : bk, mb * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(b.counts, in_b ? tc : bc, mb * 4, hipMemcpyDeviceToDevice, c->stream));
-        if (!mbm.empty()) { c->big_maps.push_back(std::move(mbm)); b.big = (int)c->big_maps.size() - 1; }
-        c->runs.push_back(b);
+        if (!mbm.empty()) { c->build.big_maps.push_back(std::move(mbm)); b.big = (int)c->build.big_maps.size() - 1; }
+        c->build.runs.push_back(b);
     }
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->arena.release(mark);
-    if (c->debug) std::fprintf(stderr, "libgossgpu: %llu strand pairs expanded (%llu palindromes)\n", (unsigned long long)m, (unsigned long long)npads);
+    if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: %llu strand pairs expanded (%llu palindromes)\n", (unsigned long long)m, (unsigned long long)npads);
 }
 
 // ---- merging runs ---------------------------------------------------------------------------
@@ -1167,7 +1161,7 @@ inline bool merge_by_table(const MergeInput<Key2>& in, Run* out)
 {
     goss_gpu_ctx* c = in.c;
     const uint32_t keybits = 2 * c->len, nruns = in.nruns;
-    if (!(c->table96 && keybits >= 16 + 8 && keybits - 16 <= 96 && nruns <= (uint32_t)kMergeRuns && in.total >= c->hash_merge_min)) return false;
+    if (!(c->knobs.table96 && keybits >= 16 + 8 && keybits - 16 <= 96 && nruns <= (uint32_t)kMergeRuns && in.total >= c->knobs.hash_merge_min)) return false;
     const uint32_t nseg = 65536, shift = keybits - 16;
     uint64_t m2 = c->arena.mark();
     uint64_t* bounds = (uint64_t*)c->arena.temp((uint64_t)nruns * (nseg + 1) * 8);
@@ -1182,8 +1176,8 @@ inline bool merge_by_table(const MergeInput<Key2>& in, Run* out)
     st.gather(out);
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->seg_merges++;
-    c->hash_merges++;
+    c->stats.seg_merges++;
+    c->stats.hash_merges++;
     return true;
 }
 
@@ -1223,7 +1217,7 @@ bool merge_by_segments(const MergeInput<K>& in, Run* out)
         t.stop();
         HIP_TRY(hipStreamSynchronize(c->stream));
         resolve_big_counts<K>(c, *out, in.ka, in.va, in.run_off, in.in_bigs);
-        c->seg_merges++;
+        c->stats.seg_merges++;
         return true;
     }
     return false;
@@ -1244,23 +1238,23 @@ void merge_by_sort(const MergeInput<K>& in, Run* out)
 template <class K>
 void merge_runs(goss_gpu_ctx* c)
 {
-    if (c->runs.size() <= 1) return;
+    if (c->build.runs.size() <= 1) return;
     bool all_rep = true, any_rep = false;
-    for (auto& r : c->runs) { all_rep = all_rep && r.rep; any_rep = any_rep || r.rep; }
+    for (auto& r : c->build.runs) { all_rep = all_rep && r.rep; any_rep = any_rep || r.rep; }
     if (any_rep && !all_rep)
     {
-        const size_t nr = c->runs.size();
+        const size_t nr = c->build.runs.size();
         for (size_t i = 0; i < nr; ++i)
-            if (c->runs[i].rep)
+            if (c->build.runs[i].rep)
             {
                 if (c->mode == GOSS_MODE_GRAPH) expand_graph_run<K>(c, i);          // (appends the reverse complements as a run of their own)
-                else if constexpr (std::is_same<K, Key1>::value) canonicalize_run<K>(c, c->runs[i]);
+                else if constexpr (std::is_same<K, Key1>::value) canonicalize_run<K>(c, c->build.runs[i]);
                 else throw StatusError{GOSS_ERR_STATE, "a two-word run in representative space"};
             }
     }
     const bool rep_out = all_rep;
     uint64_t total = 0;
-    for (auto& r : c->runs) total += r.m;
+    for (auto& r : c->build.runs) total += r.m;
     {
         // two copies of all entries + segment tables; low-duplication inputs do not shrink
         const uint64_t need = 2 * total * (sizeof(K) + 4) + (512ULL << 20);
@@ -1268,13 +1262,13 @@ void merge_runs(goss_gpu_ctx* c)
     }
     uint64_t mark = c->arena.mark();
     MergeInput<K> in;
-    in.c = c; in.total = total; in.nruns = (uint32_t)c->runs.size();
+    in.c = c; in.total = total; in.nruns = (uint32_t)c->build.runs.size();
     in.ka = (K*)c->arena.temp(total * sizeof(K));
     in.kb = (K*)c->arena.temp(total * sizeof(K));
     in.va = (uint32_t*)c->arena.temp(total * 4);
     in.vb = (uint32_t*)c->arena.temp(total * 4);
     uint64_t off = 0;
-    for (auto& r : c->runs)
+    for (auto& r : c->build.runs)
     {
         HIP_TRY(hipMemcpyAsync(in.ka + off, r.keys, r.m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(in.va + off, r.counts, r.m * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -1285,14 +1279,14 @@ void merge_runs(goss_gpu_ctx* c)
     in.run_off.push_back(off);
     HIP_TRY(hipStreamSynchronize(c->stream));
     // the old runs' permanent storage is dead now: rewind the permanent end to the first run
-    c->arena.lo = (uint64_t)((uint8_t*)c->runs.front().keys - c->arena.base);
-    c->runs.clear();
+    c->arena.lo = (uint64_t)((uint8_t*)c->build.runs.front().keys - c->arena.base);
+    c->build.runs.clear();
 
     Run r{nullptr, nullptr, 0};
     bool merged = false;
     if constexpr (std::is_same<K, Key2>::value) merged = merge_by_table(in, &r);
     if (!merged && !merge_by_segments(in, &r)) merge_by_sort(in, &r);
     r.rep = rep_out;
-    c->runs.push_back(r);
+    c->build.runs.push_back(r);
     c->arena.release(mark);
 }

@@ -77,30 +77,30 @@ FusedForm choose_form(const goss_gpu_ctx* c, uint32_t keybits, uint64_t m_est, b
     FusedForm f;
     f.segbits = kSegBits;
     while (f.segbits < (uint32_t)kSegBitsMax && (m_est >> f.segbits) > limit * 3 / 4) f.segbits += 4;
-    const bool big_ok = c->fused_msd && c->big_table && f.segbits > (uint32_t)kSegBits;
+    const bool big_ok = c->knobs.fused_msd && c->knobs.big_table && f.segbits > (uint32_t)kSegBits;
     // one-word keys: between 3/4 of the small table and 3/4 of the big one per 16-bit segment, the
     // two-level form with the big counting table saves the third partition digit
     // (up to 4 workgroups sharing a segment, each counting the keys of one value of the next bits)
     if (kOne && big_ok && keybits >= (uint32_t)kSegBits + 8 + 2)
-        for (int r = std::max(0, c->big_rounds_min); r <= kBigRoundsMax; ++r)
+        for (int r = std::max(0, c->knobs.big_rounds_min); r <= kBigRoundsMax; ++r)
             if ((m_est >> (kSegBits + r)) <= (uint64_t)kSegBigLimit * 17 / 20) { f.segbits = kSegBits; f.table = FusedForm::kBig; f.rounds = (uint32_t)r; break; }   // (an overflow costs one more counting pass, no more)
     // two-word keys: the 4096-slot table, up to two workgroups per segment (a pass over 16-byte
     // keys costs more than one over 8-byte keys)
     // two-word keys whose bits below a 16-bit prefix fit 96: 16-byte slots, 8192 of them
-    if (!kOne && big_ok && c->table96 && keybits - kSegBits <= 96 && c->big_rounds_min == 0 && (m_est >> kSegBits) <= (uint64_t)kSeg96Limit * 3 / 4)
+    if (!kOne && big_ok && c->knobs.table96 && keybits - kSegBits <= 96 && c->knobs.big_rounds_min == 0 && (m_est >> kSegBits) <= (uint64_t)kSeg96Limit * 3 / 4)
     { f.segbits = kSegBits; f.table = FusedForm::k96; }
     else if (!kOne && big_ok)
-        for (int r = std::max(0, c->big_rounds_min); r <= std::min(1, kBigRoundsMax); ++r)
+        for (int r = std::max(0, c->knobs.big_rounds_min); r <= std::min(1, kBigRoundsMax); ++r)
         {
             if ((m_est >> (kSegBits + r)) <= (uint64_t)kSegBigLimit2 * 3 / 4) { f.segbits = kSegBits; f.table = FusedForm::kBig; f.rounds = (uint32_t)r; break; }
             // between the two: the 6144-slot table, still one workgroup (and one read) per segment
-            if (r == 0 && c->wide_table && (m_est >> kSegBits) <= (uint64_t)kSegWideLimit2 * 3 / 4) { f.segbits = kSegBits; f.table = FusedForm::kWide; break; }
+            if (r == 0 && c->knobs.wide_table && (m_est >> kSegBits) <= (uint64_t)kSegWideLimit2 * 3 / 4) { f.segbits = kSegBits; f.table = FusedForm::kWide; break; }
         }
     // one-word keys whose bits below a 17- to 20-bit prefix fit 32 (an odd-length k-mer's strand representative has one
     // bit that is always clear): 9 to 12 bits at the second level, which then writes -- and the counting kernel reads --
     // 4-byte remainders instead of 8-byte keys (kernels_partition.hpp: subpart32_kernel).  The fewest bits whose
     // segments hold the estimated distinct keys in an LDS table (2048 slots at 9 bits when they do, else 4096).
-    if (kOne && c->rem32 && c->fused_msd && c->big_rounds_min == 0)
+    if (kOne && c->knobs.rem32 && c->knobs.fused_msd && c->knobs.big_rounds_min == 0)
     {
         // (second-level bits, third-level bits) in the order of what they cost on C2's 12.6 G keys: the second level 31 ms
         // with 9 bits and 46 with 10 (shorter runs), the third level ~30 ms whatever it splits into -- so ten bits before a
@@ -115,28 +115,28 @@ FusedForm choose_form(const goss_gpu_ctx* c, uint32_t keybits, uint64_t m_est, b
         for (const auto& cand : order)
         {
             const uint32_t b2 = cand[0], b3 = cand[1], table = cand[2];
-            if (table > 4096u && c->rem32_slots) continue;          // (a forced table: the candidates' own do not apply)
-            if (b2 < c->rem32_bits_min || b3 < c->rem32_split_min) continue;
+            if (table > 4096u && c->knobs.rem32_slots) continue;          // (a forced table: the candidates' own do not apply)
+            if (b2 < c->knobs.rem32_bits_min || b3 < c->knobs.rem32_split_min) continue;
             if (keybits < 8 + b2 + 8) continue;
             const uint32_t rb = keybits - 8 - b2;
             const bool sq = !graph_mode && !canon_l1 && (c->len & 1u) && rb == 33;
             if (rb - (sq ? 1u : 0u) > 32 || rb - (sq ? 1u : 0u) < b3 + 8) continue;
             const uint64_t per = m_est >> (8 + b2 + b3);
             int slots = 0;
-            if (c->rem32_slots) slots = per <= (uint64_t)(c->rem32_slots / 4 * 3) || (b2 == 10 && b3 == (uint32_t)kSub32SplitMax) ? c->rem32_slots : 0;
+            if (c->knobs.rem32_slots) slots = per <= (uint64_t)(c->knobs.rem32_slots / 4 * 3) || (b2 == 10 && b3 == (uint32_t)kSub32SplitMax) ? c->knobs.rem32_slots : 0;
             // (buckets of four: what is not at home costs a second look, and at a load of 0.37 that is 1.5 % of the keys, at
             // 0.19 a per-mille -- the small table only where it stays that empty)
-            else if (per <= (c->r32_small_max ? c->r32_small_max : 400u) && b3 == 0 && b2 == (uint32_t)kSub32BitsMin) slots = 2048;
+            else if (per <= (c->knobs.r32_small_max ? c->knobs.r32_small_max : 400u) && b3 == 0 && b2 == (uint32_t)kSub32BitsMin) slots = 2048;
             else if (per <= (uint64_t)table / 4 * 3 * 3 / 4) slots = (int)table;
             if (!slots) continue;
             f = FusedForm{};
             f.table = FusedForm::kRem32; f.segbits = kSegBits;
             f.r32_slots = slots; f.r32_bits = b2; f.rbits32 = rb; f.squeeze = sq; f.r32_split = b3;
-            f.narrow = c->narrow;          // remainder + digit between the two levels, 5.33 bytes a key
+            f.narrow = c->knobs.narrow;          // remainder + digit between the two levels, 5.33 bytes a key
             break;
         }
     }
-    f.msd = c->fused_msd && f.segbits == 16;
+    f.msd = c->knobs.fused_msd && f.segbits == 16;
     return f;
 }
 
@@ -164,12 +164,12 @@ struct FusedChunk {
 
     int decline(const char* why) const
     {
-        if (c->debug) std::fprintf(stderr, "libgossgpu: fused path declined (%s), %llu window starts\n", why, (unsigned long long)nstarts);
+        if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: fused path declined (%s), %llu window starts\n", why, (unsigned long long)nstarts);
         return (int)kFusedDeclined;
     }
     void lap(const char* what) const
     {
-        if (!c->debug) return;
+        if (!c->knobs.debug) return;
         HIP_TRY(hipStreamSynchronize(c->stream));
         std::fprintf(stderr, "libgossgpu: fused path: %-28s at %8.3f ms\n", what,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
@@ -196,7 +196,7 @@ int plan_sample(const FusedChunk<K>& ch, FusedSample* sm)
     constexpr bool kOne = FusedChunk<K>::kOne;
     const goss_gpu_ctx* c = ch.c;
     const uint64_t nstarts = ch.nstarts;
-    const bool want_msd = c->fused_msd;
+    const bool want_msd = c->knobs.fused_msd;
     uint64_t sample_starts = nstarts <= (16u << 20) ? nstarts : (4u << 20);
     if (want_msd) sample_starts = nstarts <= (640u << 20) ? nstarts : std::max<uint64_t>(160u << 20, nstarts / 64);
     // keys that the 32-bit-remainder forms take (by their width): half the sample -- their sub-regions are 4-byte slots,
@@ -204,7 +204,7 @@ int plan_sample(const FusedChunk<K>& ch, FusedSample* sm)
     // sample's extraction, spectrum and joint histogram are 3 ms of a 97 ms step
     {
         bool width_ok = false;
-        if (kOne && c->rem32 && ch.keybits >= 8 + 9 + 8)
+        if (kOne && c->knobs.rem32 && ch.keybits >= 8 + 9 + 8)
             for (uint32_t b2 = kSub32BitsMin; b2 <= (uint32_t)kSub32BitsMax; ++b2)
             {
                 const uint32_t rb = ch.keybits - 8 - b2;
@@ -254,7 +254,7 @@ uint64_t extract_sample(const FusedChunk<K>& ch, const FusedSample& sm, bool rep
     const ReadSrc& src = ch.src;
     const uint64_t nstarts = ch.nstarts, navail = ch.navail, nslices = sm.nslices, slice_starts = sm.slice_starts, slice_stride = sm.slice_stride;
     K* ka = ch.ka;
-    c->mute_timing = true;
+    Scoped<bool> mute(&c->mute_timing, true);
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(ExtractCounters), c->stream));
     {
         // (a packed string whose sample is the whole chunk: the slice kernels below, told to take every tile in turn --
@@ -292,13 +292,12 @@ uint64_t extract_sample(const FusedChunk<K>& ch, const FusedSample& sm, bool rep
     ExtractCounters* hcs = (ExtractCounters*)c->h_pinned;
     HIP_TRY(hipMemcpyAsync(hcs, c->d_ctr, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->mute_timing = false;
     return (uint64_t)hcs->keys_out;
 }
 
 // ---- the key space -----------------------------------------------------------------------------
 // Whether the first level of this chunk computes gossamer's canonical form itself.  The only stage that writes
-// c->space_choice.
+// c->build.space_choice.
 // One-word k-mer sets are counted as strand representatives and mapped to gossamer's canonical form afterwards -- a
 // re-ordering of the DISTINCT keys (0.06 ms per million), cheap beside two FNV hashes per WINDOW in the first level
 // (+ ~2.4 ms per 10^9 windows) while distinct keys are few.  Reads with many errors turn that round (2e9 distinct
@@ -316,25 +315,25 @@ uint64_t extract_sample(const FusedChunk<K>& ch, const FusedSample& sm, bool rep
 inline bool choose_key_space(goss_gpu_ctx* c, bool rep_kmer, uint64_t m_est, uint64_t m_rare, uint64_t n_exp)
 {
     bool canon_auto = (double)m_est > kCanonL1At * (double)n_exp;
-    if (rep_kmer && c->canon_l1 == 1)
+    if (rep_kmer && c->knobs.canon_l1 == 1)
     {
-        if (c->space_choice >= 0 && !c->runs.empty()) canon_auto = c->space_choice == 1;
+        if (c->build.space_choice >= 0 && !c->build.runs.empty()) canon_auto = c->build.space_choice == 1;
         else
         {
             const double w_c = (double)n_exp;
             // (what follows: known for the rest of the push being counted; a guess -- three times as much again -- when
             // that push is a staging buffer that filled up under a caller who goes on pushing)
             const double w_push = w_c + (double)c->more_starts * std::min(1.0, c->valid_frac);          // this push, from this chunk on
-            double w_all = (double)c->windows + w_push * (c->more_follows ? 4.0 : 1.0);
-            if (c->expect_bases) w_all = std::max(w_all, (double)c->expect_bases * std::min(1.0, c->valid_frac));
+            double w_all = (double)c->build.windows + w_push * (c->more_follows ? 4.0 : 1.0);
+            if (c->build.expect_bases) w_all = std::max(w_all, (double)c->build.expect_bases * std::min(1.0, c->valid_frac));
             const double d_all = (double)(m_est - m_rare) + (double)m_rare * (w_all / w_c);
             canon_auto = d_all > kCanonL1At * w_all;
-            if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: %.0f distinct keys (%.0f of multiplicity ~1) of %.0f windows here, %.0f of %.0f in all: %s\n",
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: fused path: %.0f distinct keys (%.0f of multiplicity ~1) of %.0f windows here, %.0f of %.0f in all: %s\n",
                                        (double)m_est, (double)m_rare, w_c, d_all, w_all, canon_auto ? "canonical forms in the first level" : "strand representatives");
         }
     }
-    const bool canon_l1 = rep_kmer && (c->canon_l1 == 2 || (c->canon_l1 == 1 && canon_auto));
-    if (rep_kmer && c->canon_l1 == 1) c->space_choice = canon_l1 ? 1 : 0;
+    const bool canon_l1 = rep_kmer && (c->knobs.canon_l1 == 2 || (c->knobs.canon_l1 == 1 && canon_auto));
+    if (rep_kmer && c->knobs.canon_l1 == 1) c->build.space_choice = canon_l1 ? 1 : 0;
     return canon_l1;
 }
 
@@ -358,12 +357,13 @@ SampleHist sample_histograms(const FusedChunk<K>& ch, const FusedForm& form, uin
         // with the bins in LDS (a 16-bit partition of the sample + segment bounds took 2.4 ms on C2, this 0.9);
         // 17 bits (four sweeps) for the 32-bit-remainder form, whose pairs of bins are the 16-bit form's
         const uint32_t jbins = form.rem32() ? form.r32_regions() : 65536u;
-        c->mute_timing = true;
         unsigned long long* jh = (unsigned long long*)c->arena.temp((uint64_t)jbins * 8);
         HIP_TRY(hipMemsetAsync(jh, 0, (uint64_t)jbins * 8, c->stream));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(joint_hist_kernel<K>), dim3(256), dim3(kJointThreads), 0, c->stream, (const K*)ch.ka, ns,
-                           form.rem32() ? form.rbits32 : shift, jh, jbins / 32768u);
-        c->mute_timing = false;
+        {
+            Scoped<bool> mute(&c->mute_timing, true);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(joint_hist_kernel<K>), dim3(256), dim3(kJointThreads), 0, c->stream, (const K*)ch.ka, ns,
+                               form.rem32() ? form.rbits32 : shift, jh, jbins / 32768u);
+        }
         std::vector<uint64_t> ho(jbins);
         HIP_TRY(hipMemcpyAsync(ho.data(), jh, (uint64_t)jbins * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -381,9 +381,10 @@ SampleHist sample_histograms(const FusedChunk<K>& ch, const FusedForm& form, uin
     {
         unsigned long long* shist = (unsigned long long*)c->arena.temp(256 * 8);
         HIP_TRY(hipMemsetAsync(shist, 0, 256 * 8, c->stream));
-        c->mute_timing = true;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(global_hist_kernel<K>), dim3(256), dim3(kTB), 0, c->stream, (const K*)ch.ka, ns, shift, 1u, shist);
-        c->mute_timing = false;
+        {
+            Scoped<bool> mute(&c->mute_timing, true);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(global_hist_kernel<K>), dim3(256), dim3(kTB), 0, c->stream, (const K*)ch.ka, ns, shift, 1u, shist);
+        }
         HIP_TRY(hipMemcpyAsync(h.hh.data(), shist, 256 * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -565,7 +566,7 @@ void launch_first_level(const FusedChunk<K>& ch, const FusedForm& form, bool can
     const uint32_t shift = ch.keybits - form.segbits, npass = (form.segbits + 7) / 8;
     FirstLevelLaunch a{};
     a.in = ch.src.launch();
-    if (ch.src.packed()) c->pk_fused_chunks++;
+    if (ch.src.packed()) c->stats.pk_fused_chunks++;
     a.nstarts = ch.nstarts; a.navail = ch.navail;
     a.ka = ch.ka; a.pc = pc; a.dgt = dgt;
     a.part_shift = form.msd ? ch.keybits - 8 : shift;           // the fused kernel's digit
@@ -577,10 +578,10 @@ void launch_first_level(const FusedChunk<K>& ch, const FusedForm& form, bool can
     if constexpr (FusedChunk<K>::kOne)
     {
         // the 32-bit forms of the kernel: the partition digit is the key's top eight bits (msd) and lies at bit 34 or above
-        const bool fastk = a.nh == 0 && 2 * c->len >= 32 && a.part_shift >= 34 && !c->no_fast32;
+        const bool fastk = a.nh == 0 && 2 * c->len >= 32 && a.part_shift >= 34 && !c->knobs.no_fast32;
         const bool narrow = form.msd && form.rem32() && form.narrow;
         const uint32_t nr_rbits = form.rbits32, nr_sqbit = form.squeeze ? c->len - 1 : 0u, nr_dmask = (1u << form.r32_bits) - 1u;
-        const uint32_t nr_capg = std::max(576u, c->narrow_capg);          // (the kernel takes its LDS layout's own number of granules where that is less: kernels_extract.hpp, kSlots)
+        const uint32_t nr_capg = std::max(576u, c->knobs.narrow_capg);          // (the kernel takes its LDS layout's own number of granules where that is less: kernels_extract.hpp, kSlots)
         if (ch.graph_mode) launch_extract1_part<1, 0>(c, a, fastk, narrow, nr_rbits, nr_sqbit, nr_dmask, nr_capg);
         // gossamer's canonical form computed per window (many distinct keys: choose_key_space)
         else if (canon_l1) launch_extract1_part<0, 2>(c, a, fastk, narrow, nr_rbits, nr_sqbit, nr_dmask, nr_capg);
@@ -618,7 +619,7 @@ int read_first_level(const FusedChunk<K>& ch, const FusedForm& form, const Bucke
     HIP_TRY(hipMemcpyAsync(hpc.data(), pc, sizeof(PartCounters), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const PartCounters* hp = (const PartCounters*)hpc.data();
-    if (hp->overflow) { c->fused_overflows++; return ch.decline("a bucket region overflowed"); }
+    if (hp->overflow) { c->stats.fused_overflows++; return ch.decline("a bucket region overflowed"); }
     ch.lap("extraction + first level");
 #if defined(GOSS_STAMPS)
     // (timing build: wave 0's cycles per phase and tile, averaged over the workgroups)
@@ -718,7 +719,7 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
                        (const uint32_t*)cur2, r32_regions, seg_beg, seg_end);
     HIP_TRY(hipMemcpyAsync(lb.hctl, lb.ctl, sizeof(LookbackCtl), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (lb.hctl->error) { c->fused_overflows++; return ch.decline("a 32-bit sub-region overflowed"); }
+    if (lb.hctl->error) { c->stats.fused_overflows++; return ch.decline("a 32-bit sub-region overflowed"); }
     ch.lap("second level (32-bit remainders)");
     // third level: every segment split into 2^r32_split sub-segments, from kb into ka (same offsets); the counts are
     // then staged in kb
@@ -747,28 +748,28 @@ inline int count_rem32(const FusedChunk<Key1>& ch, FusedForm form, const Sub32Re
     {
         const Rem32Layout lay{seg_beg, seg_end, nseg32, form.r32_slots, squeeze, image, rbits32, sqbit32, r32_split};
         rc = segment_reduce32(c, rems, spare32, n, r, lay);
-        if (rc != 1 || form.r32_slots >= 16384 || c->rem32_slots) break;
+        if (rc != 1 || form.r32_slots >= 16384 || c->knobs.rem32_slots) break;
         // the remainders are still in their sub-regions: only the counting is redone, in the next larger table
-        c->segment_retries++;
+        c->stats.segment_retries++;
         form = form.larger_r32_table();
     }
     if (rc != 0)
     {
         // more distinct keys per segment than this form takes: the chunk again
-        c->segment_retries++;
+        c->stats.segment_retries++;
         // more second-level bits while the remainder allows them (the chunk's first level is redone: the staging of
         // the counts has overwritten its regions), else the 8-byte form and its ladder of tables
-        if (rc == 1 && r32_split < (uint32_t)kSub32SplitMax) c->rem32_split_min = r32_split + 1;
-        else c->rem32 = false;
-        if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: 32-bit form with %u + %u bits overflowed (%d), redoing the chunk %s\n", r32_bits, r32_split, rc,
-                                   c->rem32 ? "with more sub-segments" : "in the 8-byte form");
+        if (rc == 1 && r32_split < (uint32_t)kSub32SplitMax) c->knobs.rem32_split_min = r32_split + 1;
+        else c->knobs.rem32 = false;
+        if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: fused path: 32-bit form with %u + %u bits overflowed (%d), redoing the chunk %s\n", r32_bits, r32_split, rc,
+                                   c->knobs.rem32 ? "with more sub-segments" : "in the 8-byte form");
         return kFusedAgain;
     }
-    c->fused_msd_chunks++;
-    c->rem32_chunks++;
-    if (narrow) c->narrow_chunks++;
-    c->rem32_bits_last = r32_bits;
-    c->rem32_split_last = r32_split;
+    c->stats.fused_msd_chunks++;
+    c->stats.rem32_chunks++;
+    if (narrow) c->stats.narrow_chunks++;
+    c->stats.rem32_bits_last = r32_bits;
+    c->stats.rem32_split_last = r32_split;
     return kFusedGoOn;
 }
 
@@ -799,7 +800,7 @@ int count_sub8(const FusedChunk<K>& ch, FusedForm form, const Sub8Regions& sub, 
                        (const unsigned long long*)cur2, seg_beg, seg_end);
     HIP_TRY(hipMemcpyAsync(lb.hctl, lb.ctl, sizeof(LookbackCtl), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (lb.hctl->error) { c->fused_overflows++; return ch.decline("a sub-region overflowed"); }
+    if (lb.hctl->error) { c->stats.fused_overflows++; return ch.decline("a sub-region overflowed"); }
     ch.lap("second level");
     int rc;
     for (;;)
@@ -809,24 +810,24 @@ int count_sub8(const FusedChunk<K>& ch, FusedForm form, const Sub8Regions& sub, 
         // is redone, with the next larger form -- 8192 slots, then 2 and 4 workgroups per segment -- instead of
         // the whole chunk with the unfused kernels
         const bool ladder = form.table == FusedForm::kSmall || (form.table == FusedForm::kBig && form.rounds < (uint32_t)kBigRoundsMax);
-        if (rc != 1 || !FusedChunk<K>::kOne || !c->big_table || !ladder) break;
-        c->segment_retries++;
+        if (rc != 1 || !FusedChunk<K>::kOne || !c->knobs.big_table || !ladder) break;
+        c->stats.segment_retries++;
         form = form.larger_table();
-        if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: a counting table overflowed, next form %d\n", 1 + (int)form.rounds);
+        if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: fused path: a counting table overflowed, next form %d\n", 1 + (int)form.rounds);
     }
     if (rc != 0)
     {
-        c->segment_retries++;
+        c->stats.segment_retries++;
         // this input is too skewed for it: the next smaller form from now on
-        if (form.table == FusedForm::k96) c->table96 = false;
-        else if (form.table == FusedForm::kWide) c->wide_table = false;
-        else if (form.table == FusedForm::kBig) c->big_table = false;
+        if (form.table == FusedForm::k96) c->knobs.table96 = false;
+        else if (form.table == FusedForm::kWide) c->knobs.wide_table = false;
+        else if (form.table == FusedForm::kBig) c->knobs.big_table = false;
         return ch.decline("a segment table overflowed");
     }
-    c->fused_msd_chunks++;
-    if (form.table != FusedForm::kSmall) c->big_table_chunks++;
-    if (form.table == FusedForm::kWide) c->wide_table_chunks++;
-    if (form.table == FusedForm::k96) c->table96_chunks++;
+    c->stats.fused_msd_chunks++;
+    if (form.table != FusedForm::kSmall) c->stats.big_table_chunks++;
+    if (form.table == FusedForm::kWide) c->stats.wide_table_chunks++;
+    if (form.table == FusedForm::k96) c->stats.table96_chunks++;
     return kFusedGoOn;
 }
 
@@ -873,8 +874,8 @@ int count_dense(const FusedChunk<K>& ch, const FusedForm& form, const FirstLevel
         if (lb.hctl->error)
         {
             std::fprintf(stderr, "libgossgpu: radix look-back chain gave up in the fused path; redoing the chunk unfused\n");
-            c->lookback_failures++;
-            c->ordered_tiles = true;
+            c->stats.lookback_failures++;
+            c->knobs.ordered_tiles = true;
             return kFusedDeclined;
         }
         std::swap(src, dst);
@@ -882,7 +883,7 @@ int count_dense(const FusedChunk<K>& ch, const FusedForm& form, const FirstLevel
     // src = partitioned keys (dense: npass >= 2), dst = spare
     c->arena.release(mark);
     const int rc = segment_reduce<K>(c, src, dst, n, form.segbits, r);
-    if (rc != 0) { c->segment_retries++; return ch.decline("a segment table overflowed"); }
+    if (rc != 0) { c->stats.segment_retries++; return ch.decline("a segment table overflowed"); }
     return kFusedGoOn;
 }
 
@@ -892,14 +893,14 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
 {
     constexpr bool kOne = FusedChunk<K>::kOne;
     const uint32_t keybits = 2 * c->len;
-    if (src.records() && !kOne && c->mode == GOSS_MODE_GRAPH && !c->graph_rep) return kFusedDeclined;          // (the record form extracts one key per window)
+    if (src.records() && !kOne && c->mode == GOSS_MODE_GRAPH && !c->knobs.graph_rep) return kFusedDeclined;          // (the record form extracts one key per window)
     FusedChunk<K> ch{c, src, nstarts, navail, ka, ka_slots, kb, kb_slots, keybits};
-    ch.rep_graph = c->mode == GOSS_MODE_GRAPH && c->graph_rep;
+    ch.rep_graph = c->mode == GOSS_MODE_GRAPH && c->knobs.graph_rep;
     ch.rep_kmer = c->mode != GOSS_MODE_GRAPH && kOne;
     ch.use_rep = ch.rep_graph || ch.rep_kmer;
     ch.graph_mode = c->mode == GOSS_MODE_GRAPH && !ch.rep_graph;
     ch.reduced = ka_slots < nstarts * (ch.graph_mode ? 2 : 1) || kb_slots < nstarts * (ch.graph_mode ? 2 : 1);
-    if (!c->fused || c->path != 0 || !c->lookback || c->ordered_tiles || nstarts < c->fused_min || keybits < (uint32_t)kSegBits + 8)
+    if (!c->knobs.fused || c->path != 0 || !c->knobs.lookback || c->knobs.ordered_tiles || nstarts < c->knobs.fused_min || keybits < (uint32_t)kSegBits + 8)
         return kFusedDeclined;
     const uint64_t mark = c->arena.mark();
     struct Release { goss_gpu_ctx* c; uint64_t m; ~Release() { c->arena.release(m); } } release{c, mark};
@@ -914,7 +915,7 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     sm.n_exp = (uint64_t)((double)sm.ns * sm.scale);
     uint64_t m_rare = 0;
     uint64_t m_est = spectrum_estimate<K>(c, ka, sm.ns, (double)sm.n_exp, &m_rare);
-    if (c->est_scale != 1.0) m_est = (uint64_t)((double)m_est * c->est_scale);      // tests: a wrong estimate on purpose
+    if (c->knobs.est_scale != 1.0) m_est = (uint64_t)((double)m_est * c->knobs.est_scale);      // tests: a wrong estimate on purpose
     m_rare = std::min(m_rare, m_est);
     ch.lap("distinct keys estimated");
     if (m_est == 0 || m_est > sm.n_exp / 3) return ch.decline("too little duplication for the segment path");
@@ -928,7 +929,7 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     // buffers sized from the estimated share of valid windows must hold what the sample promises
     if (ch.reduced && ((double)sm.n_exp * 1.035 + 262144.0 > (double)ka_slots || (double)sm.n_exp * 1.02 + 6.0e6 > (double)kb_slots))
     {
-        if (c->debug) std::fprintf(stderr, "libgossgpu: fused path: %llu keys expected, buffers of %llu / %llu slots too small\n",
+        if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: fused path: %llu keys expected, buffers of %llu / %llu slots too small\n",
                                    (unsigned long long)sm.n_exp, (unsigned long long)ka_slots, (unsigned long long)kb_slots);
         return (int)kFusedNeedFull;
     }
@@ -946,10 +947,10 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     Sub8Regions sub8;
     if (form.msd && form.rem32())
     {
-        sub32 = size_sub32_regions(hist.joint17, form, sm, c->fused_capscale, ka_slots, kb_slots);
+        sub32 = size_sub32_regions(hist.joint17, form, sm, c->knobs.fused_capscale, ka_slots, kb_slots);
         if (sub32.misfit)
         {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: 32-bit sub-regions need %llu slots of %llu: 8-byte form\n",
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: 32-bit sub-regions need %llu slots of %llu: 8-byte form\n",
                                        (unsigned long long)sub32.slots, (unsigned long long)(2 * kb_slots));
             form = form.eight_byte();
             if ((m_est >> form.segbits) > limit) return ch.decline("too many distinct keys per segment");
@@ -957,15 +958,15 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     }
     if (form.msd && !form.rem32())
     {
-        sub8 = size_sub8_regions(hist.joint, sm, c->fused_capscale);
+        sub8 = size_sub8_regions(hist.joint, sm, c->knobs.fused_capscale);
         if (sub8.slots > kb_slots && ch.reduced)
         {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu\n", (unsigned long long)sub8.slots, (unsigned long long)kb_slots);
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu\n", (unsigned long long)sub8.slots, (unsigned long long)kb_slots);
             return (int)kFusedNeedFull;
         }
         if (sub8.slots > kb_slots)
         {
-            if (c->debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu: one-level form\n",
+            if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: sub-regions need %llu slots of %llu: one-level form\n",
                                        (unsigned long long)sub8.slots, (unsigned long long)kb_slots);
             if (form.table != FusedForm::kSmall) return ch.decline("sub-regions do not fit and the big table needs them");
             form = form.one_level();
@@ -976,7 +977,7 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     }
     ch.lap("sample histograms");
     BucketRegions br;
-    size_bucket_regions<K>(hist.hh, sm, nstarts, ch.graph_mode, ka_slots, c->fused_capscale, c->blk_log2_max, &br);
+    size_bucket_regions<K>(hist.hh, sm, nstarts, ch.graph_mode, ka_slots, c->knobs.fused_capscale, c->knobs.blk_log2_max, &br);
     // (buffers sized from the share of valid windows: the caller retries with one slot per window start)
     if (!br.fits) return ch.reduced ? (int)kFusedNeedFull : ch.decline("bucket regions do not fit the key buffer");
 
@@ -1001,19 +1002,19 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     ch.lap("segments counted");
 
     // 5. the run
-    if (canon_l1) c->canon_chunks++;
+    if (canon_l1) c->stats.canon_chunks++;
     if (ch.use_rep && !canon_l1)
     {
         // the run stays in representative space: it is mapped to gossamer's canonical forms when it meets a run
         // that is not, or at finish -- a build of several chunks pays for the re-ordering once, on the merged run
         r.rep = true;
-        c->rep_chunks++;
+        c->stats.rep_chunks++;
     }
-    c->runs.push_back(r);
-    c->windows += fl.windows;
-    c->keys_total += ch.rep_graph ? 2 * fl.n : fl.n;          // (the adapter's key stream: two keys per window of a graph)
-    c->fused_chunks++;
-    if (src.records()) c->rec_chunks++;
+    c->build.runs.push_back(r);
+    c->build.windows += fl.windows;
+    c->build.keys_total += ch.rep_graph ? 2 * fl.n : fl.n;          // (the adapter's key stream: two keys per window of a graph)
+    c->stats.fused_chunks++;
+    if (src.records()) c->stats.rec_chunks++;
     return kFusedDone;
 }
 

@@ -23,371 +23,16 @@
 #include "goss_kernels.hpp"
 #include "goss_reader.hpp"
 #include "goss_read_src.hpp"
+#include "goss_knobs.hpp"
 
 using namespace goss;
 
-namespace {
+namespace { constexpr uint32_t kAbiVersion = 1; }
 
-constexpr uint32_t kAbiVersion = 1;
-
-struct HipError { hipError_t e; const char* what; };
-
-#define HIP_TRY(expr)                                                         \
-    do {                                                                      \
-        hipError_t _e = (expr);                                               \
-        if (_e != hipSuccess) throw HipError{_e, #expr};                      \
-    } while (0)
-
-struct StatusError { int status; std::string msg; };
-
-// Two-ended bump arena over one hipMalloc: permanent blocks grow from the bottom, temporary
-// blocks from the top (released by mark).
-struct Arena {
-    uint8_t* base = nullptr;
-    uint64_t size = 0;
-    uint64_t lo = 0;        // permanent top
-    uint64_t hi = 0;        // temporary bottom (offset from base)
-
-    void* perm(uint64_t bytes)
-    {
-        uint64_t a = (lo + 255) & ~255ULL;
-        if (a + bytes > hi) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (permanent)"};
-        lo = a + bytes;
-        return base + a;
-    }
-    void* temp(uint64_t bytes)
-    {
-        if (bytes + 256 > hi) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (temporary)"};
-        uint64_t a = (hi - bytes) & ~255ULL;
-        if (a < lo) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (temporary)"};
-        hi = a;
-        return base + a;
-    }
-    uint64_t mark() const { return hi; }
-    void release(uint64_t m) { hi = m; }
-    uint64_t avail() const { return hi > lo ? hi - lo : 0; }
-};
-
-struct OutFile {
-    std::string suffix;
-    uint64_t size = 0;
-    const uint8_t* dev = nullptr;      // device-resident image, or
-    std::vector<uint8_t> host;         // host-built bytes
-};
-
-typedef std::map<std::pair<uint64_t, uint64_t>, uint64_t> BigMap;     // key (hi, lo) -> count that does not fit 32 bits
-struct Run { void* keys; uint32_t* counts; uint64_t m; int big = -1; bool rep = false; };
-// big: index into ctx.big_maps, or -1.  rep: the keys are strand representatives (extract1_part_kernel), not yet
-// gossamer's canonical forms -- runs of ONE space are merged as they are, and the result is canonicalised once
-
-struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
-
-// What a build entry point left on top of the permanent room for later calls to read (graph_passes.hpp): the segment
-// table and text of goss_gpu_segments_build, the images of goss_gpu_entries_build, or the marks, labels and table of the
-// components entry points.  One record: at most one is held.
-enum class Held : uint8_t { None, Segments, Entries, Components, Pool };
-struct HeldResult { Held kind = Held::None; uint64_t lo = 0; };          // lo: the permanent top before the build
-
-// Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
-// itself (goss_gpu_ctx::canon_l1 == 1).
-// (0.05: re-ordering M distinct pairs into the canonical order costs 53 ms per 10^9 of them, two FNV hashes per window
-// 34 ms per 12.6 G windows -- even at M = 0.051 x windows, and the counting of canonical keys is the faster above that
-// (C2 with 0.3 % / 0.5 % errors: 160 -> 148 / 216 -> 170 ms); 0.10 until the end of round 5)
-constexpr double kCanonL1At = 0.05;
-// At most 2^kBigRoundsMax workgroups share a 16-bit segment counted in the big table.
-constexpr int kBigRoundsMax = 2;
-
-}  // namespace
-
-struct goss_gpu_ctx {
-    int device = 0;
-    uint32_t k = 0, len = 0;
-    int mode = 0;
-    int words = 1;
-    int path = 0;                       // 0 auto, 1 LSD sort only
-    bool lookback = true;               // single-pass radix scatter (GOSS_GPU_NO_LOOKBACK=1 disables)
-    double est_scale = 1.0;             // GOSS_GPU_EST_SCALE: factor on the distinct-key estimate of the fused path (tests)
-    uint32_t order_bits = 0;            // group bits of the canonical re-ordering (GOSS_GPU_ORDER_BITS=16|20; 0 = by size)
-    bool ordered_tiles = false;         // take tile numbers from a ticket instead of blockIdx
-    uint32_t lookback_failures = 0;
-    uint64_t emit_estimate = 0;         // SparseArray estimate M for the next emit (merges)
-    bool has_emit_estimate = false;
-    struct Pending { hipEvent_t ev; void (*fn)(void*); void* user; };
-    std::vector<Pending> pending;       // asynchronous host pushes whose buffers the caller has not got back yet
-    uint64_t flush_wait_us = 0, flush_count_us = 0, flushes = 0;   // staging buffer counted: waiting for queued copies / counting (host wall)
-    // Host pushes are staged in one of TWO buffers (device memory of their own, beside the arena) by copies on a stream of
-    // their own; a full buffer is counted by a thread of the library while the caller goes on filling the other
-    // A packed staging buffer (round 5): what goss_gpu_push_packed_host* hands over stays 2-bit codes + flags in HBM --
-    // u32 of codes per sixteen positions from the buffer's start, u16 of flags per sixteen positions behind them -- and the
-    // kernels that read bases take it as it is (load_group16, kernels_common.hpp).  A buffer holds bytes OR packed
-    // groups (stage_pk[i]); staged_src makes the ReadSrc (goss_read_src.hpp) of what one holds, and that value -- the
-    // two arrays and a position for a packed string -- is what travels from the entry points to the launch sites.
-    bool stage_pk[2] = {false, false};
-    uint8_t* stage_buf[2] = {nullptr, nullptr};
-    int stage_cur = 0;
-    hipStream_t copy_stream = nullptr;
-    std::thread bg;                     // counts a full staging buffer (one at a time)
-    int bg_status = GOSS_OK;
-    std::string bg_error;
-    std::vector<hipEvent_t> pend_pool;  // events of `pending` (the counting thread has event_pool to itself)
-    uint8_t* stage = nullptr;           // the staging buffer being filled (= stage_buf[stage_cur])
-    uint64_t stage_cap = 0, stage_fill = 0;
-    bool mute_timing = false;           // set around auxiliary launches (the distinct-count estimate)
-    uint32_t segment_retries = 0;       // segment path attempts that overflowed an LDS table
-    uint32_t extract_hist_shift = 0xFFFFFFFFu;   // digits histogrammed by the last extraction (or none)
-    uint32_t rep_chunks = 0;            // chunks counted in strand-representative space and mapped to canonical order afterwards
-    bool graph_rep = true;              // GOSS_GPU_NO_GRAPH_REP=1: the fused path of a graph build counts both strands of every window (round 3's form)
-    int canon_l1 = 1;                   // GOSS_GPU_CANON_L1=0|1|2: the fused first level computes gossamer's canonical form itself never / from kCanonL1At distinct keys per window on / always
-    // more of the same input is known to follow the push being counted (a staging buffer that filled up while the caller
-    // keeps pushing): its runs will be merged with the runs of the others
-    // in representative space and the re-ordering into canonical order paid ONCE, on the merged run -- the chunk's own
-    // share of distinct keys then says little about what that costs (C2 from FASTQ: thirteen chunks of 0.8 G windows
-    // that each see all 10^8 k-mers of the genome, 12 %, took the canonical form per window -- 67 ms of first level
-    // where the representatives take 31, ten second-level bits, and a re-ordering per run)
-    bool more_follows = false;
-    uint64_t more_starts = 0;           // ... and how many window starts of the push being counted lie behind this chunk (a device push knows)
-    uint64_t expect_bases = 0;          // goss_gpu_expect_bases: bases the caller means to push in all (0: not said)
-    int space_choice = -1;              // the key space the build's fused chunks count in once one has chosen: 0 representatives, 1 canonical forms (-1: none yet)
-    uint32_t canon_chunks = 0;          // chunks counted that way
-    bool fused = true;                  // GOSS_GPU_NO_FUSED=1: never fuse the first partition pass into the extraction
-    uint64_t fused_min = 32u << 20;     // GOSS_GPU_FUSED_MIN=<window starts>: smallest chunk the fused path takes
-    uint32_t fused_overflows = 0;       // fused chunks redone because a bucket region was too small
-    uint32_t valid_sized_chunks = 0;    // chunks counted in key buffers sized from the estimated share of valid windows
-    uint32_t valid_resizes = 0;         // chunks whose estimate was too low: redone in full-size buffers
-    uint64_t dump_lo = 0;               // permanent top before the current dump piece
-    bool dump_live = false;
-    uint64_t budget_limit = 0;          // the arena may grow up to this many bytes (goss_gpu_set_budget_limit; 0 = fixed)
-    uint32_t arena_grows = 0;
-    uint64_t arena_ms = 0;              // time hipMalloc took to map the arena
-    std::thread arena_thread;           // goss_gpu_prepare: the arena is being mapped in the background
-    int arena_status = GOSS_OK;         // ... and how that went
-    std::string arena_error;
-    uint32_t seg_merges = 0;            // merges done by segments
-    uint32_t hash_merges = 0;           // ... of them through the counting table (seg_hash_merge96_kernel)
-    uint64_t hash_merge_min = 1u << 20; // GOSS_GPU_HASH_MERGE_MIN=<entries>: smallest merge that goes that way (65 536 workgroups)
-    bool fused_msd = true;              // GOSS_GPU_NO_MSD=1: never use the two-level (sub-region) form
-    uint32_t fused_msd_chunks = 0;      // chunks counted by the two-level form
-    bool rem32 = true;                  // GOSS_GPU_NO_REM32=1: never take the 32-bit-remainder form of the second level and the counting
-    int rem32_slots = 0;                // GOSS_GPU_REM32_SLOTS=2048|4096|8192|16384: counting table of that form (0 = by the distinct-key estimate)
-    uint32_t narrow_capg = 0xFFFFFFFFu; // GOSS_GPU_NARROW_CAPG (tests): granules a tile of the narrow form may lay out before it sends its carried granules off short (576 at least; by default and at most what the kernel's LDS layout holds)
-    bool narrow = true;                 // GOSS_GPU_NARROW=0: 8-byte keys between the two levels of the 32-bit-remainder form (rounds 3-4)
-    uint32_t r32_small_max = 0;         // distinct keys per segment up to which the 2048-slot table is taken (GOSS_GPU_R32_SMALL_MAX; 0 = the form's default)
-    bool overflow_by_sort = true;       // GOSS_GPU_OVERFLOW_BY_SORT=0: a table that overflows sends the whole chunk up the ladder of forms (rounds 1-5)
-    uint64_t overflow_units = 0;        // segments counted by sort because their table overflowed
-    uint32_t rem32_chunks = 0;          // chunks counted in that form
-    uint32_t narrow_chunks = 0;         // ... of them with remainder + digit (5.33 bytes a key) between the two levels
-    uint64_t assemble_us = 0;           // host clock of the last goss_gpu_emit_assemble
-    uint64_t ds_blocks_ranges = 0, ds_blocks_own = 0;      // DenseSelect blocks of the last assembly: taken from the ranges' records / built here from the bitmap
-    uint32_t pk_fused_chunks = 0;       // chunks of a packed string the fused kernels read as they were
-    uint32_t pk_unpacked_chunks = 0;    // ... and chunks (or samples) unpacked to bytes for the plain kernels
-    uint32_t rem32_bits_min = 0;        // GOSS_GPU_REM32_BITS=<9..12>: at least that many second-level bits (tests)
-    uint32_t rem32_bits_last = 0;       // second-level bits of the last chunk counted in that form
-    uint32_t rem32_split_min = 0;       // GOSS_GPU_REM32_SPLIT=<0..4>: at least that many third-level bits (tests; raised when tables overflow)
-    uint32_t rem32_split_last = 0;      // third-level bits of the last chunk counted in that form
-    uint32_t fused_chunks = 0;          // chunks counted by the fused path
-    bool debug = false;                 // GOSS_GPU_DEBUG=1: say on stderr why a fast path was not taken
-    double fused_capscale = 1.0;        // GOSS_GPU_FUSED_CAPSCALE: multiplies the bucket regions (tests force overflows)
-    uint32_t blk_log2_max = 0;          // GOSS_GPU_BLK_LOG2=<b>: blocks of the fused extraction of at most 2^b slots (experiments)
-    bool no_fast32 = false;             // GOSS_GPU_NO_FAST32=1: the fused extraction of one-word keys in its 64-bit form (tests of both forms)
-    bool table96 = true;                // GOSS_GPU_NO_TABLE96=1: never count two-word keys as 96-bit remainders in 16-byte slots
-    uint32_t table96_chunks = 0;
-    bool wide_table = true;             // GOSS_GPU_NO_WIDE_TABLE=1: never count two-word keys in the 6144-slot table
-    bool big_table = true;              // GOSS_GPU_NO_BIG_TABLE=1: never count 16-bit segments in the 8192-slot table
-    int big_rounds_min = 0;             // GOSS_GPU_BIG_ROUNDS_MIN=<r>: at least 2^r (tests)
-    uint32_t big_table_chunks = 0;      // chunks counted that way
-    uint32_t wide_table_chunks = 0;     // ... of them, two-word keys in the 6144-slot table
-    uint32_t rec_chunks = 0;            // chunks counted from records by the fused path
-    bool deferred = false;              // goss_gpu_set_deferred: host pushes only stage; a full staging buffer is reported, not counted
-                                        // (the caller then runs goss_gpu_group_route_exchange: the exchange before counting)
-    uint8_t* grp_send = nullptr;        // goss_gpu_group_route_exchange: this member's routed records (device memory of its own) ...
-    uint64_t grp_send_cap = 0;          // ... record slots
-    uint8_t* grp_inbox = nullptr;       // ... and what the other members sent it
-    uint64_t grp_inbox_cap = 0;
-    hipStream_t xstream = nullptr;      // stream of the transfers into this member's inbox
-    double valid_frac = 1.0;            // estimated valid windows per window start of the current push (sizes the key buffers)
-    bool size_by_valid = true;          // GOSS_GPU_NO_VALID_SIZING=1: key buffers always hold one key per window start
-    uint64_t budget = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string last_error;
-    Arena arena;
-    std::vector<Run> runs;
-    std::vector<BigMap> big_maps;       // per run that has them: the counts >= 2^32 - 1 (graph mode; marker 0xFFFFFFFF in the run)
-    BigMap res_big;                     // ... of the result (its u32 counts hold the value modulo 2^32, as the reference stores it)
-    bool pushed_counts = false;         // a run came in with its counts (goss_gpu_push_run_*): an entry 0xFFFFFFFF of it is that number
-    uint64_t windows = 0, keys_total = 0;
-    bool finished = false, emitted = false;
-    // a group's route-and-exchange round failed half way: what this context had staged may be in records that were
-    // lost with the round -- every later push, exchange and finish is refused (GOSS_ERR_STATE) until goss_gpu_reset
-    bool broken = false;
-    double grp_count_ms = 0;            // how long the background thread of the last exchange round took to count this member's records
-    void* res_keys = nullptr;
-    uint32_t* res_counts = nullptr;
-    uint64_t M = 0;
-    void* tips_keys = nullptr;            // result arrays that goss_gpu_prune_tips allocated: the next iteration compacts
-    uint32_t* tips_counts = nullptr;      // back into them instead of taking new permanent room
-    float paths_ms[5] = {};               // link, flag, gather, walk, compact of the last trim-paths / clip-links pass
-    float relative_ms[3] = {};            // judge, mirror, compact of the last trim-relative pass; lookup, -, compact of the last recount
-    // the held result: permanent room above everything else from held.lo on, held until its release entry point or
-    // the next call that may allocate (guarded() gives it back first).  goss_gpu_segments_build: the segment table and
-    // the text (seg_*); goss_gpu_entries_build: the images of the EntryEdgeSet, which are the file list
-    HeldResult held;
-    bool keep_held = false;               // the entry point that runs now only reads: what is held stays
-    void* seg_recs = nullptr;
-    uint8_t* seg_text = nullptr;
-    uint64_t seg_count = 0, seg_text_bytes = 0;
-    // Held::Components, bottom to top: the marks (goss_gpu_components_mark_*; null = none), then from cmp_built_lo on
-    // what goss_gpu_components_build left: a component index per edge and the table
-    uint32_t* cmp_marks = nullptr;
-    uint64_t cmp_mark_words = 0, cmp_built_lo = 0, cmp_marked = 0;      // cmp_marked: bits set in the marks
-    uint32_t* cmp_labels = nullptr;
-    void* cmp_recs = nullptr;
-    uint64_t cmp_count = 0;
-    bool cmp_built = false;
-    // Held::Pool (pool_path.hpp), bottom to top: the bit rows, the samples' sizes, then from pool_top on the positions
-    // and file images of goss_gpu_pool_emit_index
-    unsigned long long* pool_rows = nullptr;
-    unsigned long long* pool_sizes = nullptr;
-    uint64_t pool_z = 0, pool_top = 0;
-    uint32_t pool_sets = 0;
-    std::vector<bool> pool_added;         // per sample: its row has been written
-    std::vector<OutFile> files;
-    ExtractCounters* d_ctr = nullptr;     // device counters
-    uint32_t* d_flags = nullptr;          // device error flags [0]=count overflow [1]=ef overflow
-    void* d_route = nullptr;              // RouteCounters + the parts' first slots and capacities (goss_gpu_route_records_device)
-    void* h_pinned = nullptr;             // pinned scratch (>= 64 bytes)
-    std::vector<PhaseEvents> events;
-    std::vector<hipEvent_t> event_pool;
-    goss_gpu_timing timing{};
-};
+// ---- the context: its records, the arena, the phase timer, guarded() ----------------------------------
+#include "goss_ctx.hpp"
 
 namespace {
-
-// HIP-event timer around the launches of one kernel class (GOSS_T_*).
-struct PhaseTimer {
-    goss_gpu_ctx* c;
-    PhaseEvents pe;
-    PhaseTimer(goss_gpu_ctx* ctx, int phase, uint64_t units = 0) : c(ctx)
-    {
-        muted = c->mute_timing;
-        if (muted) return;
-        pe.units = units;
-        auto get = [&]() {
-            hipEvent_t e;
-            if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-            else HIP_TRY(hipEventCreate(&e));
-            return e;
-        };
-        pe.a = get(); pe.b = get(); pe.phase = phase;
-        HIP_TRY(hipEventRecord(pe.a, c->stream));
-    }
-    void stop()
-    {
-        if (muted) return;
-        HIP_TRY(hipEventRecord(pe.b, c->stream));
-        c->events.push_back(pe);
-    }
-    bool muted = false;
-};
-
-void resolve_timing(goss_gpu_ctx* c)
-{
-    for (auto& pe : c->events)
-    {
-        HIP_TRY(hipEventSynchronize(pe.b));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, pe.a, pe.b));
-        c->timing.ms[pe.phase] += ms;
-        c->timing.launches[pe.phase] += 1;
-        c->timing.units[pe.phase] += pe.units;
-        c->event_pool.push_back(pe.a);
-        c->event_pool.push_back(pe.b);
-    }
-    c->events.clear();
-}
-
-inline uint32_t grid_for(uint64_t n, uint32_t per_block)
-{
-    uint64_t g = (n + per_block - 1) / per_block;
-    if (g == 0) g = 1;
-    if (g > 0x7FFFFFFFULL) throw StatusError{GOSS_ERR_INVALID_ARG, "launch grid too large"};
-    return (uint32_t)g;
-}
-
-void map_arena(goss_gpu_ctx* c)
-{
-    uint64_t budget = c->budget;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (budget == 0) budget = (uint64_t)((double)free_b * 0.8);
-    if (budget > (uint64_t)((double)free_b * 0.92)) budget = (uint64_t)((double)free_b * 0.92);   // a request, not a demand
-    void* p = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = hipMalloc(&p, budget);
-    if (e != hipSuccess) throw StatusError{GOSS_ERR_OOM, std::string("hipMalloc(budget) failed: ") + hipGetErrorString(e)};
-    c->arena_ms = (uint64_t)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->arena.base = (uint8_t*)p;
-    c->arena.size = budget;
-    c->arena.lo = 0;
-    c->arena.hi = budget;
-    c->budget = budget;
-}
-
-void ensure_arena(goss_gpu_ctx* c)
-{
-    if (c->arena_thread.joinable())
-    {
-        c->arena_thread.join();
-        if (c->arena_status != GOSS_OK) throw StatusError{c->arena_status, c->arena_error};
-    }
-    if (c->arena.base) return;
-    map_arena(c);
-}
-
-// Grow the arena so that at least `want_avail` bytes are free (or double it when want_avail is 0),
-// up to budget_limit (0 = the budget is fixed): a new mapping, the permanent part copied over, every
-// pointer into the arena rebased.  Only legal where no temporary is live (start of a chunk, start of a
-// merge; the staging buffers of host pushes are memory of their own).  False = not possible.
-bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
-{
-    Arena& a = c->arena;
-    if (!a.base || c->budget_limit <= a.size) return false;
-    const uint64_t top = a.size - a.hi;                    // live temporaries at the top: none where growing is legal
-    if (top != 0) return false;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t target = std::max<uint64_t>(a.size * 2, a.lo + top + want_avail + (1ULL << 30));
-    target = std::min<uint64_t>(target, c->budget_limit);
-    target = std::min<uint64_t>(target, (uint64_t)((double)free_b * 0.95));        // the old mapping is still there
-    if (target < a.size + (1ULL << 30) || (want_avail && target < a.lo + top + want_avail)) return false;
-    void* p = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (hipMalloc(&p, target) != hipSuccess) { (void)hipGetLastError(); return false; }
-    c->arena_ms += (uint64_t)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    uint8_t* nb = (uint8_t*)p;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (a.lo) HIP_TRY(hipMemcpyAsync(nb, a.base, a.lo, hipMemcpyDeviceToDevice, c->stream));
-    if (top) HIP_TRY(hipMemcpyAsync(nb + target - top, a.base + a.hi, top, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    auto rebase = [&](auto*& ptr) {
-        if (!ptr) return;
-        uint8_t* q = (uint8_t*)ptr;
-        if (q >= a.base && q < a.base + a.size) ptr = (std::remove_reference_t<decltype(ptr)>)(nb + (q - a.base));
-    };
-    for (auto& r : c->runs) { rebase(r.keys); rebase(r.counts); }
-    rebase(c->res_keys); rebase(c->res_counts);
-    rebase(c->tips_keys); rebase(c->tips_counts);
-    rebase(c->seg_recs); rebase(c->seg_text);
-    rebase(c->cmp_marks); rebase(c->cmp_labels); rebase(c->cmp_recs);
-    rebase(c->pool_rows); rebase(c->pool_sizes);
-    for (auto& f : c->files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
-    (void)hipFree(a.base);
-    a.base = nb; a.hi = target - top; a.size = target;
-    c->budget = target;
-    c->arena_grows++;
-    if (c->debug) std::fprintf(stderr, "libgossgpu: arena grown to %llu GB\n", (unsigned long long)(target >> 30));
-    return true;
-}
 
 // ---- counting a chunk of keys and merging runs; the fused path; the chunk loop over a push ----------
 #include "count_path.hpp"
@@ -502,7 +147,7 @@ void emit_dense_select(goss_gpu_ctx* c, const K* keys, uint64_t m, uint32_t D, i
     HIP_TRY(hipStreamSynchronize(c->stream));    // host vectors / header go out of scope
     c->arena.release(mark);
     OutFile f; f.suffix = suffix; f.size = size; f.dev = image;
-    c->files.push_back(std::move(f));
+    c->build.files.push_back(std::move(f));
 }
 
 // ---- DenseSelect blocks per range (round 5) ---------------------------------------------------------------------------
@@ -583,7 +228,7 @@ void ds_compose(goss_gpu_ctx* c, int invert, uint64_t count, const std::vector<s
         HIP_TRY(hipMemcpyAsync(type.data() + b0, a_type, nb * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (uint64_t b = b0; b < b0 + nb; ++b) { if (have[b]) throw StatusError{GOSS_ERR_INVALID_ARG, "emit_assemble: a block built twice"}; have[b] = 1; }
-        c->ds_blocks_ranges += nb;
+        c->stats.ds_blocks_ranges += nb;
         segs.push_back({b0, nb, a_type + ((nb * 4 + 7) & ~7ULL), head[1]});
     }
     // the blocks nobody built (they straddle two ranges, or their range gave no record): runs of them, from the bitmap
@@ -607,7 +252,7 @@ void ds_compose(goss_gpu_ctx* c, int invert, uint64_t count, const std::vector<s
         for (uint64_t x = b; x < e; ++x) { type[x] = o.plan.type[x - b]; bytes[x] = o.plan.bytes[x - b]; rank[x] = o.plan.rank[x - b]; have[x] = 1; }
         segs.push_back({b, e - b, o.rec + 32 + (e - b) * 16 + (((e - b) * 4 + 7) & ~7ULL), o.plan.payload});
         own.push_back(std::move(o));
-        c->ds_blocks_own += e - b;
+        c->stats.ds_blocks_own += e - b;
         b = e;
     }
     DsHeader h{};
@@ -650,7 +295,7 @@ void ds_compose(goss_gpu_ctx* c, int invert, uint64_t count, const std::vector<s
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->arena.release(mark);
     OutFile f; f.suffix = suffix; f.size = size; f.dev = image;
-    c->files.push_back(std::move(f));
+    c->build.files.push_back(std::move(f));
 }
 
 struct SaHeader { uint64_t version, D, quantizedD, mask_lo, mask_hi, size_lo, size_hi, count; };
@@ -677,7 +322,7 @@ void emit_sparse_header(goss_gpu_ctx* c, uint32_t D, uint64_t Nend_lo, uint64_t 
     h.size_lo = Nend_lo; h.size_hi = Nend_hi; h.count = count;
     OutFile f; f.suffix = base + ".header"; f.size = sizeof h;
     f.host.assign((uint8_t*)&h, (uint8_t*)&h + sizeof h);
-    c->files.push_back(std::move(f));
+    c->build.files.push_back(std::move(f));
 }
 
 // The index part of a SparseArray: high-bits bitmap, -d0 (zeros), -d1 (ones), from keys whose high part
@@ -699,7 +344,7 @@ void emit_sparse_index(goss_gpu_ctx* c, const K* keys, uint64_t m, uint32_t D, u
         hipLaunchKernelGGL(HIP_KERNEL_NAME(ef_high_bits_kernel<K>), dim3(grid_for(nwords, 256)), dim3(256), 0, c->stream,
                            keys, m, D, nwords, words);
     OutFile f; f.suffix = base + ".high-bits"; f.size = nwords * 8; f.dev = (const uint8_t*)words;
-    c->files.push_back(std::move(f));
+    c->build.files.push_back(std::move(f));
     emit_dense_select<K>(c, keys, m, D, 1, nd + 2, base + "-d0");
     emit_dense_select<K>(c, keys, m, D, 0, m, base + "-d1");
 }
@@ -718,7 +363,7 @@ void emit_sparse_low_bits(goss_gpu_ctx* c, const K* keys, uint64_t m, uint32_t D
         uint8_t* dst = (uint8_t*)c->arena.perm(std::max<uint64_t>(m * cols[i].bytes, 8));
         ec.c[i] = EfColumn{dst, cols[i].bytes, cols[i].shift};
         OutFile f; f.suffix = base + ".low-bits" + cols[i].suffix; f.size = m * cols[i].bytes; f.dev = dst;
-        c->files.push_back(std::move(f));
+        c->build.files.push_back(std::move(f));
     }
     if (m)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(ef_low_bits_kernel<K>), dim3(grid_for(m, 256)), dim3(256), 0, c->stream,
@@ -748,7 +393,7 @@ void add_host_file(goss_gpu_ctx* c, const std::string& suffix, const void* p, si
 {
     OutFile f; f.suffix = suffix; f.size = n;
     f.host.assign((const uint8_t*)p, (const uint8_t*)p + n);
-    c->files.push_back(std::move(f));
+    c->build.files.push_back(std::move(f));
 }
 
 // VariableByteArray + counts histogram (VariableByteArray.hh:76-118, Graph.cc:115-134) of any u32 column on the
@@ -795,12 +440,12 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
     if (!pos2) pos2 = (Key1*)c->arena.perm(8);
     if (!ord1) ord1 = (uint8_t*)c->arena.perm(8);
     if (!ord2) ord2 = (uint16_t*)c->arena.perm(8);
-    { OutFile f; f.suffix = out_counts + ".ord0"; f.size = m; f.dev = ord0; c->files.push_back(std::move(f)); }
+    { OutFile f; f.suffix = out_counts + ".ord0"; f.size = m; f.dev = ord0; c->build.files.push_back(std::move(f)); }
     const uint64_t mest = (uint64_t)((double)num_items * 0.001);
     emit_sparse_array<Key1>(c, pos1, n1, num_items, 0, mest, m, 0, out_counts + ".ord1p");
-    { OutFile f; f.suffix = out_counts + ".ord1"; f.size = n1; f.dev = ord1; c->files.push_back(std::move(f)); }
+    { OutFile f; f.suffix = out_counts + ".ord1"; f.size = n1; f.dev = ord1; c->build.files.push_back(std::move(f)); }
     emit_sparse_array<Key1>(c, pos2, n2, num_items, 0, mest, n1, 0, out_counts + ".ord2p");
-    { OutFile f; f.suffix = out_counts + ".ord2"; f.size = n2 * 2; f.dev = (const uint8_t*)ord2; c->files.push_back(std::move(f)); }
+    { OutFile f; f.suffix = out_counts + ".ord2"; f.size = n2 * 2; f.dev = (const uint8_t*)ord2; c->build.files.push_back(std::move(f)); }
 
     // histogram of counts: sort the counts as keys, run-length them, format on the host
     std::string text;
@@ -833,8 +478,8 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
         for (uint64_t i = 0; i < nd; ++i) hist[hv[i]] = (i + 1 < nd ? hs[i + 1] : m) - hs[i];
         // the result's counts beyond 32 bits sit in the array modulo 2^32; the histogram is keyed by the count
         // itself (Graph.hh:101-106: mHist[count]++ on the u64 before it is narrowed)
-        if (counts == c->res_counts)
-            for (auto& kv : c->res_big)
+        if (counts == c->build.res_counts)
+            for (auto& kv : c->build.res_big)
             {
                 auto it = hist.find(kv.second & 0xFFFFFFFFULL);
                 if (it != hist.end() && --it->second == 0) hist.erase(it);
@@ -854,13 +499,13 @@ void emit_counts(goss_gpu_ctx* c, const uint32_t* counts, uint64_t m, uint64_t n
 }
 
 template <class K>
-void emit_object(goss_gpu_ctx* c)
+void emit_object(goss_gpu_ctx* c, const uint64_t* m_estimate)
 {
-    const K* keys = (const K*)c->res_keys;
-    const uint64_t m = c->M;
+    const K* keys = (const K*)c->build.res_keys;
+    const uint64_t m = c->build.M;
     // the SparseArray estimate: the exact distinct count (single-pass build) unless the caller
     // gave one (merges use the sum of the inputs' counts, GossCmdMerge.tcc:256-258,296)
-    const uint64_t est = c->has_emit_estimate ? c->emit_estimate : m;
+    const uint64_t est = m_estimate ? *m_estimate : m;
     PhaseTimer t(c, GOSS_T_EMIT, m);
     if (c->mode == GOSS_MODE_KMER_SET)
     {
@@ -878,7 +523,7 @@ void emit_object(goss_gpu_ctx* c)
         uint32_t bits = 2 * c->k + 2;
         uint64_t nlo = bits < 64 ? (1ULL << bits) : 0, nhi = bits >= 64 ? (1ULL << (bits - 64)) : 0;
         emit_sparse_array<K>(c, keys, m, nlo, nhi, est, nlo, nhi, "-edges");
-        emit_counts(c, c->res_counts, m, est, "-counts", "-counts-hist.txt");
+        emit_counts(c, c->build.res_counts, m, est, "-counts", "-counts-hist.txt");
     }
     t.stop();
 }
@@ -898,8 +543,8 @@ void object_universe(const goss_gpu_ctx* c, uint64_t* nlo, uint64_t* nhi, std::s
 template <class K>
 void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t estimate, uint64_t prev_high = 0, bool have_prev = false)
 {
-    const K* keys = (const K*)c->res_keys;
-    const uint64_t m = c->M;
+    const K* keys = (const K*)c->build.res_keys;
+    const uint64_t m = c->build.M;
     PhaseTimer t(c, GOSS_T_EMIT, m);
     uint64_t nlo, nhi; std::string base;
     object_universe(c, &nlo, &nhi, &base);
@@ -978,11 +623,11 @@ void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t e
         HIP_TRY(hipStreamSynchronize(c->stream));            // (the headers go out of scope)
         c->arena.release(tmark);
         OutFile f; f.suffix = ".part.span"; f.size = bytes; f.dev = (const uint8_t*)blob;
-        c->files.push_back(std::move(f));
+        c->build.files.push_back(std::move(f));
     }
     if (c->mode == GOSS_MODE_GRAPH)
     {
-        const uint32_t* counts = c->res_counts;
+        const uint32_t* counts = c->build.res_counts;
         uint64_t mark = c->arena.mark();
         uint8_t* ord0 = (uint8_t*)c->arena.perm(std::max<uint64_t>(m, 8));
         uint64_t nbig = 0;
@@ -1006,9 +651,7 @@ void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t e
             Key1* ka = (Key1*)c->arena.temp(m * 8);
             Key1* kb = (Key1*)c->arena.temp(m * 8);
             hipLaunchKernelGGL(widen_counts_kernel, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, counts, m, ka);
-            const bool mute = c->mute_timing; c->mute_timing = true;
-            const bool in_b = radix_sort<Key1, false>(c, ka, kb, nullptr, nullptr, m, 4);
-            c->mute_timing = mute;
+            const bool in_b = [&]() { Scoped<bool> mute(&c->mute_timing, true); return radix_sort<Key1, false>(c, ka, kb, nullptr, nullptr, m, 4); }();
             const Key1* sorted = in_b ? kb : ka;
             Key1* distinct = in_b ? ka : kb;
             const uint64_t ntiles = (m + kRedTile - 1) / kRedTile;
@@ -1029,7 +672,7 @@ void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t e
             HIP_TRY(hipStreamSynchronize(c->stream));
             std::map<uint64_t, uint64_t> hm;
             for (uint64_t i = 0; i < nv; ++i) hm[hv[i]] = (i + 1 < nv ? hs[i + 1] : m) - hs[i];
-            for (auto& kv : c->res_big)              // counts beyond 32 bits: keyed by the count itself (see emit_counts)
+            for (auto& kv : c->build.res_big)              // counts beyond 32 bits: keyed by the count itself (see emit_counts)
             {
                 auto it = hm.find(kv.second & 0xFFFFFFFFULL);
                 if (it != hm.end() && --it->second == 0) hm.erase(it);
@@ -1037,8 +680,8 @@ void emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t e
             }
             for (auto& kv : hm) { hist.push_back(kv.first); hist.push_back(kv.second); }
         }
-        { OutFile f; f.suffix = "-counts.ord0"; f.size = m; f.dev = ord0; c->files.push_back(std::move(f)); }
-        { OutFile f; f.suffix = ".part.big"; f.size = nbig * sizeof(BigCount); f.dev = (const uint8_t*)big; if (!big) f.host.clear(); c->files.push_back(std::move(f)); }
+        { OutFile f; f.suffix = "-counts.ord0"; f.size = m; f.dev = ord0; c->build.files.push_back(std::move(f)); }
+        { OutFile f; f.suffix = ".part.big"; f.size = nbig * sizeof(BigCount); f.dev = (const uint8_t*)big; if (!big) f.host.clear(); c->build.files.push_back(std::move(f)); }
         add_host_file(c, ".part.hist", hist.data(), hist.size() * 8);
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
@@ -1060,7 +703,7 @@ void emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_bytes, ui
     object_universe(c, &nlo, &nhi, &base);
     const uint32_t D = (uint32_t)sparse_d(nlo, nhi, estimate);
     const uint64_t nd = sparse_nd(D, nlo, nhi);
-    c->ds_blocks_ranges = c->ds_blocks_own = 0;
+    c->stats.ds_blocks_ranges = c->stats.ds_blocks_own = 0;
     // the bitmap: the ranges' spans ORed together (neighbours share their boundary words); the ranges' DenseSelect blocks
     // noted for the composition below
     const uint64_t nwords = (nd + total + 3) / 64 + 1;
@@ -1092,7 +735,7 @@ void emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_bytes, ui
     exclusive_scan_u64(c, ones, nwords);
     auto index_files = [&]() {
         OutFile f; f.suffix = base + ".high-bits"; f.size = nwords * 8; f.dev = (const uint8_t*)words;
-        c->files.push_back(std::move(f));
+        c->build.files.push_back(std::move(f));
         ds_compose(c, 1, nd + 2, ds_recs[1], (const unsigned long long*)words, nwords, ones, base + "-d0");
         ds_compose(c, 0, total, ds_recs[0], (const unsigned long long*)words, nwords, ones, base + "-d1");
     };
@@ -1145,72 +788,6 @@ void emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_bytes, ui
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->arena.release(mark);
-}
-
-void wait_background_thread(goss_gpu_ctx* c);
-
-// Give back what the context holds (segments, an entry edge set or components), if anything: the permanent room from held.lo on.
-void release_held(goss_gpu_ctx* c)
-{
-    if (c->held.kind != Held::None) c->arena.lo = c->held.lo;
-    if (c->held.kind == Held::Entries || c->held.kind == Held::Pool) c->files.clear();
-    c->held = HeldResult();
-    c->pool_rows = nullptr; c->pool_sizes = nullptr; c->pool_z = c->pool_top = 0; c->pool_sets = 0; c->pool_added.clear();
-    c->seg_recs = nullptr; c->seg_text = nullptr; c->seg_count = c->seg_text_bytes = 0;
-    c->cmp_marks = nullptr; c->cmp_labels = nullptr; c->cmp_recs = nullptr;
-    c->cmp_mark_words = c->cmp_built_lo = c->cmp_count = c->cmp_marked = 0;
-    c->cmp_built = false;
-}
-
-// wait_bg: the call works on the arena or the runs -- the thread that counts a full staging buffer must have ended
-// (its failure becomes this call's).  Only the host pushes, which touch nothing but the other staging buffer, go on
-// beside it.
-template <class F>
-int guarded(goss_gpu_ctx* c, F&& f, bool wait_bg = true)
-{
-    try
-    {
-        if (c) HIP_TRY(hipSetDevice(c->device));
-        // forget what the calling thread left behind (e.g. hipErrorNotReady from an event or stream
-        // poll of the host process): from here on an error is ours
-        (void)hipGetLastError();
-        if (c && wait_bg) wait_background_thread(c);
-        // a held result lies on top of the permanent room: whatever may allocate there, or change the result it was
-        // read from, gives it back first
-        if (c && !c->keep_held) release_held(c);
-        if (c) c->keep_held = false;
-        f();
-        // a refused kernel launch raises no exception by itself and leaves its outputs untouched:
-        // no entry point returns success over one
-        check_launch("a kernel launch was refused");
-        return GOSS_OK;
-    }
-    catch (const HipError& e)
-    {
-        if (c) c->last_error = std::string(e.what) + ": " + hipGetErrorString(e.e);
-        return GOSS_ERR_HIP;
-    }
-    catch (const StatusError& e)
-    {
-        if (c) c->last_error = e.msg;
-        return e.status;
-    }
-    catch (const std::bad_alloc&)
-    {
-        if (c) c->last_error = "host allocation failed";
-        return GOSS_ERR_OOM;
-    }
-    catch (const std::system_error& e)
-    {
-        // (a thread that could not be started: nothing may cross the C boundary)
-        if (c) c->last_error = std::string("a host resource is exhausted: ") + e.what();
-        return GOSS_ERR_OOM;
-    }
-    catch (const std::exception& e)
-    {
-        if (c) c->last_error = std::string("unexpected failure: ") + e.what();
-        return GOSS_ERR_STATE;
-    }
 }
 
 // ---- prune-tips, print-contigs, build-entry-edge-set: the passes over a finished graph ---------
@@ -1269,33 +846,7 @@ int goss_gpu_create(goss_gpu_ctx** out, int device, uint32_t k, int mode, uint64
     c->len = mode == GOSS_MODE_GRAPH ? k + 1 : k;
     c->words = (2 * c->len <= 62) ? 1 : 2;
     c->budget = hbm_budget;
-    { const char* e = std::getenv("GOSS_GPU_NO_LOOKBACK"); if (e && *e == '1') c->lookback = false; }
-    { const char* e = std::getenv("GOSS_GPU_ORDERED_TILES"); if (e && *e == '1') c->ordered_tiles = true; }
-    { const char* e = std::getenv("GOSS_GPU_EST_SCALE"); if (e && std::atof(e) > 0) c->est_scale = std::atof(e); }
-    { const char* e = std::getenv("GOSS_GPU_ORDER_BITS"); if (e && std::atoi(e) >= 16 && std::atoi(e) <= 24) c->order_bits = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_NO_FUSED"); if (e && *e == '1') c->fused = false; }
-    { const char* e = std::getenv("GOSS_GPU_NO_MSD"); if (e && *e == '1') c->fused_msd = false; }
-    { const char* e = std::getenv("GOSS_GPU_NO_GRAPH_REP"); if (e && *e && *e != '0') c->graph_rep = false; }
-    { const char* e = std::getenv("GOSS_GPU_CANON_L1"); if (e && *e >= '0' && *e <= '2') c->canon_l1 = *e - '0'; }
-    { const char* e = std::getenv("GOSS_GPU_NO_REM32"); if (e && *e && *e != '0') c->rem32 = false; }
-    { const char* e = std::getenv("GOSS_GPU_REM32_BITS"); if (e && std::atoi(e) >= 9 && std::atoi(e) <= 10) c->rem32_bits_min = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_REM32_SPLIT"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 4) c->rem32_split_min = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_REM32_SLOTS"); if (e && (std::atoi(e) == 2048 || std::atoi(e) == 4096 || std::atoi(e) == 8192 || std::atoi(e) == 16384)) c->rem32_slots = std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_NARROW"); if (e) c->narrow = std::atoi(e) != 0; }
-    { const char* e = std::getenv("GOSS_GPU_OVERFLOW_BY_SORT"); if (e) c->overflow_by_sort = std::atoi(e) != 0; }
-    { const char* e = std::getenv("GOSS_GPU_NARROW_CAPG"); if (e && std::atoi(e) > 0) c->narrow_capg = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_R32_SMALL_MAX"); if (e) c->r32_small_max = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_NO_BIG_TABLE"); if (e && *e && *e != '0') c->big_table = false; }
-    { const char* e = std::getenv("GOSS_GPU_HASH_MERGE_MIN"); if (e && *e) c->hash_merge_min = std::strtoull(e, nullptr, 10); }
-    { const char* e = std::getenv("GOSS_GPU_BLK_LOG2"); if (e && *e) c->blk_log2_max = (uint32_t)std::atoi(e); }
-    { const char* e = std::getenv("GOSS_GPU_NO_FAST32"); if (e && *e == '1') c->no_fast32 = true; }
-    { const char* e = std::getenv("GOSS_GPU_NO_TABLE96"); if (e && *e && *e != '0') c->table96 = false; }
-    { const char* e = std::getenv("GOSS_GPU_NO_WIDE_TABLE"); if (e && *e && *e != '0') c->wide_table = false; }
-    { const char* e = std::getenv("GOSS_GPU_BIG_ROUNDS_MIN"); if (e && *e) c->big_rounds_min = std::min(3, std::max(0, std::atoi(e))); }
-    { const char* e = std::getenv("GOSS_GPU_NO_VALID_SIZING"); if (e && *e && *e != '0') c->size_by_valid = false; }
-    { const char* e = std::getenv("GOSS_GPU_FUSED_MIN"); if (e && *e) c->fused_min = std::strtoull(e, nullptr, 10); }
-    { const char* e = std::getenv("GOSS_GPU_FUSED_CAPSCALE"); if (e && *e) c->fused_capscale = std::atof(e); }
-    { const char* e = std::getenv("GOSS_GPU_DEBUG"); if (e && *e == '1') c->debug = true; }
+    c->knobs = knobs_from_env();
     int rc = guarded(c, [&]() {
         if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
         else { HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
@@ -1380,8 +931,8 @@ static void count_staged(goss_gpu_ctx* c, const uint8_t* buf, uint64_t n, bool p
 {
     const auto t1 = std::chrono::steady_clock::now();
     push_source(c, staged_src(c, buf, packed), n);
-    c->flush_count_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
-    c->flushes++;
+    c->stats.flush_count_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
+    c->stats.flushes++;
 }
 
 // What is staged is counted now, on the caller's thread (finish, a device push, anything that needs the runs).
@@ -1393,7 +944,7 @@ static void flush_staging(goss_gpu_ctx* c)
     c->stage_fill = 0;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipStreamSynchronize(c->copy_stream));      // (the copies queued so far: counted apart from the chunk's own time)
-    c->flush_wait_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    c->stats.flush_wait_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     count_staged(c, c->stage, n, c->stage_pk[c->stage_cur]);
 }
 
@@ -1428,8 +979,7 @@ static void flush_staging_background(goss_gpu_ctx* c)
             HIP_TRY(hipSetDevice(c->device));
             (void)hipGetLastError();
             // (the buffer filled up under a caller that goes on pushing: this chunk is one of several)
-            struct MoreOff { goss_gpu_ctx* c; ~MoreOff() { c->more_follows = false; } } moreOff{c};
-            c->more_follows = true;
+            Scoped<bool> more(&c->more_follows, true);
             count_staged(c, buf, n, packed);
             check_launch("a kernel launch was refused");
         }
@@ -1451,8 +1001,8 @@ static void flush_staging_background(goss_gpu_ctx* c)
 int goss_gpu_push_bases_device(goss_gpu_ctx* c, const void* d_bases, uint64_t nbytes)
 {
     if (!c || (!d_bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         flush_staging(c);
         push_source(c, ReadSrc::of_bytes(d_bases), nbytes);
@@ -1464,7 +1014,7 @@ int goss_gpu_push_bases_device(goss_gpu_ctx* c, const void* d_bases, uint64_t nb
 int goss_gpu_expect_bases(goss_gpu_ctx* c, uint64_t total_bases)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    c->expect_bases = total_bases;
+    c->build.expect_bases = total_bases;
     return GOSS_OK;
 }
 
@@ -1473,8 +1023,8 @@ int goss_gpu_push_packed_device(goss_gpu_ctx* c, const uint32_t* d_codes, const 
 {
     if (!c || (nbases && (!d_codes || !d_nonbase))) return GOSS_ERR_INVALID_ARG;
     if (((uintptr_t)d_codes & 3u) || ((uintptr_t)d_nonbase & 1u)) { c->last_error = "packed arrays must be aligned to their elements"; return GOSS_ERR_INVALID_ARG; }
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (c->deferred) { c->last_error = "a deferred context takes host pushes only (its staging buffer is what the group routes)"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         flush_staging(c);
@@ -1610,8 +1160,7 @@ static void push_bases_host(goss_gpu_ctx* c, const char* bases, uint64_t nbytes,
             c->stage_pk[c->stage_cur] = false;
             HIP_TRY(hipMemcpyAsync(c->stage, bases + done, nb, hipMemcpyHostToDevice, c->copy_stream));
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
-            struct MoreOff { goss_gpu_ctx* c; ~MoreOff() { c->more_starts = 0; } } moreOff{c};
-            c->more_starts = nstarts_total - done - ns;          // (the pieces behind this one: the chunks choose their key space for all of them)
+            Scoped<uint64_t> more(&c->more_starts, nstarts_total - done - ns);          // (the pieces behind this one: the chunks choose their key space for all of them)
             count_staged(c, c->stage, nb);
             HIP_TRY(hipStreamSynchronize(c->stream));
             done += ns;
@@ -1729,16 +1278,16 @@ static void push_packed_host(goss_gpu_ctx* c, const uint32_t* codes, const uint1
 int goss_gpu_push_bases_host(goss_gpu_ctx* c, const char* bases, uint64_t nbytes)
 {
     if (!c || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() { push_bases_host(c, bases, nbytes, false, nullptr, nullptr); }, false);
 }
 
 int goss_gpu_push_bases_host_async(goss_gpu_ctx* c, const char* bases, uint64_t nbytes, goss_gpu_release_fn release, void* user)
 {
     if (!c || (!bases && nbytes)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         // (a failed push hands the buffer back to the caller on return: what was queued from it must have run)
         try { push_bases_host(c, bases, nbytes, true, release, user); }
@@ -1749,8 +1298,8 @@ int goss_gpu_push_bases_host_async(goss_gpu_ctx* c, const char* bases, uint64_t 
 int goss_gpu_push_packed_host(goss_gpu_ctx* c, const uint32_t* codes, const uint16_t* nonbase, uint64_t nbases)
 {
     if (!c || (nbases && (!codes || !nonbase))) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() { push_packed_host(c, codes, nonbase, nbases, false, nullptr, nullptr); }, false);
 }
 
@@ -1758,8 +1307,8 @@ int goss_gpu_push_packed_host_async(goss_gpu_ctx* c, const uint32_t* codes, cons
                                     goss_gpu_release_fn release, void* user)
 {
     if (!c || (nbases && (!codes || !nonbase))) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         try { push_packed_host(c, codes, nonbase, nbases, true, release, user); }
         catch (...) { if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream); throw; }
@@ -1775,19 +1324,19 @@ int goss_gpu_flush(goss_gpu_ctx* c)
 int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "finish called twice"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "finish called twice"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     int rc = guarded(c, [&]() {
         ensure_arena(c);
         flush_staging(c);
         release_pending(c, true);          // (every asynchronous push has been copied by now: the buffers go back)
-        const bool unmerged = c->runs.size() == 1;          // (a merge resolves its own counts: resolve_big_counts)
+        const bool unmerged = c->build.runs.size() == 1;          // (a merge resolves its own counts: resolve_big_counts)
         if (c->words == 1) merge_runs<Key1>(c); else merge_runs<Key2>(c);
-        if (unmerged && c->pushed_counts)
+        if (unmerged && c->build.pushed_counts)
         {
-            if (c->words == 1) adopt_literal_counts<Key1>(c, c->runs[0]); else adopt_literal_counts<Key2>(c, c->runs[0]);
+            if (c->words == 1) adopt_literal_counts<Key1>(c, c->build.runs[0]); else adopt_literal_counts<Key2>(c, c->build.runs[0]);
         }
-        if (!c->runs.empty() && c->runs[0].rep)
+        if (!c->build.runs.empty() && c->build.runs[0].rep)
         {
             if (c->mode == GOSS_MODE_GRAPH)
             {
@@ -1798,11 +1347,11 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
             else
             {
                 if (c->words != 1) throw StatusError{GOSS_ERR_STATE, "a two-word run in representative space"};
-                canonicalize_run<Key1>(c, c->runs[0]);
+                canonicalize_run<Key1>(c, c->build.runs[0]);
             }
         }
-        if (!c->runs.empty()) { c->res_keys = c->runs[0].keys; c->res_counts = c->runs[0].counts; c->M = c->runs[0].m; }
-        else { c->res_keys = c->arena.perm(16); c->res_counts = (uint32_t*)c->arena.perm(16); c->M = 0; }
+        if (!c->build.runs.empty()) { c->build.res_keys = c->build.runs[0].keys; c->build.res_counts = c->build.runs[0].counts; c->build.M = c->build.runs[0].m; }
+        else { c->build.res_keys = c->arena.perm(16); c->build.res_counts = (uint32_t*)c->arena.perm(16); c->build.M = 0; }
         uint32_t* hf = (uint32_t*)c->h_pinned;
         HIP_TRY(hipMemcpyAsync(hf, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1810,21 +1359,21 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
         // of such keys beside the run (resolve_big_counts); its u32 count becomes the value modulo 2^32, which is
         // what the reference stores (Graph::Builder::push_back hands a u64 to VariableByteArray's u32 value_type,
         // Graph.hh:101-106, VariableByteArray.hh:72,81), and its histogram is keyed by the exact count.
-        c->res_big.clear();
+        c->build.res_big.clear();
         if (c->mode == GOSS_MODE_GRAPH)
         {
             if (hf[0]) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "a key occurred 2^32 times or more (unresolved)"};
-            if (!c->runs.empty() && c->runs[0].big >= 0 && !c->big_maps[c->runs[0].big].empty())
+            if (!c->build.runs.empty() && c->build.runs[0].big >= 0 && !c->build.big_maps[c->build.runs[0].big].empty())
             {
-                c->res_big = c->big_maps[c->runs[0].big];
+                c->build.res_big = c->build.big_maps[c->build.runs[0].big];
                 uint64_t mark = c->arena.mark();
-                const Saturated sat = find_saturated(c, c->res_keys, c->res_counts, c->M);
+                const Saturated sat = find_saturated(c, c->build.res_keys, c->build.res_counts, c->build.M);
                 const uint32_t nq = (uint32_t)sat.at.size();
                 std::vector<uint32_t> vals(nq);
                 for (uint32_t q = 0; q < nq; ++q)
                 {
-                    auto it = c->res_big.find(sat.key[q]);
-                    if (it == c->res_big.end()) throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated result entry without its exact count"};
+                    auto it = c->build.res_big.find(sat.key[q]);
+                    if (it == c->build.res_big.end()) throw StatusError{GOSS_ERR_HIP, "count bookkeeping: a saturated result entry without its exact count"};
                     vals[q] = (uint32_t)(it->second & 0xFFFFFFFFULL);
                 }
                 if (nq)
@@ -1833,18 +1382,18 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
                     unsigned long long* dat = (unsigned long long*)c->arena.temp(nq * 8);
                     HIP_TRY(hipMemcpyAsync(dv, vals.data(), nq * 4, hipMemcpyHostToDevice, c->stream));
                     HIP_TRY(hipMemcpyAsync(dat, sat.at.data(), nq * 8, hipMemcpyHostToDevice, c->stream));
-                    hipLaunchKernelGGL(patch_counts_kernel, dim3(grid_for(nq, 64)), dim3(64), 0, c->stream, c->res_counts,
+                    hipLaunchKernelGGL(patch_counts_kernel, dim3(grid_for(nq, 64)), dim3(64), 0, c->stream, c->build.res_counts,
                                        (const unsigned long long*)dat, (const uint32_t*)dv, nq);
                     HIP_TRY(hipStreamSynchronize(c->stream));
                 }
                 c->arena.release(mark);
             }
         }
-        c->finished = true;
+        c->build.finished = true;
     });
     if (rc == GOSS_OK && out)
     {
-        out->windows = c->windows; out->keys = c->keys_total; out->distinct = c->M;
+        out->windows = c->build.windows; out->keys = c->build.keys_total; out->distinct = c->build.M;
         out->key_words = (uint32_t)c->words; out->reserved = 0;
     }
     return rc;
@@ -1853,52 +1402,56 @@ int goss_gpu_finish(goss_gpu_ctx* c, goss_gpu_counts* out)
 int goss_gpu_result(goss_gpu_ctx* c, const void** d_keys, const uint32_t** d_counts, uint64_t* distinct)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
-    if (d_keys) *d_keys = c->res_keys;
-    if (d_counts) *d_counts = c->res_counts;
-    if (distinct) *distinct = c->M;
+    if (!c->build.finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
+    if (d_keys) *d_keys = c->build.res_keys;
+    if (d_counts) *d_counts = c->build.res_counts;
+    if (distinct) *distinct = c->build.M;
     return GOSS_OK;
 }
 
 int goss_gpu_result_copy(goss_gpu_ctx* c, uint64_t first, uint64_t n, uint64_t* h_keys, uint32_t* h_counts)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
-    if (first > c->M || n > c->M - first) return GOSS_ERR_INVALID_ARG;
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    if (!c->build.finished) { c->last_error = "result before finish"; return GOSS_ERR_STATE; }
+    if (first > c->build.M || n > c->build.M - first) return GOSS_ERR_INVALID_ARG;
+    return guarded_reading(c, [&]() {
         const uint64_t ksz = c->words * 8;
-        if (h_keys && n) HIP_TRY(hipMemcpyAsync(h_keys, (const uint8_t*)c->res_keys + first * ksz, n * ksz, hipMemcpyDeviceToHost, c->stream));
-        if (h_counts && n) HIP_TRY(hipMemcpyAsync(h_counts, c->res_counts + first, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (h_keys && n) HIP_TRY(hipMemcpyAsync(h_keys, (const uint8_t*)c->build.res_keys + first * ksz, n * ksz, hipMemcpyDeviceToHost, c->stream));
+        if (h_counts && n) HIP_TRY(hipMemcpyAsync(h_counts, c->build.res_counts + first, n * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
 }
 
-int goss_gpu_emit(goss_gpu_ctx* c)
+// goss_gpu_emit and goss_gpu_emit_estimate: m_estimate is the SparseArray estimate the caller gave, or null
+static int emit_result(goss_gpu_ctx* c, const uint64_t* m_estimate)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished || c->emitted) { c->last_error = "emit needs exactly one finish before it"; return GOSS_ERR_STATE; }
+    if (!c->build.finished || c->build.emitted) { c->last_error = "emit needs exactly one finish before it"; return GOSS_ERR_STATE; }
     int rc = guarded(c, [&]() {
-        c->files.clear();
+        c->build.files.clear();
         {
             // file images: low bits (up to 16 B), bitmap, DenseSelect blocks, counts per element
-            const uint64_t need = c->M * 40 + (256ULL << 20);
+            const uint64_t need = c->build.M * 40 + (256ULL << 20);
             if (c->arena.avail() < need) grow_arena(c, need);
         }
-        if (c->words == 1) emit_object<Key1>(c); else emit_object<Key2>(c);
+        if (c->words == 1) emit_object<Key1>(c, m_estimate); else emit_object<Key2>(c, m_estimate);
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
-    if (rc == GOSS_OK) c->emitted = true;
+    if (rc == GOSS_OK) c->build.emitted = true;
     return rc;
 }
+
+int goss_gpu_emit(goss_gpu_ctx* c) { return emit_result(c, nullptr); }
+
+int goss_gpu_emit_estimate(goss_gpu_ctx* c, uint64_t m_estimate) { return emit_result(c, &m_estimate); }
 
 int goss_gpu_big_counts(goss_gpu_ctx* c, uint64_t* keys, uint64_t* counts, uint32_t cap, uint32_t* n)
 {
     if (!c || !n) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished) { c->last_error = "big_counts before finish"; return GOSS_ERR_STATE; }
-    *n = (uint32_t)c->res_big.size();
+    if (!c->build.finished) { c->last_error = "big_counts before finish"; return GOSS_ERR_STATE; }
+    *n = (uint32_t)c->build.res_big.size();
     uint32_t i = 0;
-    for (auto& kv : c->res_big)
+    for (auto& kv : c->build.res_big)
     {
         if (i >= cap) break;
         if (keys) { keys[2 * i] = kv.first.second; keys[2 * i + 1] = kv.first.first; }
@@ -1911,12 +1464,12 @@ int goss_gpu_big_counts(goss_gpu_ctx* c, uint64_t* keys, uint64_t* counts, uint3
 static int emit_part_entry(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t estimate, uint64_t prev_high, bool have_prev)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished || c->emitted) { c->last_error = "emit_part needs exactly one finish before it"; return GOSS_ERR_STATE; }
-    if (first_index + c->M > total) { c->last_error = "emit_part: the range does not fit the total"; return GOSS_ERR_INVALID_ARG; }
+    if (!c->build.finished || c->build.emitted) { c->last_error = "emit_part needs exactly one finish before it"; return GOSS_ERR_STATE; }
+    if (first_index + c->build.M > total) { c->last_error = "emit_part: the range does not fit the total"; return GOSS_ERR_INVALID_ARG; }
     int rc = guarded(c, [&]() {
-        c->files.clear();
+        c->build.files.clear();
         {
-            const uint64_t need = c->M * 48 + (256ULL << 20);
+            const uint64_t need = c->build.M * 48 + (256ULL << 20);
             if (c->arena.avail() < need) grow_arena(c, need);
         }
         const uint64_t est = estimate ? estimate : total;
@@ -1924,7 +1477,7 @@ static int emit_part_entry(goss_gpu_ctx* c, uint64_t first_index, uint64_t total
         else emit_part<Key2>(c, first_index, total, est, prev_high, have_prev);
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
-    if (rc == GOSS_OK) c->emitted = true;
+    if (rc == GOSS_OK) c->build.emitted = true;
     return rc;
 }
 int goss_gpu_emit_part(goss_gpu_ctx* c, uint64_t first_index, uint64_t total, uint64_t estimate)
@@ -1938,24 +1491,24 @@ int goss_gpu_emit_part_ranges(goss_gpu_ctx* c, uint64_t first_index, uint64_t to
 int goss_gpu_emit_last_high(goss_gpu_ctx* c, uint64_t total, uint64_t estimate, uint64_t* high, int* nonempty)
 {
     if (!c || !high || !nonempty) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished) { c->last_error = "emit_last_high needs a finished range"; return GOSS_ERR_STATE; }
+    if (!c->build.finished) { c->last_error = "emit_last_high needs a finished range"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
-        *high = 0; *nonempty = c->M ? 1 : 0;
-        if (!c->M) return;
+        *high = 0; *nonempty = c->build.M ? 1 : 0;
+        if (!c->build.M) return;
         uint64_t nlo, nhi; std::string base;
         object_universe(c, &nlo, &nhi, &base);
         const uint32_t D = (uint32_t)sparse_d(nlo, nhi, estimate ? estimate : total);
         if (c->words == 1)
         {
             Key1 k;
-            HIP_TRY(hipMemcpyAsync(&k, (const Key1*)c->res_keys + (c->M - 1), sizeof k, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&k, (const Key1*)c->build.res_keys + (c->build.M - 1), sizeof k, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             *high = D >= 128 ? 0 : key_shr64(k, D);
         }
         else
         {
             Key2 k;
-            HIP_TRY(hipMemcpyAsync(&k, (const Key2*)c->res_keys + (c->M - 1), sizeof k, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&k, (const Key2*)c->build.res_keys + (c->build.M - 1), sizeof k, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             *high = D >= 128 ? 0 : key_shr64(k, D);
         }
@@ -1967,7 +1520,7 @@ int goss_gpu_emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_b
 {
     if (!c || (span_bytes & 7u) || (span_bytes && !d_spans) || (total && !span_bytes) || (nbig && !h_big) || (nhist && !h_hist))
         return GOSS_ERR_INVALID_ARG;
-    if (!c->finished && (!c->runs.empty() || c->stage_fill))
+    if (!c->build.finished && (!c->build.runs.empty() || c->stage_fill))
     {
         c->last_error = "emit_assemble while a count is in progress";
         return GOSS_ERR_STATE;
@@ -1981,7 +1534,7 @@ int goss_gpu_emit_assemble(goss_gpu_ctx* c, const void* d_spans, uint64_t span_b
         const auto t0 = std::chrono::steady_clock::now();
         emit_assemble(c, d_spans, span_bytes, total, estimate ? estimate : total, (const BigCount*)h_big, nbig, h_hist, nhist);
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->assemble_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        c->stats.assemble_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     });
 }
 
@@ -2000,13 +1553,13 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
     for (uint32_t i = 0; i < n; ++i)
     {
         goss_gpu_ctx* c = ctxs[i];
-        const uint64_t m = c->M;
+        const uint64_t m = c->build.M;
         if (m == 0) continue;
         HIP_TRY(hipSetDevice(c->device));
         const uint64_t take = std::min<uint64_t>(m, sample);
         const uint64_t stride = m / take;
         std::vector<K> h(take);
-        HIP_TRY(hipMemcpy2DAsync(h.data(), ksz, (const uint8_t*)c->res_keys + (stride / 2) * ksz, stride * ksz, ksz, take,
+        HIP_TRY(hipMemcpy2DAsync(h.data(), ksz, (const uint8_t*)c->build.res_keys + (stride / 2) * ksz, stride * ksz, ksz, take,
                                  hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         pool.insert(pool.end(), h.begin(), h.end());
@@ -2020,8 +1573,8 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
     for (uint32_t i = 0; i < n; ++i)
     {
         goss_gpu_ctx* c = ctxs[i];
-        cut[i][n] = c->M;
-        if (n == 1 || c->M == 0) { for (uint32_t p = 1; p < n; ++p) cut[i][p] = 0; if (c->M == 0) continue; }
+        cut[i][n] = c->build.M;
+        if (n == 1 || c->build.M == 0) { for (uint32_t p = 1; p < n; ++p) cut[i][p] = 0; if (c->build.M == 0) continue; }
         if (n == 1) continue;
         HIP_TRY(hipSetDevice(c->device));
         uint64_t mark = c->arena.mark();
@@ -2029,7 +1582,7 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
         uint64_t* dout = (uint64_t*)c->arena.temp((n - 1) * 8);
         HIP_TRY(hipMemcpyAsync(dq, split.data(), (n - 1) * ksz, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(lower_bound_keys_kernel<K>), dim3((n - 1 + 63) / 64), dim3(64), 0, c->stream,
-                           (const K*)c->res_keys, c->M, (const K*)dq, n - 1, dout);
+                           (const K*)c->build.res_keys, c->build.M, (const K*)dq, n - 1, dout);
         HIP_TRY(hipMemcpyAsync(&cut[i][1], dout, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
@@ -2078,9 +1631,9 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
                 const uint64_t cnt = cut[i][j + 1] - cut[i][j];
                 if (!cnt) continue;
                 goss_gpu_ctx* s = ctxs[i];
-                HIP_TRY(hipMemcpyPeerAsync(in.keys + in.off[i] * ksz, d->device, (const uint8_t*)s->res_keys + cut[i][j] * ksz, s->device,
+                HIP_TRY(hipMemcpyPeerAsync(in.keys + in.off[i] * ksz, d->device, (const uint8_t*)s->build.res_keys + cut[i][j] * ksz, s->device,
                                            cnt * ksz, d->stream));
-                HIP_TRY(hipMemcpyPeerAsync(in.counts + in.off[i], d->device, s->res_counts + cut[i][j], s->device, cnt * 4, d->stream));
+                HIP_TRY(hipMemcpyPeerAsync(in.counts + in.off[i], d->device, s->build.res_counts + cut[i][j], s->device, cnt * 4, d->stream));
             }
         }
         for (uint32_t j = 0; j < n; ++j)
@@ -2094,7 +1647,7 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
         for (uint32_t j = 0; j < n; ++j)
             pool_t.emplace_back([&, j]() {
                 goss_gpu_ctx* d = ctxs[j];
-                const uint64_t windows = d->windows, keys_total = d->keys_total;
+                const uint64_t windows = d->build.windows, keys_total = d->build.keys_total;
                 int rc = goss_gpu_reset(d);
                 if (inbox[j].in_arena) d->arena.hi = inbox[j].fence;          // (the reset has given the whole arena back: the inbox lives on)
                 for (uint32_t i = 0; i < n && rc == GOSS_OK; ++i)
@@ -2103,7 +1656,7 @@ void group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t sample)
                     if (cnt) rc = goss_gpu_push_run_device(d, inbox[j].keys + inbox[j].off[i] * ksz, inbox[j].counts + inbox[j].off[i], cnt);
                 }
                 if (inbox[j].in_arena) d->arena.hi = d->arena.size;           // (the runs are copies: the inbox is done)
-                d->windows = windows; d->keys_total = keys_total;
+                d->build.windows = windows; d->build.keys_total = keys_total;
                 goss_gpu_counts cts;
                 if (rc == GOSS_OK) rc = goss_gpu_finish(d, &cts);
                 status[j] = rc;
@@ -2132,9 +1685,9 @@ int goss_gpu_group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t samp
     {
         goss_gpu_ctx* c = ctxs[i];
         if (c->k != c0->k || c->mode != c0->mode) { c0->last_error = "group: contexts of different k or mode"; return GOSS_ERR_INVALID_ARG; }
-        if (!c->finished || c->emitted) { c0->last_error = "group exchange needs every context finished and not emitted"; return GOSS_ERR_STATE; }
+        if (!c->build.finished || c->build.emitted) { c0->last_error = "group exchange needs every context finished and not emitted"; return GOSS_ERR_STATE; }
         for (uint32_t j = 0; j < i; ++j) if (ctxs[j] == c) { c0->last_error = "group: the same context twice"; return GOSS_ERR_INVALID_ARG; }
-        if (!c->res_big.empty())
+        if (!c->build.res_big.empty())
         {
             c0->last_error = "group exchange: a multiplicity of 2^32 - 1 or more (exact counts do not travel between contexts)";
             return GOSS_ERR_COUNT_OVERFLOW;
@@ -2144,7 +1697,7 @@ int goss_gpu_group_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, uint32_t samp
         const uint32_t sample = sample_per_context ? sample_per_context : 1024u;
         if (c0->words == 1) group_exchange<Key1>(ctxs, n, sample); else group_exchange<Key2>(ctxs, n, sample);
     });
-    if (rc == GOSS_OK && range_sizes) for (uint32_t i = 0; i < n; ++i) range_sizes[i] = ctxs[i]->M;
+    if (rc == GOSS_OK && range_sizes) for (uint32_t i = 0; i < n; ++i) range_sizes[i] = ctxs[i]->build.M;
     return rc;
 }
 
@@ -2157,7 +1710,7 @@ int goss_gpu_group_emit(goss_gpu_ctx* const* ctxs, uint32_t n, uint64_t estimate
         if (ctxs[i]->k != c0->k || ctxs[i]->mode != c0->mode) { c0->last_error = "group: contexts of different k or mode"; return GOSS_ERR_INVALID_ARG; }
     uint64_t total = 0;
     std::vector<uint64_t> first(n);
-    for (uint32_t i = 0; i < n; ++i) { first[i] = total; total += ctxs[i]->M; }
+    for (uint32_t i = 0; i < n; ++i) { first[i] = total; total += ctxs[i]->build.M; }
     // the high part of the last key of the ranges below every range: which zeros of the bitmap a range owns
     std::vector<uint64_t> prev(n, 0);
     {
@@ -2202,7 +1755,7 @@ int goss_gpu_group_emit(goss_gpu_ctx* const* ctxs, uint32_t n, uint64_t estimate
         {
             goss_gpu_ctx* c = ctxs[i];
             HIP_TRY(hipSetDevice(c->device));
-            for (const OutFile& f : c->files)
+            for (const OutFile& f : c->build.files)
             {
                 if (f.suffix == ".part.span")
                 {
@@ -2411,7 +1964,7 @@ void group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int transport, 
             prev_count_ms = std::max(prev_count_ms, ctxs[i]->grp_count_ms);
             ctxs[i]->grp_count_ms = 0;
         }
-        if (bad != GOSS_OK) { for (uint32_t i = 0; i < n; ++i) ctxs[i]->broken = true; throw StatusError{bad, why}; }
+        if (bad != GOSS_OK) { for (uint32_t i = 0; i < n; ++i) ctxs[i]->build.broken = true; throw StatusError{bad, why}; }
     }
     const double wait_ms = ms_since(tw);
     const auto t0 = std::chrono::steady_clock::now();
@@ -2424,7 +1977,7 @@ void group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int transport, 
         // the whole group is marked and refuses further work)
         std::vector<std::thread> pool;
         auto join_all = [&]() { for (auto& t : pool) if (t.joinable()) t.join(); };
-        auto mark_broken = [&]() { for (uint32_t i = 0; i < n; ++i) ctxs[i]->broken = true; };
+        auto mark_broken = [&]() { for (uint32_t i = 0; i < n; ++i) ctxs[i]->build.broken = true; };
         auto start = [&](std::function<void()> f) {
             try { pool.emplace_back(std::move(f)); }
             catch (const std::system_error& e) { join_all(); mark_broken(); throw StatusError{GOSS_ERR_OOM, std::string("no thread for a member of the group: ") + e.what()}; }
@@ -2600,7 +2153,7 @@ void group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int transport, 
 int goss_gpu_set_deferred(goss_gpu_ctx* c, int on)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "deferred counting is set before the pushes"; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "deferred counting is set before the pushes"; return GOSS_ERR_STATE; }
     c->deferred = on != 0;
     return GOSS_OK;
 }
@@ -2625,8 +2178,8 @@ int goss_gpu_group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int tra
     {
         goss_gpu_ctx* c = ctxs[i];
         if (c->k != c0->k || c->mode != c0->mode) { c0->last_error = "group: contexts of different k or mode"; return GOSS_ERR_INVALID_ARG; }
-        if (c->finished) { c0->last_error = "group route exchange after finish"; return GOSS_ERR_STATE; }
-        if (c->broken) { c0->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+        if (c->build.finished) { c0->last_error = "group route exchange after finish"; return GOSS_ERR_STATE; }
+        if (c->build.broken) { c0->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
         if (c->len > 63) { c0->last_error = "records carry windows of at most 63 bases"; return GOSS_ERR_INVALID_ARG; }
         for (uint32_t j = 0; j < i; ++j) if (ctxs[j] == c) { c0->last_error = "group: the same context twice"; return GOSS_ERR_INVALID_ARG; }
     }
@@ -2641,8 +2194,8 @@ int goss_gpu_group_route_exchange(goss_gpu_ctx* const* ctxs, uint32_t n, int tra
 
 int goss_gpu_file_device(goss_gpu_ctx* c, uint32_t i, const void** d_ptr)
 {
-    if (!c || !d_ptr || i >= c->files.size()) return GOSS_ERR_INVALID_ARG;
-    *d_ptr = c->files[i].dev;          // NULL for a file built on the host
+    if (!c || !d_ptr || i >= c->build.files.size()) return GOSS_ERR_INVALID_ARG;
+    *d_ptr = c->build.files[i].dev;          // NULL for a file built on the host
     return GOSS_OK;
 }
 
@@ -2652,14 +2205,14 @@ int goss_gpu_emit_sparse_array(goss_gpu_ctx* c, const void* d_positions, uint32_
     if (!c || (key_words != 1 && key_words != 2) || (!d_positions && n)) return GOSS_ERR_INVALID_ARG;
     // its key copy and file images are permanent allocations: between pushes a later merge or an
     // out-of-memory rollback would rewind the permanent end underneath them
-    if (!c->finished && (!c->runs.empty() || c->stage_fill))
+    if (!c->build.finished && (!c->build.runs.empty() || c->stage_fill))
     {
         c->last_error = "emit_sparse_array while a count is in progress (reset or finish first)";
         return GOSS_ERR_STATE;
     }
     return guarded(c, [&]() {
         ensure_arena(c);
-        c->files.clear();
+        c->build.files.clear();
         PhaseTimer t(c, GOSS_T_EMIT, n);
         // private copy so the caller's buffer need not outlive the call
         const uint64_t ksz = key_words * 8;
@@ -2675,27 +2228,26 @@ int goss_gpu_emit_sparse_array(goss_gpu_ctx* c, const void* d_positions, uint32_
 int goss_gpu_file_count(goss_gpu_ctx* c, uint32_t* n)
 {
     if (!c || !n) return GOSS_ERR_INVALID_ARG;
-    *n = (uint32_t)c->files.size();
+    *n = (uint32_t)c->build.files.size();
     return GOSS_OK;
 }
 
 int goss_gpu_file_info(goss_gpu_ctx* c, uint32_t i, char* suffix, size_t cap, uint64_t* size)
 {
-    if (!c || i >= c->files.size()) return GOSS_ERR_INVALID_ARG;
-    if (suffix && cap) { std::snprintf(suffix, cap, "%s", c->files[i].suffix.c_str()); }
-    if (size) *size = c->files[i].size;
+    if (!c || i >= c->build.files.size()) return GOSS_ERR_INVALID_ARG;
+    if (suffix && cap) { std::snprintf(suffix, cap, "%s", c->build.files[i].suffix.c_str()); }
+    if (size) *size = c->build.files[i].size;
     return GOSS_OK;
 }
 
 int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, uint64_t n)
 {
-    if (!c || i >= c->files.size() || (!dst && n)) return GOSS_ERR_INVALID_ARG;
-    const OutFile& f = c->files[i];
+    if (!c || i >= c->build.files.size() || (!dst && n)) return GOSS_ERR_INVALID_ARG;
+    const OutFile& f = c->build.files[i];
     if (offset > f.size || n > f.size - offset) return GOSS_ERR_INVALID_ARG;
     if (n == 0) return GOSS_OK;
     if (!f.dev) { std::memcpy(dst, f.host.data() + offset, n); return GOSS_OK; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    return guarded_reading(c, [&]() {
         HIP_TRY(hipMemcpyAsync(dst, f.dev + offset, n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
@@ -2704,8 +2256,7 @@ int goss_gpu_file_read(goss_gpu_ctx* c, uint32_t i, uint64_t offset, void* dst, 
 int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 {
     if (!c || !out) return GOSS_ERR_INVALID_ARG;
-    c->keep_held = true;
-    int rc = guarded(c, [&]() { resolve_timing(c); });
+    int rc = guarded_reading(c, [&]() { resolve_timing(c); });
     *out = c->timing;
     return rc;
 }
@@ -2713,8 +2264,7 @@ int goss_gpu_timing_get(goss_gpu_ctx* c, goss_gpu_timing* out)
 int goss_gpu_timing_reset(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    c->keep_held = true;
-    int rc = guarded(c, [&]() { resolve_timing(c); });
+    int rc = guarded_reading(c, [&]() { resolve_timing(c); });
     c->timing = goss_gpu_timing{};
     return rc;
 }
@@ -2759,23 +2309,11 @@ int goss_gpu_reset(goss_gpu_ctx* c)
         if (c->arena_thread.joinable()) ensure_arena(c);      // a background mapping (goss_gpu_prepare) ends first
         HIP_TRY(hipStreamSynchronize(c->stream));
         release_pending(c, true);
-        c->runs.clear();
-        c->big_maps.clear();
-        c->res_big.clear();
-        c->pushed_counts = false;
-        c->files.clear();
-        c->windows = c->keys_total = 0;
-        c->space_choice = -1;
-        c->expect_bases = 0;
-        c->finished = c->emitted = false;
-        c->broken = false;
-        c->res_keys = nullptr; c->res_counts = nullptr; c->M = 0;
-        c->tips_keys = nullptr; c->tips_counts = nullptr;
+        c->build = Build{};                                   // (the knobs, demoted or not, and the counters stay)
         release_held(c);
         c->arena.lo = 0; c->arena.hi = c->arena.size;
         if (c->copy_stream) HIP_TRY(hipStreamSynchronize(c->copy_stream));
         c->stage_cur = 0; c->stage = c->stage_buf[0]; c->stage_fill = 0;          // (the staging buffers stay)
-        c->dump_live = false;
         HIP_TRY(hipMemsetAsync(c->d_flags, 0, 16, c->stream));
     });
 }
@@ -2783,8 +2321,8 @@ int goss_gpu_reset(goss_gpu_ctx* c)
 int goss_gpu_push_run_device(goss_gpu_ctx* c, const void* d_keys, const uint32_t* d_counts, uint64_t m)
 {
     if (!c || (m && (!d_keys || !d_counts))) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (m == 0) return GOSS_OK;
     return guarded(c, [&]() {
         ensure_arena(c);
@@ -2797,8 +2335,8 @@ int goss_gpu_push_run_device(goss_gpu_ctx* c, const void* d_keys, const uint32_t
         HIP_TRY(hipMemcpyAsync(r.keys, d_keys, m * ksz, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(r.counts, d_counts, m * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->runs.push_back(r);
-        c->pushed_counts = true;
+        c->build.runs.push_back(r);
+        c->build.pushed_counts = true;
         // keys_total keeps meaning "keys inserted": a run stands for the sum of its counts,
         // which the caller accounts for; windows are not known here.
     });
@@ -2807,8 +2345,8 @@ int goss_gpu_push_run_device(goss_gpu_ctx* c, const void* d_keys, const uint32_t
 int goss_gpu_push_run_host(goss_gpu_ctx* c, const uint64_t* keys, const uint32_t* counts, uint64_t m)
 {
     if (!c || (m && (!keys || !counts))) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (m == 0) return GOSS_OK;
     return guarded(c, [&]() {
         ensure_arena(c);
@@ -2821,8 +2359,8 @@ int goss_gpu_push_run_host(goss_gpu_ctx* c, const uint64_t* keys, const uint32_t
         HIP_TRY(hipMemcpyAsync(r.keys, keys, m * ksz, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(r.counts, counts, m * 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->runs.push_back(r);
-        c->pushed_counts = true;
+        c->build.runs.push_back(r);
+        c->build.pushed_counts = true;
     });
 }
 
@@ -2840,7 +2378,7 @@ static void push_keys(goss_gpu_ctx* c, const void* keys, uint64_t n, bool on_hos
         // two key buffers, the sort's tables and the worst-case run of the piece (chunk_capacity's pessimistic sizing)
         auto capacity = [&]() { return (uint64_t)((double)c->arena.avail() * 0.95 / (2.0 * ksz + 1.2 + (ksz + 12.0))) & ~4095ULL; };
         uint64_t cap = capacity();
-        if (cap < 4096 && c->runs.size() > 1) { merge_runs<K>(c); cap = capacity(); }
+        if (cap < 4096 && c->build.runs.size() > 1) { merge_runs<K>(c); cap = capacity(); }
         if (cap < 4096 && grow_arena(c, 0)) cap = capacity();
         if (cap < 4096) throw StatusError{GOSS_ERR_OOM, "HBM budget too small for one piece of keys"};
         const uint64_t m = std::min(cap, n - done);
@@ -2868,15 +2406,15 @@ static void push_keys(goss_gpu_ctx* c, const void* keys, uint64_t n, bool on_hos
         if (hf[0]) { c->arena.release(mark); throw StatusError{GOSS_ERR_INVALID_ARG, "a pushed key has bits beyond 2*len"}; }
         c->extract_hist_shift = 0xFFFFFFFFu;          // no extraction kernel histogrammed THESE keys
         Run r = count_keys<K>(c, ka, kb, m);
-        c->runs.push_back(r);
+        c->build.runs.push_back(r);
         c->arena.release(mark);
         // a k-mer is one window and one key; a graph key is one of the two a rho-mer window contributes
-        c->keys_total += m;
-        c->windows += c->mode == GOSS_MODE_GRAPH ? m / 2 : m;
+        c->build.keys_total += m;
+        c->build.windows += c->mode == GOSS_MODE_GRAPH ? m / 2 : m;
         done += m;
         uint64_t run_bytes = 0;
-        for (auto& q : c->runs) run_bytes += q.m * (ksz + 4);
-        if (c->runs.size() > 1 && run_bytes > c->arena.size / 4 &&
+        for (auto& q : c->build.runs) run_bytes += q.m * (ksz + 4);
+        if (c->build.runs.size() > 1 && run_bytes > c->arena.size / 4 &&
             (c->arena.avail() >= 2 * run_bytes + (512ULL << 20) || grow_arena(c, 2 * run_bytes + (512ULL << 20)))) merge_runs<K>(c);
     }
 }
@@ -2885,8 +2423,8 @@ static void push_keys(goss_gpu_ctx* c, const void* keys, uint64_t n, bool on_hos
 static int push_keys_entry(goss_gpu_ctx* c, const void* keys, uint64_t n, bool on_host)
 {
     if (!c || (n && !keys)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (n == 0) return GOSS_OK;
     return guarded(c, [&]() {
         if (c->words == 1) push_keys<Key1>(c, keys, n, on_host); else push_keys<Key2>(c, keys, n, on_host);
@@ -2904,8 +2442,8 @@ int goss_gpu_route_records_device(goss_gpu_ctx* c, const void* d_bases, uint64_t
 int goss_gpu_push_records_device(goss_gpu_ctx* c, const void* d_records, uint64_t nrecords, uint64_t nwindows)
 {
     if (!c || (nrecords && !d_records)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (c->len > 63) { c->last_error = "records carry windows of at most 63 bases"; return GOSS_ERR_INVALID_ARG; }
     return guarded(c, [&]() {
         flush_staging(c);
@@ -2952,8 +2490,8 @@ static uint64_t sparse_run_need(const goss_gpu_sparse_run* s)
 int goss_gpu_push_run_sparse(goss_gpu_ctx* c, const goss_gpu_sparse_run* s)
 {
     if (!c || !sparse_run_ok(s)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     if (s->count == 0) return GOSS_OK;
     return guarded(c, [&]() {
         ensure_arena(c);
@@ -2972,16 +2510,16 @@ int goss_gpu_push_run_sparse(goss_gpu_ctx* c, const goss_gpu_sparse_run* s)
         else hipLaunchKernelGGL(fill_u32_kernel, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, r.counts, m, s->weight ? s->weight : 1u);
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
-        c->runs.push_back(r);
-        c->pushed_counts = true;
+        c->build.runs.push_back(r);
+        c->build.pushed_counts = true;
     });
 }
 
 int goss_gpu_push_run_graph(goss_gpu_ctx* c, const goss_gpu_sparse_run* edges, const goss_gpu_vba* v)
 {
     if (!c || !sparse_run_ok(edges) || !v || !sparse_run_ok(&v->ord1p) || !sparse_run_ok(&v->ord2p)) return GOSS_ERR_INVALID_ARG;
-    if (c->finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
-    if (c->broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
+    if (c->build.finished) { c->last_error = "push after finish"; return GOSS_ERR_STATE; }
+    if (c->build.broken) { c->last_error = kBrokenMsg; return GOSS_ERR_STATE; }
     const uint64_t m = edges->count, n1 = v->ord1p.count, n2 = v->ord2p.count;
     if (m == 0) return GOSS_OK;
     if (v->ord0_bytes < m || v->ord1_bytes < n1 || v->ord2_bytes < 2 * n2 || (m && !v->ord0) || (n1 && !v->ord1) || (n2 && !v->ord2))
@@ -3026,8 +2564,8 @@ int goss_gpu_push_run_graph(goss_gpu_ctx* c, const goss_gpu_sparse_run* edges, c
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
-        c->runs.push_back(r);
-        c->pushed_counts = true;
+        c->build.runs.push_back(r);
+        c->build.pushed_counts = true;
     });
 }
 
@@ -3035,13 +2573,13 @@ extern "C++" {
 template <class K>
 static void select_counts(goss_gpu_ctx* c, uint32_t lo, uint32_t hi)
 {
-    const uint64_t n = c->M;
+    const uint64_t n = c->build.M;
     if (n == 0) return;
     uint64_t mark = c->arena.mark();
     const uint64_t ntiles = (n + kRedTile - 1) / kRedTile;
     uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
     hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(n, kRedTile)), dim3(kTB), 0, c->stream,
-                       (const uint32_t*)c->res_counts, n, lo, hi, tile_counts);
+                       (const uint32_t*)c->build.res_counts, n, lo, hi, tile_counts);
     HIP_TRY(hipMemsetAsync(tile_counts + ntiles, 0, 8, c->stream));
     exclusive_scan_u64(c, tile_counts, ntiles + 1);
     uint64_t* h = (uint64_t*)c->h_pinned;
@@ -3051,19 +2589,19 @@ static void select_counts(goss_gpu_ctx* c, uint32_t lo, uint32_t hi)
     K* keys = (K*)c->arena.perm(std::max<uint64_t>(m * sizeof(K), 16));
     uint32_t* counts = (uint32_t*)c->arena.perm(std::max<uint64_t>(m * 4, 16));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(select_write_kernel<K>), dim3(grid_for(n, kRedTile)), dim3(kTB), 0, c->stream,
-                       (const K*)c->res_keys, (const uint32_t*)c->res_counts, n, lo, hi, (const uint64_t*)tile_counts, keys, counts);
+                       (const K*)c->build.res_keys, (const uint32_t*)c->build.res_counts, n, lo, hi, (const uint64_t*)tile_counts, keys, counts);
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->arena.release(mark);
-    c->res_keys = keys; c->res_counts = counts; c->M = m;
+    c->build.res_keys = keys; c->build.res_counts = counts; c->build.M = m;
 }
 }  // extern "C++"
 
 int goss_gpu_select_counts(goss_gpu_ctx* c, uint32_t lo, uint32_t hi)
 {
     if (!c || lo > hi) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished || c->emitted) { c->last_error = "select_counts belongs between finish and emit"; return GOSS_ERR_STATE; }
+    if (!c->build.finished || c->build.emitted) { c->last_error = "select_counts belongs between finish and emit"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         if (c->words == 1) select_counts<Key1>(c, lo, hi); else select_counts<Key2>(c, lo, hi);
         t.stop();
     });
@@ -3072,22 +2610,22 @@ int goss_gpu_select_counts(goss_gpu_ctx* c, uint32_t lo, uint32_t hi)
 int goss_gpu_select_normal(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished || c->emitted) { c->last_error = "select_normal belongs between finish and emit"; return GOSS_ERR_STATE; }
+    if (!c->build.finished || c->build.emitted) { c->last_error = "select_normal belongs between finish and emit"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
-        if (c->M)
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
+        if (c->build.M)
         {
-            const dim3 grid = unit_grid((c->M + kTB - 1) / kTB);
+            const dim3 grid = unit_grid((c->build.M + kTB - 1) / kTB);
             if (c->words == 1)
             {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(mark_normal_kernel<Key1>), grid, dim3(kTB), 0, c->stream,
-                                   (const Key1*)c->res_keys, c->M, c->len, c->res_counts);
+                                   (const Key1*)c->build.res_keys, c->build.M, c->len, c->build.res_counts);
                 select_counts<Key1>(c, 1, 1);
             }
             else
             {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(mark_normal_kernel<Key2>), grid, dim3(kTB), 0, c->stream,
-                                   (const Key2*)c->res_keys, c->M, c->len, c->res_counts);
+                                   (const Key2*)c->build.res_keys, c->build.M, c->len, c->build.res_counts);
                 select_counts<Key2>(c, 1, 1);
             }
         }
@@ -3131,10 +2669,10 @@ int goss_gpu_check_index(goss_gpu_ctx* c, const goss_gpu_sparse_files* f, goss_g
 {
     if (!c || !f || !out || f->ncols == 0 || f->ncols > 4) return GOSS_ERR_INVALID_ARG;
     static_assert(sizeof(goss_gpu_index_report) == sizeof(IndexReport), "index report layout");
-    if (!c->finished) { c->last_error = "check_index before finish"; return GOSS_ERR_STATE; }
+    if (!c->build.finished) { c->last_error = "check_index before finish"; return GOSS_ERR_STATE; }
     std::memset(out, 0, sizeof *out);
-    if (c->M != f->count) { c->last_error = "the object's count differs from the number of decoded elements"; return GOSS_ERR_STATE; }
-    if (c->M == 0) return GOSS_OK;
+    if (c->build.M != f->count) { c->last_error = "the object's count differs from the number of decoded elements"; return GOSS_ERR_STATE; }
+    if (c->build.M == 0) return GOSS_OK;
     return guarded(c, [&]() {
         uint64_t mark = c->arena.mark();
         RdSparse s{};
@@ -3154,11 +2692,11 @@ int goss_gpu_check_index(goss_gpu_ctx* c, const goss_gpu_sparse_files* f, goss_g
         IndexReport* rep = (IndexReport*)c->arena.temp(sizeof(IndexReport));
         HIP_TRY(hipMemsetAsync(rep, 0, sizeof(IndexReport), c->stream));
         if (c->words == 1)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(check_index_kernel<Key1>), dim3(grid_for(c->M, 256)), dim3(256), 0, c->stream, s,
-                               (const Key1*)c->res_keys, c->M, rep);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(check_index_kernel<Key1>), dim3(grid_for(c->build.M, 256)), dim3(256), 0, c->stream, s,
+                               (const Key1*)c->build.res_keys, c->build.M, rep);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(check_index_kernel<Key2>), dim3(grid_for(c->M, 256)), dim3(256), 0, c->stream, s,
-                               (const Key2*)c->res_keys, c->M, rep);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(check_index_kernel<Key2>), dim3(grid_for(c->build.M, 256)), dim3(256), 0, c->stream, s,
+                               (const Key2*)c->build.res_keys, c->build.M, rep);
         HIP_TRY(hipMemcpyAsync(out, rep, sizeof(IndexReport), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
@@ -3176,52 +2714,21 @@ int goss_gpu_set_budget_limit(goss_gpu_ctx* c, uint64_t max_bytes)
 int goss_gpu_stat(goss_gpu_ctx* c, const char* name, uint64_t* value)
 {
     if (!c || !name || !value) return GOSS_ERR_INVALID_ARG;
-    const std::string n = name;
-    if (n == "fused_chunks") *value = c->fused_chunks;
-    else if (n == "rep_chunks") *value = c->rep_chunks;
-    else if (n == "canon_chunks") *value = c->canon_chunks;
-    else if (n == "rec_chunks") *value = c->rec_chunks;
-    else if (n == "flush_wait_us") *value = c->flush_wait_us;
-    else if (n == "flush_count_us") *value = c->flush_count_us;
-    else if (n == "flushes") *value = c->flushes;
-    else if (n == "fused_overflows") *value = c->fused_overflows;
-    else if (n == "fused_msd_chunks") *value = c->fused_msd_chunks;
-    else if (n == "rem32_chunks") *value = c->rem32_chunks;
-    else if (n == "narrow_chunks") *value = c->narrow_chunks;
-    else if (n == "overflow_units") *value = c->overflow_units;
-    else if (n == "packed_fused_chunks") *value = c->pk_fused_chunks;
-    else if (n == "ds_blocks_from_ranges") *value = c->ds_blocks_ranges;
-    else if (n == "assemble_us") *value = c->assemble_us;
-    else if (n == "ds_blocks_assembled") *value = c->ds_blocks_own;
-    else if (n == "packed_unpacked_chunks") *value = c->pk_unpacked_chunks;
-    else if (n == "rem32_bits") *value = c->rem32_bits_last;
-    else if (n == "rem32_split") *value = c->rem32_split_last;
-    else if (n == "big_table_chunks") *value = c->big_table_chunks;
-    else if (n == "wide_table_chunks") *value = c->wide_table_chunks;
-    else if (n == "table96_chunks") *value = c->table96_chunks;
-    else if (n == "valid_sized_chunks") *value = c->valid_sized_chunks;
-    else if (n == "valid_resizes") *value = c->valid_resizes;
-    else if (n == "seg_merges") *value = c->seg_merges;
-    else if (n == "hash_merges") *value = c->hash_merges;
-    else if (n == "segment_retries") *value = c->segment_retries;
-    else if (n == "lookback_failures") *value = c->lookback_failures;
-    else if (n == "runs") *value = c->runs.size();
-    else if (n == "arena_ms") *value = c->arena_ms;
-    else if (n == "arena_grows") *value = c->arena_grows;
-    else if (n == "arena_bytes") *value = c->arena.size;
-    else return GOSS_ERR_INVALID_ARG;
+    if (std::strcmp(name, "runs") == 0) *value = c->build.runs.size();
+    else if (std::strcmp(name, "arena_bytes") == 0) *value = c->arena.size;
+    else if (!stat_lookup(c->stats, name, value)) return GOSS_ERR_INVALID_ARG;
     return GOSS_OK;
 }
 
 int goss_gpu_emit_dump_range(goss_gpu_ctx* c, uint64_t flags, uint64_t first, uint64_t count)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    if (!c->finished) { c->last_error = "dump before finish"; return GOSS_ERR_STATE; }
-    if (first > c->M || count > c->M - first) return GOSS_ERR_INVALID_ARG;
+    if (!c->build.finished) { c->last_error = "dump before finish"; return GOSS_ERR_STATE; }
+    if (first > c->build.M || count > c->build.M - first) return GOSS_ERR_INVALID_ARG;
     return guarded(c, [&]() {
-        c->files.clear();
+        c->build.files.clear();
         // the previous piece's text is dead: give its room back (nothing else was allocated since)
-        if (c->dump_live) { c->arena.lo = c->dump_lo; c->dump_live = false; }
+        if (c->build.dump_live) { c->arena.lo = c->dump_lo; c->build.dump_live = false; }
         PhaseTimer t(c, GOSS_T_EMIT, count);
         const uint64_t m = count;
         const uint32_t len = c->len;
@@ -3231,12 +2738,12 @@ int goss_gpu_emit_dump_range(goss_gpu_ctx* c, uint64_t flags, uint64_t first, ui
         int hl = 0;
         if (first == 0)
             hl = c->mode == GOSS_MODE_KMER_SET
-                     ? std::snprintf(head, sizeof head, "#%llu\n%u\t%llu\n", 2011101701ULL, c->k, (unsigned long long)c->M)
-                     : std::snprintf(head, sizeof head, "#%llu\n%u\t%llu\t%llu\n", 2011101014ULL, c->k, (unsigned long long)c->M,
+                     ? std::snprintf(head, sizeof head, "#%llu\n%u\t%llu\n", 2011101701ULL, c->k, (unsigned long long)c->build.M)
+                     : std::snprintf(head, sizeof head, "#%llu\n%u\t%llu\t%llu\n", 2011101014ULL, c->k, (unsigned long long)c->build.M,
                                      (unsigned long long)flags);
         const uint64_t ksz = c->words * 8;
-        const uint8_t* keys = (const uint8_t*)c->res_keys + first * ksz;
-        const uint32_t* counts = c->res_counts + first;
+        const uint8_t* keys = (const uint8_t*)c->build.res_keys + first * ksz;
+        const uint32_t* counts = c->build.res_counts + first;
         uint64_t body = 0;
         uint64_t mark = c->arena.mark();
         uint64_t* offs = nullptr;
@@ -3254,7 +2761,7 @@ int goss_gpu_emit_dump_range(goss_gpu_ctx* c, uint64_t flags, uint64_t first, ui
         }
         c->dump_lo = c->arena.lo;
         uint8_t* text = (uint8_t*)c->arena.perm(hl + body + 16);
-        c->dump_live = true;
+        c->build.dump_live = true;
         if (hl) HIP_TRY(hipMemcpyAsync(text, head, hl, hipMemcpyHostToDevice, c->stream));
         if (m)
         {
@@ -3279,35 +2786,34 @@ int goss_gpu_emit_dump_range(goss_gpu_ctx* c, uint64_t flags, uint64_t first, ui
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
         OutFile f; f.suffix = ".dump"; f.size = hl + body; f.dev = text;
-        c->files.push_back(std::move(f));
+        c->build.files.push_back(std::move(f));
     });
 }
 
 int goss_gpu_emit_dump(goss_gpu_ctx* c, uint64_t flags)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
-    return goss_gpu_emit_dump_range(c, flags, 0, c->M);
+    return goss_gpu_emit_dump_range(c, flags, 0, c->build.M);
 }
 
 int goss_gpu_lint(goss_gpu_ctx* c, int asymmetric, goss_gpu_lint_report* out)
 {
     if (!c || !out) return GOSS_ERR_INVALID_ARG;
     static_assert(sizeof(goss_gpu_lint_report) == sizeof(LintReport), "lint report layout");
-    if (!c->finished) { c->last_error = "lint before finish"; return GOSS_ERR_STATE; }
+    if (!c->build.finished) { c->last_error = "lint before finish"; return GOSS_ERR_STATE; }
     if (c->mode != GOSS_MODE_GRAPH) { c->last_error = "lint checks a graph"; return GOSS_ERR_STATE; }
     std::memset(out, 0, sizeof *out);
-    if (c->M == 0) return GOSS_OK;
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    if (c->build.M == 0) return GOSS_OK;
+    return guarded_reading(c, [&]() {
         uint64_t mark = c->arena.mark();
         LintReport* rep = (LintReport*)c->arena.temp(sizeof(LintReport));
         HIP_TRY(hipMemsetAsync(rep, 0, sizeof(LintReport), c->stream));
         if (c->words == 1)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(lint_edges_kernel<Key1>), dim3(grid_for(c->M, 256)), dim3(256), 0, c->stream,
-                               (const Key1*)c->res_keys, (const uint32_t*)c->res_counts, c->M, c->len, asymmetric, rep);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(lint_edges_kernel<Key1>), dim3(grid_for(c->build.M, 256)), dim3(256), 0, c->stream,
+                               (const Key1*)c->build.res_keys, (const uint32_t*)c->build.res_counts, c->build.M, c->len, asymmetric, rep);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(lint_edges_kernel<Key2>), dim3(grid_for(c->M, 256)), dim3(256), 0, c->stream,
-                               (const Key2*)c->res_keys, (const uint32_t*)c->res_counts, c->M, c->len, asymmetric, rep);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(lint_edges_kernel<Key2>), dim3(grid_for(c->build.M, 256)), dim3(256), 0, c->stream,
+                               (const Key2*)c->build.res_keys, (const uint32_t*)c->build.res_counts, c->build.M, c->len, asymmetric, rep);
         HIP_TRY(hipMemcpyAsync(out, rep, sizeof(LintReport), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->arena.release(mark);
@@ -3354,7 +2860,7 @@ int goss_gpu_trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report
     if (const int st = graph_pass_state(c, "trim_relative", "trim_relative works on a graph", "trim_relative belongs between finish and emit")) return st;
     if (!std::isfinite(rel)) { c->last_error = "trim_relative: the relative cutoff must be a finite number"; return GOSS_ERR_INVALID_ARG; }
     const int rc = guarded(c, [&]() {
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         if (c->words == 1) trim_relative<Key1>(c, rel, out); else trim_relative<Key2>(c, rel, out);
         t.stop();
     });
@@ -3382,8 +2888,7 @@ int goss_gpu_segments_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, gos
     if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind != Held::Segments) { c->last_error = "segments_table needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
     if (first > c->seg_count || count > c->seg_count - first) { c->last_error = "segments_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    return guarded_reading(c, [&]() {
         if (count) HIP_TRY(hipMemcpyAsync(out, (const SegRec*)c->seg_recs + first, count * sizeof(SegRec), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
@@ -3394,8 +2899,7 @@ int goss_gpu_segments_text(goss_gpu_ctx* c, uint64_t text_offset, uint64_t bytes
     if (!c || (bytes && !dst)) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind != Held::Segments) { c->last_error = "segments_text needs goss_gpu_segments_build before it"; return GOSS_ERR_STATE; }
     if (text_offset > c->seg_text_bytes || bytes > c->seg_text_bytes - text_offset) { c->last_error = "segments_text: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    return guarded_reading(c, [&]() {
         if (bytes) HIP_TRY(hipMemcpyAsync(dst, c->seg_text + text_offset, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
@@ -3464,8 +2968,7 @@ int goss_gpu_components_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, g
     if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind != Held::Components || !c->cmp_built) { c->last_error = "components_table needs goss_gpu_components_build before it"; return GOSS_ERR_STATE; }
     if (first > c->cmp_count || count > c->cmp_count - first) { c->last_error = "components_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    return guarded_reading(c, [&]() {
         if (count) HIP_TRY(hipMemcpyAsync(out, (const CompRec*)c->cmp_recs + first, count * sizeof(CompRec), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
@@ -3475,9 +2978,8 @@ int goss_gpu_components_labels(goss_gpu_ctx* c, uint64_t first, uint64_t count, 
 {
     if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind != Held::Components || !c->cmp_built) { c->last_error = "components_labels needs goss_gpu_components_build before it"; return GOSS_ERR_STATE; }
-    if (first > c->M || count > c->M - first) { c->last_error = "components_labels: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    if (first > c->build.M || count > c->build.M - first) { c->last_error = "components_labels: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    return guarded_reading(c, [&]() {
         if (count) HIP_TRY(hipMemcpyAsync(out, c->cmp_labels + first, count * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     });
@@ -3488,7 +2990,7 @@ int goss_gpu_components_keep(goss_gpu_ctx* c, uint64_t edge_rank, uint64_t* kept
     if (!c || !kept) return GOSS_ERR_INVALID_ARG;
     *kept = 0;
     if (const int st = graph_pass_state(c, "components", "a component is kept of a graph", "keeping a component belongs between finish and emit")) return st;
-    if (edge_rank >= c->M) { c->last_error = "components_keep: the graph has no edge of that rank"; return GOSS_ERR_INVALID_ARG; }
+    if (edge_rank >= c->build.M) { c->last_error = "components_keep: the graph has no edge of that rank"; return GOSS_ERR_INVALID_ARG; }
     return guarded(c, [&]() { *kept = components_keep(c, (uint32_t)edge_rank); });
 }
 
@@ -3520,9 +3022,8 @@ int goss_gpu_components_marks(goss_gpu_ctx* c, uint64_t first, uint64_t count, u
 {
     if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
     if (c->held.kind != Held::Components || !c->cmp_marks) { c->last_error = "components_marks needs goss_gpu_components_mark_host / _device before it"; return GOSS_ERR_STATE; }
-    if (first > c->M || count > c->M - first) { c->last_error = "components_marks: a range past the end"; return GOSS_ERR_INVALID_ARG; }
-    c->keep_held = true;
-    return guarded(c, [&]() {
+    if (first > c->build.M || count > c->build.M - first) { c->last_error = "components_marks: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    return guarded_reading(c, [&]() {
         if (!count) return;
         const uint64_t w0 = first / 32, w1 = (first + count + 31) / 32;
         std::vector<uint32_t> words((size_t)(w1 - w0));
@@ -3546,8 +3047,8 @@ int goss_gpu_components_keep_marked(goss_gpu_ctx* c, uint64_t* kept)
         c->last_error = "components_keep_marked needs goss_gpu_components_mark_host / _device before it";
         return GOSS_ERR_STATE;
     }
-    c->keep_held = true;                                 // (the marks are read first; components_keep_marked gives them back)
-    const int rc = guarded(c, [&]() { *kept = components_keep_marked(c); });
+    // (the marks are read first; components_keep_marked gives them back)
+    const int rc = guarded_reading(c, [&]() { *kept = components_keep_marked(c); });
     if (c->held.kind != Held::None) release_held(c);
     return rc;
 }
@@ -3567,7 +3068,7 @@ int goss_gpu_pool_begin(goss_gpu_ctx* c, uint32_t nsets, uint64_t z)
     if (z > ~0ULL / nsets) { c->last_error = "pool_begin: z * nsets does not fit 64 bits"; return GOSS_ERR_INVALID_ARG; }
     // the rows are permanent allocations: between pushes a later merge or an out-of-memory rollback would rewind the
     // permanent end underneath them (the rule of goss_gpu_emit_sparse_array)
-    if (!c->finished && (!c->runs.empty() || c->stage_fill))
+    if (!c->build.finished && (!c->build.runs.empty() || c->stage_fill))
     {
         c->last_error = "pool_begin while a count is in progress (reset or finish first)";
         return GOSS_ERR_STATE;
@@ -3585,33 +3086,29 @@ int goss_gpu_pool_add_masks(goss_gpu_ctx* c, uint32_t first_set, uint32_t nbits,
     if (first_set >= c->pool_sets || nbits > c->pool_sets - first_set) { c->last_error = "pool_add_masks: sets past the end"; return GOSS_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < nbits; ++i)
         if (c->pool_added[first_set + i]) { c->last_error = "pool_add_masks: set " + std::to_string(first_set + i) + " was added before"; return GOSS_ERR_STATE; }
-    c->keep_held = true;
-    return guarded(c, [&]() { pool_add_masks(c, first_set, nbits, d_masks); });
+    return guarded_reading(c, [&]() { pool_add_masks(c, first_set, nbits, d_masks); });
 }
 
 int goss_gpu_pool_sizes(goss_gpu_ctx* c, uint64_t* sizes)
 {
     if (!c || !sizes) return GOSS_ERR_INVALID_ARG;
     if (const int st = pool_state(c, "pool_sizes")) return st;
-    c->keep_held = true;
-    return guarded(c, [&]() { pool_sizes(c, sizes); });
+    return guarded_reading(c, [&]() { pool_sizes(c, sizes); });
 }
 
 int goss_gpu_pool_intersections(goss_gpu_ctx* c, uint64_t* inter)
 {
     if (!c || !inter) return GOSS_ERR_INVALID_ARG;
     if (const int st = pool_state(c, "pool_intersections")) return st;
-    c->keep_held = true;
-    return guarded(c, [&]() { pool_intersections(c, inter); });
+    return guarded_reading(c, [&]() { pool_intersections(c, inter); });
 }
 
 int goss_gpu_pool_emit_index(goss_gpu_ctx* c)
 {
     if (!c) return GOSS_ERR_INVALID_ARG;
     if (const int st = pool_state(c, "pool_emit_index")) return st;
-    c->keep_held = true;
-    const int rc = guarded(c, [&]() { pool_emit_index(c); });
-    if (rc != GOSS_OK) { c->files.clear(); c->arena.lo = c->pool_top; }       // the rows stay; no half-built index does
+    const int rc = guarded_reading(c, [&]() { pool_emit_index(c); });
+    if (rc != GOSS_OK) { c->build.files.clear(); c->arena.lo = c->pool_top; }       // the rows stay; no half-built index does
     return rc;
 }
 
@@ -3625,30 +3122,20 @@ int goss_gpu_pool_release(goss_gpu_ctx* c)
 int goss_gpu_emit_count_bits(goss_gpu_ctx* c, uint32_t mask, const char* suffix)
 {
     if (!c || !suffix || !mask) return GOSS_ERR_INVALID_ARG;
-    if (!c->emitted) { c->last_error = "emit_count_bits follows emit"; return GOSS_ERR_STATE; }
+    if (!c->build.emitted) { c->last_error = "emit_count_bits follows emit"; return GOSS_ERR_STATE; }
     return guarded(c, [&]() {
         // WordyBitVector::Builder after M push_backX calls and end(): floor((M-1)/64)+1 words,
         // one (zero) word when nothing was pushed (WordyBitVector.hh:90-116, .cc:18-29)
-        const uint64_t m = c->M, nwords = m ? (m - 1) / 64 + 1 : 1;
+        const uint64_t m = c->build.M, nwords = m ? (m - 1) / 64 + 1 : 1;
         uint64_t* words = (uint64_t*)c->arena.perm(nwords * 8);
         if (m == 0) HIP_TRY(hipMemsetAsync(words, 0, 8, c->stream));
         else
             hipLaunchKernelGGL(count_bits_kernel, dim3(grid_for((nwords + 63) / 64 * 64, 256)), dim3(256), 0, c->stream,
-                               (const uint32_t*)c->res_counts, m, mask, words, nwords);
+                               (const uint32_t*)c->build.res_counts, m, mask, words, nwords);
         HIP_TRY(hipStreamSynchronize(c->stream));
         OutFile f; f.suffix = suffix; f.size = nwords * 8; f.dev = (const uint8_t*)words;
-        c->files.push_back(std::move(f));
+        c->build.files.push_back(std::move(f));
     });
-}
-
-int goss_gpu_emit_estimate(goss_gpu_ctx* c, uint64_t m_estimate)
-{
-    if (!c) return GOSS_ERR_INVALID_ARG;
-    c->emit_estimate = m_estimate;
-    c->has_emit_estimate = true;
-    int rc = goss_gpu_emit(c);
-    c->has_emit_estimate = false;
-    return rc;
 }
 
 int goss_gpu_synth_reads(goss_gpu_ctx* c, void* d_out, uint64_t nreads, uint32_t read_len, uint64_t genome_len,
@@ -3709,7 +3196,7 @@ int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* c)
     *out = nullptr;
     t_open_error.clear();
     ObjFiles fs;
-    for (auto& f : c->files) fs[f.suffix] = ObjSrc{f.dev ? f.dev : f.host.data(), f.size, f.dev != nullptr};
+    for (auto& f : c->build.files) fs[f.suffix] = ObjSrc{f.dev ? f.dev : f.host.data(), f.size, f.dev != nullptr};
     int kind = -1;
     std::string base;
     if (fs.count(".kmers.header")) kind = GOSS_OBJECT_KMER_SET;
@@ -3718,8 +3205,7 @@ int goss_gpu_object_open_emitted(goss_gpu_object** out, goss_gpu_ctx* c)
     else if (fs.count("-entries.header")) { kind = GOSS_OBJECT_ENTRY_EDGE_SET; base = "-entries"; }
     if (kind < 0) { t_open_error = "the context holds no emitted KmerSet, Graph, SparseArray or EntryEdgeSet"; return GOSS_ERR_STATE; }
     // what the context's stream still writes into its files (the call only reads: what is held stays)
-    c->keep_held = true;
-    int rc = guarded(c, [&]() { HIP_TRY(hipStreamSynchronize(c->stream)); });
+    int rc = guarded_reading(c, [&]() { HIP_TRY(hipStreamSynchronize(c->stream)); });
     if (rc != GOSS_OK) { t_open_error = c->last_error; return rc; }
     return object_open(out, c->device, nullptr, kind, base, fs);
 }
@@ -3800,7 +3286,7 @@ int goss_gpu_recount_from(goss_gpu_ctx* c, goss_gpu_object* ref, goss_gpu_recoun
     if (ref->device != c->device) { c->last_error = "recount_from: the reference lives on another device"; return GOSS_ERR_INVALID_ARG; }
     const int rc = guarded(c, [&]() {
         HIP_TRY(hipStreamSynchronize(ref->stream));      // (what the reference's own stream still does with its images)
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         if (c->words == 1) recount_from<Key1>(c, ref->q, out); else recount_from<Key2>(c, ref->q, out);
         t.stop();
     });

@@ -60,8 +60,8 @@ struct NothingQueued { template <class... A> void operator()(A&&...) const {} };
 int graph_pass_state(goss_gpu_ctx* c, const char* who, const char* not_a_graph, const char* out_of_place)
 {
     if (c->mode != GOSS_MODE_GRAPH) { c->last_error = not_a_graph; return GOSS_ERR_STATE; }
-    if (!c->finished || c->emitted) { c->last_error = out_of_place; return GOSS_ERR_STATE; }
-    if (!c->res_big.empty())
+    if (!c->build.finished || c->build.emitted) { c->last_error = out_of_place; return GOSS_ERR_STATE; }
+    if (!c->build.res_big.empty())
     {
         c->last_error = std::string(who) + ": the graph has multiplicities of 2^32 - 1 or more";
         return GOSS_ERR_INVALID_ARG;
@@ -78,14 +78,14 @@ template <class Info, class F>
 int build_held(goss_gpu_ctx* c, Held kind, Info* out, F&& body, bool extend = false)
 {
     bool began = false;
-    c->keep_held = extend;
-    const int rc = guarded(c, [&]() {
+    auto build = [&]() {
         if (!extend) c->held = {kind, c->arena.lo};
         began = true;
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         body();
         t.stop();
-    });
+    };
+    const int rc = extend ? guarded_reading(c, build) : guarded(c, build);
     if (rc != GOSS_OK)
     {
         if (began) release_held(c);
@@ -109,9 +109,9 @@ uint32_t tips_bucket_bits(uint64_t n, uint32_t len)
 // The edges of the result as the 32-bit number the link arrays rank them by, or the refusal.
 uint32_t link_edges(const goss_gpu_ctx* c, const char* who)
 {
-    if (c->M >= 0xFFFFFFFFULL)
+    if (c->build.M >= 0xFFFFFFFFULL)
         throw StatusError{GOSS_ERR_INVALID_ARG, std::string(who) + ": the link arrays hold 32-bit ranks; this graph has 2^32 - 1 edges or more"};
-    return (uint32_t)c->M;
+    return (uint32_t)c->build.M;
 }
 
 inline uint64_t link_table_bytes(uint32_t bits) { return bits ? ((1ULL << bits) + 1) * 4 : 0; }
@@ -141,8 +141,8 @@ template <class K, class F = NothingQueued>
 GraphLinks<K> link_graph(goss_gpu_ctx* c, const char* who, TipsReport* report = nullptr, F&& before_wait = F())
 {
     GraphLinks<K> l{};
-    l.keys = (const K*)c->res_keys;
-    l.counts = c->res_counts;
+    l.keys = (const K*)c->build.res_keys;
+    l.counts = c->build.res_counts;
     l.n = link_edges(c, who);
     l.bits = tips_bucket_bits(l.n, c->len);
     const uint64_t n64 = l.n;
@@ -262,19 +262,19 @@ void replace_result(goss_gpu_ctx* c, const K* keys, const uint32_t* counts, uint
                     uint64_t ntiles, uint64_t m)
 {
     const uint64_t kb = std::max<uint64_t>(m * sizeof(K), 16), cb = std::max<uint64_t>(m * 4, 16);
-    const bool own = c->tips_keys && c->res_keys == c->tips_keys && c->res_counts == c->tips_counts;
+    const bool own = c->build.tips_keys && c->build.res_keys == c->build.tips_keys && c->build.res_counts == c->build.tips_counts;
     K* okeys = (K*)(own ? c->arena.temp(kb) : c->arena.perm(kb));
     uint32_t* ocounts = (uint32_t*)(own ? c->arena.temp(cb) : c->arena.perm(cb));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(tips_keep_write_kernel<K>), dim3((uint32_t)ntiles), dim3(kTB), 0, c->stream, keys, counts, n64, zap,
                        tile_offsets, okeys, ocounts);
     if (own)
     {
-        if (m) HIP_TRY(hipMemcpyAsync(c->tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
-        if (m) HIP_TRY(hipMemcpyAsync(c->tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (m) HIP_TRY(hipMemcpyAsync(c->build.tips_keys, okeys, m * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+        if (m) HIP_TRY(hipMemcpyAsync(c->build.tips_counts, ocounts, m * 4, hipMemcpyDeviceToDevice, c->stream));
     }
     sync_checked(c);
-    if (!own) { c->tips_keys = okeys; c->tips_counts = ocounts; c->res_keys = okeys; c->res_counts = ocounts; }
-    c->M = m;
+    if (!own) { c->build.tips_keys = okeys; c->build.tips_counts = ocounts; c->build.res_keys = okeys; c->build.res_counts = ocounts; }
+    c->build.M = m;
 }
 
 // One iteration of prune-tips over the result (GossCmdPruneTips.cc:279-319).  Nothing of the context changes
@@ -284,7 +284,7 @@ void prune_tips_once(goss_gpu_ctx* c, goss_gpu_tips_report* out)
 {
     static_assert(sizeof(goss_gpu_tips_report) == 11 * 8 && sizeof(TipsReport) == 13 * 8, "tips report layout");
     goss_gpu_tips_report rep{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     rep.edges_before = rep.edges_after = n64;
     if (out) *out = rep;
     if (n64 == 0) return;
@@ -339,7 +339,7 @@ void prune_tips(goss_gpu_ctx* c, uint32_t iterations, goss_gpu_tips_report* repo
 {
     for (uint32_t it = 0; it < iterations; ++it)
     {
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         goss_gpu_tips_report* r = reports ? reports + it : nullptr;
         if (c->words == 1) prune_tips_once<Key1>(c, r); else prune_tips_once<Key2>(c, r);
         t.stop();
@@ -360,7 +360,7 @@ template <class K, class Rule>
 PathsOutcome paths_pass(goss_gpu_ctx* c, const char* who, bool forks, Rule rule, uint64_t* missing)
 {
     PathsOutcome o{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     o.before = o.after = n64;
     if (n64 == 0) return o;
     const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
@@ -472,7 +472,7 @@ int paths_entry(goss_gpu_ctx* c, R* out, const char* who, const char* not_a_grap
     out->missing_rc = GOSS_PATHS_NO_EDGE;
     if (const int st = graph_pass_state(c, who, not_a_graph, out_of_place)) return st;
     const int rc = guarded(c, [&]() {
-        PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+        PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
         pass();
         t.stop();
     });
@@ -494,7 +494,7 @@ void segments_build(goss_gpu_ctx* c, uint64_t min_length, uint64_t min_coverage,
 {
     static_assert(sizeof(goss_gpu_segment) == sizeof(SegRec) && sizeof(SegRec) == 64, "segment layout");
     goss_gpu_segments_info inf{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     if (n64 == 0) { *out = inf; return; }
     const uint32_t Kn = c->k;
     const uint32_t line = (flags & GOSS_SEGMENTS_NO_LINE_BREAKS) ? 0u : 60u;
@@ -590,7 +590,7 @@ template <class K>
 void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
 {
     goss_gpu_entries_info inf{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     inf.walk_steps = contigs_walk_steps();
     {
         // the links, the ranking with its weights, the scan (8): 55 bytes per edge and the table; then per entry the
@@ -665,7 +665,7 @@ void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
         for (size_t i = 0; i < cols.size() && i < 2; ++i)
         {
             OutFile f; f.suffix = cols[i].suffix; f.size = nent * cols[i].bytes; f.dev = img[i];
-            c->files.push_back(std::move(f));
+            c->build.files.push_back(std::move(f));
         }
     }
     const uint64_t hdr[2] = {2011041901ULL, c->k};
@@ -679,7 +679,7 @@ void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
 
 void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
 {
-    c->files.clear();
+    c->build.files.clear();
     if (c->words == 1) entries_build<Key1>(c, out); else entries_build<Key2>(c, out);
 }
 
@@ -728,7 +728,7 @@ void components_mark(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, bool o
     uint32_t* table = bits ? (uint32_t*)c->arena.temp(link_table_bytes(bits)) : nullptr;
     CompReport* d_rep = (CompReport*)c->arena.temp(sizeof(CompReport));
     CompReport* h = pinned_report<CompReport>(c);
-    const K* keys = (const K*)c->res_keys;
+    const K* keys = (const K*)c->build.res_keys;
     const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
     HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(CompReport), c->stream));
     HIP_TRY(hipEventRecord(ev.e[0], c->stream));
@@ -778,7 +778,7 @@ void components_build(goss_gpu_ctx* c, uint32_t flags, goss_gpu_components_info*
 {
     static_assert(sizeof(goss_gpu_component) == sizeof(CompRec), "component layout");
     goss_gpu_components_info inf{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     const uint32_t* marks = (flags & GOSS_COMPONENTS_MARKED) ? c->cmp_marks : nullptr;
     c->cmp_built = true;
     if (n64 == 0) { *out = inf; return; }
@@ -841,7 +841,7 @@ void components_build(goss_gpu_ctx* c, uint32_t flags, goss_gpu_components_info*
 template <class K>
 uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
 {
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
     const uint64_t zap_words = ntiles * (kRedTile / 32);
     static_assert(kRedTile % 64 == 0, "a wave writes 64 bits of the bitmap");
@@ -868,7 +868,7 @@ uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
 
 uint64_t components_keep(goss_gpu_ctx* c, uint32_t e)
 {
-    PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+    PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
     const uint64_t m = c->words == 1 ? components_keep<Key1>(c, e) : components_keep<Key2>(c, e);
     t.stop();
     return m;
@@ -889,7 +889,7 @@ void components_grow(goss_gpu_ctx* c, uint32_t radius, uint32_t flags, uint64_t*
 {
     goss_gpu_grow_info inf{};
     const bool linear = (flags & GOSS_GROW_LINEAR_PATHS) != 0;
-    const uint64_t n64 = c->M, words = c->cmp_mark_words;
+    const uint64_t n64 = c->build.M, words = c->cmp_mark_words;
     inf.marked_before = inf.mirrored = inf.marked_total = c->cmp_marked;
     if (n64 == 0) { *out = inf; return; }
     {
@@ -998,7 +998,7 @@ void components_grow(goss_gpu_ctx* c, uint32_t radius, uint32_t flags, uint64_t*
 template <class K>
 uint64_t components_keep_marked(goss_gpu_ctx* c)
 {
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     const uint64_t ntiles = (n64 + kRedTile - 1) / kRedTile;
     const uint64_t zap_words = ntiles * (kRedTile / 32);
     {
@@ -1018,13 +1018,13 @@ uint64_t components_keep_marked(goss_gpu_ctx* c)
     scan_with_total(c, tile_counts, ntiles, hm);
     sync_checked(c);
     const uint64_t m = hm[0];
-    if (m != n64) replace_result<K>(c, (const K*)c->res_keys, c->res_counts, n64, zap, tile_counts, ntiles, m);
+    if (m != n64) replace_result<K>(c, (const K*)c->build.res_keys, c->build.res_counts, n64, zap, tile_counts, ntiles, m);
     return m;
 }
 
 uint64_t components_keep_marked(goss_gpu_ctx* c)
 {
-    PhaseTimer t(c, GOSS_T_REDUCE, c->M);
+    PhaseTimer t(c, GOSS_T_REDUCE, c->build.M);
     const uint64_t m = c->words == 1 ? components_keep_marked<Key1>(c) : components_keep_marked<Key2>(c);
     t.stop();
     return m;
@@ -1047,14 +1047,14 @@ inline RelativeBitmaps relative_bitmaps(uint64_t n64)
 template <class K>
 uint64_t relative_compact(goss_gpu_ctx* c, const uint32_t* counts, const uint32_t* zap, const RelativeBitmaps& b, bool new_counts)
 {
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     uint64_t* tile_counts = (uint64_t*)c->arena.temp((b.ntiles + 1) * 8);
     hipLaunchKernelGGL(tips_keep_count_kernel, dim3((uint32_t)b.ntiles), dim3(kTB), 0, c->stream, zap, n64, tile_counts);
     uint64_t* hm = pinned_words(c);
     scan_with_total(c, tile_counts, b.ntiles, hm);
     sync_checked(c);
     const uint64_t m = hm[0];
-    if (m != n64 || new_counts) replace_result<K>(c, (const K*)c->res_keys, counts, n64, zap, tile_counts, b.ntiles, m);
+    if (m != n64 || new_counts) replace_result<K>(c, (const K*)c->build.res_keys, counts, n64, zap, tile_counts, b.ntiles, m);
     return m;
 }
 
@@ -1067,7 +1067,7 @@ void trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
 {
     static_assert(sizeof(goss_gpu_relative_report) == 5 * 8 && sizeof(RelativeReport) <= 128, "relative report layout");
     goss_gpu_relative_report rep{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     rep.edges_before = rep.edges_after = n64;
     for (float& x : c->relative_ms) x = 0.f;
     if (n64 == 0) { *out = rep; return; }
@@ -1080,7 +1080,7 @@ void trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
     }
     ArenaScope scope(c->arena);
     EventPair ev;
-    const K* keys = (const K*)c->res_keys;
+    const K* keys = (const K*)c->build.res_keys;
     uint32_t* below = (uint32_t*)c->arena.temp(b.zap_words * 4);
     uint32_t* zap = (uint32_t*)c->arena.temp(b.zap_words * 4);
     RelativeReport* d_rep = (RelativeReport*)c->arena.temp(sizeof(RelativeReport));
@@ -1091,7 +1091,7 @@ void trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
     HIP_TRY(hipMemsetAsync(below, 0, b.zap_words * 4, c->stream));
     HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(RelativeReport), c->stream));
     HIP_TRY(hipMemsetAsync(&d_rep->bad, 0xFF, 8, c->stream));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_judge_kernel<K>), few, block, 0, c->stream, keys, (const uint32_t*)c->res_counts, n64, rel, below, d_rep);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_judge_kernel<K>), few, block, 0, c->stream, keys, (const uint32_t*)c->build.res_counts, n64, rel, below, d_rep);
     HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(RelativeReport), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(ev.e[1], c->stream));
     sync_checked(c);
@@ -1113,7 +1113,7 @@ void trim_relative(goss_gpu_ctx* c, double rel, goss_gpu_relative_report* out)
     if (h->bad != kRelativeNoEdge)
         throw StatusError{GOSS_ERR_INVALID_ARG, "trim_relative: edge " + std::to_string(h->bad) +
                                                     " has no reverse complement in the graph (lint-graph reports such edges)"};
-    const uint64_t m = relative_compact<K>(c, c->res_counts, zap, b, false);
+    const uint64_t m = relative_compact<K>(c, c->build.res_counts, zap, b, false);
     HIP_TRY(hipEventRecord(ev.e[3], c->stream));
     sync_checked(c);
     HIP_TRY(hipEventElapsedTime(&c->relative_ms[1], ev.e[1], ev.e[2]));
@@ -1130,7 +1130,7 @@ template <class K>
 void recount_from(goss_gpu_ctx* c, const QueryObj& q, goss_gpu_recount_report* out)
 {
     goss_gpu_recount_report rep{};
-    const uint64_t n64 = c->M;
+    const uint64_t n64 = c->build.M;
     rep.edges_before = rep.edges_after = n64;
     for (float& x : c->relative_ms) x = 0.f;
     if (n64 == 0) { *out = rep; return; }
@@ -1150,7 +1150,7 @@ void recount_from(goss_gpu_ctx* c, const QueryObj& q, goss_gpu_recount_report* o
     HIP_TRY(hipEventRecord(ev.e[0], c->stream));
     HIP_TRY(hipMemsetAsync(absent, 0, b.zap_words * 4, c->stream));
     HIP_TRY(hipMemsetAsync(d_rep, 0xFF, sizeof(RelativeReport), c->stream));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_recount_kernel<K>), few, block, 0, c->stream, q, (const K*)c->res_keys, n64, counts, absent, d_rep);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(relative_recount_kernel<K>), few, block, 0, c->stream, q, (const K*)c->build.res_keys, n64, counts, absent, d_rep);
     HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(RelativeReport), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(ev.e[1], c->stream));
     sync_checked(c);

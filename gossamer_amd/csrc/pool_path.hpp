@@ -75,7 +75,7 @@ void pool_emit_index(goss_gpu_ctx* c)
 {
     const uint32_t S = c->pool_sets;
     const uint64_t z = c->pool_z, W = pool_words(z);
-    c->files.clear();
+    c->build.files.clear();
     c->arena.lo = c->pool_top;             // an earlier index goes
     const uint64_t nblk = (W + kPoolPosWords - 1) / kPoolPosWords, nunits = nblk * S;
     if (nunits >= (1ULL << 36)) throw StatusError{GOSS_ERR_INVALID_ARG, "pool_emit_index: rows too long for one launch"};

@@ -260,6 +260,9 @@ int goss_gpu_timing_reset(goss_gpu_ctx* ctx);
  * Forget everything counted so far but keep the HBM arena, the stream and (k, mode):
  * the context can then be used for a new build.  Role of BackyardHash::clear()
  * (GossCmdBuildKmerSet.tcc:288).
+ * What the context took from GOSS_GPU_* when it was created stays as well, and so does a counting form that an
+ * earlier build demoted because it did not fit its input (a table that overflowed, tiles that had to take tickets):
+ * the next build starts from the demoted form.  The counters of goss_gpu_stat and the timing run on.
  */
 int goss_gpu_reset(goss_gpu_ctx* ctx);
 
@@ -489,7 +492,10 @@ int goss_gpu_set_budget_limit(goss_gpu_ctx* ctx, uint64_t max_bytes);
 /*
  * Diagnostic counters of the context, by name: "fused_chunks" (chunks counted by the extraction
  * that partitions), "fused_overflows" (chunks redone unfused because a bucket region was too
- * small), "segment_retries", "lookback_failures", "runs".
+ * small), "segment_retries", "lookback_failures", "runs"; the full list is stat_table in
+ * gossamer_amd/csrc/goss_knobs.hpp, besides "runs" and "arena_bytes".  The counters are cumulative over
+ * goss_gpu_reset: a context that served several builds reports their sum (or, for a "last" figure, the latest).
+ * GOSS_ERR_INVALID_ARG for a name that is not known.
  */
 int goss_gpu_stat(goss_gpu_ctx* ctx, const char* name, uint64_t* value);
 

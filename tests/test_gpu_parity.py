@@ -162,6 +162,56 @@ def test_empty_and_degenerate_inputs(oracle):
             assert got[name] == exp[name], name
 
 
+def test_reset_starts_a_second_build_and_counters_run_on():
+    """One context, two builds with goss_gpu_reset between them: the second build's files are the first's, byte for
+    byte, and a fresh context's; the counters of goss_gpu_stat are not reset with the build ("flushes" doubles).  Then the
+    same with a held result in the way: a graph whose segments are built and read before the reset."""
+    reads = g.synth_reads_host(3000, 150, 20000, seed=17)
+
+    def build(ctx):
+        ctx.push_host(reads)
+        return ctx.finish()
+
+    with g.Context(25, g.MODE_KMER_SET, hbm_budget=256 * MB) as fresh:
+        c0 = build(fresh)
+        exp = fresh.emit()
+    assert c0.distinct > 0 and len(exp) > 3
+    with g.Context(25, g.MODE_KMER_SET, hbm_budget=256 * MB) as ctx:
+        c1 = build(ctx)
+        first = ctx.emit()
+        flushes1 = ctx.stat("flushes")
+        ctx.reset()
+        assert ctx.files() == {} and ctx.stat("runs") == 0
+        c2 = build(ctx)
+        second = ctx.emit()
+        assert (c1.windows, c1.keys, c1.distinct) == (c0.windows, c0.keys, c0.distinct) == (c2.windows, c2.keys, c2.distinct)
+        assert first == exp and second == exp
+        assert flushes1 > 0 and ctx.stat("flushes") == 2 * flushes1
+
+    with g.Context(27, g.MODE_GRAPH, hbm_budget=256 * MB) as fresh:
+        c0 = build(fresh)
+        exp = fresh.emit()
+    with g.Context(27, g.MODE_GRAPH, hbm_budget=256 * MB) as ctx:
+        c1 = build(ctx)
+        info1 = ctx.segments_build()
+        table1 = ctx.segments_table(0, info1["segments"])          # (a read: what is held stays)
+        text1 = ctx.segments_text(0, info1["text_bytes"])
+        flushes1 = ctx.stat("flushes")
+        ctx.reset()                                                 # (gives the segments back with everything else)
+        assert ctx.files() == {} and ctx.stat("runs") == 0
+        c2 = build(ctx)
+        info2 = ctx.segments_build()
+        figures = lambda info: {n: v for n, v in info.items() if not n.startswith("ms_")}
+        assert figures(info2) == figures(info1) and info1["segments"] > 0
+        assert ctx.segments_table(0, info2["segments"]).tobytes() == table1.tobytes()
+        assert ctx.segments_text(0, info2["text_bytes"]) == text1
+        ctx.segments_release()
+        second = ctx.emit()
+        assert (c1.windows, c1.keys, c1.distinct) == (c0.windows, c0.keys, c0.distinct) == (c2.windows, c2.keys, c2.distinct)
+        assert second == exp
+        assert flushes1 > 0 and ctx.stat("flushes") == 2 * flushes1
+
+
 def _sparse_case(oracle, positions, N, M, words):
     import torch
     exp = _suffix_map(oracle.write_sparse_array(positions, N, M, base="sa"), "sa")

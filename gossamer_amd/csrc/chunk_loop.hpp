@@ -9,7 +9,7 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
 {
     const uint32_t S = c->mode == GOSS_MODE_GRAPH ? 2 : 1;
     const uint64_t cap = nstarts * S;              // upper bound on keys
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     // the fused path wants room for its bucket regions (expected keys + slack): up to cap/8 more
     // slots in the first buffer when the arena can spare them beyond the two buffers and the
     // partition / segment tables
@@ -42,21 +42,17 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
     K* ka = (K*)c->arena.temp(ka_slots * sizeof(K));
     K* kb = (K*)c->arena.temp(kb_slots * sizeof(K));
     int frc = process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots);
-    if (frc == kFusedDone) { if (reduced) c->stats.valid_sized_chunks++; c->arena.release(mark); return; }
+    if (frc == kFusedDone) { if (reduced) c->stats.valid_sized_chunks++; return; }
     if (reduced)
     {
         c->stats.valid_resizes++;
         // the unfused kernels (and a fused retry) want one slot per window start
-        c->arena.release(mark);
+        scope.rewind();
         c->valid_frac = 1.0;
         full_slots(cap);
         ka = (K*)c->arena.temp(ka_slots * sizeof(K));
         kb = (K*)c->arena.temp(kb_slots * sizeof(K));
-        if (frc == kFusedNeedFull && process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots) == kFusedDone)
-        {
-            c->arena.release(mark);
-            return;
-        }
+        if (frc == kFusedNeedFull && process_chunk_fused<K>(c, src, nstarts, navail, ka, ka_slots, kb, kb_slots) == kFusedDone) return;
     }
     HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(ExtractCounters), c->stream));
     {
@@ -78,7 +74,6 @@ void process_chunk(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint64
     }
     c->build.windows += nwin;           // only once the chunk has succeeded (it may be retried)
     c->build.keys_total += n;
-    c->arena.release(mark);
 }
 
 // Largest number of window starts one chunk may cover with the memory currently free.
@@ -188,7 +183,7 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
         }
         const uint64_t ns = std::min(capn, nstarts_total - done);          // (a multiple of 4096 slots = whole records, but for the last)
         const uint64_t navail = recs ? 0 : std::min(n - done, ns + c->len - 1);
-        const uint64_t lo0 = c->arena.lo, hi0 = c->arena.hi;
+        const uint64_t lo0 = c->arena.lo;
         const size_t runs0 = c->build.runs.size();
         // (behind this chunk of a base string: the rest of this push and what the push's own caller has said lies behind
         // IT; a push of records leaves the figure as it is)
@@ -202,7 +197,7 @@ void push_source(goss_gpu_ctx* c, const ReadSrc& src, uint64_t n, uint64_t nwind
             if (e.status != GOSS_ERR_OOM || ns <= 8192) throw;
             // undo the partial chunk; retry it in a larger arena if the budget may grow, else in halves
             HIP_TRY(hipStreamSynchronize(c->stream));
-            c->arena.lo = lo0; c->arena.hi = hi0;
+            c->arena.lo = lo0;               // (the temporaries went with process_chunk's scope)
             c->build.runs.resize(runs0);
             if (grow_arena(c, 0)) continue;
             limit = (ns / 2) & ~4095ULL;

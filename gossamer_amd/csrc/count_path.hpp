@@ -16,14 +16,30 @@ void exclusive_scan_u64(goss_gpu_ctx* c, uint64_t* a, uint64_t n)
         hipLaunchKernelGGL(scan_apply_kernel, dim3(1), dim3(kTB), 0, c->stream, a, n, (const uint64_t*)nullptr);
         return;
     }
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     uint64_t* partial = (uint64_t*)c->arena.temp(nchunks * 8);
     hipLaunchKernelGGL(scan_reduce_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, c->stream, (const uint64_t*)a, n, partial);
     exclusive_scan_u64(c, partial, nchunks);
     hipLaunchKernelGGL(scan_apply_kernel, dim3(grid_for(n, kScanChunk)), dim3(kTB), 0, c->stream, a, n, (const uint64_t*)partial);
     // the stream orders the kernels; the scratch can be reused by later launches on the
-    // same stream once released
-    c->arena.release(mark);
+    // same stream once the scope has given it back
+}
+
+// a[0, n) becomes its exclusive prefix sums and a[n] their total, which is on its way to *total (pinned) when this
+// returns: the caller's next synchronisation delivers it.
+inline void scan_with_total(goss_gpu_ctx* c, uint64_t* a, uint64_t n, uint64_t* total)
+{
+    HIP_TRY(hipMemsetAsync(a + n, 0, 8, c->stream));
+    exclusive_scan_u64(c, a, n + 1);
+    HIP_TRY(hipMemcpyAsync(total, a + n, 8, hipMemcpyDeviceToHost, c->stream));
+}
+// ... for the caller that needs the number at once: through the first pinned word, waited for
+inline uint64_t scan_total(goss_gpu_ctx* c, uint64_t* a, uint64_t n)
+{
+    uint64_t* h = (uint64_t*)c->h_pinned;
+    scan_with_total(c, a, n, h);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return h[0];
 }
 
 // ---- LSD radix sort -------------------------------------------------------------------
@@ -62,7 +78,7 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
     if (n < 2) return false;
     constexpr int tile = SortCfg<K, HAS_VAL>::kTile;
     const uint64_t ntiles = (n + tile - 1) / tile;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     bool in_b = false;
     // the per-tile table (classic passes) and the look-back status words share one buffer
     uint64_t* table = (uint64_t*)c->arena.temp(256ULL * ntiles * 8);
@@ -146,7 +162,6 @@ bool radix_sort(goss_gpu_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, uint6
         in_b = !in_b;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arena.release(mark);
     return in_b;
 }
 
@@ -161,14 +176,13 @@ struct Saturated { uint64_t n = 0; std::vector<uint64_t> at; std::vector<std::pa
 static Saturated find_saturated(goss_gpu_ctx* c, const void* keys, const uint32_t* counts, uint64_t m)
 {
     Saturated s;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     unsigned long long* found = (unsigned long long*)c->arena.temp((kMaxBig + 1) * 8);
     HIP_TRY(hipMemsetAsync(found, 0, 8, c->stream));
     hipLaunchKernelGGL(find_saturated_kernel, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, counts, m, found, kMaxBig);
     std::vector<unsigned long long> hfound(kMaxBig + 1);
     HIP_TRY(hipMemcpyAsync(hfound.data(), found, (kMaxBig + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arena.release(mark);
     s.n = hfound[0];
     const uint32_t nq = (uint32_t)std::min<unsigned long long>(hfound[0], kMaxBig);
     for (uint32_t q = 0; q < nq; ++q)
@@ -190,7 +204,7 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
     HIP_TRY(hipMemcpyAsync(hf, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!hf[0]) return;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     const Saturated sat = find_saturated(c, out.keys, out.counts, out.m);
     if (sat.n > kMaxBig) throw StatusError{GOSS_ERR_COUNT_OVERFLOW, "more than 256 keys occurred 2^32 times or more"};
     const uint32_t nruns = (uint32_t)run_off.size() - 1;
@@ -237,7 +251,6 @@ void resolve_big_counts(goss_gpu_ctx* c, Run& out, const K* keys, const uint32_t
         out.big = (int)c->build.big_maps.size() - 1;
     }
     HIP_TRY(hipMemsetAsync(c->d_flags, 0, 4, c->stream));
-    c->arena.release(mark);
 }
 
 // A pushed run that reaches the result through no merge (it was the only one): its entries 0xFFFFFFFF are the
@@ -264,18 +277,12 @@ Run reduce_runs(goss_gpu_ctx* c, const K* keys, const uint32_t* vals, uint64_t n
 {
     Run r{nullptr, nullptr, 0};
     if (n == 0) return r;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     const uint64_t ntiles = (n + kRedTile - 1) / kRedTile;
     uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_count_kernel<K>), dim3(grid_for(n, kRedTile)), dim3(kTB), 0, c->stream,
                        keys, n, tile_counts);
-    // total = last offset + last count: append a zero element and scan ntiles+1 entries
-    HIP_TRY(hipMemsetAsync(tile_counts + ntiles, 0, 8, c->stream));
-    exclusive_scan_u64(c, tile_counts, ntiles + 1);
-    uint64_t* h = (uint64_t*)c->h_pinned;
-    HIP_TRY(hipMemcpyAsync(h, tile_counts + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t m = h[0];
+    const uint64_t m = scan_total(c, tile_counts, ntiles);
     uint64_t* starts = (uint64_t*)c->arena.temp(m * 8);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_write_kernel<K>), dim3(grid_for(n, kRedTile)), dim3(kTB), 0, c->stream,
                        keys, n, (const uint64_t*)tile_counts, scratch_keys, starts);
@@ -290,9 +297,8 @@ Run reduce_runs(goss_gpu_ctx* c, const K* keys, const uint32_t* vals, uint64_t n
     else
         hipLaunchKernelGGL(run_lengths_kernel, dim3(grid_for(m, 256)), dim3(256), 0, c->stream,
                            (const uint64_t*)starts, m, n, r.counts, c->d_flags);
-    HIP_TRY(hipStreamSynchronize(c->stream));   // temporaries are released below
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the temporaries go with the scope
     resolve_big_counts<K>(c, r, keys, vals, std::vector<uint64_t>{0, n}, in_bigs ? *in_bigs : std::vector<int>());
-    c->arena.release(mark);
     return r;
 }
 
@@ -542,7 +548,7 @@ template <class K>
 uint64_t count_distinct_sample(goss_gpu_ctx* c, const K* keys, uint64_t s)
 {
     if (s < 2) return s;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     K* a = (K*)c->arena.temp(s * sizeof(K));
     K* b = (K*)c->arena.temp(s * sizeof(K));
     HIP_TRY(hipMemcpyAsync(a, keys, s * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
@@ -557,14 +563,7 @@ uint64_t count_distinct_sample(goss_gpu_ctx* c, const K* keys, uint64_t s)
     uint64_t* tile_counts = (uint64_t*)c->arena.temp((ntiles + 1) * 8);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_count_kernel<K>), dim3(grid_for(s, kRedTile)), dim3(kTB), 0, c->stream,
                        (const K*)(in_b ? b : a), s, tile_counts);
-    HIP_TRY(hipMemsetAsync(tile_counts + ntiles, 0, 8, c->stream));
-    exclusive_scan_u64(c, tile_counts, ntiles + 1);
-    uint64_t* h = (uint64_t*)c->h_pinned;
-    HIP_TRY(hipMemcpyAsync(h, tile_counts + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t d = h[0];
-    c->arena.release(mark);
-    return d;
+    return scan_total(c, tile_counts, ntiles);
 }
 
 // Number of equally likely keys M from which s draws show d distinct ones: the root of
@@ -606,7 +605,7 @@ uint64_t spectrum_estimate(goss_gpu_ctx* c, const K* keys, uint64_t avail, doubl
     uint32_t q = 1;
     while ((scan / q) > (3u << 20) && q < (1u << 16)) q <<= 1;          // 1.5 to 3 M keys survive
     const uint64_t cap = scan / q + scan / q / 4 + (1u << 16);
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     K* a = (K*)c->arena.temp(cap * sizeof(K));
     K* b = (K*)c->arena.temp(cap * sizeof(K));
     unsigned long long* ctr = (unsigned long long*)c->arena.temp(64);
@@ -651,7 +650,6 @@ uint64_t spectrum_estimate(goss_gpu_ctx* c, const K* keys, uint64_t avail, doubl
             std::fprintf(stderr, "libgossgpu: spectrum of 1/%u of the key space over %llu keys (p = %.4f): d %.0f f1 %.0f f2 %.0f f3 %.0f -> plain %llu, fitted %.0f, estimate %llu\n",
                          q, (unsigned long long)scan, p, d, f1, f2, f3, (unsigned long long)plain, model * scale_q, (unsigned long long)est);
     }
-    c->arena.release(mark);
     return est;
 }
 
@@ -666,7 +664,7 @@ uint64_t estimate_distinct(goss_gpu_ctx* c, const K* keys, uint64_t n)
 
 // The staging area of a segment pass -- a kernel counts or merges every unit (a segment, or one of the 2^rounds shares of
 // one) into `keys` / `counts` at the cursor of the device's SegOut, and notes where (`pos`) and how many (`cnt`) -- with
-// its bookkeeping: taken from the arena under the caller's mark, read back, and gathered in unit order into a run.
+// its bookkeeping: taken from the arena under the caller's scope, read back, and gathered in unit order into a run.
 template <class K>
 struct SegStage {
     goss_gpu_ctx* c;
@@ -742,7 +740,10 @@ int count_overflowed_units(SegStage<K>& st, const uint64_t* d_beg, const uint64_
     // cost half a millisecond of launches and waits each
     const uint64_t need = total * (3 * sizeof(K) + 16) + units.size() * (2 * sizeof(K) + 16) + (64ULL << 20);
     if (c->arena.avail() < need) return 1;
-    const uint64_t mark = c->arena.mark(), lo0 = c->arena.lo;
+    ArenaScope scope(c->arena);
+    // the permanent end is put back on every way out, an exception included: r's permanent blocks are only a stopover
+    // on the way into the staging area
+    Scoped<uint64_t> perm_end(&c->arena.lo, c->arena.lo);
     const size_t maps0 = c->build.big_maps.size();
     K* a = (K*)c->arena.temp(total * sizeof(K));
     K* b = (K*)c->arena.temp(total * sizeof(K));
@@ -790,17 +791,15 @@ int count_overflowed_units(SegStage<K>& st, const uint64_t* d_beg, const uint64_
         if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: %u segment(s) with more distinct keys than a table holds counted by sort (%llu keys, %llu distinct)\n",
                                    nu, (unsigned long long)total, (unsigned long long)r.m);
     }
-    c->arena.lo = lo0;               // (the run's storage: it lives on in the staging area)
-    c->arena.release(mark);
     return rc;
 }
 
 // How segment_reduce and segment_reduce32 end once their kernel's SegOut is read: tables that overflowed and nothing
 // else go by sort where the form allows it (`by_sort`; `expand` and `unit_low` as count_overflowed_units takes them);
 // what overflow is left is the answer -- 1 a table, 2 the staging area -- and else the staged entries become *out.
-// Stops the caller's timer and releases its mark either way.
+// Stops the caller's timer either way; the caller's scope gives the temporaries back.
 template <class K, class Expand, class UnitLow>
-int finish_segments(SegStage<K>& st, bool by_sort, const uint64_t* seg_beg, const uint64_t* seg_end, PhaseTimer& t, uint64_t mark, Run* out,
+int finish_segments(SegStage<K>& st, bool by_sort, const uint64_t* seg_beg, const uint64_t* seg_end, PhaseTimer& t, Run* out,
                     Expand expand, UnitLow unit_low)
 {
     goss_gpu_ctx* c = st.c;
@@ -810,13 +809,11 @@ int finish_segments(SegStage<K>& st, bool by_sort, const uint64_t* seg_beg, cons
     {
         const int why = (st.h.overflow & 1u) ? 1 : 2;
         t.stop();
-        c->arena.release(mark);
         return why;
     }
     st.gather(out);
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arena.release(mark);
     return 0;
 }
 
@@ -831,7 +828,7 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
     const uint32_t shift = keybits - segbits;
     const uint32_t nseg = 1u << segbits;
     const uint32_t nunit = nseg << how.rounds;      // (segment, round) units of the staging area
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     PhaseTimer t(c, GOSS_T_REDUCE, n);
     uint64_t* seg_off = (uint64_t*)c->arena.temp(((uint64_t)nseg + 1) * 8);
     SegStage<K> st(c, nunit, spare, n);
@@ -845,7 +842,7 @@ int segment_reduce(goss_gpu_ctx* c, K* part, K* spare, uint64_t n, uint32_t segb
     check_launch("segment counting kernel");
     st.read();
     // (by sort: not the forms in which several workgroups share a segment, whose units are not ranges of `part`)
-    return finish_segments(st, how.rounds == 0, seg_beg, seg_end, t, mark, out,
+    return finish_segments(st, how.rounds == 0, seg_beg, seg_end, t, out,
         [&](uint32_t u, uint64_t first, uint64_t cnt_u, K* dst) {
             if constexpr (std::is_same<K, Key2>::value)
             {
@@ -878,7 +875,6 @@ int segment_count(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n, uint32_t segbits, b
     const uint32_t keybits = 2 * c->len;
     const uint32_t shift = keybits - segbits;
     const uint32_t npass = (segbits + 7) / 8;
-    uint64_t mark = c->arena.mark();
     const unsigned long long* prehist =
         (segbits == kSegBits && c->extract_hist_shift == shift && c->knobs.lookback && !*in_b_out) ? c->d_ctr->hist : nullptr;
     K* src = *in_b_out ? kb : ka;
@@ -887,7 +883,6 @@ int segment_count(goss_gpu_ctx* c, K* ka, K* kb, uint64_t n, uint32_t segbits, b
     K* part = moved ? dst : src;          // partitioned keys
     K* spare = moved ? src : dst;         // free half of the ping-pong: staging area
     *in_b_out = (part == kb);
-    c->arena.release(mark);
     return segment_reduce<K>(c, part, spare, n, segbits, out);
 }
 
@@ -906,7 +901,7 @@ int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_
 {
     const bool squeeze = lay.squeeze, image = lay.image;
     const uint32_t rbits = lay.rbits, sqbit = lay.sqbit, split_bits = lay.split_bits;
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     PhaseTimer t(c, GOSS_T_REDUCE, n);
     SegStage<Key1> st(c, lay.nseg, spare, n);
     // (buckets of four remainders, home bucket only in the fast path)
@@ -930,7 +925,7 @@ int segment_reduce32(goss_gpu_ctx* c, const uint32_t* rems, Key1* spare, uint64_
                      (double)st.h.stamps[0] / st.h.stamps[7], (double)st.h.stamps[1] / st.h.stamps[7], (double)st.h.stamps[2] / st.h.stamps[7], (double)st.h.stamps[3] / st.h.stamps[7],
                      (double)st.h.stamps[4] / st.h.stamps[7], (double)st.h.stamps[5] / st.h.stamps[7], (double)st.h.stamps[6] / st.h.stamps[7], (unsigned long long)st.h.stamps[7]);
 #endif
-    return finish_segments(st, true, lay.seg_beg, lay.seg_end, t, mark, out,
+    return finish_segments(st, true, lay.seg_beg, lay.seg_end, t, out,
         [&](uint32_t u, uint64_t first, uint64_t cnt_u, Key1* dst) {
             const uint64_t prefix = (uint64_t)(u >> split_bits) << rbits;          // (as the counting kernel's write-out)
             with_bool(squeeze, [&](auto sq) { with_bool(image, [&](auto img) {
@@ -1002,7 +997,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
     // the run's own storage is one side of the sort's ping-pong, a temporary copy the other
     const uint64_t need = m * sizeof(K) + m * 4 + 512;
     if (c->arena.avail() < need + (256ULL << 20)) grow_arena(c, need + (256ULL << 20));      // (rebases r: it lives in c->build.runs)
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     K* ka = (K*)r.keys;
     uint32_t* va = r.counts;
     K* kb = (K*)c->arena.temp(m * sizeof(K));
@@ -1027,7 +1022,7 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
             in_b = radix_sort<K, true>(c, ka, kb, va, vb, m, (sb + 7) / 8, keybits - sb);
             K* sk = in_b ? kb : ka;
             uint32_t* sv = in_b ? vb : va;
-            uint64_t m2 = c->arena.mark();
+            ArenaScope groups(c->arena);          // (given back before the full sort below asks for its tables)
             uint64_t* soff = (uint64_t*)c->arena.temp(((uint64_t)nseg + 1) * 8);
             uint32_t* flag = (uint32_t*)c->arena.temp(16);
             HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
@@ -1039,7 +1034,6 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
             HIP_TRY(hipMemcpyAsync(hf, flag, 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             ordered = hf[0] == 0;
-            c->arena.release(m2);
             if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: canonical order of %llu keys by %u-bit groups: %s\n", (unsigned long long)m, sb, ordered ? "done" : "skewed, full sort");
             if (!ordered)
             {
@@ -1058,7 +1052,6 @@ void canonicalize_run(goss_gpu_ctx* c, Run& r)
     }
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arena.release(mark);
 }
 
 // A run of a graph build counted in strand-pair space (one representative per window, process_chunk_fused) -> both
@@ -1076,7 +1069,7 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
         const uint64_t need = 3 * m * (sizeof(K) + 4) + (256ULL << 20);
         if (c->arena.avail() < need) grow_arena(c, need);          // (rebases the runs: fetched by index below)
     }
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     K* bk = (K*)c->arena.temp(m * sizeof(K));
     uint32_t* bc = (uint32_t*)c->arena.temp(m * 4);
     K* tk = (K*)c->arena.temp(m * sizeof(K));
@@ -1127,7 +1120,6 @@ void expand_graph_run(goss_gpu_ctx* c, size_t ri)
     }
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arena.release(mark);
     if (c->knobs.debug) std::fprintf(stderr, "libgossgpu: %llu strand pairs expanded (%llu palindromes)\n", (unsigned long long)m, (unsigned long long)npads);
 }
 
@@ -1163,7 +1155,7 @@ inline bool merge_by_table(const MergeInput<Key2>& in, Run* out)
     const uint32_t keybits = 2 * c->len, nruns = in.nruns;
     if (!(c->knobs.table96 && keybits >= 16 + 8 && keybits - 16 <= 96 && nruns <= (uint32_t)kMergeRuns && in.total >= c->knobs.hash_merge_min)) return false;
     const uint32_t nseg = 65536, shift = keybits - 16;
-    uint64_t m2 = c->arena.mark();
+    ArenaScope scope(c->arena);
     uint64_t* bounds = (uint64_t*)c->arena.temp((uint64_t)nruns * (nseg + 1) * 8);
     uint64_t* d_off = (uint64_t*)c->arena.temp((nruns + 1) * 8);
     SegStage<Key2> st(c, nseg, in.kb, in.vb, in.total);
@@ -1172,7 +1164,7 @@ inline bool merge_by_table(const MergeInput<Key2>& in, Run* out)
     in.launch_bounds(nseg, shift, bounds);
     hipLaunchKernelGGL(seg_hash_merge96_kernel, unit_grid(nseg), dim3(kSegBigThreads), 0, c->stream, (const Key2*)in.ka, (const uint32_t*)in.va,
                        (const uint64_t*)d_off, (const uint64_t*)bounds, nruns, st.out, st.pos, st.cnt, in.kb, in.vb, shift);
-    if (st.read().overflow) { t.stop(); c->arena.release(m2); return false; }
+    if (st.read().overflow) { t.stop(); return false; }
     st.gather(out);
     t.stop();
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1194,7 +1186,7 @@ bool merge_by_segments(const MergeInput<K>& in, Run* out)
     for (int attempt = 0; attempt < 3 && segbits <= 26 && segbits <= keybits; ++attempt, segbits += 2)
     {
         const uint32_t nseg = 1u << segbits, shift = keybits - segbits;
-        uint64_t m2 = c->arena.mark();
+        ArenaScope attempt_scope(c->arena);
         const uint64_t need = (uint64_t)nruns * (nseg + 1) * 8 + (uint64_t)nseg * 32 + (1u << 20);
         if (c->arena.avail() < need) break;
         uint64_t* bounds = (uint64_t*)c->arena.temp((uint64_t)nruns * (nseg + 1) * 8);
@@ -1208,11 +1200,11 @@ bool merge_by_segments(const MergeInput<K>& in, Run* out)
         unsigned long long* hmax = (unsigned long long*)c->h_pinned;
         HIP_TRY(hipMemcpyAsync(hmax, d_max, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hmax[0] > (unsigned long long)kMergeCap) { t.stop(); c->arena.release(m2); continue; }
+        if (hmax[0] > (unsigned long long)kMergeCap) { t.stop(); continue; }
         SegStage<K> st(c, nseg, in.kb, in.vb, in.total);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_merge_kernel<K>), unit_grid(nseg), dim3(kTB), 0, c->stream, (const K*)in.ka, (const uint32_t*)in.va,
                            (const uint64_t*)d_off, (const uint64_t*)bounds, nruns, nseg, st.out, st.pos, st.cnt, in.kb, in.vb, c->d_flags);
-        if (st.read().overflow) { t.stop(); c->arena.release(m2); break; }
+        if (st.read().overflow) { t.stop(); break; }
         st.gather(out);
         t.stop();
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1260,7 +1252,7 @@ void merge_runs(goss_gpu_ctx* c)
         const uint64_t need = 2 * total * (sizeof(K) + 4) + (512ULL << 20);
         if (c->arena.avail() < need) grow_arena(c, need);
     }
-    uint64_t mark = c->arena.mark();
+    ArenaScope scope(c->arena);
     MergeInput<K> in;
     in.c = c; in.total = total; in.nruns = (uint32_t)c->build.runs.size();
     in.ka = (K*)c->arena.temp(total * sizeof(K));
@@ -1288,5 +1280,4 @@ void merge_runs(goss_gpu_ctx* c)
     if (!merged && !merge_by_segments(in, &r)) merge_by_sort(in, &r);
     r.rep = rep_out;
     c->build.runs.push_back(r);
-    c->arena.release(mark);
 }

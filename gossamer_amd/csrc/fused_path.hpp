@@ -832,10 +832,10 @@ int count_sub8(const FusedChunk<K>& ch, FusedForm form, const Sub8Regions& sub, 
 }
 
 // 4b. remaining partition passes: the first reads the bucket regions, the others are dense; then the counting.
-// `mark`: the arena mark of the chunk -- everything above it is released before the counting.
+// `chunk`: the arena scope of the chunk -- everything taken under it is given back before the counting.
 template <class K>
 int count_dense(const FusedChunk<K>& ch, const FusedForm& form, const FirstLevelResult& fl, const GapTable* dgt, PartCounters* pc, FusedLookback lb,
-                uint64_t mark, Run* r)
+                ArenaScope& chunk, Run* r)
 {
     goss_gpu_ctx* c = ch.c;
     constexpr int kTile = SortCfg<K, false>::kTile;
@@ -881,7 +881,7 @@ int count_dense(const FusedChunk<K>& ch, const FusedForm& form, const FirstLevel
         std::swap(src, dst);
     }
     // src = partitioned keys (dense: npass >= 2), dst = spare
-    c->arena.release(mark);
+    chunk.rewind();
     const int rc = segment_reduce<K>(c, src, dst, n, form.segbits, r);
     if (rc != 0) { c->stats.segment_retries++; return ch.decline("a segment table overflowed"); }
     return kFusedGoOn;
@@ -902,8 +902,7 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     ch.reduced = ka_slots < nstarts * (ch.graph_mode ? 2 : 1) || kb_slots < nstarts * (ch.graph_mode ? 2 : 1);
     if (!c->knobs.fused || c->path != 0 || !c->knobs.lookback || c->knobs.ordered_tiles || nstarts < c->knobs.fused_min || keybits < (uint32_t)kSegBits + 8)
         return kFusedDeclined;
-    const uint64_t mark = c->arena.mark();
-    struct Release { goss_gpu_ctx* c; uint64_t m; ~Release() { c->arena.release(m); } } release{c, mark};
+    ArenaScope scope(c->arena);
     ch.t_begin = std::chrono::steady_clock::now();
 
     // 1. a sample of the keys, the distinct keys it promises, and the key space the chunk is counted in
@@ -997,7 +996,7 @@ int fused_chunk_once(goss_gpu_ctx* c, const ReadSrc& src, uint64_t nstarts, uint
     int rc = kFusedDeclined;
     if (form.msd && form.rem32()) { if constexpr (kOne) rc = count_rem32(ch, form, sub32, fl, dgt, lb, &r); }          // (one-word keys only: choose_form)
     else if (form.msd) rc = count_sub8(ch, form, sub8, fl, dgt, lb, &r);
-    else rc = count_dense(ch, form, fl, dgt, pc, lb, mark, &r);
+    else rc = count_dense(ch, form, fl, dgt, pc, lb, scope, &r);
     if (rc != kFusedGoOn) return rc;
     ch.lap("segments counted");
 

@@ -1,6 +1,7 @@
-// goss_ctx.hpp -- the context behind the C ABI (goss_gpu_ctx) and what every path needs of it: the error types, the
-// arena, the phase timer and guarded(), the frame of every entry point.  Included by goss_gpu.hip ahead of the
-// *_path.hpp files; the knobs, the counters and Scoped are goss_knobs.hpp's.
+// goss_ctx.hpp -- the context behind the C ABI (goss_gpu_ctx) and what every path needs of it: the HIP error type, the
+// arena's mapping and growth, the phase timer and guarded(), the frame of every entry point.  Included by goss_gpu.hip
+// ahead of the *_path.hpp files; the knobs, the counters and Scoped are goss_knobs.hpp's, the arena itself, its scope
+// and StatusError goss_arena.hpp's.
 #pragma once
 
 namespace {
@@ -13,42 +14,16 @@ struct HipError { hipError_t e; const char* what; };
         if (_e != hipSuccess) throw HipError{_e, #expr};                      \
     } while (0)
 
-struct StatusError { int status; std::string msg; };
-
-// Two-ended bump arena over one hipMalloc: permanent blocks grow from the bottom, temporary
-// blocks from the top (released by mark).
-struct Arena {
-    uint8_t* base = nullptr;
-    uint64_t size = 0;
-    uint64_t lo = 0;        // permanent top
-    uint64_t hi = 0;        // temporary bottom (offset from base)
-
-    void* perm(uint64_t bytes)
-    {
-        uint64_t a = (lo + 255) & ~255ULL;
-        if (a + bytes > hi) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (permanent)"};
-        lo = a + bytes;
-        return base + a;
-    }
-    void* temp(uint64_t bytes)
-    {
-        if (bytes + 256 > hi) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (temporary)"};
-        uint64_t a = (hi - bytes) & ~255ULL;
-        if (a < lo) throw StatusError{GOSS_ERR_OOM, "HBM budget exceeded (temporary)"};
-        hi = a;
-        return base + a;
-    }
-    uint64_t mark() const { return hi; }
-    void release(uint64_t m) { hi = m; }
-    uint64_t avail() const { return hi > lo ? hi - lo : 0; }
-};
-
 struct OutFile {
     std::string suffix;
     uint64_t size = 0;
     const uint8_t* dev = nullptr;      // device-resident image, or
     std::vector<uint8_t> host;         // host-built bytes
 };
+
+// version words of the two objects' headers (KmerSet.hh, Graph.hh): written by emit_path.hpp, named in the text dump's
+// heading, checked by object_path.hpp
+constexpr uint64_t kKmerSetVersion = 2011101701ULL, kGraphVersion = 2011101014ULL;
 
 typedef std::map<std::pair<uint64_t, uint64_t>, uint64_t> BigMap;     // key (hi, lo) -> count that does not fit 32 bits
 struct Run { void* keys; uint32_t* counts; uint64_t m; int big = -1; bool rep = false; };

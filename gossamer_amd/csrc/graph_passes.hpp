@@ -15,16 +15,6 @@
 // and the compaction of prune-tips.
 #pragma once
 
-// Temporaries of one call, given back on every way out (an exception included).
-struct ArenaScope {
-    Arena& a;
-    uint64_t mark;
-    explicit ArenaScope(Arena& arena) : a(arena), mark(arena.mark()) {}
-    ~ArenaScope() { a.release(mark); }
-    ArenaScope(const ArenaScope&) = delete;
-    ArenaScope& operator=(const ArenaScope&) = delete;
-};
-
 struct EventPair {
     hipEvent_t e[5] = {};
     EventPair() { for (auto& x : e) HIP_TRY(hipEventCreate(&x)); }
@@ -40,15 +30,6 @@ inline void sync_checked(goss_gpu_ctx* c)
 {
     HIP_TRY(hipStreamSynchronize(c->stream));
     check_launch("a kernel launch was refused");
-}
-
-// a[0, n) becomes its exclusive prefix sums and a[n] their total, which is on its way to *total (pinned) when this
-// returns: the caller's next sync_checked delivers it.
-inline void scan_with_total(goss_gpu_ctx* c, uint64_t* a, uint64_t n, uint64_t* total)
-{
-    HIP_TRY(hipMemsetAsync(a + n, 0, 8, c->stream));
-    exclusive_scan_u64(c, a, n + 1);
-    HIP_TRY(hipMemcpyAsync(total, a + n, 8, hipMemcpyDeviceToHost, c->stream));
 }
 
 struct NothingQueued { template <class... A> void operator()(A&&...) const {} };
@@ -662,11 +643,7 @@ void entries_build(goss_gpu_ctx* c, goss_gpu_entries_info* out)
         std::vector<IaCol> cols;                          // RankBits = 40 (EntryEdgeSet.hh:41): ".upr" u8, ".lwr" u32
         ia_layout(40, base + ".ends", 0, cols);
         const uint8_t* img[2] = {upr, (const uint8_t*)lwr};
-        for (size_t i = 0; i < cols.size() && i < 2; ++i)
-        {
-            OutFile f; f.suffix = cols[i].suffix; f.size = nent * cols[i].bytes; f.dev = img[i];
-            c->build.files.push_back(std::move(f));
-        }
+        for (size_t i = 0; i < cols.size() && i < 2; ++i) add_dev_file(c, cols[i].suffix, img[i], nent * cols[i].bytes);
     }
     const uint64_t hdr[2] = {2011041901ULL, c->k};
     add_host_file(c, base + ".header", hdr, sizeof hdr);

@@ -229,7 +229,7 @@ void open_object(goss_gpu_object* o, int kind, const std::string& base, const Ob
         uint64_t h[3];
         std::memcpy(h, pl.head(hs, 24).data(), 24);
         const bool graph = kind == GOSS_OBJECT_GRAPH;
-        if (h[0] != (graph ? 2011101014ULL : 2011101701ULL))
+        if (h[0] != (graph ? kGraphVersion : kKmerSetVersion))
             throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: " + (graph ? "Graph" : "KmerSet") + " version mismatch"};
         if (h[1] == 0 || h[1] > (graph ? 62u : 63u)) throw StatusError{GOSS_ERR_INVALID_ARG, base + ".header: K out of range"};
         o->K = (uint32_t)h[1];

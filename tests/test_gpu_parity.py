@@ -212,6 +212,44 @@ def test_reset_starts_a_second_build_and_counters_run_on():
         assert flushes1 > 0 and ctx.stat("flushes") == 2 * flushes1
 
 
+def test_refused_dump_gives_its_room_back():
+    """A call that is refused for lack of room leaves the arena as it found it.  A graph of 8.7 M edges at low coverage
+    (k = 27; 40 000 reads of 150 bases from 20 Mbp) on a fixed budget of 400 MB: finish needs 320 MB and emit 384 MB of
+    budget, the whole dump -- 12 bytes an edge for the result, 8 for the line offsets, k + 5 for the text -- 448 MB, so it
+    is refused with GOSS_ERR_OOM while a 64th of it fits.  The refused call takes its 8 (M + 1) bytes of line offsets
+    before it asks for the text; N = budget // (8 (M + 1)) + 2 refusals that kept them would hold more than the arena.
+    After them the piece and emit() must come out as from a fresh context, byte for byte."""
+    k, budget = 27, 400 * MB
+    reads = g.synth_reads_host(40000, 150, 20000000, seed=5)
+
+    def build(ctx):
+        ctx.push_host(reads)
+        return ctx.finish().distinct
+
+    with g.Context(k, g.MODE_GRAPH, hbm_budget=budget) as fresh:
+        M = build(fresh)
+        exp_piece = fresh.emit_dump_range(0, 0, M // 64)
+        exp_files = fresh.emit()
+    assert M > 4000000 and len(exp_piece[".dump"]) > (k + 4) * (M // 64) and len(exp_files) > 10
+    N = budget // (8 * (M + 1)) + 2
+    with g.Context(k, g.MODE_GRAPH, hbm_budget=budget) as ctx:
+        assert build(ctx) == M
+        assert ctx.stat("arena_bytes") == budget and ctx.stat("arena_grows") == 0          # (fixed: nothing grew)
+        # the preconditions: the whole dump is refused for room, a 64th of it is not
+        with pytest.raises(g.GossGpuError) as refusal:
+            ctx.emit_dump()
+        assert refusal.value.status == -3          # GOSS_ERR_OOM
+        assert ctx.emit_dump_range(0, 0, M // 64) == exp_piece
+        for _ in range(N):
+            with pytest.raises(g.GossGpuError) as again:
+                ctx.emit_dump()
+            assert again.value.status == refusal.value.status
+        print("budget %d, M %d, N %d refused dumps" % (budget, M, N))
+        assert ctx.emit_dump_range(0, 0, M // 64) == exp_piece
+        assert ctx.emit() == exp_files
+        assert ctx.stat("arena_bytes") == budget and ctx.stat("arena_grows") == 0
+
+
 def _sparse_case(oracle, positions, N, M, words):
     import torch
     exp = _suffix_map(oracle.write_sparse_array(positions, N, M, base="sa"), "sa")

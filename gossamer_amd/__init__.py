@@ -10,4 +10,6 @@ from .binding import (Context, GossGpuError, MODE_GRAPH, MODE_KMER_SET, SYMBOLS,
                       POOL_PAIR_WORDS, POOL_POS_WORDS, POOL_TILE, format_double, pool_similarity_text,
                       TAXO_MANY, TAXO_NONE, TAXO_NORMALIZE, TAXO_SYMBOLS, format_phylogeny, parse_phylogeny, phylogeny_nodes,
                       ELECT_MAX_COLOURS, ELECT_NORMALIZE, ELECT_SYMBOLS, elect,
-                      RECOUNT_REPORT_FIELDS, RELATIVE_REPORT_FIELDS, RELATIVE_SYMBOLS)
+                      RECOUNT_REPORT_FIELDS, RELATIVE_REPORT_FIELDS, RELATIVE_SYMBOLS,
+                      LINK_DTYPE, LINK_MISS, LINK_NONE, LINK_NON_UNIQUE, READ_LINKS_SYMBOLS, estimate_coverage, filter_links,
+                      unique_segments)

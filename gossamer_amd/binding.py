@@ -62,6 +62,11 @@ TAXO_SYMBOLS = ["goss_gpu_object_taxo_tree_host", "goss_gpu_object_taxo_annotati
 # every symbol include/goss_gpu_relative.h declares (trim-relative and merge-graph-with-reference on a finished graph)
 RELATIVE_SYMBOLS = ["goss_gpu_trim_relative", "goss_gpu_recount_from", "goss_gpu_relative_timing"]
 
+# every symbol include/goss_gpu_links.h declares (read links: reads threaded over the linear segments of a finished graph)
+READ_LINKS_SYMBOLS = ["goss_gpu_read_links_begin", "goss_gpu_read_links_segments", "goss_gpu_read_links_windows_host",
+                      "goss_gpu_read_links_add_host", "goss_gpu_read_links_finish", "goss_gpu_read_links_table",
+                      "goss_gpu_read_links_release"]
+
 RECORD_BYTES = 12          # one-word keys (2 * len <= 62); two-word keys: 20 (record_bytes)
 
 
@@ -126,6 +131,92 @@ COMPONENT_NONE = 0xFFFFFFFF
 GROW_INFO_FIELDS = (("marked_before", C.c_uint64), ("mirrored", C.c_uint64), ("marked_total", C.c_uint64), ("passes_run", C.c_uint32),
                     ("launches", C.c_uint32), ("ms_link", C.c_float), ("ms_label", C.c_float), ("ms_grow", C.c_float))
 GROW_LINEAR_PATHS = 1
+
+
+# goss_gpu_read_links_info, goss_gpu_read_links_batch, goss_gpu_read_links_table_info and goss_gpu_link_row
+READ_LINKS_INFO_FIELDS = (("edges", C.c_uint64), ("entries", C.c_uint64), ("edges_without_segment", C.c_uint64),
+                          ("ms_link", C.c_float), ("ms_rank", C.c_float), ("ms_segments", C.c_float), ("reserved", C.c_uint32))
+READ_LINKS_BATCH_FIELDS = (("reads", C.c_uint64), ("windows", C.c_uint64), ("misses", C.c_uint64), ("carried", C.c_uint64),
+                           ("hits", C.c_uint64), ("records", C.c_uint64), ("ms_windows", C.c_float), ("ms_scans", C.c_float),
+                           ("ms_compact", C.c_float), ("reserved", C.c_uint32))
+READ_LINKS_TABLE_FIELDS = (("records", C.c_uint64), ("rows", C.c_uint64), ("ms_sort", C.c_float), ("ms_reduce", C.c_float))
+LINK_DTYPE = [("a", "<u4"), ("b", "<u4"), ("count", "<u8"), ("gap_sum", "<u8")]
+LINKS_CARRY = 1
+LINK_NONE = 0xFFFFFFFF                           # Context.segment_of_edges: an edge on a cycle without an entry edge
+LINK_MISS = 0xFFFFFFFF                           # Context.thread_windows: a window that was not aligned
+LINK_NON_UNIQUE = 0x80000000                     # ... set on the segment of a window whose segment is not unique
+
+
+class ReadLinksInfo(C.Structure):
+    _fields_ = list(READ_LINKS_INFO_FIELDS)
+
+
+class ReadLinksBatch(C.Structure):
+    _fields_ = list(READ_LINKS_BATCH_FIELDS)
+
+
+class ReadLinksTableInfo(C.Structure):
+    _fields_ = list(READ_LINKS_TABLE_FIELDS)
+
+
+def unique_segments(lengths, multiplicities, k, coverage):
+    """SuperGraph::unique (SuperGraph.cc:667-700) for superpaths of one segment each, as they are straight after
+    build-supergraph: np.bool_ per entry from the EntryEdgeSet's lengths and multiplicities.  False where
+    length + k < 50; else f = ln(2) / 2 + (n / (2 rho)) (rho^2 - c^2 / 2) >= 5.0 with n = length, c = (n * multiplicity)
+    / n and rho = coverage, in float64 with the reference's operations in its order, one rounding each.  Pure numpy."""
+    import numpy as np
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    n = lengths.astype(np.float64)
+    m = np.asarray(multiplicities, dtype=np.uint32).astype(np.float64)
+    rho = np.float64(coverage)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = (n * m) / n
+        k0 = np.float64(np.log(np.float64(2.0))) / np.float64(2.0)
+        f = k0 + (n / (np.float64(2) * rho)) * (rho * rho - (c * c) / np.float64(2.0))
+        ok = f >= np.float64(5.0)
+    return ok & ~(lengths + np.uint64(k) < np.uint64(50))
+
+
+def estimate_coverage(hist):
+    """EstimateCoverageOnly (EstimateGraphStatistics.cc:306-364) over a multiplicity histogram -- a dict or (x, y) pairs,
+    taken in ascending x.  Integer logic over the first 50 rows: the x of the largest y from the first rise on.  Fewer
+    than 50 rows, or a gap between two of the first 50 x, raise ValueError with the reference's text.  The reference's
+    two errors are kept: rows beyond the fiftieth are never looked at, so a peak there is missed; and a histogram that
+    never rises among them answers 0 instead of failing.  Pure Python."""
+    rows = sorted(dict(hist).items()) if not isinstance(hist, dict) else sorted(hist.items())
+    if len(rows) < 50:
+        raise ValueError("Not enough data to estimate coverage.")
+    fit, best_x, best_y = False, 0, 0
+    prev_x, prev_y = rows[0]
+    for x, y in rows[1:50]:
+        if prev_x + 1 != x:
+            raise ValueError("Coverage histogram appears to be discontinuous. Cannot estimate coverage.")
+        if prev_y < y:
+            fit = True
+        if fit and best_y < y:
+            best_x, best_y = x, y
+        prev_x, prev_y = x, y
+    return int(best_x)
+
+
+def filter_links(table, min_count):
+    """The three filters of GossCmdThreadReads.cc:795-886 over a LINK_DTYPE table, as a new LINK_DTYPE table ascending by
+    (a, b).  One: a row of count < min_count goes; a row that stays becomes (a, b, count 1, gap_sum = gap_sum // count) --
+    the reference re-adds it with its average gap and the default count.  Two: of the rows of one a the best supported
+    stays; three: of the rows of one b likewise.  After the first filter every count is 1, so both choices are ties:
+    the reference takes the first of a vector filled in unordered_map order, which depends on the library's hash; here
+    the tie goes to the smallest id.  Pure numpy, no device work."""
+    import numpy as np
+    t = np.sort(np.asarray(table, dtype=LINK_DTYPE), order=["a", "b"])
+    t = t[t["count"] >= min_count]
+    t["gap_sum"] = t["gap_sum"] // np.maximum(t["count"], 1)
+    t["count"] = 1
+    if len(t):                                       # (sorted by (a, b): the first row of an a has its smallest b)
+        t = t[np.concatenate(([True], t["a"][1:] != t["a"][:-1]))]
+        t = np.sort(t, order=["b", "a"])
+        t = t[np.concatenate(([True], t["b"][1:] != t["b"][:-1]))]
+        t = np.sort(t, order=["a", "b"])
+    return t
 
 
 class MarkInfo(C.Structure):
@@ -961,6 +1052,99 @@ class Context:
     def components_release(self):
         self._L.goss_gpu_components_release.argtypes = [C.c_void_p]
         self._check(self._L.goss_gpu_components_release(self._h))
+
+    # ---- read links (include/goss_gpu_links.h) --------------------------------------------------------------------
+
+    def read_links_begin(self, unique=None, carry=True):
+        """Between finish and emit, graph mode: build and hold the segment of every edge (goss_gpu_read_links_begin).
+        unique: a truth value per entry rank, or None for "every segment is unique".  Returns the info dict."""
+        import numpy as np
+        inf = ReadLinksInfo()
+        bits, nbits = None, 0
+        if unique is not None:
+            u = np.asarray(unique, dtype=np.bool_)
+            nbits = len(u)
+            bits = np.packbits(u, bitorder="little").tobytes() + b"\0"
+        self._L.goss_gpu_read_links_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(ReadLinksInfo)]
+        self._check(self._L.goss_gpu_read_links_begin(self._h, LINKS_CARRY if carry else 0, bits, nbits, C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in READ_LINKS_INFO_FIELDS if name != "reserved"}
+
+    def read_links_release(self):
+        self._L.goss_gpu_read_links_release.argtypes = [C.c_void_p]
+        self._check(self._L.goss_gpu_read_links_release(self._h))
+
+    def read_links_segments(self, first=0, count=None):
+        """After read_links_begin: np.uint32 per edge of rank [first, first + count), LINK_NONE where it has no segment."""
+        import numpy as np
+        if count is None:
+            count = self.result_ptrs()[2] - first
+        out = np.zeros(count, dtype=np.uint32)
+        self._L.goss_gpu_read_links_segments.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_read_links_segments(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def read_links_windows(self, bases):
+        """After read_links_begin: (np.uint32 per window of the batch in read order, info dict)
+        (goss_gpu_read_links_windows_host)."""
+        import numpy as np
+        inf = ReadLinksBatch()
+        out = np.zeros(max(len(bases), 1), dtype=np.uint32)
+        self._L.goss_gpu_read_links_windows_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                             C.POINTER(ReadLinksBatch)]
+        self._check(self._L.goss_gpu_read_links_windows_host(self._h, bases, len(bases), out.ctypes.data_as(C.c_void_p), len(out),
+                                                             C.byref(inf)))
+        return out[:inf.windows].copy(), {name: getattr(inf, name) for name, _ in READ_LINKS_BATCH_FIELDS if name != "reserved"}
+
+    def read_links_add(self, bases):
+        """After read_links_begin: the records of one batch of whole reads join those held (goss_gpu_read_links_add_host);
+        returns the info dict."""
+        inf = ReadLinksBatch()
+        self._L.goss_gpu_read_links_add_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(ReadLinksBatch)]
+        self._check(self._L.goss_gpu_read_links_add_host(self._h, bases, len(bases), C.byref(inf)))
+        return {name: getattr(inf, name) for name, _ in READ_LINKS_BATCH_FIELDS if name != "reserved"}
+
+    def read_links_table(self):
+        """After read_links_begin: reduce the records held (goss_gpu_read_links_finish) and return (LINK_DTYPE array
+        ascending by (a, b), info dict).  The records stay: more batches may follow, and a second call answers alike."""
+        import numpy as np
+        inf = ReadLinksTableInfo()
+        self._L.goss_gpu_read_links_finish.argtypes = [C.c_void_p, C.POINTER(ReadLinksTableInfo)]
+        self._check(self._L.goss_gpu_read_links_finish(self._h, C.byref(inf)))
+        table = np.zeros(inf.rows, dtype=LINK_DTYPE)
+        self._L.goss_gpu_read_links_table.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._check(self._L.goss_gpu_read_links_table(self._h, 0, inf.rows, table.ctypes.data_as(C.c_void_p)))
+        return table, {name: getattr(inf, name) for name, _ in READ_LINKS_TABLE_FIELDS}
+
+    def segment_of_edges(self):
+        """The segment of every edge of the graph: np.uint32[M], the entry rank of the linear path that holds the edge,
+        LINK_NONE on a cycle without an entry edge.  The context's result is untouched; nothing stays held."""
+        self.read_links_begin(carry=False)
+        try:
+            return self.read_links_segments()
+        finally:
+            self.read_links_release()
+
+    def thread_windows(self, bases, unique=None, carry=True):
+        """The read-to-path primitive: per forward (K+1)-window of the reads in `bases` (bytes, '\\n' between reads), in
+        read order, the segment it is aligned to -- | LINK_NON_UNIQUE where `unique` says so -- or LINK_MISS.  carry=True
+        is the aligner of the reference's thread-reads, carry=False the exact answer (include/goss_gpu_links.h).  The
+        context's result is untouched; nothing stays held."""
+        self.read_links_begin(unique, carry)
+        try:
+            return self.read_links_windows(bases)[0]
+        finally:
+            self.read_links_release()
+
+    def read_links(self, batches, unique=None, carry=True):
+        """The link table of the reads in `batches` (an iterable of bytes, whole reads each): LINK_DTYPE rows
+        (a, b, count, gap_sum) ascending by (a, b), 64-bit sums.  The context's result is untouched; nothing stays held."""
+        self.read_links_begin(unique, carry)
+        try:
+            for bases in batches:
+                self.read_links_add(bases)
+            return self.read_links_table()[0]
+        finally:
+            self.read_links_release()
 
     def pool_begin(self, nsets, z):
         """goss_gpu_pool_begin: zeroed bit rows of nsets samples over a union of z k-mers, held by the context"""

@@ -35,7 +35,7 @@ struct PhaseEvents { hipEvent_t a, b; int phase; uint64_t units; };
 // What a build entry point left on top of the permanent room for later calls to read (graph_passes.hpp): the segment
 // table and text of goss_gpu_segments_build, the images of goss_gpu_entries_build, or the marks, labels and table of the
 // components entry points.  One record: at most one is held.
-enum class Held : uint8_t { None, Segments, Entries, Components, Pool };
+enum class Held : uint8_t { None, Segments, Entries, Components, Pool, Links };
 struct HeldResult { Held kind = Held::None; uint64_t lo = 0; };          // lo: the permanent top before the build
 
 // Distinct keys per window from which the fused first level of a one-word k-mer set computes gossamer's canonical form
@@ -173,6 +173,19 @@ struct goss_gpu_ctx {
     uint64_t pool_z = 0, pool_top = 0;
     uint32_t pool_sets = 0;
     std::vector<bool> pool_added;         // per sample: its row has been written
+    // Held::Links (read_links_*, graph_passes.hpp), bottom to top: the segment of every edge, the flag "only edge out
+    // of its node", the bucket table of the window lookup, the uniqueness bitmap; then the records batch by batch;
+    // then, from lnk_rows_lo on, the table of goss_gpu_read_links_finish (dropped when another batch is added)
+    struct LinkChunk { unsigned long long* keys; uint32_t* gaps; uint64_t n; };
+    uint32_t* lnk_seg_of = nullptr;
+    uint8_t* lnk_single = nullptr;
+    uint32_t* lnk_table = nullptr;
+    uint32_t* lnk_unique = nullptr;
+    uint32_t lnk_bits = 0, lnk_flags = 0;
+    uint64_t lnk_entries = 0, lnk_records = 0, lnk_rows_lo = 0, lnk_row_count = 0;
+    std::vector<LinkChunk> lnk_chunks;
+    void* lnk_rows = nullptr;
+    bool lnk_reduced = false;
 };
 
 namespace {
@@ -294,6 +307,8 @@ bool grow_arena(goss_gpu_ctx* c, uint64_t want_avail)
     rebase(c->seg_recs); rebase(c->seg_text);
     rebase(c->cmp_marks); rebase(c->cmp_labels); rebase(c->cmp_recs);
     rebase(c->pool_rows); rebase(c->pool_sizes);
+    rebase(c->lnk_seg_of); rebase(c->lnk_single); rebase(c->lnk_table); rebase(c->lnk_unique); rebase(c->lnk_rows);
+    for (auto& k : c->lnk_chunks) { rebase(k.keys); rebase(k.gaps); }
     for (auto& f : c->build.files) rebase(f.dev);          // file images already emitted (stand-alone SparseArray builds)
     (void)hipFree(a.base);
     a.base = nb; a.hi = target - top; a.size = target;
@@ -317,6 +332,11 @@ void release_held(goss_gpu_ctx* c)
     c->cmp_marks = nullptr; c->cmp_labels = nullptr; c->cmp_recs = nullptr;
     c->cmp_mark_words = c->cmp_built_lo = c->cmp_count = c->cmp_marked = 0;
     c->cmp_built = false;
+    c->lnk_seg_of = nullptr; c->lnk_single = nullptr; c->lnk_table = nullptr; c->lnk_unique = nullptr; c->lnk_rows = nullptr;
+    c->lnk_bits = c->lnk_flags = 0;
+    c->lnk_entries = c->lnk_records = c->lnk_rows_lo = c->lnk_row_count = 0;
+    c->lnk_chunks.clear();
+    c->lnk_reduced = false;
 }
 
 // wait_bg: the call works on the arena or the runs -- the thread that counts a full staging buffer must have ended

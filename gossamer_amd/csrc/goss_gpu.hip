@@ -2288,6 +2288,97 @@ int goss_gpu_components_keep_marked(goss_gpu_ctx* c, uint64_t* kept)
     return rc;
 }
 
+// ---- read links -------------------------------------------------------------------------------------------------------
+
+int goss_gpu_read_links_begin(goss_gpu_ctx* c, uint32_t flags, const uint8_t* unique, uint64_t unique_bits, goss_gpu_read_links_info* out)
+{
+    if (!c || !out || (flags & ~(uint32_t)GOSS_LINKS_CARRY) || (!unique && unique_bits)) return GOSS_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (const int st = graph_pass_state(c, "read_links", "reads are threaded over a graph", "read links belong between finish and emit")) return st;
+    return build_held(c, Held::Links, out, [&]() {
+        if (c->words == 1) read_links_begin<Key1>(c, flags, unique, unique_bits, out);
+        else read_links_begin<Key2>(c, flags, unique, unique_bits, out);
+    });
+}
+
+static int read_links_state(goss_gpu_ctx* c, const char* who)
+{
+    if (c->held.kind == Held::Links) return GOSS_OK;
+    c->last_error = std::string(who) + " needs goss_gpu_read_links_begin before it";
+    return GOSS_ERR_STATE;
+}
+
+int goss_gpu_read_links_segments(goss_gpu_ctx* c, uint64_t first, uint64_t count, uint32_t* out)
+{
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (const int st = read_links_state(c, "read_links_segments")) return st;
+    if (first > c->build.M || count > c->build.M - first) { c->last_error = "read_links_segments: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    return guarded_reading(c, [&]() {
+        if (count) HIP_TRY(hipMemcpyAsync(out, c->lnk_seg_of + first, count * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+static int read_links_batch_entry(goss_gpu_ctx* c, const void* bases, uint64_t n, uint32_t* out, uint64_t capacity, bool accumulate,
+                                  goss_gpu_read_links_batch* info, const char* who)
+{
+    if (!c || !info || (!bases && n) || (!accumulate && capacity && !out)) return GOSS_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    if (const int st = read_links_state(c, who)) return st;
+    const int rc = guarded_reading(c, [&]() {
+        PhaseTimer t(c, GOSS_T_REDUCE, n);
+        if (c->words == 1) read_links_batch<Key1>(c, bases, n, out, capacity, accumulate, info);
+        else read_links_batch<Key2>(c, bases, n, out, capacity, accumulate, info);
+        t.stop();
+    });
+    if (rc != GOSS_OK) std::memset(info, 0, sizeof *info);
+    return rc;
+}
+
+int goss_gpu_read_links_windows_host(goss_gpu_ctx* c, const void* bases, uint64_t n, uint32_t* out, uint64_t capacity, goss_gpu_read_links_batch* info)
+{
+    return read_links_batch_entry(c, bases, n, out, capacity, false, info, "read_links_windows");
+}
+
+int goss_gpu_read_links_add_host(goss_gpu_ctx* c, const void* bases, uint64_t n, goss_gpu_read_links_batch* info)
+{
+    return read_links_batch_entry(c, bases, n, nullptr, 0, true, info, "read_links_add");
+}
+
+int goss_gpu_read_links_finish(goss_gpu_ctx* c, goss_gpu_read_links_table_info* info)
+{
+    if (!c || !info) return GOSS_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    if (const int st = read_links_state(c, "read_links_finish")) return st;
+    const int rc = guarded_reading(c, [&]() {
+        PhaseTimer t(c, GOSS_T_REDUCE, c->lnk_records);
+        read_links_finish(c, info);
+        t.stop();
+    });
+    if (rc != GOSS_OK) std::memset(info, 0, sizeof *info);
+    return rc;
+}
+
+int goss_gpu_read_links_table(goss_gpu_ctx* c, uint64_t first, uint64_t count, goss_gpu_link_row* out)
+{
+    static_assert(sizeof(goss_gpu_link_row) == sizeof(LinkRow), "link row layout");
+    if (!c || (count && !out)) return GOSS_ERR_INVALID_ARG;
+    if (const int st = read_links_state(c, "read_links_table")) return st;
+    if (!c->lnk_reduced) { c->last_error = "read_links_table needs goss_gpu_read_links_finish before it"; return GOSS_ERR_STATE; }
+    if (first > c->lnk_row_count || count > c->lnk_row_count - first) { c->last_error = "read_links_table: a range past the end"; return GOSS_ERR_INVALID_ARG; }
+    return guarded_reading(c, [&]() {
+        if (count) HIP_TRY(hipMemcpyAsync(out, (const LinkRow*)c->lnk_rows + first, count * sizeof(LinkRow), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    });
+}
+
+int goss_gpu_read_links_release(goss_gpu_ctx* c)
+{
+    if (!c) return GOSS_ERR_INVALID_ARG;
+    if (c->held.kind == Held::Links) release_held(c);
+    return GOSS_OK;
+}
+
 // ---- pool-samples ---------------------------------------------------------------------------------------------------
 
 static int pool_state(goss_gpu_ctx* c, const char* who)

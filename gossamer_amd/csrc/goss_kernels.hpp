@@ -32,3 +32,4 @@
 #include "kernels_relative.hpp"
 #include "kernels_near.hpp"
 #include "kernels_pool.hpp"
+#include "kernels_links.hpp"

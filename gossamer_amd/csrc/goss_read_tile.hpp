@@ -1,5 +1,6 @@
 // goss_read_tile.hpp -- one tile of read bytes staged in LDS, and the window that starts at a position of it.  Shared by
-// match_reads_kernel (kernels_match.hpp) and components_mark_kernel (kernels_components.hpp).
+// match_reads_kernel (kernels_match.hpp), components_mark_kernel (kernels_components.hpp) and links_windows_kernel
+// (kernels_links.hpp).
 //
 // A tile is kMatchTile byte positions, one workgroup each.  Every lane turns 8 bytes into 16 bits of 2-bit codes, 8
 // non-base flags and, where asked for, 8 newline flags (base_codes: the extraction kernels' decoder) and stores them

@@ -1,5 +1,5 @@
 // graph_passes.hpp -- the passes over the decoded, sorted edge list of a finished graph: prune-tips, the linear segments
-// of print-contigs, the EntryEdgeSet of build-entry-edge-set, count-components, build-subgraph.
+// of print-contigs, the EntryEdgeSet of build-entry-edge-set, count-components, build-subgraph, read links.
 // Part of goss_gpu.hip (included there, inside its unnamed namespace, once guarded() and the emit helpers it calls are
 // defined).  Two steps are shared and live here once each:
 //
@@ -9,7 +9,8 @@
 //
 // prune_tips_once is link_graph and the tip walk; segments_build and entries_build are link_graph, rank_lists and
 // their own records; components_build and components_keep are link_graph and a union-find over the links;
-// components_grow is link_graph and the passes of build-subgraph over the marks.  What a build leaves behind for
+// components_grow is link_graph and the passes of build-subgraph over the marks; read_links_begin is link_graph,
+// rank_lists and the segment of every edge, read_links_batch and read_links_finish the scans and the sort over it.  What a build leaves behind for
 // later calls is the context's one held result (build_held).  trim_relative and recount_from (kernels_relative.hpp)
 // need no links: a judge or lookup pass over the edges, the bucket table alone where mirror images are looked up,
 // and the compaction of prune-tips.
@@ -111,6 +112,7 @@ struct GraphLinks {
     uint32_t *rcr, *nxt;              // rank of the reverse complement; of the first edge that leaves to(E[i])
     uint8_t* info;                    // out-degree of to(E[i]) and the size of the group E[i] lies in (kernels_tips.hpp)
     uint32_t n, bits;
+    const uint32_t* table;            // the bucket table of the lookups (null when bits == 0): a temporary like the arrays
     dim3 grid, block;                 // one thread per edge
 };
 
@@ -131,6 +133,7 @@ GraphLinks<K> link_graph(goss_gpu_ctx* c, const char* who, TipsReport* report = 
     l.nxt = (uint32_t*)c->arena.temp(n64 * 4);
     l.info = (uint8_t*)c->arena.temp(n64);
     uint32_t* table = l.bits ? (uint32_t*)c->arena.temp(link_table_bytes(l.bits)) : nullptr;
+    l.table = table;
     if (!report) report = (TipsReport*)c->arena.temp(sizeof(TipsReport));
     l.grid = dim3(grid_for(n64, kTB));
     l.block = dim3(kTB);
@@ -1139,4 +1142,234 @@ void recount_from(goss_gpu_ctx* c, const QueryObj& q, goss_gpu_recount_report* o
     HIP_TRY(hipEventElapsedTime(&c->relative_ms[0], ev.e[0], ev.e[1]));
     HIP_TRY(hipEventElapsedTime(&c->relative_ms[2], ev.e[1], ev.e[2]));
     *out = rep;
+}
+
+// ---- read links -------------------------------------------------------------------------------------------------------
+
+// One scan of kernels_links.hpp over n slots, queued: tile aggregates, one workgroup over them, the tiles again.
+template <class Op>
+void links_scan(goss_gpu_ctx* c, const Op& op, uint64_t n)
+{
+    if (n == 0) return;
+    ArenaScope scope(c->arena);
+    const uint32_t ntiles = grid_for(n, kLinkTile);
+    uint2* agg = (uint2*)c->arena.temp((uint64_t)ntiles * sizeof(uint2));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(links_scan_reduce_kernel<Op>), dim3(ntiles), dim3(kTB), 0, c->stream, op, n, agg);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(links_scan_tiles_kernel<Op>), dim3(1), dim3(kTB), 0, c->stream, agg, (uint64_t)ntiles);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(links_scan_apply_kernel<Op>), dim3(ntiles), dim3(kTB), 0, c->stream, op, n, (const uint2*)agg);
+    // (the stream orders the kernels; the scope may give the aggregates back to later launches on it)
+}
+
+// goss_gpu_read_links_begin: link_graph, rank_lists and the numbering of the starts as entries_build has them, then the
+// segment of every edge.  Working arrays under an ArenaScope; seg_of, the flags, the bucket table and the bitmap are
+// permanent room on top of everything else: the held result.
+template <class K>
+void read_links_begin(goss_gpu_ctx* c, uint32_t flags, const uint8_t* unique, uint64_t unique_bits, goss_gpu_read_links_info* out)
+{
+    goss_gpu_read_links_info inf{};
+    const uint64_t n64 = c->build.M;
+    const uint32_t n = link_edges(c, "read_links");
+    const uint32_t bits = n ? tips_bucket_bits(n, c->len) : 0;
+    {
+        const uint64_t need = link_bytes(c, "read_links") + n64 * (rank_bytes_per_edge(false) + 8) + n64 * 5 + link_table_bytes(bits) +
+                              (unique ? unique_bits / 8 + 8 : 0) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    c->lnk_flags = flags;
+    c->lnk_bits = bits;
+    c->lnk_seg_of = (uint32_t*)c->arena.perm(std::max<uint64_t>(n64 * 4, 16));
+    c->lnk_single = (uint8_t*)c->arena.perm(std::max<uint64_t>(n64, 16));
+    c->lnk_table = bits ? (uint32_t*)c->arena.perm(link_table_bytes(bits)) : nullptr;
+    uint64_t nent = 0;
+    inf.edges = n64;
+    if (n)
+    {
+        ArenaScope scope(c->arena);
+        EventPair ev;
+        LinkReport* d_rep = (LinkReport*)c->arena.temp(sizeof(LinkReport));
+        uint64_t* hx = pinned_words(c);
+        HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(LinkReport), c->stream));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+        const GraphLinks<K> l = link_graph<K>(c, "read_links", nullptr, [&](const GraphLinks<K>&) { HIP_TRY(hipEventRecord(ev.e[1], c->stream)); });
+        uint64_t* sc = (uint64_t*)c->arena.temp((n64 + 1) * 8);
+        const ListRanks r = rank_lists(c, l, nullptr, [&](const uint8_t* flag) {
+            hipLaunchKernelGGL(entries_flags_kernel, l.grid, l.block, 0, c->stream, flag, n, sc);
+            scan_with_total(c, sc, n64, hx);
+        });
+        nent = hx[0];
+        HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+        if (bits) HIP_TRY(hipMemcpyAsync(c->lnk_table, l.table, link_table_bytes(bits), hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(links_segments_kernel, l.grid, l.block, 0, c->stream, (const uint2*)r.cur, (const uint8_t*)r.st, (const uint64_t*)sc,
+                           (const uint8_t*)l.info, n, c->lnk_seg_of, c->lnk_single, d_rep);
+        LinkReport* h = pinned_report<LinkReport>(c);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(LinkReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        sync_checked(c);
+        inf.edges_without_segment = h->none;
+        float* ms[3] = {&inf.ms_link, &inf.ms_rank, &inf.ms_segments};
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    }
+    inf.entries = nent;
+    if (nent >= 0x7FFFFFFFULL)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "read_links: a window's answer holds a 31-bit segment; this graph has 2^31 - 1 entry edges or more"};
+    if (unique && unique_bits != nent)
+        throw StatusError{GOSS_ERR_INVALID_ARG, "read_links: the bitmap has " + std::to_string(unique_bits) + " bits; the graph has " +
+                                                    std::to_string(nent) + " entry edges"};
+    if (unique)
+    {
+        const uint64_t bytes = (nent + 7) / 8, room = (bytes + 3) / 4 * 4 + 16;
+        c->lnk_unique = (uint32_t*)c->arena.perm(room);
+        HIP_TRY(hipMemsetAsync(c->lnk_unique, 0, room, c->stream));
+        if (bytes) HIP_TRY(hipMemcpyAsync(c->lnk_unique, unique, bytes, hipMemcpyHostToDevice, c->stream));
+        sync_checked(c);
+    }
+    c->lnk_entries = nent;
+    *out = inf;
+}
+
+// What a batch of n bytes takes from the arena: its copy; win, segu, pa, nh (4 each) and the flags per slot; the
+// compacted windows (4) or the records (12); the scans' aggregates.
+inline uint64_t read_links_batch_bytes(uint64_t n) { return n * (1 + 4 * 4 + 1 + 12) + (n / kLinkTile + 2) * 8 + (16u << 20); }
+
+// One batch: the windows, the aligner, and either the answers per window (`out`, up to `capacity` of them) or the
+// records, which become permanent room on top of what is held.
+template <class K>
+void read_links_batch(goss_gpu_ctx* c, const void* bases, uint64_t nbytes, uint32_t* out, uint64_t capacity, bool accumulate,
+                      goss_gpu_read_links_batch* info)
+{
+    goss_gpu_read_links_batch inf{};
+    if (nbytes >= 0xFFFFFFFEULL) throw StatusError{GOSS_ERR_INVALID_ARG, "read_links: a batch holds fewer than 2^32 - 2 bytes"};
+    if (nbytes == 0) { *info = inf; return; }
+    if (accumulate && c->lnk_rows_lo)
+    {
+        // (another batch after a finish: the table goes, the records stay)
+        c->arena.lo = c->lnk_rows_lo;
+        c->lnk_rows = nullptr; c->lnk_rows_lo = 0; c->lnk_row_count = 0; c->lnk_reduced = false;
+    }
+    {
+        const uint64_t need = read_links_batch_bytes(nbytes);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    const uint32_t n = (uint32_t)c->build.M;
+    const bool carry = (c->lnk_flags & GOSS_LINKS_CARRY) != 0;
+    ArenaScope scope(c->arena);
+    EventPair ev;
+    uint8_t* d_bases = (uint8_t*)c->arena.temp(nbytes);
+    uint32_t* win = (uint32_t*)c->arena.temp(nbytes * 4);
+    uint32_t* segu = (uint32_t*)c->arena.temp(nbytes * 4);
+    uint8_t* flags = (uint8_t*)c->arena.temp(nbytes);
+    LinkReport* d_rep = (LinkReport*)c->arena.temp(sizeof(LinkReport));
+    LinkReport* h = pinned_report<LinkReport>(c);
+    static_assert(sizeof(LinkReport) <= 128, "pinned scratch");
+    unsigned long long* ctr = &d_rep->carried;          // (the three counters of a scan: carried, hits, records)
+    const uint64_t ntiles = (nbytes + kMatchTile - 1) / kMatchTile;
+
+    HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep, 0, sizeof(LinkReport), c->stream));
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(links_windows_kernel<K>), unit_grid(ntiles), dim3(kTB), 0, c->stream, (const K*)c->build.res_keys, n, c->len,
+                       c->lnk_bits, (const uint32_t*)c->lnk_table, (const uint8_t*)c->lnk_single, (const uint8_t*)d_bases, nbytes, ntiles,
+                       (uint32_t)(((uintptr_t)d_bases & 7u) == 0), win, flags, d_rep);
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    if (carry)
+    {
+        links_scan(c, LinkPrevOp{win, flags, d_bases, c->k, nullptr}, nbytes);
+        links_scan(c, LinkCarryOp{win, flags, c->lnk_seg_of, c->lnk_unique, segu, ctr}, nbytes);
+    }
+    else
+        hipLaunchKernelGGL(links_exact_kernel, dim3(grid_for(nbytes, kTB)), dim3(kTB), 0, c->stream, (const uint32_t*)win,
+                           (const uint32_t*)c->lnk_seg_of, (const uint32_t*)c->lnk_unique, nbytes, segu);
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+
+    uint64_t nrec = 0;
+    if (!accumulate)
+    {
+        uint32_t* packed = (uint32_t*)c->arena.temp(nbytes * 4);
+        links_scan(c, LinkPackOp{segu, packed, nullptr}, nbytes);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(LinkReport), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        sync_checked(c);
+        const uint64_t m = std::min<uint64_t>(h->windows, capacity);
+        if (m) HIP_TRY(hipMemcpyAsync(out, packed, m * 4, hipMemcpyDeviceToHost, c->stream));
+        sync_checked(c);
+    }
+    else
+    {
+        uint32_t* pa = (uint32_t*)c->arena.temp(nbytes * 4);
+        uint32_t* nh = (uint32_t*)c->arena.temp(nbytes * 4);
+        links_scan(c, LinkHitOp{segu, flags, pa, nh, ctr}, nbytes);
+        HIP_TRY(hipMemcpyAsync(h, d_rep, sizeof(LinkReport), hipMemcpyDeviceToHost, c->stream));
+        sync_checked(c);
+        nrec = h->records;
+        if (nrec)
+        {
+            goss_gpu_ctx::LinkChunk k{};
+            k.keys = (unsigned long long*)c->arena.perm(nrec * 8);
+            k.gaps = (uint32_t*)c->arena.perm((nrec * 4 + 15) & ~15ULL);
+            k.n = nrec;
+            links_scan(c, LinkEmitOp{segu, pa, nh, k.keys, k.gaps, nullptr}, nbytes);
+            c->lnk_chunks.push_back(k);
+            c->lnk_records += nrec;
+        }
+        HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+        sync_checked(c);
+    }
+    inf.windows = h->windows; inf.misses = h->misses; inf.carried = h->carried; inf.hits = h->hits; inf.records = nrec;
+    inf.reads = h->lines + (((const uint8_t*)bases)[nbytes - 1] != '\n' ? 1 : 0);
+    float* ms[3] = {&inf.ms_windows, &inf.ms_scans, &inf.ms_compact};
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(ms[i], ev.e[i], ev.e[i + 1]));
+    *info = inf;
+}
+
+// goss_gpu_read_links_finish: the records of every batch side by side, the radix sort of count_path.hpp over the 64-bit
+// key with the gaps as values, heads, their scan, and the rows.  The table is permanent room above the records.
+void read_links_finish(goss_gpu_ctx* c, goss_gpu_read_links_table_info* out)
+{
+    goss_gpu_read_links_table_info inf{};
+    if (c->lnk_rows_lo) c->arena.lo = c->lnk_rows_lo;
+    c->lnk_rows = nullptr; c->lnk_rows_lo = 0; c->lnk_row_count = 0; c->lnk_reduced = false;
+    const uint64_t R = c->lnk_records;
+    inf.records = R;
+    {
+        // both arrays twice, the sort's tables, the heads; the rows stay
+        const uint64_t need = R * (2 * 12 + 8 + 24) + 256ULL * 8 * (R / 1024 + 2) + (16u << 20);
+        if (c->arena.avail() < need) grow_arena(c, need);
+    }
+    const uint64_t rows_lo = c->arena.lo;
+    uint64_t nrows = 0;
+    LinkRow* rows = nullptr;
+    if (R)
+    {
+        ArenaScope scope(c->arena);
+        EventPair ev;
+        Key1* ka = (Key1*)c->arena.temp(R * 8);
+        Key1* kb = (Key1*)c->arena.temp(R * 8);
+        uint32_t* va = (uint32_t*)c->arena.temp(R * 4);
+        uint32_t* vb = (uint32_t*)c->arena.temp(R * 4);
+        uint64_t* head = (uint64_t*)c->arena.temp((R + 1) * 8);
+        uint64_t at = 0;
+        for (const auto& k : c->lnk_chunks)
+        {
+            HIP_TRY(hipMemcpyAsync(ka + at, k.keys, k.n * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(va + at, k.gaps, k.n * 4, hipMemcpyDeviceToDevice, c->stream));
+            at += k.n;
+        }
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+        const bool in_b = radix_sort<Key1, true>(c, ka, kb, va, vb, R, 8);
+        const unsigned long long* keys = (const unsigned long long*)(in_b ? kb : ka);
+        const uint32_t* gaps = in_b ? vb : va;
+        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+        hipLaunchKernelGGL(links_heads_kernel, dim3(grid_for(R, kTB)), dim3(kTB), 0, c->stream, keys, R, head);
+        nrows = scan_total(c, head, R);
+        rows = (LinkRow*)c->arena.perm(nrows * sizeof(LinkRow));
+        HIP_TRY(hipMemsetAsync(rows, 0, nrows * sizeof(LinkRow), c->stream));
+        hipLaunchKernelGGL(links_rows_kernel, dim3(grid_for(R, kTB)), dim3(kTB), 0, c->stream, keys, gaps, (const uint64_t*)head, R, rows);
+        HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+        sync_checked(c);
+        HIP_TRY(hipEventElapsedTime(&inf.ms_sort, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&inf.ms_reduce, ev.e[1], ev.e[2]));
+    }
+    c->lnk_rows = rows; c->lnk_rows_lo = rows_lo; c->lnk_row_count = nrows; c->lnk_reduced = true;
+    inf.rows = nrows;
+    *out = inf;
 }

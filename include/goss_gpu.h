@@ -1081,6 +1081,11 @@ int goss_gpu_entries_end_rank(goss_gpu_object* obj, const uint64_t* d_ranks, uin
  * TransCmdMergeGraphWithReference.cc:47-114; likewise a header of its own. */
 #include "goss_gpu_relative.h"
 
+/* read links on a finished graph (goss_gpu_read_links_*): every forward window of every read aligned to the linear
+ * segment that holds it, and the table of the changes from one segment to the next with their gaps -- the "mapping
+ * reads" stage of GossCmdThreadReads.cc:321-402 over KmerAligner.hh:169-229; likewise a header of its own. */
+#include "goss_gpu_links.h"
+
 #ifdef __cplusplus
 }
 #endif
